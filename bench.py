@@ -1,6 +1,7 @@
 """bench.py -- clips/s of the encode/fuse/score hot path on 1..8 MI355X (one process per GPU).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -76,7 +77,15 @@ def parse():
     ap.add_argument("--no-priority", action="store_true", help="A/B: same stream priority for both modalities")
     ap.add_argument("--no-kv-first", action="store_true", help="A/B: let the light modality start beside the heavy K/V projection")
     ap.add_argument("--no-encode", action="store_true", help="skip the separately timed ViT-g encode stage")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (fuse_score's arrays) as DIR/<name>.npy "
+                         "(float32; spans float64; at most 64 MB, see dump_outputs); inputs and weights are seeded, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "finetune":
+        ap.error("--dump-outputs covers the encode/fuse/score path (clip32x32 / ref workloads), not the finetune step")
+    return args
 
 
 def main():
@@ -170,6 +179,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     assert torch.isfinite(out["fused"]).all()
+    if args.dump_outputs and rank == 0:   # before anything else runs on the library's workspaces; outside the timed region
+        dump_outputs(out, args.dump_outputs)
     value = n_total * args.steps / dt
     log(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step")
 
@@ -290,6 +301,39 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out, dst):
+    """What the caller of the timed path (XInstructBLIP.fuse_score) receives from the last timed step, one .npy per array:
+    per modality m the query embeddings z_m [N, 32, 768], [CLS] vectors cls_m [N, 768], cosine scores sim_m [N, 32] and logits
+    logit_m [N]; the fused logits fused [N] and the integer spans spans [B, 2].  float32, spans float64 (exact).  N is every clip
+    of the step (after the all-gather when N > 1).  Should the arrays exceed 64 MB (many GPUs), each z_m keeps the same seeded
+    sample of clips, listed in z_rows.npy."""
+    arrays = {}
+    for k in ("z", "cls", "sim", "logit"):
+        for m, t in sorted(out[k].items()):
+            arrays[f"{k}_{m}"] = t.detach().float().cpu().numpy()
+    arrays["fused"] = out["fused"].detach().float().cpu().numpy()
+    arrays["spans"] = out["spans"].detach().cpu().numpy().astype("float64")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        zs = [k for k in arrays if k.startswith("z_")]
+        n = arrays[zs[0]].shape[0]
+        row_bytes = sum(arrays[k][0].nbytes for k in zs)
+        keep = (DUMP_CAP_BYTES - (total - n * row_bytes) - 8 * n) // row_bytes
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+        for k in zs:
+            arrays[k] = arrays[k][rows]
+        arrays["z_rows"] = rows.astype("float64")
+    os.makedirs(dst, exist_ok=True)
+    import numpy as np
+
+    for k, a in arrays.items():
+        np.save(os.path.join(dst, f"{k}.npy"), a)
+    log(f"dumped {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB) to {dst}")
 
 
 def time_encode(dev, clips, frames_per_clip, fuse_s):
