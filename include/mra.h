@@ -172,13 +172,34 @@ int mra_qformer_set_cross_mode(mra_qformer* h, int32_t mode);
  *      unchanged).  Forces the folded form at any Kv; needs heads * n_query == 384.  The f32 copies of W_cq / W_k live in the parameter
  *      arena (kept current by mra_qformer_load / _load_flat); the first call with mode 1 allocates the prepared-weight arena
  *      (ncross x (3 H H + 3 H E) operand elements) -- the one allocation after create.  Cost and accuracy: DESIGN.md section 8.
- * mra_qformer_workspace_bytes follows the precision in force. */
+ *   2  auto: 0 or 1, chosen on the GPU from how peaked the attention is.  Same preconditions as 1; allocates the
+ *      split weight arena (and 2 x ncross x 1 KB of histograms, device and pinned host) up front and marks the probe stale, as do every
+ *      mra_qformer_load / _load_flat / _adam_step and every further call with mode 2.  The first mra_qformer_forward with a stale probe runs
+ *      the mode-0 folded chain (at any Kv and cross mode; never the streaming kernels, nor the rescale pass where enc_width % 176 == 0
+ *      gives the in-register row factors) with the probe variant of the row-factor (or rescale) kernel, which bins every row's softmax maximum p_max = 1 / L into a 256-bin histogram per cross layer; it copies the
+ *      histograms to the host and synchronises `stream` once (the only host sync, on this call only; it returns MRA_ESTATE "auto precision
+ *      unresolved: run one forward outside capture" while the stream is capturing) and resolves to 1 iff the largest per-layer median p_max is
+ *      >= tau, otherwise to 0.  Resolved to 1 -- or to 0 where mode 0 runs another form (the K/V cache, the streaming kernels) -- the same
+ *      call re-runs the forward in the resolved precision: the outputs returned are always those of the precision in force from then on.  Later forwards run the resolved mode with no probe and no sync (resolved to 0: the kernels of
+ *      mode 0 exactly).  tau = 0.5 by default (mra_qformer_set_option "auto_split_pmax_milli"): the mode-0 chain is measured inside the
+ *      1e-3 similarity-logit bar at a median p_max of 0.6 (7.3e-4, worst formulation) and outside it at 0.8, so 0.5 keeps a margin and sends
+ *      those 0.6 cases to split (peaked fixtures only -- no trained checkpoint was measured).  mra_qformer_forward_pair
+ *      accepts the handle only once it resolved to 0 (MRA_ESTATE otherwise).  Governs inference forwards only: the training entry points
+ *      run the mode-0 chain whatever the precision.
+ * mra_qformer_workspace_bytes follows the precision in force; under 2 it returns the largest of the mode-0 form in force, the mode-0 folded
+ * form of the probe and mode 1, so neither the probe nor its resolution needs a larger workspace. */
 int mra_qformer_set_cross_precision(mra_qformer* h, int32_t mode);
+/* State of the cross-attention precision (no reference counterpart: the reference has one fixed precision, fp16 under autocast,
+ * models/xinstructblip.py:58-66).  resolved: 0 op / 1 split in force, -1 while an automatic-precision probe is pending; probes: probes run
+ * since create (a steady state adds none); median_pmax (may be NULL, else n_layers >= the number of cross layers): per cross layer the
+ * median softmax row maximum the last probe measured, at the centre of its 1/256 bin (-1 before any probe).  Any pointer may be NULL. */
+int mra_qformer_cross_precision_report(mra_qformer* h, int32_t* resolved, int32_t* probes, float* median_pmax, int32_t n_layers);
 /* Per-handle tuning options (no reference counterpart; results are the same to fp32 summation order).
  *   "chain_ring"  mask: which GEMMs of the 12-layer chain run on the ring kernel's exact-fit tiles when the launch has ~1 k rows or more:
  *                 bit 0 QKV (144 x 128), bit 1 FFN-up (192 x 128), bit 2 the residual projections (96 x 64), bit 3 (with bit 2) their LayerNorm inside the same
  *                 launch (the last-arriving column tile of a 64-row block normalises it).  DESIGN.md section 8.
- *   "train_ring"  the same mask (bits 0 and 2) for the GEMMs of mra_qformer_forward_train / mra_qformer_backward; default 4. */
+ *   "train_ring"  the same mask (bits 0 and 2) for the GEMMs of mra_qformer_forward_train / mra_qformer_backward; default 4.
+ *   "auto_split_pmax_milli"  tau of the automatic cross-attention precision in thousandths, 0..1000 (default 500); applies from the next probe. */
 int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value);
 /* Derives what the folded path needs from the loaded weights (W_k of every cross layer regrouped per head) on
  * `stream`, if a load made it stale.  mra_qformer_forward does this itself; a caller that runs SEVERAL forwards of one

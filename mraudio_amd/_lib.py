@@ -56,6 +56,7 @@ PROTOTYPES = {
     "mra_qformer_set_kv_done_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mra_qformer_set_cross_mode": (C.c_int, [C.c_void_p, C.c_int32]),
     "mra_qformer_set_cross_precision": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mra_qformer_cross_precision_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32]),
     "mra_qformer_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mra_qformer_prepare": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mra_kv_cache_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -84,9 +84,11 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(const float* S, long 
 // tile statistics (m_tile, l_tile) of every row; here one workgroup per row finds m_row = max m_tile,
 // L = sum exp2(m_tile - m_row) l_tile and rescales the row in place by g_tile = exp2(m_tile - m_row) / L.
 // Columns from ntiles * tile_cols to kvp were never written by the GEMM and are zeroed.
-template <typename T>
+// PROBE: also adds the row's softmax maximum 1 / L to the 256-bin histogram hist[256] of [0, 1] (one global atomic per row, i.e. per
+// workgroup; see fold_rowfactor_kernel).  P is the plain kernel's, bit for bit.
+template <typename T, bool PROBE>
 __global__ void __launch_bounds__(256) softmax_rescale_kernel(T* P, long long ld_p, const float* stat_m, const float* stat_l, int ntiles,
-                                                              int tile_cols, int kvp) {
+                                                              int tile_cols, int kvp, int* hist) {
   __shared__ float g[128];
   const int tid = threadIdx.x;
   const float* sm = stat_m + (long long)blockIdx.x * ntiles;
@@ -100,6 +102,9 @@ __global__ void __launch_bounds__(256) softmax_rescale_kernel(T* P, long long ld
     l = wave_sum(l);
     const float inv = 1.0f / l;
     for (int t = tid; t < ntiles; t += 64) g[t] = __builtin_amdgcn_exp2f(sm[t] - m) * inv;
+    if constexpr (PROBE) {
+      if (tid == 0) atomicAdd(hist + (int)fminf(fmaxf(inv * 256.f, 0.f), 255.f), 1);   // fmaxf maps a NaN to bin 0
+    }
   }
   __syncthreads();
   using V8 = typename Vec8<T>::type;
@@ -125,22 +130,40 @@ __global__ void __launch_bounds__(256) softmax_rescale_kernel(T* P, long long ld
 // the P . enc GEMM's loader waves copy into LDS one tile slice (2 KB) at a time.
 // It also zeroes the row's P~ columns from ntiles * tile_cols to kvp, which the scores GEMM never writes and the P . enc GEMM reads
 // (its K runs to kvp): zero times any finite factor is zero, so that GEMM needs no column test of its own.
+// PROBE (automatic cross-attention precision, mra_qformer_set_cross_precision 2): the row's softmax maximum is exactly 1 / L (the entry at
+// s = m_row); each wave bins it into a 256-bin LDS histogram of [0, 1], and the workgroup adds its non-empty bins to hist[256] with one
+// global atomic each.  Factors and P are the plain kernel's, bit for bit.
+template <bool PROBE>
 __global__ void __launch_bounds__(256) fold_rowfactor_kernel(const float* stat_m, const float* stat_l, float* factors, int rows, int R, int ntiles,
-                                                             unsigned short* P, long long ld_p, int tile_cols, int kvp) {
+                                                             unsigned short* P, long long ld_p, int tile_cols, int kvp, int* hist) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  for (int c = ntiles * tile_cols + lane; c < kvp; c += 64) P[(long long)row * ld_p + c] = 0;
-  const float* sm = stat_m + (long long)row * ntiles;
-  const float* sl = stat_l + (long long)row * ntiles;
-  float m = -3.0e38f;
-  for (int t = lane; t < ntiles; t += 64) m = fmaxf(m, sm[t]);
-  m = wave_max(m);
-  float l = 0.f;
-  for (int t = lane; t < ntiles; t += 64) l += __builtin_amdgcn_exp2f(sm[t] - m) * sl[t];
-  l = wave_sum(l);
-  const float inv = 1.0f / l;
-  const int item = row / R, r = row - item * R;
-  for (int t = lane; t < ntiles; t += 64) factors[((long long)item * ntiles + t) * 512 + r] = __builtin_amdgcn_exp2f(sm[t] - m) * inv;
+  __shared__ int bins[PROBE ? 256 : 1];
+  if constexpr (PROBE) {
+    bins[threadIdx.x] = 0;
+    __syncthreads();
+  }
+  if (row < rows) {
+    for (int c = ntiles * tile_cols + lane; c < kvp; c += 64) P[(long long)row * ld_p + c] = 0;
+    const float* sm = stat_m + (long long)row * ntiles;
+    const float* sl = stat_l + (long long)row * ntiles;
+    float m = -3.0e38f;
+    for (int t = lane; t < ntiles; t += 64) m = fmaxf(m, sm[t]);
+    m = wave_max(m);
+    float l = 0.f;
+    for (int t = lane; t < ntiles; t += 64) l += __builtin_amdgcn_exp2f(sm[t] - m) * sl[t];
+    l = wave_sum(l);
+    const float inv = 1.0f / l;
+    const int item = row / R, r = row - item * R;
+    for (int t = lane; t < ntiles; t += 64) factors[((long long)item * ntiles + t) * 512 + r] = __builtin_amdgcn_exp2f(sm[t] - m) * inv;
+    if constexpr (PROBE) {
+      if (lane == 0) atomicAdd(&bins[(int)fminf(fmaxf(inv * 256.f, 0.f), 255.f)], 1);   // fmaxf maps a NaN to bin 0
+    }
+  }
+  if constexpr (PROBE) {
+    __syncthreads();
+    const int n = bins[threadIdx.x];
+    if (n) atomicAdd(hist + threadIdx.x, n);
+  }
 }
 
 // dst[b][c][r] = src[b][r][c] for r < R, 0 for R <= r < ld_d; 32 x 32 tiles, grid (ceil(C/32), ceil(ld_d/32), batch)
@@ -213,20 +236,26 @@ int launch_softmax_rows(const float* S, long long ld_s, void* P, long long ld_p,
 }
 
 int launch_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int rows, int R, int ntiles, void* P, long long ld_p, int tile_cols,
-                          int kvp, hipStream_t stream) {
+                          int kvp, hipStream_t stream, int* hist) {
   if (rows <= 0) return 0;
   if (ntiles <= 0 || R <= 0 || R > 512 || rows % R || !P || ld_p < kvp || ntiles * tile_cols > kvp) return -1;
-  hipLaunchKernelGGL(fold_rowfactor_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, stat_m, stat_l, factors, rows, R, ntiles, (unsigned short*)P, ld_p,
-                     tile_cols, kvp);
+  if (hist)
+    hipLaunchKernelGGL(fold_rowfactor_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, stream, stat_m, stat_l, factors, rows, R, ntiles,
+                       (unsigned short*)P, ld_p, tile_cols, kvp, hist);
+  else
+    hipLaunchKernelGGL(fold_rowfactor_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, stream, stat_m, stat_l, factors, rows, R, ntiles,
+                       (unsigned short*)P, ld_p, tile_cols, kvp, (int*)nullptr);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 int launch_softmax_rescale(void* P, long long ld_p, const float* stat_m, const float* stat_l, int rows, int ntiles, int tile_cols, int kvp,
-                           int op_dtype, hipStream_t stream) {
+                           int op_dtype, hipStream_t stream, int* hist) {
   if (rows <= 0) return 0;
   if (ntiles <= 0 || ntiles > 128 || (tile_cols & 7) || (kvp & 7) || (ld_p & 7) || ld_p < kvp) return -1;
-  if (op_dtype == OP_F16) hipLaunchKernelGGL(softmax_rescale_kernel<f16>, dim3(rows), dim3(256), 0, stream, (f16*)P, ld_p, stat_m, stat_l, ntiles, tile_cols, kvp);
-  else hipLaunchKernelGGL(softmax_rescale_kernel<bf16>, dim3(rows), dim3(256), 0, stream, (bf16*)P, ld_p, stat_m, stat_l, ntiles, tile_cols, kvp);
+#define MRA_RS(T, PR) hipLaunchKernelGGL((softmax_rescale_kernel<T, PR>), dim3(rows), dim3(256), 0, stream, (T*)P, ld_p, stat_m, stat_l, ntiles, tile_cols, kvp, hist)
+  if (op_dtype == OP_F16) { if (hist) MRA_RS(f16, true); else MRA_RS(f16, false); }
+  else { if (hist) MRA_RS(bf16, true); else MRA_RS(bf16, false); }
+#undef MRA_RS
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -250,10 +250,13 @@ int launch_softmax_rows(const float* S, long long ld_s, void* P, long long ld_p,
 // split softmax, second half without a pass over P: factors[(row / R * ntiles + t) * 512 + row % R] = exp2(m_tile - m_row) / L_row from the
 // tile statistics stat_*[row * ntiles + t] (rows = items * R, R <= 512); read by the P . enc GEMM through GemmProb::pscale.  Also zeroes
 // the 16-bit P~ rows (row stride ld_p elements) from column ntiles * tile_cols to kvp, which the scores GEMM leaves unwritten.
+// hist != nullptr: the probe variant, which also adds every row's softmax maximum 1 / L_row to the 256-bin histogram hist[256] of [0, 1]
+// (automatic cross-attention precision); the factors and P~ are the same bits.
 int launch_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int rows, int R, int ntiles, void* P, long long ld_p, int tile_cols,
-                          int kvp, hipStream_t stream);
+                          int kvp, hipStream_t stream, int* hist = nullptr);
+// hist != nullptr: the probe variant (as launch_fold_rowfactor's)
 int launch_softmax_rescale(void* P, long long ld_p, const float* stat_m, const float* stat_l, int rows, int ntiles, int tile_cols, int kvp,
-                           int op_dtype, hipStream_t stream);
+                           int op_dtype, hipStream_t stream, int* hist = nullptr);
 // dst[b][c][r] = src[b][r][c] (r < R), 0 for R <= r < ld_d; src [batch][R][C], dst [batch][C][ld_d]
 int launch_transpose_pad(const void* src, void* dst, int R, int C, int ld_d, long long src_bs, long long dst_bs, int batch, int op_dtype,
                          hipStream_t stream);

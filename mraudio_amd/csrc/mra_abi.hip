@@ -157,6 +157,7 @@ struct Work {
   float* gfac;                     // split softmax: row factors exp2(m_tile - m_row) / L as [N][ntiles][512] for the P . enc GEMM
   float *st_m, *st_l, *ginv;       // streaming kernels: statistics [N * R][stat_ld], 1 / L [N * R]
   char* gexp;                      // tile factors f16 [N * R][stat_ld]
+  int* hist;                       // probing forward of the automatic precision: p_max histograms [ncross][256] (nullptr otherwise)
   int nsplit;
   size_t bytes;
 };
@@ -186,6 +187,7 @@ void layout_cross(const mra_qformer* h, Carver& cv, Work& w, int N, int Kv) {
   w.qc32 = w.qp32 = nullptr;
   w.s32 = w.stat = w.gfac = w.st_m = w.st_l = w.ginv = nullptr;
   w.gexp = nullptr;
+  w.hist = nullptr;
   if (h->ncross > 0 && use_fold(h, Kv) && fold_streams(h, Kv)) {
     const size_t E = c.enc_width, R = (size_t)c.heads * Q, kvp = fold_kvp(Kv), sld = fold_stream_stat_ld((int)kvp);
     w.qp16 = cv.take<char>((size_t)N * R * E, 2);
@@ -335,10 +337,12 @@ int cross_core(mra_qformer* h, const Work& w, const LayerW& Lw, const void* enc,
       if (w.gfac) {
         // second half of the softmax without a pass over P: only the row factors are computed here, the P . enc GEMM applies them
         // to its P~ fragments in registers (same arithmetic, same rounding as the rescale pass)
-        rc = launch_fold_rowfactor(sc.stat_m, sc.stat_l, w.gfac, N * R, R, ntiles, w.p16, kvp, 176, kvp, stream);
+        rc = launch_fold_rowfactor(sc.stat_m, sc.stat_l, w.gfac, N * R, R, ntiles, w.p16, kvp, 176, kvp, stream,
+                                   w.hist ? w.hist + (size_t)ci * 256 : nullptr);
         if (rc) return chk(rc, "fold row factors");
       } else {
-        rc = launch_softmax_rescale(w.p16, kvp, sc.stat_m, sc.stat_l, N * R, ntiles, 176, kvp, op, stream);
+        rc = launch_softmax_rescale(w.p16, kvp, sc.stat_m, sc.stat_l, N * R, ntiles, 176, kvp, op, stream,
+                                    w.hist ? w.hist + (size_t)ci * 256 : nullptr);
         if (rc) return chk(rc, "fold softmax rescale");
       }
     } else {
@@ -501,6 +505,8 @@ void mra_qformer_destroy(mra_qformer* h) {
   if (h->arena_t) (void)hipFree(h->arena_t);
   if (h->arena_f) (void)hipFree(h->arena_f);
   if (h->arena_p) (void)hipFree(h->arena_p);
+  if (h->auto_hist) (void)hipFree(h->auto_hist);
+  if (h->auto_hist_host) (void)hipHostFree(h->auto_hist_host);
   if (h->flat_segs) (void)hipFree(h->flat_segs);
   if (h->tr_jobs) (void)hipFree(h->tr_jobs);
   if (h->adam_jobs) (void)hipFree(h->adam_jobs);
@@ -531,6 +537,7 @@ int mra_qformer_load(mra_qformer* h, const char* name, const void* src, int32_t 
   h->transposes_stale = true;
   h->fold_stale = true;
   h->precise_stale = true;
+  h->auto_stale = true;
   return MRA_OK;
 }
 
@@ -545,6 +552,7 @@ int mra_qformer_load_flat(mra_qformer* h, const float* master, size_t master_byt
   h->transposes_stale = true;
   h->fold_stale = true;
   h->precise_stale = true;
+  h->auto_stale = true;
   return MRA_OK;
 }
 
@@ -576,10 +584,28 @@ int mra_modality_ln(mra_qformer* h, const void* x, int32_t x_dtype, const int64_
              "modality_ln");
 }
 
-size_t mra_qformer_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
-  if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
+namespace {
+size_t workspace_in_force(const mra_qformer* h, int items, int L, int kv) {
   Work w = layout_work(h, nullptr, items, L, kv);
   return w.bytes + align_up(attn_partial_bytes(items, h->cfg.heads, h->cfg.n_query, w.nsplit));
+}
+}  // namespace
+
+size_t mra_qformer_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
+  if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
+  if (!h->cross_auto || h->probe_fold) return workspace_in_force(h, items, L, kv);
+  // automatic precision: the largest of the op form in force, the probing forward's op-precision folded form and split precision, so
+  // neither the probe nor its resolution ever needs a larger workspace
+  const int precise = h->cross_precise;
+  h->cross_precise = 0;
+  size_t need = workspace_in_force(h, items, L, kv);
+  h->probe_fold = true;
+  need = std::max(need, workspace_in_force(h, items, L, kv));
+  h->probe_fold = false;
+  h->cross_precise = 1;
+  need = std::max(need, workspace_in_force(h, items, L, kv));
+  h->cross_precise = precise;
+  return need;
 }
 
 double mra_qformer_flops(mra_qformer* h, int32_t items, int32_t L, int32_t kv, int32_t with_last_text) {
@@ -592,10 +618,11 @@ double mra_qformer_flops(mra_qformer* h, int32_t items, int32_t L, int32_t kv, i
   return per_item * items;
 }
 
-int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask,
-                        const float* query_embeds, int32_t query_items, const void* enc, int32_t items, int32_t L,
-                        int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
-                        size_t workspace_bytes, void* stream_) {
+namespace {
+// mra_qformer_forward in the precision and form in force (the probing forward of the automatic precision sets them around it)
+int forward_run(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const float* query_embeds, int32_t query_items,
+                const void* enc, int32_t items, int32_t L, int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
+                size_t workspace_bytes, void* stream_) {
   if (!h) return fail(MRA_EINVAL, "null handle");
   if (items < 0 || L < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
   if (items == 0) return MRA_OK;
@@ -627,6 +654,7 @@ int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t*
   const int op = h->op();
   Work w = layout_work(h, (char*)workspace, N, L, kv);
   w.part = w.nsplit > 1 ? reinterpret_cast<float*>((char*)workspace + w.bytes) : nullptr;
+  w.hist = h->probe_fold ? h->auto_hist : nullptr;
   const long long SH = (long long)S * H;
   const size_t esz = 2;
 
@@ -882,6 +910,67 @@ int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t*
   return MRA_OK;
 }
 
+// Lower median of the p_max histogram of one cross layer, at the centre of its bin (-1 for an empty histogram)
+float hist_median(const int* bins) {
+  long long n = 0;
+  for (int b = 0; b < 256; ++b) n += bins[b];
+  if (n == 0) return -1.f;
+  long long acc = 0;
+  for (int b = 0; b < 256; ++b) {
+    acc += bins[b];
+    if (2 * acc >= n) return (b + 0.5f) / 256.f;
+  }
+  return -1.f;
+}
+
+// The probing forward of the automatic precision: the op-precision folded chain with the probe kernel, ONE copy of the histograms to pinned
+// host memory and ONE synchronisation of the caller's stream, the decision, and -- when it is split, or op in a form other than the probe's --
+// the same forward again in the resolved precision, so the caller receives the outputs of the precision in force from here on.
+int forward_probe(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const float* query_embeds, int32_t query_items,
+                  const void* enc, int32_t items, int32_t L, int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
+                  size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = as_stream(stream_);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(MRA_ESTATE, "auto precision unresolved: run one forward outside capture");
+  const size_t hist_bytes = (size_t)h->ncross * 256 * sizeof(int);
+  HIP_TRY(hipMemsetAsync(h->auto_hist, 0, hist_bytes, stream));
+  h->cross_precise = 0;
+  h->probe_fold = true;
+  int rc = forward_run(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+                       workspace_bytes, stream_);
+  h->probe_fold = false;
+  if (rc) return rc;   // the probe stays pending
+  HIP_TRY(hipMemcpyAsync(h->auto_hist_host, h->auto_hist, hist_bytes, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  float worst = 0.f;
+  for (int ci = 0; ci < h->ncross; ++ci) {
+    h->auto_median[ci] = hist_median(h->auto_hist_host + (size_t)ci * 256);
+    worst = std::max(worst, h->auto_median[ci]);
+  }
+  ++h->auto_probes;
+  h->auto_stale = false;
+  h->auto_resolved = worst * 1000.f >= (float)h->auto_tau_milli ? 1 : 0;
+  h->cross_precise = h->auto_resolved;
+  // resolved to op: the probe's outputs are op's own bits when op runs the same form here (the folded form with in-register factors or the
+  // rescale pass: same bits); the K/V-cache form (Kv < 2048 in cross mode 0, or mode 1) and the streaming kernels are re-run
+  if (h->auto_resolved == 0 && use_fold(h, kv) && !fold_streams(h, kv)) return MRA_OK;
+  return forward_run(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+                     workspace_bytes, stream_);
+}
+}  // namespace
+
+int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask,
+                        const float* query_embeds, int32_t query_items, const void* enc, int32_t items, int32_t L,
+                        int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
+                        size_t workspace_bytes, void* stream_) {
+  if (h && h->cross_auto && h->auto_stale && h->ncross > 0 && items > 0)
+    return forward_probe(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+                         workspace_bytes, stream_);
+  return forward_run(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+                     workspace_bytes, stream_);
+}
+
 size_t mra_qformer_pair_workspace_bytes(mra_qformer* h0, mra_qformer* h1, int32_t items, int32_t L, int32_t kv0, int32_t kv1) {
   if (!h0 || !h1 || items <= 0 || L < 0 || kv0 <= 0 || kv1 <= 0) return 0;
   return layout_pair(h0, h1, nullptr, items, L, kv0, kv1).bytes;
@@ -913,6 +1002,8 @@ int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* in
   for (int l = 0; l < 2; ++l) {
     if (!outq[l] && !outc[l]) return fail(MRA_EINVAL, "no output requested for a lane");
     if (hs[l]->cross_precise) return fail(MRA_ESTATE, "pair forward runs the operand-dtype score chain: use mra_qformer_forward for split precision");
+    if (hs[l]->cross_auto && (hs[l]->auto_stale || hs[l]->auto_resolved != 0))
+      return fail(MRA_ESTATE, "pair forward runs the operand-dtype score chain: auto precision must have resolved to op (use mra_qformer_forward)");
     if (hs[l]->ncross > 0 && use_fold(hs[l], kvs[l]) && fold_streams(hs[l], kvs[l])) return fail(MRA_ESTATE, "pair forward: the streaming fold kernels are not supported");
     char names[256];
     const int miss = mra_qformer_missing(hs[l], names, sizeof(names));
@@ -1140,22 +1231,45 @@ int mra_qformer_set_cross_mode(mra_qformer* h, int32_t mode) {
 
 int mra_qformer_set_cross_precision(mra_qformer* h, int32_t mode) {
   if (!h) return fail(MRA_EINVAL, "null handle");
-  if (mode != 0 && mode != 1) return fail(MRA_EINVAL, "cross precision must be 0 (operand dtype) or 1 (split: hi + lo pairs along the score chain)");
-  if (mode == 1) {
+  if (mode < 0 || mode > 2)
+    return fail(MRA_EINVAL, "cross precision must be 0 (operand dtype), 1 (split: hi + lo pairs along the score chain) or 2 (auto: chosen by a probe)");
+  if (mode >= 1) {
     const mra_cfg& c = h->cfg;
     if (h->ncross == 0) return fail(MRA_EINVAL, "no cross-attention layers");
     if (c.heads * c.n_query != 384 || h->sc_tile != 5 || !h->split_softmax)
       return fail(MRA_EINVAL, "split precision needs heads * n_query == 384 (the 176 x 384 scores tile)");
-    if (!h->arena_p) {
+    if (!h->arena_p || (mode == 2 && !h->auto_hist)) {   // allocations happen on the handle's device
       int dev = 0;
       HIP_TRY(hipGetDevice(&dev));
       if (dev != h->device) return fail(MRA_EINVAL, "handle belongs to another device");
+    }
+    if (!h->arena_p) {
       const hipError_t e = hipMalloc((void**)&h->arena_p, (size_t)h->ncross * precise_layer_bytes(h));
       if (e != hipSuccess) return fail(MRA_ENOMEM, std::string("split-precision weight arena: ") + hipGetErrorString(e));
       h->precise_stale = true;
     }
+    if (mode == 2 && !h->auto_hist) {
+      const size_t hist_bytes = (size_t)h->ncross * 256 * sizeof(int);
+      hipError_t e = hipMalloc((void**)&h->auto_hist, hist_bytes);
+      if (e != hipSuccess) return fail(MRA_ENOMEM, std::string("auto-precision histograms: ") + hipGetErrorString(e));
+      e = hipHostMalloc((void**)&h->auto_hist_host, hist_bytes, hipHostMallocDefault);
+      if (e != hipSuccess) return fail(MRA_ENOMEM, std::string("auto-precision pinned histograms: ") + hipGetErrorString(e));
+      h->auto_median.assign(h->ncross, -1.f);
+    }
   }
-  h->cross_precise = mode;
+  h->cross_auto = mode == 2;
+  h->auto_stale = true;          // (again) mode 2: the next forward probes
+  h->cross_precise = mode == 1;  // auto runs op until a probe resolves it
+  return MRA_OK;
+}
+
+int mra_qformer_cross_precision_report(mra_qformer* h, int32_t* resolved, int32_t* probes, float* median_pmax, int32_t n_layers) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (median_pmax && n_layers < h->ncross) return fail(MRA_EINVAL, "median_pmax needs one float per cross layer (" + std::to_string(h->ncross) + ")");
+  if (resolved) *resolved = h->cross_auto ? (h->auto_stale ? -1 : h->auto_resolved) : h->cross_precise;
+  if (probes) *probes = h->auto_probes;
+  if (median_pmax)
+    for (int ci = 0; ci < h->ncross; ++ci) median_pmax[ci] = ci < (int)h->auto_median.size() ? h->auto_median[ci] : -1.f;
   return MRA_OK;
 }
 
@@ -1165,6 +1279,11 @@ int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value) {
   if (key == "train_ring") {
     if (value < 0 || value > 7) return fail(MRA_EINVAL, "train_ring is a mask of bits 0-2");
     h->train_ring = value;
+    return MRA_OK;
+  }
+  if (key == "auto_split_pmax_milli") {
+    if (value < 0 || value > 1000) return fail(MRA_EINVAL, "auto_split_pmax_milli is a threshold on p_max in [0, 1000] thousandths");
+    h->auto_tau_milli = value;   // applies from the next probe on
     return MRA_OK;
   }
   if (key == "chain_ring") {

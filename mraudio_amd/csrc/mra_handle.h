@@ -114,6 +114,18 @@ struct mra_qformer {
   float* wk32 = nullptr;
   char* arena_p = nullptr;
   bool precise_stale = true;
+  // automatic precision (mra_qformer_set_cross_precision 2): the first forward after a weight upload runs the op-precision folded chain with
+  // the probe variant of the row-factor kernel, which bins every row's softmax maximum p_max = 1 / L into auto_hist [ncross][256]; the largest
+  // per-layer median p_max >= auto_tau_milli / 1000 resolves to split (cross_precise = 1), otherwise to op (cross_precise = 0)
+  bool cross_auto = false;
+  bool auto_stale = true;                         // a probe is pending (set wherever precise_stale is)
+  bool probe_fold = false;                        // inside the probing forward: folded form (in-register factors where they exist), probe kernels
+  int auto_resolved = -1;                         // 0 op, 1 split, -1 never probed
+  int auto_probes = 0;                            // probes run since create
+  int auto_tau_milli = 500;                       // mra_qformer_set_option "auto_split_pmax_milli"
+  int* auto_hist = nullptr;                       // device histograms [ncross][256]
+  int* auto_hist_host = nullptr;                  // pinned host copy
+  std::vector<float> auto_median;                 // per cross layer median p_max of the last probe (-1: none yet)
   hipEvent_t kv_done = nullptr;                   // optional scheduling hook (mra_qformer_set_kv_done_event)
   hipEvent_t kv_ev0 = nullptr, kv_ev1 = nullptr;  // optional instrumentation (mra_qformer_set_kv_events)
   // training
@@ -139,18 +151,18 @@ struct mra_qformer {
 
 namespace mra_host {
 // folded cross-attention pays once the encoder sequence is long (fewer flops at any Kv, but five launches per layer)
-inline bool use_fold(const mra_qformer* h, int kv) { return h->cross_precise || h->cross_mode == 2 || (h->cross_mode == 0 && kv >= 2048); }
+inline bool use_fold(const mra_qformer* h, int kv) { return h->cross_precise || h->probe_fold || h->cross_mode == 2 || (h->cross_mode == 0 && kv >= 2048); }
 // padded score-row length: whole 128- and 176-row tiles of the scores GEMM, and a multiple of 128 (K of P . enc)
 // P . enc on the 176 x 384 tile with K-major weights: no transposed copy of the encoder tokens is needed
 inline bool fold_kmajor(const mra_qformer* h) {
   return h->pv_kmajor && h->pv_tile == 5 && h->cfg.heads * h->cfg.n_query == 384 && h->cfg.enc_width % 176 == 0;
 }
 // split softmax without the rescale pass: needs the 176-column score tiles and the K-major 176 x 384 P . enc tile
-inline bool fold_inreg_rescale(const mra_qformer* h) { return h->inreg_rescale && h->split_softmax && h->sc_tile == 5 && fold_kmajor(h); }
+inline bool fold_inreg_rescale(const mra_qformer* h) { return (h->inreg_rescale || h->probe_fold) && h->split_softmax && h->sc_tile == 5 && fold_kmajor(h); }
 inline int fold_kvp(int kv) { return (std::max((kv + 127) / 128 * 128, (kv + 175) / 176 * 176) + 127) / 128 * 128; }
 // the streaming kernels (fold_stream.hip): f16 operands, 384 (head, query) rows, E a multiple of 176
 inline bool fold_streams(const mra_qformer* h, int kv) {
-  return !h->cross_precise && h->fold_stream && mra::fold_stream_supported(h->cfg.heads * h->cfg.n_query, h->cfg.enc_width, kv, fold_kvp(kv), h->op());
+  return !h->cross_precise && !h->probe_fold && h->fold_stream && mra::fold_stream_supported(h->cfg.heads * h->cfg.n_query, h->cfg.enc_width, kv, fold_kvp(kv), h->op());
 }
 // split-precision cross-attention: bytes of one cross layer's prepared weights, W_cq [H][3H] then W_k [heads][E][192] (operand dtype)
 inline size_t precise_wk_off(const mra_qformer* h) { return align_up((size_t)h->cfg.hidden * 3 * h->cfg.hidden * 2); }

@@ -300,6 +300,7 @@ int mra_qformer_adam_step(mra_qformer* h, float* master, float* grad, float* exp
   h->transposes_stale = false;   // the pass wrote the transposed copies too
   h->fold_stale = true;
   h->precise_stale = true;
+  h->auto_stale = true;
   return MRA_OK;
 }
 

@@ -40,17 +40,23 @@ def run_inference(model, dataloader: Iterable[dict], output_file: Optional[str] 
             records.append(rec)
             if fh:
                 fh.write(json.dumps(rec) + "\n")
+        if len(records) == len(outputs) and hasattr(model, "cross_precision_report"):   # once, after the first batch
+            print(f"cross-attention precision: {format_cross_precision(model.cross_precision_report())}")
     if fh:
         fh.close()
     return records
 
 
-def main(argv=None) -> None:
-    from torch.utils.data import DataLoader
+def format_cross_precision(report: dict) -> str:
+    """One line per model: for each modality the mode set, the precision in force and the probe's per-cross-layer median p_max."""
+    parts = []
+    for m, r in report.items():
+        med = ", ".join(f"{x:.3f}" for x in r["median_pmax"]) if r["probes"] else "-"
+        parts.append(f"{m}: {r['mode']} -> {r['resolved'] or 'unresolved'} (median p_max per cross layer: {med})")
+    return "; ".join(parts)
 
-    from .models.xinstructblip import XInstructBLIP
-    from .utils.mr_dataset import MRDataset, SyntheticMRDataset, collate_fn
 
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="X-InstructBLIP")
     ap.add_argument("--model-path", default=None)
@@ -66,9 +72,22 @@ def main(argv=None) -> None:
     ap.add_argument("--num-workers", type=int, default=0)
     ap.add_argument("--dataset", default="Charades_STA", choices=["QVH", "Charades_STA"])
     ap.add_argument("--synthetic", type=int, default=0, help="evaluate N seeded synthetic videos instead of a corpus")
-    args = ap.parse_args(argv)
+    ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],
+                    help="precision of the Q-Formers' cross-attention score chain: op (f16 / bf16 operands), split (~22-bit hi + lo pairs, "
+                         "+28 %% of the step) or auto (measured on the first batch after the weights are loaded: split for sharply attending weights)")
+    return ap
+
+
+def main(argv=None) -> None:
+    from torch.utils.data import DataLoader
+
+    from .models.xinstructblip import XInstructBLIP
+    from .utils.mr_dataset import MRDataset, SyntheticMRDataset, collate_fn
+
+    args = build_parser().parse_args(argv)
     n_frms = 60 if args.dataset == "QVH" else 20
-    model = XInstructBLIP(args.model_path, args.audio_encoder, device=args.device, checkpoint=args.checkpoint, checkpoint_strict=not args.partial_checkpoint)
+    model = XInstructBLIP(args.model_path, args.audio_encoder, device=args.device, checkpoint=args.checkpoint, checkpoint_strict=not args.partial_checkpoint,
+                          cross_precision=args.cross_precision)
     print(f"weights: {model.weights_source}")
     if args.synthetic:
         ds = SyntheticMRDataset(args.synthetic, T=n_frms)

@@ -41,7 +41,7 @@ def run_train(args):
     return out
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="X-InstructBLIP")
     ap.add_argument("--model-path", default=None)
@@ -62,7 +62,14 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--warmup-steps", type=int, default=1000)
-    args = ap.parse_args(argv)
+    ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],
+                    help="precision of the Q-Formers' cross-attention score chain in the validation forwards (training always runs op): "
+                         "op, split or auto (measured on the first forward after every weight update)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     return run_train(args)
 

@@ -117,7 +117,8 @@ class XInstructBLIP(nn.Module):
                  perturb: bool = False, op_dtype: torch.dtype = torch.float16, device=None,
                  compat_repeat: bool = True, score_alpha: float = 0.5, fuse_weights: Optional[Sequence[float]] = None,
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
-                 llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True):
+                 llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
+                 cross_precision: str = "op"):
         super().__init__()
         self.model_path, self.audio_path = model_path, audio_path
         self.modalities = list(modalities) if modalities is not None else ["audio", "video"]  # reference :71
@@ -153,6 +154,8 @@ class XInstructBLIP(nn.Module):
             cfg = QFormerConfig(enc_width=ENC_WIDTH[m], op_dtype=op_dtype, llm_hidden=self.llm_hidden_size,
                                 **(qformer_overrides or {}))
             qf, qt = self.init_Qformer(self.num_query_token, ENC_WIDTH[m], cfg=cfg, device=self._device)
+            if cross_precision != "op":   # "split" / "auto": QFormer.set_cross_precision (inference forwards only)
+                qf.set_cross_precision(cross_precision)
             setattr(self, f"{m}_Qformer", qf)
             setattr(self, f"{m}_query_tokens", qt)
             ln = self.init_ln(ENC_WIDTH[m])
@@ -480,11 +483,21 @@ class XInstructBLIP(nn.Module):
         return out
 
     def _pair_ok(self, live) -> bool:
-        """The two live modalities can share one launch sequence: equal Q-Former shapes, operand-dtype score chain, no streaming fold."""
+        """The two live modalities can share one launch sequence: equal Q-Former shapes, operand-dtype score chain (automatic precision
+        only once it resolved to op), no streaming fold."""
         a, b = (getattr(self, f"{m}_Qformer").cfg for m in live)
         same = all(getattr(a, k) == getattr(b, k) for k in ("hidden", "heads", "inter", "layers", "cross_freq", "n_query", "op_dtype"))
-        return same and not any(getattr(getattr(self, f"{m}_Qformer"), "_cross_precision", "op") != "op" or getattr(getattr(self, f"{m}_Qformer"), "_cross_mode", "auto") == "fold_stream"
-                                for m in live)
+
+        def op_chain(qf) -> bool:
+            mode = getattr(qf, "_cross_precision", "op")
+            return mode == "op" or (mode == "auto" and qf.cross_precision_report()["resolved"] == "op")
+
+        return same and all(op_chain(getattr(self, f"{m}_Qformer")) and getattr(getattr(self, f"{m}_Qformer"), "_cross_mode", "auto") != "fold_stream"
+                            for m in live)
+
+    def cross_precision_report(self) -> Dict[str, dict]:
+        """Per modality ``QFormer.cross_precision_report()``: the precision mode set, the one in force and the measured attention sharpness."""
+        return {m: getattr(self, f"{m}_Qformer").cross_precision_report() for m in self.modalities}
 
     @torch.no_grad()
     def encode_fuse(self, samples, want_llm: bool = False, want_full: bool = False) -> Dict[str, object]:

@@ -409,13 +409,28 @@ class QFormer(nn.Module):
         check(lib().mra_qformer_set_option(self._handle, name.encode(), int(value)), f"mra_qformer_set_option({name})")
 
     def set_cross_precision(self, mode) -> None:
-        """Precision of the cross-attention score chain: ``"op"`` (default: f16 / bf16 operands) or ``"split"`` (hidden state, W_cq, Q,
-        W_k and Q' as hi + lo pairs, ~22 bits; folded form at any Kv; ``mra_qformer_set_cross_precision``).  For sharply attending
-        (trained) weights, where the f16 rounding of the score operands is amplified by the softmax."""
-        code = {"op": 0, "f16": 0, "split": 1}.get(mode, mode)
+        """Precision of the cross-attention score chain: ``"op"`` (default: f16 / bf16 operands), ``"split"`` (hidden state, W_cq, Q,
+        W_k and Q' as hi + lo pairs, ~22 bits; folded form at any Kv) or ``"auto"`` (``mra_qformer_set_cross_precision``).  Split is
+        for sharply attending (trained) weights, where the f16 rounding of the score operands is amplified by the softmax; auto measures
+        how peaked the attention is on the first forward after every weight upload (one host sync on that call) and runs split iff the
+        largest per-cross-layer median softmax row maximum reaches the threshold (0.5; option ``auto_split_pmax_milli``), op otherwise.
+        The workspace size follows the mode (under auto: the largest of the forms the handle may run)."""
+        code = {"op": 0, "f16": 0, "split": 1, "auto": 2}.get(mode, mode)
         with torch.cuda.device(self._device):
             check(lib().mra_qformer_set_cross_precision(self._handle, int(code)), "mra_qformer_set_cross_precision")
-        self._cross_precision = "split" if int(code) == 1 else "op"
+        self._cross_precision = {0: "op", 1: "split", 2: "auto"}[int(code)]
+
+    def cross_precision_report(self) -> Dict[str, object]:
+        """``{"mode", "resolved", "probes", "median_pmax"}``: the mode set (``"op"`` / ``"split"`` / ``"auto"``), the precision in force
+        (``"op"`` / ``"split"``, ``None`` while an auto probe is pending), the number of auto probes since the handle was created and,
+        per cross layer, the median softmax row maximum of the last probe (-1 before any; ``mra_qformer_cross_precision_report``)."""
+        ncross = -(-self.cfg.layers // self.cfg.cross_freq) if self.cfg.cross_freq > 0 else 0   # layers i with i % cross_freq == 0
+        resolved, probes = C.c_int32(), C.c_int32()
+        med = (C.c_float * max(1, ncross))()
+        check(lib().mra_qformer_cross_precision_report(self._handle, C.byref(resolved), C.byref(probes), med, max(1, ncross)),
+              "mra_qformer_cross_precision_report")
+        return {"mode": getattr(self, "_cross_precision", "op"), "resolved": {0: "op", 1: "split"}.get(int(resolved.value)),
+                "probes": int(probes.value), "median_pmax": [float(med[i]) for i in range(ncross)]}
 
     def flops(self, items: int, L: int, kv: int, with_last_text: bool) -> float:
         return float(lib().mra_qformer_flops(self._handle, items, L, kv, int(with_last_text)))

@@ -81,7 +81,8 @@ class Trainer:
             from ..models.xinstructblip import XInstructBLIP
             model = XInstructBLIP(getattr(args, "model_path", None), getattr(args, "audio_encoder", None), device=self.device,
                                   op_dtype=getattr(args, "op_dtype", torch.bfloat16), checkpoint=getattr(args, "checkpoint", None),
-                                  checkpoint_strict=not getattr(args, "partial_checkpoint", False))
+                                  checkpoint_strict=not getattr(args, "partial_checkpoint", False),
+                                  cross_precision=getattr(args, "cross_precision", "op"))
         self.model = model
         if hasattr(model, "clip_parallel"):
             model.clip_parallel = False            # ranks see different samples
@@ -196,6 +197,10 @@ class Trainer:
         for samples in self.val_dataloader:
             samples = prepare_sample(samples, self.device if self.device.type == "cuda" else None)
             outputs = self.model.generate(samples)
+            if not results and self.rank == 0 and hasattr(self.model, "cross_precision_report") and not getattr(self, "_precision_logged", False):
+                from ..evaluate import format_cross_precision   # once, after the first validation batch
+                logging.info("cross-attention precision: %s", format_cross_precision(self.model.cross_precision_report()))
+                self._precision_logged = True
             for qid, query, vid, target, output in zip(samples["qid"], samples["query"], samples["vid"], samples["text_output"], outputs):
                 results.append({"qid": qid, "query": query, "vid": vid, "relevant_windows": moment_str_to_list(post_process(target)),
                                 "pred_relevant_windows": moment_str_to_list(post_process(output))})
