@@ -321,6 +321,54 @@ double mra_vit_flops(mra_vit* h, int32_t frames);
  * next (frame, head) unit into registers while it works on the current one (bit-identical results; measured slower). */
 int mra_vit_set_option(mra_vit* h, const char* name, int32_t value);
 
+/* ---- BEATs audio encoder (row A1 / N4, the audio half) ----------------------------------------------------
+ * replaces: self.audio_encoder(fbank) inside the per-position loop of XInstructBLIP.generate / forward
+ * (models/xinstructblip.py:267-275), the module LAVIS BeatsEncoder(checkpoint_path) builds (init_audio_encoder, :670-676), whose
+ * forward is BEATs' extract_features(fbank, padding_mask=None, feature_only=True)[0].
+ * One call encodes ALL clip chunks of a step.  Parameter names are the state_dict keys of mraudio_amd/models/beats.py, which are
+ * BEATs' checkpoint keys (patch_embedding.weight, layer_norm.{weight,bias}, post_extract_proj.{weight,bias},
+ * encoder.pos_conv.0.{weight,bias}, encoder.layer_norm.{weight,bias},
+ * encoder.layers.{i}.self_attn.{q_proj,k_proj,v_proj,out_proj,grep_linear}.{weight,bias}, encoder.layers.{i}.self_attn.grep_a,
+ * encoder.layers.0.self_attn.relative_attention_bias.weight, encoder.layers.{i}.{self_attn_layer_norm,fc1,fc2,final_layer_norm}.{weight,bias})
+ * with one exception: the positional convolution is loaded as its EFFECTIVE weight "encoder.pos_conv.0.weight" [dim, dim / groups, conv_pos]
+ * (weight_g * weight_v / ||weight_v||, folded by the caller: the encoder is frozen).  k_proj.bias is optional (zero when not loaded).
+ * BEATs.hf_state_dict / load_hf_state_dict map the transformer part to transformers' WavLMEncoder. */
+#define MRA_BEATS_GATE_Q 0      /* BEATs: the gate of the relative-position bias is computed from the unscaled q projection */
+#define MRA_BEATS_GATE_INPUT 1  /* WavLM: from the layer input */
+typedef struct mra_beats mra_beats;
+typedef struct mra_beats_cfg {
+  int32_t dim;              /* encoder_embed_dim 768; heads * 64, multiple of 256 */
+  int32_t heads;            /* encoder_attention_heads 12 (head dimension 64) */
+  int32_t ffn;              /* encoder_ffn_embed_dim 3072; multiple of 256 */
+  int32_t layers;           /* encoder_layers 12 */
+  int32_t embed_dim;        /* patch embedding width 512; multiple of 256 */
+  int32_t patch;            /* input_patch_size 16 */
+  int32_t mel_bins;         /* 128 -> mel_bins / patch = 8 tokens per patch row */
+  int32_t conv_pos;         /* 128 taps of the positional convolution (even) */
+  int32_t conv_pos_groups;  /* 16: dim / groups = 48 channels per group */
+  int32_t num_buckets;      /* 320 relative-position buckets */
+  int32_t max_distance;     /* 800 */
+  float ln_eps;             /* 1e-5 */
+  float deep_norm_alpha;    /* residual scale of the post-LN layers: (2 * layers)^0.25 for BEATs, 1 for WavLM */
+  int32_t gate_from;        /* MRA_BEATS_GATE_Q (BEATs) or MRA_BEATS_GATE_INPUT (WavLM) */
+  int32_t op_dtype;         /* MRA_F16: MFMA operand type (the reference autocasts the encoders to fp16) */
+} mra_beats_cfg;
+void mra_beats_cfg_default(mra_beats_cfg* cfg);
+int mra_beats_create(const mra_beats_cfg* cfg, mra_beats** out);
+void mra_beats_destroy(mra_beats* h);
+int mra_beats_load(mra_beats* h, const char* name, const void* src, int32_t dtype, const int64_t* shape, int32_t ndim, void* stream);
+/* number of required parameters not loaded yet (0 = ready) */
+int mra_beats_missing(mra_beats* h);
+size_t mra_beats_workspace_bytes(mra_beats* h, int32_t n, int32_t frames);
+/* fbank [n, frames, mel_bins] (MRA_F32 or MRA_F16, the normalised filterbank BeatsAudioProcessor emits; frames are truncated to a
+ * multiple of patch) -> out [n, P, dim] fp32 with P = frames / patch * mel_bins / patch tokens (<= 512): the last layer's output. */
+int mra_beats_forward(mra_beats* h, const void* fbank, int32_t dtype, int32_t n, int32_t frames, void* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* executed flops of one forward over n chunks of `frames` frames (2 per MAC) */
+double mra_beats_flops(mra_beats* h, int32_t n, int32_t frames);
+/* Per-handle options.  "gemm_persist" (default 1): the QKV / fc1 GEMMs as one persistent workgroup per CU (as mra_vit_set_option). */
+int mra_beats_set_option(mra_beats* h, const char* name, int32_t value);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------
  * Number of GEMM launches of one main loop ("family") with one epilogue since the library was loaded; read-only, the only
  * process-wide state of the library.  Families (csrc/kernels.h GemmFamily): 0 / 1 two-buffer 64x64 / 128x128, 3 loader-wave 256x256,

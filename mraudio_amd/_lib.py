@@ -33,6 +33,16 @@ class mra_vit_cfg(C.Structure):
                 ("img", C.c_int32), ("ln_eps", C.c_float), ("op_dtype", C.c_int32), ("residual_dtype", C.c_int32)]
 
 
+MRA_BEATS_GATE_Q, MRA_BEATS_GATE_INPUT = 0, 1
+
+
+class mra_beats_cfg(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32), ("layers", C.c_int32), ("embed_dim", C.c_int32),
+                ("patch", C.c_int32), ("mel_bins", C.c_int32), ("conv_pos", C.c_int32), ("conv_pos_groups", C.c_int32),
+                ("num_buckets", C.c_int32), ("max_distance", C.c_int32), ("ln_eps", C.c_float), ("deep_norm_alpha", C.c_float),
+                ("gate_from", C.c_int32), ("op_dtype", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/mra.h declares (tests check this)
 PROTOTYPES = {
     "mra_cfg_default": (None, [C.POINTER(mra_cfg), C.c_int32]),
@@ -89,6 +99,15 @@ PROTOTYPES = {
     "mra_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mra_vit_flops": (C.c_double, [C.c_void_p, C.c_int32]),
     "mra_vit_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
+    "mra_beats_cfg_default": (None, [C.POINTER(mra_beats_cfg)]),
+    "mra_beats_create": (C.c_int, [C.POINTER(mra_beats_cfg), C.POINTER(C.c_void_p)]),
+    "mra_beats_destroy": (None, [C.c_void_p]),
+    "mra_beats_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]),
+    "mra_beats_missing": (C.c_int, [C.c_void_p]),
+    "mra_beats_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mra_beats_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mra_beats_flops": (C.c_double, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mra_beats_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mra_debug_gemm_launches": (C.c_int64, [C.c_int32, C.c_int32]),
 }
 

@@ -13,7 +13,7 @@ What differs, on purpose: the reference hands the projected query
 8-bit Vicuna-7B and parses generated text; here ``generate`` scores clips with the cosine scorer and
 formats the span as the same ``"[[start, end]]"`` string, so ``evaluate.py``-shaped callers
 (``moment_str_to_list(post_process(out))``, ``evaluate.py:48``) run unchanged.  The ViT-g / BEATs
-encoders (row A1) are pluggable stock PyTorch modules; pre-computed encoder outputs can be passed
+encoders (row A1) are pluggable modules (``audio_encoder="beats"`` builds the HIP BEATs encoder, ``models/beats.py``); pre-computed encoder outputs can be passed
 as ``samples["video_embeds"] [B,T,Kv,1408]`` / ``samples["audio_embeds"] [B,T,Kv,768]``.
 
 All arithmetic between the encoder output and the span runs in ``libmra_hip.so``: modality
@@ -113,7 +113,7 @@ ENC_WIDTH = {"video": 1408, "audio": 768}  # EVA ViT-g / BEATs num_features (ref
 class XInstructBLIP(nn.Module):
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
-                 audio_encoder: Optional[nn.Module] = None, tokenizer=None, seed: Optional[int] = 0,
+                 audio_encoder=None, tokenizer=None, seed: Optional[int] = 0,
                  perturb: bool = False, op_dtype: torch.dtype = torch.float16, device=None,
                  compat_repeat: bool = True, score_alpha: float = 0.5, fuse_weights: Optional[Sequence[float]] = None,
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
@@ -143,6 +143,11 @@ class XInstructBLIP(nn.Module):
         self._device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.tokenizer = tokenizer if tokenizer is not None else self.init_tokenizer(truncation_side="left")
         self.video_encoder = video_encoder
+        if isinstance(audio_encoder, str):   # "beats": the reference's init_audio_encoder (:670-676), BeatsEncoder(audio_path) on the HIP kernels
+            if audio_encoder != "beats":
+                raise ValueError(f"audio_encoder: an nn.Module, None or 'beats', got {audio_encoder!r}")
+            from .beats import BeatsEncoder
+            audio_encoder = BeatsEncoder(checkpoint_path=audio_path, backend="hip", device=self._device)
         self.audio_encoder = audio_encoder
         self.llm_hidden_size = llm_hidden_size   # Vicuna-7B: 4096 (reference :167)
         self.llm_model = None                    # stock causal LM, attached by attach_llm (row N2)
