@@ -2,6 +2,7 @@
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full     # + the measurements that take runs of their own (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,15 +12,20 @@ BASELINE "32-clip x 32-frame" shape) + 10 s of audio (496 BEATs to
 32-token prompt.  Timed: modality LayerNorm -> video Q-Former -> audio Q-Former -> (N > 1: RCCL
 all-gather of the query embeddings) -> cosine scores -> fusion -> integer spans.  Nothing is skipped
 or cached between steps.  The ViT-g / BEATs encoders are NOT in the timed region of `value`: the features
-are the synthetic input (BASELINE configs 1-4).  The ViT-g encode of the same 1024 frames -- on this build's own
-kernels (mra_vit_forward) and, beside it, stock PyTorch -- is timed separately and reported under `encode_stage`.
+are the synthetic input (BASELINE configs 1-4).
 Weak scaling: every GPU holds its own 32 clips of a 32*N-clip video; value = all clips / time.
 
 Also on the JSON line: `roofline` of the dominant kernels -- with the folded cross-attention (Kv >= 2048, the
 headline shape) the block of one cross layer (per-head Q' GEMM, scores + split-softmax statistics, P.enc, per-head
 context GEMM), timed inside the steps by an event pair the library records on the launch stream; `frac` is EXECUTED
-flops / dense f16 MFMA peak, the reference formulation's algorithmic flops are reported beside it -- and
-`cpu_baseline` (the CPU oracle on a bounded sample, median of five passes, rank 0, N = 1).
+flops / dense f16 MFMA peak, the reference formulation's algorithmic flops are reported beside it.
+
+A plain run does only what these figures need: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+what takes runs of its own (off by default; their fields are null without it):
+  - the stand-alone timing of the K/V projection GEMM (roofline `kv_cache_mode_gemm` / `standalone_*`);
+  - `encode_stage`: the ViT-g encode of the same 1024 frames -- on this build's own kernels (mra_vit_forward) and, beside
+    it, stock PyTorch -- timed separately (rank 0, N = 1; --no-encode skips it);
+  - `cpu_baseline`: the CPU oracle on a bounded sample, median of five passes (rank 0, N = 1; --cpu-clips 0 skips it).
 """
 from __future__ import annotations
 
@@ -65,7 +71,10 @@ def parse():
                          "finetune: BASELINE config 5 (Q-Former fwd + bwd + optimizer step, bf16, B = 1 x T = 20 per GPU; tools/bench_finetune.py's line)")
     ap.add_argument("--clips", type=int, default=32, help="clips per GPU")
     ap.add_argument("--text-len", type=int, default=32)
-    ap.add_argument("--cpu-clips", type=int, default=-1, help="clips in the CPU-baseline sample (0 = skip, -1 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own: the stand-alone K/V projection GEMM timing, "
+                         "the ViT-g encode stage and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--cpu-clips", type=int, default=-1, help="clips in the CPU-baseline sample of --full (0 = skip, -1 = auto)")
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
     ap.add_argument("--cross-mode", default="auto", choices=["auto", "kv_cache", "fold", "fold_stream", "fold384", "fold_rescale_pass"],
                     help="cross-attention formulation (auto = folded from Kv >= 2048; fold_stream / fold384: A/B variants)")
@@ -76,7 +85,7 @@ def parse():
                                                         "measured slower (6.72-6.87 vs 6.57 ms per step), although the folded block runs at 0.65 instead of 0.79 ms")
     ap.add_argument("--no-priority", action="store_true", help="A/B: same stream priority for both modalities")
     ap.add_argument("--no-kv-first", action="store_true", help="A/B: let the light modality start beside the heavy K/V projection")
-    ap.add_argument("--no-encode", action="store_true", help="skip the separately timed ViT-g encode stage")
+    ap.add_argument("--no-encode", action="store_true", help="skip the separately timed ViT-g encode stage of --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (fuse_score's arrays) as DIR/<name>.npy "
                          "(float32; spans float64; at most 64 MB, see dump_outputs); inputs and weights are seeded, so two builds compare output for output")
@@ -184,21 +193,24 @@ def main():
     value = n_total * args.steps / dt
     log(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step")
 
-    # ---- stand-alone timing of the K/V projection GEMM of the video Q-Former (the dominant kernel of the K/V-cache path; with the
-    #      folded path it is reported beside the block's roofline as kv_cache_mode_gemm) ----
-    enc = qf.modality_ln(feats["video"])
-    nb = int(lib.mra_kv_cache_bytes(qf._handle, n_local, kv["video"]))
-    cache = torch.empty(nb, dtype=torch.uint8, device=dev)
-    reps = 5
-    for _ in range(2):
-        _lib.check(lib.mra_kv_project(qf._handle, _lib.ptr(enc), n_local, kv["video"], _lib.ptr(cache), _lib.current_stream()), "kv_project")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()  # torch's current stream == the stream the launches go to
-    for _ in range(reps):
-        _lib.check(lib.mra_kv_project(qf._handle, _lib.ptr(enc), n_local, kv["video"], _lib.ptr(cache), _lib.current_stream()), "kv_project")
-    e1.record()
-    torch.cuda.synchronize()
-    kv_ms = e0.elapsed_time(e1) / reps
+    # ---- --full: stand-alone timing of the K/V projection GEMM of the video Q-Former (the dominant kernel of the K/V-cache path;
+    #      with the folded path it is reported beside the block's roofline as kv_cache_mode_gemm) ----
+    kv_ms = None
+    if args.full:
+        enc = qf.modality_ln(feats["video"])
+        nb = int(lib.mra_kv_cache_bytes(qf._handle, n_local, kv["video"]))
+        cache = torch.empty(nb, dtype=torch.uint8, device=dev)
+        reps = 5
+        for _ in range(2):
+            _lib.check(lib.mra_kv_project(qf._handle, _lib.ptr(enc), n_local, kv["video"], _lib.ptr(cache), _lib.current_stream()), "kv_project")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()  # torch's current stream == the stream the launches go to
+        for _ in range(reps):
+            _lib.check(lib.mra_kv_project(qf._handle, _lib.ptr(enc), n_local, kv["video"], _lib.ptr(cache), _lib.current_stream()), "kv_project")
+        e1.record()
+        torch.cuda.synchronize()
+        kv_ms = e0.elapsed_time(e1) / reps
+        del cache, enc
     ncross, H, E = 6, 768, ENC_WIDTH["video"]
     kv_flops = 2.0 * n_local * kv["video"] * E * (ncross * 2 * H)
     Q, R = 32, 12 * 32
@@ -215,7 +227,6 @@ def main():
     else:
         block_alg = block_exec = kv_flops
         achieved = kv_flops / (kv_step_ms * 1e-3) / 1e12  # priced on the in-step launches (timed region)
-    del cache, enc
 
     traffic = None
     pmc_file = os.path.join(ROOT, "profiles", "r02c_pmc_kvproj_p8.json")   # the eight-phase kernel; r01_pmc_kvproj_ws.json holds the loader-wave kernel's
@@ -236,17 +247,19 @@ def main():
     flops_step = sum(getattr(model, f"{m}_Qformer").flops(n_local, L, kv[m], True) for m in ("video", "audio"))   # reference formulation
     flops_exec = flops_step - (ncross * (block_alg - block_exec) if folded else 0.0)
 
-    # ---- the encode stage (row A1), timed SEPARATELY: EVA ViT-g over every frame of the step (mra_vit_forward, and stock PyTorch beside it) ----
+    # ---- --full: the encode stage (row A1), timed SEPARATELY: EVA ViT-g over every frame of the step (mra_vit_forward, and stock PyTorch beside it) ----
     encode = None
-    if rank == 0 and world == 1 and not args.no_encode and args.workload == "clip32x32":
+    if args.full and rank == 0 and world == 1 and not args.no_encode and args.workload == "clip32x32":
         encode = time_encode(dev, n_local, 32, dt / args.steps)
 
-    # ---- CPU baseline: the oracle (a CPU port of the same path) on a bounded sample ----
+    # ---- --full: CPU baseline: the oracle (a CPU port of the same path) on a bounded sample ----
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_clips != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_clips != 0:
         cpu = cpu_baseline(args, kv, L)
 
     if rank == 0:
+        kv_alone_ms = None if kv_ms is None else round(kv_ms, 4)
+        kv_alone_tflops = None if kv_ms is None else round(kv_flops / (kv_ms * 1e-3) / 1e12, 1)
         line = {
             "metric": "clips/s encode+fuse+score, 32-clip x 32-frame synthetic",
             "value": round(value, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -259,7 +272,7 @@ def main():
                              "32 items/GPU, reference item shape: video Kv=257 x1408 + audio Kv=256 x768, L=32; LN + 2 Q-Formers + score + span"),
                 "clips_per_gpu": n_local, "global_clips": n_total, "text_len": L, "kv_video": kv["video"], "kv_audio": kv["audio"],
                 "parallelism": f"clip-shard x{world}" + (" + RCCL all-gather of query embeddings" if world > 1 else ""),
-                "encoders": "not part of value (synthetic features stand in for ViT-g / BEATs outputs); the ViT-g encode of the same frames is timed separately under encode_stage",
+                "encoders": "not part of value (synthetic features stand in for ViT-g / BEATs outputs); with --full the ViT-g encode of the same frames is timed separately under encode_stage",
                 "weights": "synthetic BERT init, seed 0",
                 "cross_attention": "folded" if folded else "kv_cache", "cross_precision": args.cross_precision,
                 "modalities": "one grouped launch sequence (mra_qformer_forward_pair)" if (args.pair and args.cross_precision == "op" and args.cross_mode != "fold_stream") else "two forwards on two streams",
@@ -285,15 +298,15 @@ def main():
                           "hbm": None if not traffic else {"achieved": round(traffic / (kv_step_ms * 1e-3) / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                                                           "frac": round(traffic / (kv_step_ms * 1e-3) / 1e9 / 8000.0, 4)},
                           "kv_cache_mode_gemm": {"kernel": "gemm_p8_kernel<EPI_KV> (eight-phase 256x256x64; what --cross-mode kv_cache runs instead)",
-                                                 "standalone_launch_ms": round(kv_ms, 4),
-                                                 "standalone_tflops": round(kv_flops / (kv_ms * 1e-3) / 1e12, 1)}}
+                                                 "standalone_launch_ms": kv_alone_ms,
+                                                 "standalone_tflops": kv_alone_tflops} if kv_ms is not None else None}
                          if folded else
                          {"bound": "mfma", "kernel": "gemm_p8_kernel<EPI_KV> (eight-phase 256x256x64; K/V projection of all cross layers, video)",
                           "achieved": round(achieved, 1), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
                           "frac": round(achieved / PEAK_F16_TFLOPS, 4), "traffic": traffic,
                           "traffic_source": traffic_src,
                           "avg_launch_ms": round(kv_step_ms, 4), "flops_per_launch": kv_flops,
-                          "standalone_launch_ms": round(kv_ms, 4), "standalone_tflops": round(kv_flops / (kv_ms * 1e-3) / 1e12, 1)}),
+                          "standalone_launch_ms": kv_alone_ms, "standalone_tflops": kv_alone_tflops}),
             "cpu_baseline": cpu,
             "encode_stage": encode,
         }
