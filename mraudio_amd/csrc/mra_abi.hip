@@ -143,11 +143,44 @@ size_t layout_params(mra_qformer* h, char* base) {
   return cv.off;
 }
 
-// Workspace of one forward; with base == nullptr only measures.
+// How a forward runs its cross-attention layers: the one place that turns the handle's cross mode, with the precision and the probe the
+// caller asks for, into a form, its buffers (layout_cross) and its launches (cross_core).
+struct CrossPlan {
+  enum Form { KV_CACHE, FOLD, FOLD_STREAM } form;
+  bool precise;    // split precision: hi + lo pairs along the score chain (folded form)
+  bool probe;      // the probing forward of the automatic precision: the row-factor / rescale kernels write the p_max histograms
+  // the folded form on the batched GEMMs (FOLD):
+  bool kmajor;     // P . enc reads the encoder tokens themselves (K-major weights): no enc^T copy
+  bool softpart;   // scores on the 176 x 384 EPI_SOFTPART tile (otherwise fp32 scores + a row softmax)
+  bool inreg;      // with softpart: P . enc applies the row factors to its P~ fragments (otherwise a rescale pass over P)
+  int scores_tile, penc_tile;   // GemmProb::tile_cfg of the scores and the P . enc GEMMs
+};
+
+CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe) {
+  const mra_cfg& c = h->cfg;
+  const int R = c.heads * c.n_query;
+  CrossPlan x{};
+  x.precise = precise;
+  x.probe = probe;
+  // the folded form pays once the encoder sequence is long (fewer flops at any Kv, but five launches per layer); split precision and the
+  // probe run only in it.  The streaming kernels (fold_stream.hip): f16 operands, 384 (head, query) rows, E a multiple of 176
+  const bool fold = h->ncross > 0 && (precise || probe || h->cross_mode == 2 || (h->cross_mode == 0 && kv >= 2048));
+  const bool stream = fold && !precise && !probe && h->fold_stream && fold_stream_supported(R, c.enc_width, kv, fold_kvp(kv), h->op());
+  x.form = stream ? CrossPlan::FOLD_STREAM : fold ? CrossPlan::FOLD : CrossPlan::KV_CACHE;
+  x.kmajor = R == 384 && c.enc_width % 176 == 0;   // the 176 x 384 loader-wave tile: one workgroup per CU at E = 1408
+  x.softpart = R == 384;
+  x.inreg = (h->inreg_rescale || probe) && x.softpart && x.kmajor;
+  x.scores_tile = R == 384 ? 5 : 2;
+  x.penc_tile = x.kmajor ? 5 : (R == 384 ? h->fold_tile : 2);
+  return x;
+}
+
+// One lane's view of the workspace; with base == nullptr only measured.
 struct Work {
   float *hA32, *hB32, *pre32, *hC32, *part;
   char *hA16, *hB16, *qkv16, *ctx16, *qc16, *hC16, *ffn16, *kv16;
   char *encT, *qp16, *p16, *u16;   // folded cross-attention: enc^T [N][E][kvp], Q' [N][R][E], P [N][R][kvp], U [N][R][E]
+  char* qpb16;                     // streaming kernels: Q' in their blocked layout [N][R][E]
   char *hs16, *qs16;               // split-precision cross-attention: (hi | lo | hi) of the query rows [N*Q][3H] and of Q per head [N*Q][heads][192]
   float *qc32, *qp32;              // ... Q [N*Q][H] and Q' [N][R][E] in f32 (then Q' leaves as (hi | lo) rows [N][R][2E] in qp16)
   unsigned* lncnt;                 // fused residual + LayerNorm: one counter per 64-row tile and problem (zeroed at the start of a forward)
@@ -157,192 +190,194 @@ struct Work {
   float* gfac;                     // split softmax: row factors exp2(m_tile - m_row) / L as [N][ntiles][512] for the P . enc GEMM
   float *st_m, *st_l, *ginv;       // streaming kernels: statistics [N * R][stat_ld], 1 / L [N * R]
   char* gexp;                      // tile factors f16 [N * R][stat_ld]
-  int* hist;                       // probing forward of the automatic precision: p_max histograms [ncross][256] (nullptr otherwise)
   int nsplit;
-  size_t bytes;
 };
 
-// the layer chain's buffers for NN items (residual streams, QKV, attention context, feed-forward intermediate)
-void layout_chain(Carver& cv, Work& w, size_t NN, size_t S, size_t H, size_t I, size_t Q) {
-  w.hA32 = cv.take<float>(NN * S * H);
-  w.hB32 = cv.take<float>(NN * S * H);
-  w.pre32 = cv.take<float>(NN * S * H);
-  w.hC32 = cv.take<float>(NN * Q * H);
-  w.hA16 = cv.take<char>(NN * S * H, 2);
-  w.hB16 = cv.take<char>(NN * S * H, 2);
-  w.qkv16 = cv.take<char>(NN * S * 3 * H, 2);
-  w.ctx16 = cv.take<char>(NN * S * H, 2);
-  w.qc16 = cv.take<char>(NN * Q * H, 2);
-  w.hC16 = cv.take<char>(NN * Q * H, 2);
-  w.ffn16 = cv.take<char>(NN * S * I, 2);
+// One Q-Former of a forward: mra_qformer_forward runs one lane, mra_qformer_forward_pair two of equal shape.
+struct Lane {
+  mra_qformer* h;
+  const void* enc;
+  int kv;
+  CrossPlan plan;
+  const float* query;          // query tokens [1 or items][32][H] ...
+  long long query_stride;      // ... and their item stride (0: shared)
+  float *out_query, *out_full, *out_cls;
+  Work w;
+};
+
+// the layer chain's buffers for NN items (residual streams, QKV, attention context, feed-forward intermediate), seen from item n0 on
+void layout_chain(Carver& cv, Work& w, size_t NN, size_t n0, size_t S, size_t H, size_t I, size_t Q) {
+  auto f32 = [&](size_t per_item) { float* p = cv.take<float>(NN * per_item); return p ? p + n0 * per_item : p; };
+  auto op = [&](size_t per_item) { char* p = cv.take<char>(NN * per_item, 2); return p ? p + n0 * per_item * 2 : p; };
+  w.hA32 = f32(S * H);
+  w.hB32 = f32(S * H);
+  w.pre32 = f32(S * H);
+  w.hC32 = f32(Q * H);
+  w.hA16 = op(S * H);
+  w.hB16 = op(S * H);
+  w.qkv16 = op(S * 3 * H);
+  w.ctx16 = op(S * H);
+  w.qc16 = op(Q * H);
+  w.hC16 = op(Q * H);
+  w.ffn16 = op(S * I);
   w.lncnt_bytes = 2 * (NN * S / 64 + 2) * sizeof(unsigned);
   w.lncnt = cv.take<unsigned>(w.lncnt_bytes / sizeof(unsigned));
 }
 
-// one handle's cross-attention buffers for N items (K/V cache, or the folded form's Q' / P / U / statistics)
-void layout_cross(const mra_qformer* h, Carver& cv, Work& w, int N, int Kv) {
+// one lane's cross-attention buffers for N items (K/V cache, or the folded form's Q' / P / U / statistics)
+void layout_cross(const mra_qformer* h, const CrossPlan& x, Carver& cv, Work& w, int N, int Kv) {
   const mra_cfg& c = h->cfg;
-  const size_t H = c.hidden, Q = c.n_query;
-  w.kv16 = w.encT = w.qp16 = w.p16 = w.u16 = w.hs16 = w.qs16 = nullptr;
-  w.qc32 = w.qp32 = nullptr;
-  w.s32 = w.stat = w.gfac = w.st_m = w.st_l = w.ginv = nullptr;
-  w.gexp = nullptr;
-  w.hist = nullptr;
-  if (h->ncross > 0 && use_fold(h, Kv) && fold_streams(h, Kv)) {
-    const size_t E = c.enc_width, R = (size_t)c.heads * Q, kvp = fold_kvp(Kv), sld = fold_stream_stat_ld((int)kvp);
+  const size_t H = c.hidden, Q = c.n_query, E = c.enc_width, R = (size_t)c.heads * Q, kvp = fold_kvp(Kv);
+  if (x.form == CrossPlan::FOLD_STREAM) {
+    const size_t sld = fold_stream_stat_ld((int)kvp);
     w.qp16 = cv.take<char>((size_t)N * R * E, 2);
-    w.encT = cv.take<char>((size_t)N * R * E, 2);     // here: Q' in the streaming kernels' blocked layout
+    w.qpb16 = cv.take<char>((size_t)N * R * E, 2);
     w.st_m = cv.take<float>((size_t)N * R * sld);
     w.st_l = cv.take<float>((size_t)N * R * sld);
     w.gexp = cv.take<char>((size_t)N * R * sld, 2);
     w.ginv = cv.take<float>((size_t)N * R);
     w.p16 = cv.take<char>((size_t)N * R * kvp, 2);
     w.u16 = cv.take<char>((size_t)N * R * E, 2);
-  } else if (h->ncross > 0 && use_fold(h, Kv)) {
-    const size_t E = c.enc_width, R = (size_t)c.heads * Q, kvp = fold_kvp(Kv);
-    if (!fold_kmajor(h)) w.encT = cv.take<char>((size_t)N * E * kvp, 2);
-    w.qp16 = cv.take<char>((size_t)N * R * E * (h->cross_precise ? 2 : 1), 2);
-    if (h->cross_precise) {
+  } else if (x.form == CrossPlan::FOLD) {
+    if (!x.kmajor) w.encT = cv.take<char>((size_t)N * E * kvp, 2);
+    w.qp16 = cv.take<char>((size_t)N * R * E * (x.precise ? 2 : 1), 2);
+    if (x.precise) {
       w.hs16 = cv.take<char>((size_t)N * Q * 3 * H, 2);
       w.qs16 = cv.take<char>((size_t)N * Q * 3 * H, 2);
       w.qc32 = cv.take<float>((size_t)N * Q * H);
       w.qp32 = cv.take<float>((size_t)N * R * E);
     }
-    const bool split = R == 384 && h->sc_tile == 5 && h->split_softmax;   // then the scores never exist in fp32
-    if (!split) w.s32 = cv.take<float>((size_t)N * R * kvp);
+    if (!x.softpart) w.s32 = cv.take<float>((size_t)N * R * kvp);   // with softpart the scores never exist in fp32
     w.stat = cv.take<float>((size_t)2 * N * R * ((Kv + 175) / 176));
-    if (split && fold_inreg_rescale(h)) w.gfac = cv.take<float>((size_t)N * ((Kv + 175) / 176) * 512);
+    if (x.inreg) w.gfac = cv.take<float>((size_t)N * ((Kv + 175) / 176) * 512);
     w.p16 = cv.take<char>((size_t)N * R * kvp, 2);
     w.u16 = cv.take<char>((size_t)N * R * E, 2);
   } else {
     w.kv16 = cv.take<char>((size_t)h->ncross * 2 * N * Kv * H, 2);
   }
   w.nsplit = attn_pick_split(N, c.heads, (int)Q, Kv);
-  w.part = nullptr;
 }
 
-Work layout_work(const mra_qformer* h, char* base, int N, int L, int Kv) {
-  const mra_cfg& c = h->cfg;
+// The workspace of a forward over nl lanes of N items each; with base == nullptr only measures.  Returns its bytes.  The chain buffers hold
+// nl N items (lane 0's, then lane 1's), so attention cores and LayerNorms take every lane in one launch and each chain GEMM groups the lanes'
+// problems; behind them each lane's cross-attention buffers and grid-split attention partials, then (two lanes) the attention mask rows of both.
+size_t layout_lanes(Lane* lanes, int nl, char* base, int N, int L, long long** mask2 = nullptr) {
+  const mra_cfg& c = lanes[0].h->cfg;
+  const size_t S = (size_t)c.n_query + L;
   Carver cv(base);
-  Work w;
-  layout_chain(cv, w, (size_t)N, (size_t)c.n_query + L, c.hidden, c.inter, c.n_query);
-  layout_cross(h, cv, w, N, Kv);   // w.part: grid-split attention partials live right behind `bytes` (set by the caller)
-  w.bytes = cv.off;
-  return w;
-}
-
-// Pair forward: the layer chains of two Q-Formers of equal shape in ONE launch sequence.  The chain buffers hold 2 N items (lane 0's, then
-// lane 1's), so attention cores and LayerNorms take both lanes as one launch and every chain GEMM groups the lanes' problems; each lane
-// keeps its own cross-attention buffers.
-struct PairWork {
-  Work w[2];
-  long long* mask2;   // attention mask rows of both lanes [2 N][S]
-  size_t bytes;
-};
-
-PairWork layout_pair(const mra_qformer* h0, const mra_qformer* h1, char* base, int N, int L, int kv0, int kv1) {
-  const mra_cfg& c = h0->cfg;
-  const size_t H = c.hidden, I = c.inter, Q = c.n_query, S = Q + L;
-  Carver cv(base);
-  PairWork pw;
-  Work sh;
-  layout_chain(cv, sh, (size_t)2 * N, S, H, I, Q);
-  const mra_qformer* hs[2] = {h0, h1};
-  const int kvs[2] = {kv0, kv1};
-  for (int l = 0; l < 2; ++l) {
-    Work& w = pw.w[l];
-    w = sh;
-    const size_t n = (size_t)l * N;
-    w.hA32 = sh.hA32 ? sh.hA32 + n * S * H : nullptr; w.hB32 = sh.hB32 ? sh.hB32 + n * S * H : nullptr; w.pre32 = sh.pre32 ? sh.pre32 + n * S * H : nullptr;
-    w.hC32 = sh.hC32 ? sh.hC32 + n * Q * H : nullptr;
-    w.hA16 = sh.hA16 ? sh.hA16 + n * S * H * 2 : nullptr; w.hB16 = sh.hB16 ? sh.hB16 + n * S * H * 2 : nullptr;
-    w.qkv16 = sh.qkv16 ? sh.qkv16 + n * S * 3 * H * 2 : nullptr; w.ctx16 = sh.ctx16 ? sh.ctx16 + n * S * H * 2 : nullptr;
-    w.qc16 = sh.qc16 ? sh.qc16 + n * Q * H * 2 : nullptr; w.hC16 = sh.hC16 ? sh.hC16 + n * Q * H * 2 : nullptr;
-    w.ffn16 = sh.ffn16 ? sh.ffn16 + n * S * I * 2 : nullptr;
-    layout_cross(hs[l], cv, w, N, kvs[l]);
-    float* part = cv.take<float>(attn_partial_bytes(N, c.heads, (int)Q, w.nsplit) / sizeof(float) + 64);
-    w.part = w.nsplit > 1 ? part : nullptr;
-    w.bytes = 0;
+  const Carver chain = cv;
+  for (int l = 0; l < nl; ++l) {
+    lanes[l].w = Work{};
+    cv = chain;
+    layout_chain(cv, lanes[l].w, (size_t)nl * N, (size_t)l * N, S, c.hidden, c.inter, c.n_query);
   }
-  pw.mask2 = cv.take<long long>((size_t)2 * N * S);
-  pw.bytes = cv.off;
-  return pw;
+  for (int l = 0; l < nl; ++l) {
+    Work& w = lanes[l].w;
+    layout_cross(lanes[l].h, lanes[l].plan, cv, w, N, lanes[l].kv);
+    // (the two-lane layout has always kept 64 floats of slack behind each lane's partials)
+    float* part = cv.take<float>(attn_partial_bytes(N, c.heads, c.n_query, w.nsplit) / sizeof(float) + (nl > 1 ? 64 : 0));
+    w.part = w.nsplit > 1 ? part : nullptr;
+  }
+  long long* m2 = nl > 1 ? cv.take<long long>((size_t)nl * N * S) : nullptr;
+  if (mask2) *mask2 = m2;
+  return cv.off;
 }
 
-// Steps 6 / 6a-6e of one cross-attention layer: from the query projection Q (w.qc16, or w.qc32 in split precision) to the attention
-// context (w.ctx16 [N*Q][H]) -- the folded form (per-head Q' GEMM, scores + split softmax, P . enc, per-head context GEMM) or the core over the
-// head-major K/V cache.  Shared by mra_qformer_forward and mra_qformer_forward_pair.
-int cross_core(mra_qformer* h, const Work& w, const LayerW& Lw, const void* enc, int N, int kv, bool fold, bool stream_fold, bool precise,
-               hipStream_t stream) {
+// a lane of handle h over the encoder tokens enc (kv per item), its cross-attention planned for (precise, probe), no outputs yet
+Lane make_lane(mra_qformer* h, const void* enc, int kv, bool precise, bool probe) {
+  Lane x{};
+  x.h = h;
+  x.enc = enc;
+  x.kv = kv;
+  x.plan = cross_plan(h, kv, precise, probe);
+  x.query = h->query;
+  return x;
+}
+
+// workspace of a single-lane forward
+size_t work_bytes(Lane x, int N, int L) { return layout_lanes(&x, 1, nullptr, N, L); }
+
+// Steps 6 / 6a-6e of one cross-attention layer of one lane: from the query projection Q (w.qc16, or w.qc32 in split precision) to the
+// attention context (w.ctx16 [N*Q][H]) -- the folded form (per-head Q' GEMM, scores + split softmax, P . enc, per-head context GEMM) or the
+// core over the head-major K/V cache.
+int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
+  const mra_qformer* h = lane.h;
+  const CrossPlan& x = lane.plan;
+  const Work& w = lane.w;
+  const void* enc = lane.enc;
+  const int kv = lane.kv;
   const mra_cfg& c = h->cfg;
   const int Q = c.n_query, H = c.hidden, E = c.enc_width, R = c.heads * Q, kvp = fold_kvp(kv), op = h->op();
   const size_t esz = 2;
   const RowView qc_rows = plain(N * Q, H);
+  const int ci = Lw.cross_index;
   int rc = 0;
-  if (fold) {
-    const int ci = Lw.cross_index;
-    const bool timed = ci == 0 && h->kv_ev0 && h->kv_ev1;
-    if (timed) (void)hipEventRecord(h->kv_ev0, stream);
-    // 6a. Q' = Q_h W_k,h per head: [N*32, 64] x [E, 64]^T -> Q' [N][head*32 + q][E]
-    GemmProb d{};
-    if (precise) {
-      // Q (fp32) per head as (hi | lo | hi) over its 64 dims against W_k,h as (hi | hi | lo): K = 192; Q' in fp32, then as (hi | lo) rows
-      rc = launch_split_rows(w.qc32, qc_rows, N * Q, H, 64, 3, w.qs16, op, stream);
-      if (rc) return chk(rc, "split cross query");
-      d.A = w.qs16; d.a = plain(N * Q, 3 * H); d.a_bs = 192;
-      d.W = h->arena_p + (size_t)ci * precise_layer_bytes(h) + precise_wk_off(h); d.w_bs = (long long)E * 192;
-      d.C = w.qp32; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * 4;
-      d.M = N * Q; d.N = E; d.K = 192; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? 2 : 1;
-      rc = launch_gemm(&d, 1, EPI_F32, op, stream);
-      if (rc) return chk(rc, "fold q' gemm (split precision)");
-      rc = launch_split_rows(w.qp32, plain(N * R, E), N * R, E, E, 2, w.qp16, op, stream);
-      if (rc) return chk(rc, "split q'");
-    } else {
+  if (x.form == CrossPlan::KV_CACHE) {
+    // 6. cross-attention core over the head-major K/V cache
+    rc = launch_attention(kv_cross_attn_args(c, w.qc16, w.kv16, ci, w.ctx16, N, kv, w.nsplit, w.part), op, stream);
+    return rc ? chk(rc, "cross attention") : MRA_OK;
+  }
+  const bool timed = ci == 0 && h->kv_ev0 && h->kv_ev1;
+  if (timed) (void)hipEventRecord(h->kv_ev0, stream);
+  int* hist = x.probe ? h->auto_hist + (size_t)ci * 256 : nullptr;
+  // 6a. Q' = Q_h W_k,h per head: [N*32, 64] x [E, 64]^T -> Q' [N][head*32 + q][E]
+  GemmProb d{};
+  if (x.precise) {
+    // Q (fp32) per head as (hi | lo | hi) over its 64 dims against W_k,h as (hi | hi | lo): K = 192; Q' in fp32, then as (hi | lo) rows
+    rc = launch_split_rows(w.qc32, qc_rows, N * Q, H, 64, 3, w.qs16, op, stream);
+    if (rc) return chk(rc, "split cross query");
+    d.A = w.qs16; d.a = plain(N * Q, 3 * H); d.a_bs = 192;
+    d.W = h->arena_p + (size_t)ci * precise_layer_bytes(h) + precise_wk_off(h); d.w_bs = (long long)E * 192;
+    d.C = w.qp32; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * 4;
+    d.M = N * Q; d.N = E; d.K = 192; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? 2 : 1;
+    rc = launch_gemm(&d, 1, EPI_F32, op, stream);
+    if (rc) return chk(rc, "fold q' gemm (split precision)");
+    rc = launch_split_rows(w.qp32, plain(N * R, E), N * R, E, E, 2, w.qp16, op, stream);
+    if (rc) return chk(rc, "split q'");
+  } else {
     d.A = w.qc16; d.a = qc_rows; d.a_bs = 64;
     d.W = h->arena_f + (size_t)ci * H * E * esz; d.w_bs = (long long)E * 64;
     d.C = w.qp16; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * esz;
     d.M = N * Q; d.N = E; d.K = 64; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? 2 : 1;
     rc = launch_gemm(&d, 1, EPI_OP, op, stream);
     if (rc) return chk(rc, "fold q' gemm");
-    }
-    if (stream_fold) {
-      // 6b-6d on the streaming kernels (fold_stream.hip): P~ = exp2(s - ceil(tile max)) + tile statistics, row statistics,
-      // U = (1 / L) sum g P~ enc with the power-of-two tile factors applied in registers.  P~ is written once, read once.
-      FoldStreamArgs fs{};
-      fs.qp = w.qp16; fs.qpb = w.encT; fs.enc = enc; fs.p = w.p16; fs.u = w.u16;
-      fs.stat_m = w.st_m; fs.stat_l = w.st_l; fs.gexp = w.gexp; fs.ginv = w.ginv;
-      fs.items = N; fs.kv = kv; fs.kvp = kvp; fs.E = E;
-      fs.alpha = 0.125f * 1.4426950408889634f; fs.phase = 3;
-      rc = launch_fold_stream(fs, stream);
-      if (rc) return chk(rc, "fold scores / P.enc (streaming kernels)");
-    } else {
+  }
+  if (x.form == CrossPlan::FOLD_STREAM) {
+    // 6b-6d on the streaming kernels (fold_stream.hip): P~ = exp2(s - ceil(tile max)) + tile statistics, row statistics,
+    // U = (1 / L) sum g P~ enc with the power-of-two tile factors applied in registers.  P~ is written once, read once.
+    FoldStreamArgs fs{};
+    fs.qp = w.qp16; fs.qpb = w.qpb16; fs.enc = enc; fs.p = w.p16; fs.u = w.u16;
+    fs.stat_m = w.st_m; fs.stat_l = w.st_l; fs.gexp = w.gexp; fs.ginv = w.ginv;
+    fs.items = N; fs.kv = kv; fs.kvp = kvp; fs.E = E;
+    fs.alpha = 0.125f * 1.4426950408889634f; fs.phase = 3;
+    rc = launch_fold_stream(fs, stream);
+    if (rc) return chk(rc, "fold scores / P.enc (streaming kernels)");
+  } else {
     // 6b. scores S[n] = Q'[n] enc[n]^T: [R, E] x [kv, E]^T per item, rows padded to kvp columns
     GemmProb sc{};
     sc.A = w.qp16; sc.a = plain(R, E); sc.a_bs = (long long)R * E;
     sc.W = enc; sc.w_bs = (long long)kv * E;
     sc.M = R; sc.N = kv; sc.K = E; sc.batch = N; sc.n_ragged = 1;
-    if (precise) {   // Q' rows are (hi | lo): two passes over the same encoder slab inside one K loop
+    if (x.precise) {   // Q' rows are (hi | lo): two passes over the same encoder slab inside one K loop
       sc.a = plain(R, 2 * E); sc.a_bs = (long long)R * 2 * E; sc.K = 2 * E; sc.w_kwrap = E / 64;
     }
-    sc.tile_cfg = (R == 384 && h->sc_tile == 5) ? 5 : (R == 384 ? h->fold_tile : 2);
-    if (sc.tile_cfg == 5 && h->split_softmax) {
+    sc.tile_cfg = x.scores_tile;
+    const int ntiles = (kv + 175) / 176;
+    if (x.softpart) {
       // 6b + 6c fused: the GEMM's epilogue leaves exp2(s - tile maximum) in the operand dtype plus tile statistics;
       // one pass over P rescales every row by exp2(m_tile - m_row) / sum.  The scores never exist in fp32 in HBM.
-      const int ntiles = (kv + 175) / 176;
       sc.C = w.p16; sc.c = plain(R, kvp); sc.c_bs_bytes = (long long)R * kvp * esz;
       sc.alpha = 0.125f * 1.4426950408889634f;
       sc.stat_m = w.stat; sc.stat_l = w.stat + (size_t)N * R * ntiles;
       rc = launch_gemm(&sc, 1, EPI_SOFTPART, op, stream);
       if (rc) return chk(rc, "fold scores gemm (softmax partials)");
-      if (w.gfac) {
+      if (x.inreg) {
         // second half of the softmax without a pass over P: only the row factors are computed here, the P . enc GEMM applies them
         // to its P~ fragments in registers (same arithmetic, same rounding as the rescale pass)
-        rc = launch_fold_rowfactor(sc.stat_m, sc.stat_l, w.gfac, N * R, R, ntiles, w.p16, kvp, 176, kvp, stream,
-                                   w.hist ? w.hist + (size_t)ci * 256 : nullptr);
+        rc = launch_fold_rowfactor(sc.stat_m, sc.stat_l, w.gfac, N * R, R, ntiles, w.p16, kvp, 176, kvp, stream, hist);
         if (rc) return chk(rc, "fold row factors");
       } else {
-        rc = launch_softmax_rescale(w.p16, kvp, sc.stat_m, sc.stat_l, N * R, ntiles, 176, kvp, op, stream,
-                                    w.hist ? w.hist + (size_t)ci * 256 : nullptr);
+        rc = launch_softmax_rescale(w.p16, kvp, sc.stat_m, sc.stat_l, N * R, ntiles, 176, kvp, op, stream, hist);
         if (rc) return chk(rc, "fold softmax rescale");
       }
     } else {
@@ -356,49 +391,30 @@ int cross_core(mra_qformer* h, const Work& w, const LayerW& Lw, const void* enc,
     // 6d. U[n] = P[n] enc[n]: [R, kvp] x [E, kvp]^T per item
     GemmProb pv{};
     pv.A = w.p16; pv.a = plain(R, kvp); pv.a_bs = (long long)R * kvp;
-    if (fold_kmajor(h)) {   // the encoder tokens themselves: [kv][E] is W K-major; rows kv .. kvp repeat the last token against P = 0
+    if (x.kmajor) {   // the encoder tokens themselves: [kv][E] is W K-major; rows kv .. kvp repeat the last token against P = 0
       pv.W = enc; pv.w_bs = (long long)kv * E; pv.w_ld = E; pv.k_rows = kv;
     } else {
       pv.W = w.encT; pv.w_bs = (long long)E * kvp;
     }
     pv.C = w.u16; pv.c = plain(R, E); pv.c_bs_bytes = (long long)R * E * esz;
     pv.M = R; pv.N = E; pv.K = kvp; pv.batch = N;
-    pv.tile_cfg = (R == 384 && E % 176 == 0 && h->pv_tile == 5) ? 5 : (R == 384 ? h->fold_tile : 2);
-    if (w.gfac && sc.tile_cfg == 5 && h->split_softmax) { pv.pscale = w.gfac; pv.ps_ntiles = (kv + 175) / 176; }
+    pv.tile_cfg = x.penc_tile;
+    if (x.inreg) { pv.pscale = w.gfac; pv.ps_ntiles = ntiles; }
     rc = launch_gemm(&pv, 1, EPI_OP, op, stream);
     if (rc) return chk(rc, "fold p.enc gemm");
-    }
-    // 6e. context = U_h W_v,h^T + b_v,h per head: [N*32, E] x [64, E]^T -> ctx [N*32][head*64 + d]
-    GemmProb cx{};
-    cx.A = w.u16; cx.a = items_view((long long)R * E, Q, E); cx.a_bs = (long long)Q * E;
-    cx.W = (const char*)h->wkv + (size_t)(ci * 2 + 1) * H * E * esz; cx.w_bs = (long long)64 * E;
-    cx.bias = h->bkv + (size_t)(ci * 2 + 1) * H; cx.bias_bs = 64;
-    cx.C = w.ctx16; cx.c = qc_rows; cx.c_bs_bytes = 64 * esz;
-    cx.M = N * Q; cx.N = 64; cx.K = E; cx.batch = c.heads; cx.tile_cfg = E % 128 == 0 && N * Q >= 512 ? 6 : 1;
-    rc = launch_gemm(&cx, 1, EPI_OP, op, stream);
-    if (rc) return chk(rc, "fold context gemm");
-    if (timed) (void)hipEventRecord(h->kv_ev1, stream);
-  } else {
-  // 6. cross-attention core over the head-major K/V cache
-  AttnArgs a{};
-  const size_t per_sel = (size_t)N * c.heads * kv * 64;
-  a.Q = w.qc16;
-  a.K = w.kv16 + (size_t)(Lw.cross_index * 2 + 0) * per_sel * esz;
-  a.V = w.kv16 + (size_t)(Lw.cross_index * 2 + 1) * per_sel * esz;
-  a.O = w.ctx16;
-  a.q_item_stride = (long long)Q * H; a.q_ld = H;
-  a.k_item_stride = (long long)c.heads * kv * 64; a.k_head_stride = (long long)kv * 64; a.k_ld = 64;
-  a.v_item_stride = a.k_item_stride; a.v_head_stride = a.k_head_stride; a.v_ld = 64;
-  a.o_item_stride = (long long)Q * H; a.o_ld = H;
-  a.mask = nullptr; a.mask_ld = 0;
-  a.items = N; a.heads = c.heads; a.q_rows = Q; a.kv_len = kv;
-  a.scale = 0.125f; a.nsplit = w.nsplit; a.part = w.part;
-  rc = launch_attention(a, op, stream);
-  if (rc) return chk(rc, "cross attention");
   }
+  // 6e. context = U_h W_v,h^T + b_v,h per head: [N*32, E] x [64, E]^T -> ctx [N*32][head*64 + d]
+  GemmProb cx{};
+  cx.A = w.u16; cx.a = items_view((long long)R * E, Q, E); cx.a_bs = (long long)Q * E;
+  cx.W = (const char*)h->wkv + (size_t)(ci * 2 + 1) * H * E * esz; cx.w_bs = (long long)64 * E;
+  cx.bias = h->bkv + (size_t)(ci * 2 + 1) * H; cx.bias_bs = 64;
+  cx.C = w.ctx16; cx.c = qc_rows; cx.c_bs_bytes = 64 * esz;
+  cx.M = N * Q; cx.N = 64; cx.K = E; cx.batch = c.heads; cx.tile_cfg = E % 128 == 0 && N * Q >= 512 ? 6 : 1;
+  rc = launch_gemm(&cx, 1, EPI_OP, op, stream);
+  if (rc) return chk(rc, "fold context gemm");
+  if (timed) (void)hipEventRecord(h->kv_ev1, stream);
   return MRA_OK;
 }
-
 
 }  // namespace
 
@@ -584,28 +600,13 @@ int mra_modality_ln(mra_qformer* h, const void* x, int32_t x_dtype, const int64_
              "modality_ln");
 }
 
-namespace {
-size_t workspace_in_force(const mra_qformer* h, int items, int L, int kv) {
-  Work w = layout_work(h, nullptr, items, L, kv);
-  return w.bytes + align_up(attn_partial_bytes(items, h->cfg.heads, h->cfg.n_query, w.nsplit));
-}
-}  // namespace
-
 size_t mra_qformer_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
   if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
-  if (!h->cross_auto || h->probe_fold) return workspace_in_force(h, items, L, kv);
-  // automatic precision: the largest of the op form in force, the probing forward's op-precision folded form and split precision, so
-  // neither the probe nor its resolution ever needs a larger workspace
-  const int precise = h->cross_precise;
-  h->cross_precise = 0;
-  size_t need = workspace_in_force(h, items, L, kv);
-  h->probe_fold = true;
-  need = std::max(need, workspace_in_force(h, items, L, kv));
-  h->probe_fold = false;
-  h->cross_precise = 1;
-  need = std::max(need, workspace_in_force(h, items, L, kv));
-  h->cross_precise = precise;
-  return need;
+  if (!h->cross_auto) return work_bytes(make_lane(h, nullptr, kv, h->cross_precise, false), items, L);
+  // automatic precision: the largest of op, the probing forward's op-precision folded form and split precision, so neither the probe nor
+  // its resolution ever needs a larger workspace
+  return std::max({work_bytes(make_lane(h, nullptr, kv, false, false), items, L), work_bytes(make_lane(h, nullptr, kv, false, true), items, L),
+                   work_bytes(make_lane(h, nullptr, kv, true, false), items, L)});
 }
 
 double mra_qformer_flops(mra_qformer* h, int32_t items, int32_t L, int32_t kv, int32_t with_last_text) {
@@ -619,10 +620,298 @@ double mra_qformer_flops(mra_qformer* h, int32_t items, int32_t L, int32_t kv, i
 }
 
 namespace {
-// mra_qformer_forward in the precision and form in force (the probing forward of the automatic precision sets them around it)
-int forward_run(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const float* query_embeds, int32_t query_items,
-                const void* enc, int32_t items, int32_t L, int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
-                size_t workspace_bytes, void* stream_) {
+// every parameter loaded, except the optional modality LayerNorm (ln.*) and LLM projection (llm_proj.*)
+int check_loaded(mra_qformer* h) {
+  char names[256];
+  const int miss = mra_qformer_missing(h, names, sizeof(names));
+  int tolerated = 0;
+  for (const char* opt : {"ln.weight", "ln.bias", "llm_proj.weight", "llm_proj.bias"}) {
+    auto it = h->params.find(opt);
+    if (it != h->params.end() && !it->second.loaded) ++tolerated;
+  }
+  return miss > tolerated ? fail(MRA_ESTATE, std::string("parameters not loaded: ") + names) : MRA_OK;
+}
+
+// The Q-Former forward of nl lanes (1: mra_qformer_forward, 2: mra_qformer_forward_pair) of N items with L text rows: embeddings, the
+// layers, the last layer's LayerNorms into the lanes' outputs.  A grouped launch holds the query problems of every lane, then their text
+// problems.  Split precision, out_full, query_embeds and the fused residual + LayerNorm (chain_ring bit 3) are single-lane only.
+int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* attention_mask, int N, int L, void* workspace, hipStream_t stream) {
+  const mra_qformer* h = lanes[0].h;   // the lanes agree in hidden / heads / inter / layers / cross_freq / n_query / op dtype / ln_eps
+  const mra_cfg& c = h->cfg;
+  const bool pair = nl == 2;
+  const int Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter;
+  const int op = h->op();
+  long long* mask2 = nullptr;
+  layout_lanes(lanes, nl, (char*)workspace, N, L, &mask2);
+  const Work& w = lanes[0].w;   // the chain buffers of every lane, lane 0's first
+  const long long SH = (long long)S * H;
+  const size_t esz = 2;
+
+  // row views of the [N, S, H] streams
+  const RowView all_rows = plain(N * S, H), all_lanes = plain(nl * N * S, H);
+  const RowView q_view = items_view(SH, Q, H);              // rows [:, :32]
+  const RowView t_view = items_view(SH, L > 0 ? L : 1, H);  // rows [:, 32:] (base pointer + 32*H)
+  const RowView cls_view = items_view(SH, 1, H);            // row  [:, 32]
+  const RowView qc_rows = plain(N * Q, H);                  // compact [N*32, H]
+  const size_t t_off16 = (size_t)Q * H * esz;               // byte offset of row 32 inside an item (op dtype)
+  const size_t t_off32 = (size_t)Q * H;                     // element offset (f32)
+
+  // residual projection + LayerNorm in ONE launch (chain_ring bit 3, on the 96 x 64 ring tile): its per-row-tile counters start at zero
+  const bool ln_fuse = !pair && (h->chain_ring & 12) == 12 && H % 96 == 0 && H % 256 == 0 && H <= 1024;
+  int rc;
+  for (int l = 0; l < nl; ++l) {
+    Lane& x = lanes[l];
+    mra_qformer* hl = x.h;
+    rc = launch_embed_ln((const long long*)input_ids, N, L, Q, H, hl->cfg.vocab, x.query, x.query_stride, hl->word, hl->pos, hl->embg, hl->embb,
+                         c.ln_eps, x.w.hA32, x.w.hA16, nullptr, op, stream);
+    if (rc) return chk(rc, "embed_ln");
+    if (ln_fuse) HIP_TRY(hipMemsetAsync(w.lncnt, 0, w.lncnt_bytes, stream));
+    if (x.plan.form != CrossPlan::KV_CACHE) {
+      // folded cross-attention: enc^T per item (the K-contiguous operand of P . enc), key weights regrouped per head
+      if (x.plan.form == CrossPlan::FOLD && !x.plan.kmajor) {
+        const int E = hl->cfg.enc_width, kvp = fold_kvp(x.kv);
+        rc = launch_transpose_pad(x.enc, x.w.encT, x.kv, E, kvp, (long long)x.kv * E, (long long)E * kvp, N, op, stream);
+        if (rc) return chk(rc, "enc transpose");
+      }
+      if ((rc = mra_qformer_prepare(hl, stream))) return rc;
+    } else if (hl->ncross > 0) {
+      // K/V of every cross layer in one GEMM, scattered head-major
+      const bool timed = !pair && hl->kv_ev0 && hl->kv_ev1;
+      if (timed) (void)hipEventRecord(hl->kv_ev0, stream);
+      rc = kv_project(hl, x.enc, N, x.kv, x.w.kv16, stream);
+      if (rc) return chk(rc, "kv projection gemm");
+      if (timed) (void)hipEventRecord(hl->kv_ev1, stream);
+    }
+    if (!pair && hl->kv_done) (void)hipEventRecord(hl->kv_done, stream);   // also without cross layers: the waiter must not hang
+  }
+  const long long* mask = (const long long*)attention_mask;
+  if (pair && mask) {   // the two lanes share the prompt: their mask rows one after the other for the 2 N-item attention launch
+    HIP_TRY(hipMemcpyAsync(mask2, mask, (size_t)N * S * 8, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(mask2 + (size_t)N * S, mask, (size_t)N * S * 8, hipMemcpyDeviceToDevice, stream));
+    mask = mask2;
+  }
+
+  const bool want_text_last = lanes[0].out_full != nullptr;
+  bool want_cls_last = false;
+  for (int l = 0; l < nl; ++l) want_cls_last |= !want_text_last && lanes[l].out_cls;
+
+  // Tile choice: the grouped launch runs the tile of its first problem.  The QKV and attention-output problems each take their own lane's
+  // chain_ring mask, the feed-forward launches lane 0's.
+  for (int i = 0; i < c.layers; ++i) {
+    // Lw[l]: lane l's weights; the LayerNorm launches take lane 1's parameters from Lw[1] (lane 0's own in a single-lane forward, where
+    // no row reaches lane_rows)
+    const LayerW* Lw[2] = {&lanes[0].h->layers[i], &lanes[nl - 1].h->layers[i]};
+    const bool last = i == c.layers - 1;
+    // 1. fused Q|K|V projection of all S rows
+    {
+      GemmProb p[2] = {};
+      for (int l = 0; l < nl; ++l) {
+        p[l].A = lanes[l].w.hA16; p[l].a = all_rows;
+        p[l].W = Lw[l]->wqkv; p[l].bias = Lw[l]->bqkv;
+        p[l].C = lanes[l].w.qkv16; p[l].c = plain(N * S, 3 * H);
+        p[l].M = N * S; p[l].N = 3 * H; p[l].K = H;
+        // The chain GEMMs at ~1-2 k rows are bound by the operand bytes each CU pulls through its load path (~33 B / clk from L2),
+        // not by tile count: 128 x 128 tiles (288 of them) move half the bytes per flop of the 1152 64 x 64 tiles the automatic
+        // choice makes (headline step 6.75 -> 6.67 ms, reference item shape 2.65 -> 2.55 ms together with the down-projection below)
+        p[l].tile_cfg = N * S >= 1024 ? 2 : 0;
+        // ... and at ~2 k rows the ring kernel's 144 x 128 tile is exactly one workgroup per CU (2048 x 2304 = 16 x 16 tiles): 14.4 vs 17.6 us stand-alone
+        if ((lanes[l].h->chain_ring & 1) && N * S >= 1024 && (3 * H) % 144 == 0) p[l].tile_cfg = 9;
+      }
+      rc = launch_gemm(p, nl, EPI_OP, op, stream);
+      if (rc) return chk(rc, "qkv gemm");
+    }
+    // 2. self-attention core of all nl N items
+    rc = launch_attention(self_attn_args(c, w.qkv16, w.ctx16, mask, nl * N, S), op, stream);
+    if (rc) return chk(rc, "self attention");
+    // 3. output projection + residual, 4. LayerNorm -> hB
+    {
+      GemmProb p[2] = {};
+      for (int l = 0; l < nl; ++l) {
+        p[l].A = lanes[l].w.ctx16; p[l].a = all_rows;
+        p[l].W = Lw[l]->wo; p[l].bias = Lw[l]->bo;
+        p[l].R = lanes[l].w.hA32; p[l].r = all_rows;
+        p[l].C = lanes[l].w.pre32; p[l].c = all_rows;
+        p[l].M = N * S; p[l].N = H; p[l].K = H;
+        if ((lanes[l].h->chain_ring & 4) && N * S >= 1024 && H % 96 == 0) p[l].tile_cfg = 11;
+      }
+      if (ln_fuse && p[0].tile_cfg == 11) {
+        // HF:519-530 in one launch: the column tile of a 64-row block that finishes last normalises the block's rows
+        p[0].ln_gain = Lw[0]->ln1g; p[0].ln_bias = Lw[0]->ln1b; p[0].ln_eps = c.ln_eps;
+        p[0].ln_y32 = w.hB32; p[0].ln_y32v = all_rows; p[0].ln_y16 = w.hB16; p[0].ln_y16v = all_rows; p[0].ln_counter = w.lncnt;
+        rc = launch_gemm(p, 1, EPI_RES_LN, op, stream);
+        if (rc) return chk(rc, "attn out gemm + ln");
+      } else {
+        rc = launch_gemm(p, nl, EPI_RES_F32, op, stream);
+        if (rc) return chk(rc, "attn out gemm");
+        rc = launch_ln_rows4(w.pre32, all_lanes, nl * N * S, H, Lw[0]->ln1g, Lw[0]->ln1b, nullptr, nullptr, N * S, Lw[1]->ln1g, Lw[1]->ln1b, nullptr,
+                             nullptr, 1, 1, c.ln_eps, w.hB32, all_lanes, w.hB16, all_lanes, op, stream);
+        if (rc) return chk(rc, "attn ln");
+      }
+    }
+    // query-side state entering the feed-forward: hB[:, :32] or the cross-attention output hC
+    const bool cross = Lw[0]->cross_index >= 0;
+    const RowView fqv = cross ? qc_rows : q_view;
+    if (cross) {
+      // 5. cross query projection
+      if (lanes[0].plan.precise) {
+        // split precision: the fp32 query rows leave as (hi | lo | hi), the weight is stored as (hi | hi | lo): one GEMM over K = 3H
+        // computes xh wh + xl wh + xh wl in the fp32 accumulators; Q stays fp32
+        rc = launch_split_rows(w.hB32, q_view, N * Q, H, H, 3, w.hs16, op, stream);
+        if (rc) return chk(rc, "split query rows");
+        GemmProb p{};
+        p.A = w.hs16; p.a = plain(N * Q, 3 * H);
+        p.W = h->arena_p + (size_t)Lw[0]->cross_index * precise_layer_bytes(h); p.bias = Lw[0]->bcq;
+        p.C = w.qc32; p.c = qc_rows;
+        p.M = N * Q; p.N = H; p.K = 3 * H;
+        rc = launch_gemm(&p, 1, EPI_F32, op, stream);
+      } else {
+        GemmProb p[2] = {};
+        for (int l = 0; l < nl; ++l) {
+          p[l].A = lanes[l].w.hB16; p[l].a = q_view;
+          p[l].W = Lw[l]->wcq; p[l].bias = Lw[l]->bcq;
+          p[l].C = lanes[l].w.qc16; p[l].c = qc_rows;
+          p[l].M = N * Q; p[l].N = H; p[l].K = H;
+        }
+        rc = launch_gemm(p, nl, EPI_OP, op, stream);
+      }
+      if (rc) return chk(rc, "cross q gemm");
+      // 6. each lane's own cross-attention
+      for (int l = 0; l < nl; ++l)
+        if ((rc = cross_core(lanes[l], *Lw[l], N, stream))) return rc;
+      // 7. output projection + residual (hB[:, :32]), 8. LayerNorm -> hC (compact)
+      GemmProb o[2] = {};
+      for (int l = 0; l < nl; ++l) {
+        o[l].A = lanes[l].w.ctx16; o[l].a = qc_rows;
+        o[l].W = Lw[l]->wco; o[l].bias = Lw[l]->bco;
+        o[l].R = lanes[l].w.hB32; o[l].r = q_view;
+        o[l].C = lanes[l].w.pre32; o[l].c = qc_rows;
+        o[l].M = N * Q; o[l].N = H; o[l].K = H;
+      }
+      if (ln_fuse && N * Q >= 512) {
+        o[0].tile_cfg = 11;
+        o[0].ln_gain = Lw[0]->lncg; o[0].ln_bias = Lw[0]->lncb; o[0].ln_eps = c.ln_eps;
+        o[0].ln_y32 = w.hC32; o[0].ln_y32v = qc_rows; o[0].ln_y16 = w.hC16; o[0].ln_y16v = qc_rows; o[0].ln_counter = w.lncnt;
+        rc = launch_gemm(o, 1, EPI_RES_LN, op, stream);
+        if (rc) return chk(rc, "cross out gemm + ln");
+      } else {
+        rc = launch_gemm(o, nl, EPI_RES_F32, op, stream);
+        if (rc) return chk(rc, "cross out gemm");
+        // each lane's compact [N*Q][H] rows start at its own pre32, N*S*H floats apart: one row view with an item per lane
+        const RowView pre_v = items_view((long long)N * S * H, N * Q, H), qc_lanes = plain(nl * N * Q, H);
+        rc = launch_ln_rows4(w.pre32, pre_v, nl * N * Q, H, Lw[0]->lncg, Lw[0]->lncb, nullptr, nullptr, N * Q, Lw[1]->lncg, Lw[1]->lncb, nullptr, nullptr,
+                             1, 1, c.ln_eps, w.hC32, qc_lanes, w.hC16, qc_lanes, op, stream);
+        if (rc) return chk(rc, "cross ln");
+      }
+    }
+    // 9-14. feed-forwards: the query problems of every lane, then their text problems (own weights)
+    int text_rows = 0;
+    RowView tv = t_view;
+    if (L > 0) {
+      if (!last || want_text_last) text_rows = N * L;
+      else if (want_cls_last) { text_rows = N; tv = cls_view; }
+    }
+    const int ng = text_rows > 0 ? 2 * nl : nl;
+    {
+      GemmProb g[4] = {};
+      for (int l = 0; l < nl; ++l) {
+        const Work& v = lanes[l].w;
+        GemmProb& q = g[l];
+        q.A = cross ? v.hC16 : v.hB16; q.a = fqv;
+        q.W = Lw[l]->wiq; q.bias = Lw[l]->biq;
+        q.C = v.ffn16; q.c = plain(N * Q, I);
+        q.M = N * Q; q.N = I; q.K = H;
+        GemmProb& t = g[nl + l];
+        t.A = v.hB16 + t_off16; t.a = tv;
+        t.W = Lw[l]->wit; t.bias = Lw[l]->bit;
+        t.C = v.ffn16 + (size_t)N * Q * I * esz; t.c = plain(text_rows, I);
+        t.M = text_rows; t.N = I; t.K = H;
+      }
+      if ((h->chain_ring & 2) && N * Q >= 512 && I % 192 == 0) g[0].tile_cfg = 10;
+      rc = launch_gemm(g, ng, EPI_GELU_OP, op, stream);
+      if (rc) return chk(rc, "ffn up gemm");
+    }
+    bool ffn_ln_fused = false;
+    {
+      GemmProb g[4] = {};
+      for (int l = 0; l < nl; ++l) {
+        const Work& v = lanes[l].w;
+        GemmProb& q = g[l];
+        q.A = v.ffn16; q.a = plain(N * Q, I);
+        q.W = Lw[l]->woq; q.bias = Lw[l]->boq;
+        q.R = cross ? v.hC32 : v.hB32; q.r = fqv;
+        q.C = v.pre32; q.c = q_view;
+        q.M = N * Q; q.N = H; q.K = I;
+        GemmProb& t = g[nl + l];
+        t.A = v.ffn16 + (size_t)N * Q * I * esz; t.a = plain(text_rows, I);
+        t.W = Lw[l]->wot; t.bias = Lw[l]->bot;
+        t.R = v.hB32 + t_off32; t.r = tv;
+        t.C = v.pre32 + t_off32; t.c = tv;
+        t.M = text_rows; t.N = H; t.K = I;
+      }
+      g[0].tile_cfg = N * Q >= 512 && I % 128 == 0 ? 6 : 0;   // 64 weight rows x 128 activation rows, 128-deep K steps (see the QKV note)
+      if ((h->chain_ring & 4) && N * Q >= 512 && H % 96 == 0) g[0].tile_cfg = 11;
+      ffn_ln_fused = ln_fuse && !last && g[0].tile_cfg == 11;
+      if (ffn_ln_fused) {
+        // HF:573-587 for both row sets in the same launch: problem 0 = query rows (output_query.LayerNorm), problem 1 = text rows (output.LayerNorm)
+        g[0].ln_gain = Lw[0]->lnqg; g[0].ln_bias = Lw[0]->lnqb; g[0].ln_eps = c.ln_eps;
+        g[0].ln_y32 = w.hA32; g[0].ln_y32v = q_view; g[0].ln_y16 = w.hA16; g[0].ln_y16v = q_view; g[0].ln_counter = w.lncnt;
+        g[1].ln_gain = Lw[0]->lntg; g[1].ln_bias = Lw[0]->lntb; g[1].ln_eps = c.ln_eps;
+        g[1].ln_y32 = w.hA32 + t_off32; g[1].ln_y32v = tv; g[1].ln_y16 = w.hA16 + t_off16; g[1].ln_y16v = tv;
+        g[1].ln_counter = w.lncnt + (N * Q + 63) / 64;
+        rc = launch_gemm(g, ng, EPI_RES_LN, op, stream);
+        if (rc) return chk(rc, "ffn down gemm + ln");
+      } else {
+        rc = launch_gemm(g, ng, EPI_RES_F32, op, stream);
+        if (rc) return chk(rc, "ffn down gemm");
+      }
+    }
+    if (ffn_ln_fused) {
+      // the LayerNorms ran inside the down-projection's launch
+    } else if (!last) {
+      // query and text LayerNorms of every lane in one launch over the whole [nl N, S, H] stream
+      rc = launch_ln_rows4(w.pre32, all_lanes, nl * N * S, H, Lw[0]->lnqg, Lw[0]->lnqb, Lw[0]->lntg, Lw[0]->lntb, N * S, Lw[1]->lnqg, Lw[1]->lnqb,
+                           Lw[1]->lntg, Lw[1]->lntb, S, Q, c.ln_eps, w.hA32, all_lanes, w.hA16, all_lanes, op, stream);
+      if (rc) return chk(rc, "ffn ln");
+    } else {
+      for (int l = 0; l < nl; ++l) {   // last layer: LayerNorm straight into the caller's buffers
+        const Lane& x = lanes[l];
+        const LayerW& W = *Lw[l];
+        if (x.out_full) {
+          rc = launch_ln_rows(x.w.pre32, q_view, N * Q, H, W.lnqg, W.lnqb, c.ln_eps, x.out_full, q_view, nullptr, q_view, op, stream);
+          if (rc) return chk(rc, "final query ln");
+          if (text_rows > 0) {
+            rc = launch_ln_rows(x.w.pre32 + t_off32, tv, text_rows, H, W.lntg, W.lntb, c.ln_eps, x.out_full + t_off32, tv, nullptr, tv, op, stream);
+            if (rc) return chk(rc, "final text ln");
+          }
+          if (x.out_query) {
+            rc = launch_copy_rows_f32(x.out_full, q_view, x.out_query, qc_rows, N * Q, H, stream);
+            if (rc) return chk(rc, "copy out_query");
+          }
+          if (x.out_cls) {
+            rc = launch_copy_rows_f32(x.out_full + t_off32, cls_view, x.out_cls, plain(N, H), N, H, stream);
+            if (rc) return chk(rc, "copy out_cls");
+          }
+        } else {
+          if (x.out_query) {
+            rc = launch_ln_rows(x.w.pre32, q_view, N * Q, H, W.lnqg, W.lnqb, c.ln_eps, x.out_query, qc_rows, nullptr, qc_rows, op, stream);
+            if (rc) return chk(rc, "final query ln");
+          }
+          if (x.out_cls) {
+            rc = launch_ln_rows(x.w.pre32 + t_off32, cls_view, N, H, W.lntg, W.lntb, c.ln_eps, x.out_cls, plain(N, H), nullptr, plain(N, H), op,
+                                stream);
+            if (rc) return chk(rc, "final cls ln");
+          }
+        }
+      }
+    }
+  }
+  return MRA_OK;
+}
+
+// mra_qformer_forward in the precision in force, or (probe) as the probing forward of the automatic precision
+int forward_run(mra_qformer* h, bool probe, const int64_t* input_ids, const int64_t* attention_mask, const float* query_embeds,
+                int32_t query_items, const void* enc, int32_t items, int32_t L, int32_t kv, float* out_query, float* out_full, float* out_cls,
+                void* workspace, size_t workspace_bytes, void* stream_) {
   if (!h) return fail(MRA_EINVAL, "null handle");
   if (items < 0 || L < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
   if (items == 0) return MRA_OK;
@@ -634,280 +923,21 @@ int forward_run(mra_qformer* h, const int64_t* input_ids, const int64_t* attenti
   if (query_embeds && query_items != 1 && query_items != items)
     return fail(MRA_EINVAL, "query_items must be 1 or items");
   if (!out_query && !out_full && !out_cls) return fail(MRA_EINVAL, "no output requested");
-  {
-    char names[256];
-    const int miss = mra_qformer_missing(h, names, sizeof(names));
-    int tolerated = 0;
-    for (const char* opt : {"ln.weight", "ln.bias", "llm_proj.weight", "llm_proj.bias"}) {
-      auto it = h->params.find(opt);
-      if (it != h->params.end() && !it->second.loaded) ++tolerated;
-    }
-    if (miss > tolerated) return fail(MRA_ESTATE, std::string("parameters not loaded: ") + names);
-  }
-  const size_t need = mra_qformer_workspace_bytes(h, items, L, kv);
+  if (int rc = check_loaded(h)) return rc;
+  Lane lane = make_lane(h, enc, kv, h->cross_precise, probe);
+  // the probe needs its own form's workspace; every other forward what mra_qformer_workspace_bytes promises
+  const size_t need = probe ? work_bytes(lane, items, L) : mra_qformer_workspace_bytes(h, items, L, kv);
   if (!workspace || workspace_bytes < need)
     return fail(MRA_ENOMEM, "workspace too small: need " + std::to_string(need) + " bytes");
   if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(MRA_EINVAL, "workspace must be 256-byte aligned");
-
-  hipStream_t stream = as_stream(stream_);
-  const int N = items, Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter, E = c.enc_width;
-  const int op = h->op();
-  Work w = layout_work(h, (char*)workspace, N, L, kv);
-  w.part = w.nsplit > 1 ? reinterpret_cast<float*>((char*)workspace + w.bytes) : nullptr;
-  w.hist = h->probe_fold ? h->auto_hist : nullptr;
-  const long long SH = (long long)S * H;
-  const size_t esz = 2;
-
-  // row views of the [N, S, H] streams
-  const RowView all_rows = plain(N * S, H);
-  const RowView q_view = items_view(SH, Q, H);          // rows [:, :32]
-  const RowView t_view = items_view(SH, L > 0 ? L : 1, H);  // rows [:, 32:] (base pointer + 32*H)
-  const RowView cls_view = items_view(SH, 1, H);        // row  [:, 32]
-  const RowView qc_rows = plain(N * Q, H);              // compact [N*32, H]
-
-  // embeddings
-  const float* qsrc = query_embeds ? query_embeds : h->query;
-  const long long qstride = query_embeds && query_items == items && items > 1 ? (long long)Q * H : 0;
-  int rc = launch_embed_ln((const long long*)input_ids, N, L, Q, H, c.vocab, qsrc, qstride, h->word, h->pos, h->embg,
-                           h->embb, c.ln_eps, w.hA32, w.hA16, nullptr, op, stream);
-  if (rc) return chk(rc, "embed_ln");
-
-  // residual projection + LayerNorm in ONE launch (chain_ring bit 3, on the 96 x 64 ring tile): its per-row-tile counters start at zero
-  const bool ln_fuse = (h->chain_ring & 12) == 12 && H % 96 == 0 && H % 256 == 0 && H <= 1024;
-  if (ln_fuse) HIP_TRY(hipMemsetAsync(w.lncnt, 0, w.lncnt_bytes, stream));
-  const bool fold = h->ncross > 0 && use_fold(h, kv);
-  const bool stream_fold = fold && fold_streams(h, kv);
-  const int R = c.heads * Q, kvp = fold_kvp(kv);
-  if (fold) {
-    // folded cross-attention: enc^T per item (the K-contiguous operand of P . enc), key weights regrouped per head
-    if (!stream_fold && !fold_kmajor(h)) {
-      rc = launch_transpose_pad(enc, w.encT, kv, E, kvp, (long long)kv * E, (long long)E * kvp, N, op, stream);
-      if (rc) return chk(rc, "enc transpose");
-    }
-    if ((rc = mra_qformer_prepare(h, stream_))) return rc;
-  } else if (h->ncross > 0) {
-    // K/V of every cross layer in one GEMM, scattered head-major
-    if (h->kv_ev0 && h->kv_ev1) (void)hipEventRecord(h->kv_ev0, stream);
-    rc = kv_project(h, enc, N, kv, w.kv16, stream);
-    if (rc) return chk(rc, "kv projection gemm");
-    if (h->kv_ev0 && h->kv_ev1) (void)hipEventRecord(h->kv_ev1, stream);
+  if (query_embeds) {
+    lane.query = query_embeds;
+    lane.query_stride = query_items == items && items > 1 ? (long long)c.n_query * c.hidden : 0;
   }
-  if (h->kv_done) (void)hipEventRecord(h->kv_done, stream);   // also without cross layers: the waiter must not hang
-
-  const bool want_text_last = out_full != nullptr;
-  const bool want_cls_last = !out_full && out_cls != nullptr;
-
-  for (int i = 0; i < c.layers; ++i) {
-    const LayerW& Lw = h->layers[i];
-    const bool last = i == c.layers - 1;
-    // 1. fused Q|K|V projection of all S rows
-    {
-      GemmProb p{};
-      p.A = w.hA16; p.a = all_rows;
-      p.W = Lw.wqkv; p.bias = Lw.bqkv;
-      p.C = w.qkv16; p.c = plain(N * S, 3 * H);
-      p.M = N * S; p.N = 3 * H; p.K = H;
-      // The chain GEMMs at ~1-2 k rows are bound by the operand bytes each CU pulls through its load path (~33 B / clk from L2),
-      // not by tile count: 128 x 128 tiles (288 of them) move half the bytes per flop of the 1152 64 x 64 tiles the automatic
-      // choice makes (headline step 6.75 -> 6.67 ms, reference item shape 2.65 -> 2.55 ms together with the down-projection below)
-      p.tile_cfg = N * S >= 1024 ? 2 : 0;
-      // ... and at ~2 k rows the ring kernel's 144 x 128 tile is exactly one workgroup per CU (2048 x 2304 = 16 x 16 tiles): 14.4 vs 17.6 us stand-alone
-      if ((h->chain_ring & 1) && N * S >= 1024 && (3 * H) % 144 == 0) p.tile_cfg = 9;
-      rc = launch_gemm(&p, 1, EPI_OP, op, stream);
-      if (rc) return chk(rc, "qkv gemm");
-    }
-    // 2. self-attention core
-    {
-      AttnArgs a{};
-      a.Q = w.qkv16;
-      a.K = w.qkv16 + (size_t)H * esz;
-      a.V = w.qkv16 + (size_t)2 * H * esz;
-      a.O = w.ctx16;
-      a.q_item_stride = (long long)S * 3 * H; a.q_ld = 3 * H;
-      a.k_item_stride = (long long)S * 3 * H; a.k_head_stride = 64; a.k_ld = 3 * H;
-      a.v_item_stride = (long long)S * 3 * H; a.v_head_stride = 64; a.v_ld = 3 * H;
-      a.o_item_stride = SH; a.o_ld = H;
-      a.mask = (const long long*)attention_mask; a.mask_ld = S;
-      a.items = N; a.heads = c.heads; a.q_rows = S; a.kv_len = S;
-      a.scale = 0.125f; a.nsplit = 1; a.part = nullptr;
-      rc = launch_attention(a, op, stream);
-      if (rc) return chk(rc, "self attention");
-    }
-    // 3. output projection + residual, 4. LayerNorm -> hB
-    {
-      GemmProb p{};
-      p.A = w.ctx16; p.a = all_rows;
-      p.W = Lw.wo; p.bias = Lw.bo;
-      p.R = w.hA32; p.r = all_rows;
-      p.C = w.pre32; p.c = all_rows;
-      p.M = N * S; p.N = H; p.K = H;
-      if ((h->chain_ring & 4) && N * S >= 1024 && H % 96 == 0) p.tile_cfg = 11;
-      if (ln_fuse && p.tile_cfg == 11) {
-        // HF:519-530 in one launch: the column tile of a 64-row block that finishes last normalises the block's rows
-        p.ln_gain = Lw.ln1g; p.ln_bias = Lw.ln1b; p.ln_eps = c.ln_eps;
-        p.ln_y32 = w.hB32; p.ln_y32v = all_rows; p.ln_y16 = w.hB16; p.ln_y16v = all_rows; p.ln_counter = w.lncnt;
-        rc = launch_gemm(&p, 1, EPI_RES_LN, op, stream);
-        if (rc) return chk(rc, "attn out gemm + ln");
-      } else {
-      rc = launch_gemm(&p, 1, EPI_RES_F32, op, stream);
-      if (rc) return chk(rc, "attn out gemm");
-      rc = launch_ln_rows(w.pre32, all_rows, N * S, H, Lw.ln1g, Lw.ln1b, c.ln_eps, w.hB32, all_rows, w.hB16, all_rows, op,
-                          stream);
-      if (rc) return chk(rc, "attn ln");
-      }
-    }
-    // query-side state entering the feed-forward: hB[:, :32] or the cross-attention output hC
-    const void* fq16 = w.hB16;
-    const float* fq32 = w.hB32;
-    RowView fqv = q_view;
-    if (Lw.cross_index >= 0) {
-      const bool precise = fold && h->cross_precise;
-      // 5. cross query projection
-      GemmProb p{};
-      if (precise) {
-        // split precision: the fp32 query rows leave as (hi | lo | hi), the weight is stored as (hi | hi | lo): one GEMM over K = 3H
-        // computes xh wh + xl wh + xh wl in the fp32 accumulators; Q stays fp32
-        rc = launch_split_rows(w.hB32, q_view, N * Q, H, H, 3, w.hs16, op, stream);
-        if (rc) return chk(rc, "split query rows");
-        p.A = w.hs16; p.a = plain(N * Q, 3 * H);
-        p.W = h->arena_p + (size_t)Lw.cross_index * precise_layer_bytes(h); p.bias = Lw.bcq;
-        p.C = w.qc32; p.c = qc_rows;
-        p.M = N * Q; p.N = H; p.K = 3 * H;
-        rc = launch_gemm(&p, 1, EPI_F32, op, stream);
-      } else {
-        p.A = w.hB16; p.a = q_view;
-        p.W = Lw.wcq; p.bias = Lw.bcq;
-        p.C = w.qc16; p.c = qc_rows;
-        p.M = N * Q; p.N = H; p.K = H;
-        rc = launch_gemm(&p, 1, EPI_OP, op, stream);
-      }
-      if (rc) return chk(rc, "cross q gemm");
-      if ((rc = cross_core(h, w, Lw, enc, N, kv, fold, stream_fold, precise, stream))) return rc;
-      // 7. output projection + residual (hB[:, :32]), 8. LayerNorm -> hC (compact)
-      GemmProb o{};
-      o.A = w.ctx16; o.a = qc_rows;
-      o.W = Lw.wco; o.bias = Lw.bco;
-      o.R = w.hB32; o.r = q_view;
-      o.C = w.pre32; o.c = qc_rows;
-      o.M = N * Q; o.N = H; o.K = H;
-      if (ln_fuse && N * Q >= 512) {
-        o.tile_cfg = 11;
-        o.ln_gain = Lw.lncg; o.ln_bias = Lw.lncb; o.ln_eps = c.ln_eps;
-        o.ln_y32 = w.hC32; o.ln_y32v = qc_rows; o.ln_y16 = w.hC16; o.ln_y16v = qc_rows; o.ln_counter = w.lncnt;
-        rc = launch_gemm(&o, 1, EPI_RES_LN, op, stream);
-        if (rc) return chk(rc, "cross out gemm + ln");
-      } else {
-      rc = launch_gemm(&o, 1, EPI_RES_F32, op, stream);
-      if (rc) return chk(rc, "cross out gemm");
-      rc = launch_ln_rows(w.pre32, qc_rows, N * Q, H, Lw.lncg, Lw.lncb, c.ln_eps, w.hC32, qc_rows, w.hC16, qc_rows, op,
-                          stream);
-      if (rc) return chk(rc, "cross ln");
-      }
-      fq16 = w.hC16;
-      fq32 = w.hC32;
-      fqv = qc_rows;
-    }
-    // 9-14. feed-forwards: group 0 = query rows, group 1 = text rows (own weights)
-    int text_rows = 0;
-    RowView tv = t_view;
-    if (L > 0) {
-      if (!last || want_text_last) text_rows = N * L;
-      else if (want_cls_last) { text_rows = N; tv = cls_view; }
-    }
-    bool ffn_ln_fused = false;
-    const size_t t_off16 = (size_t)Q * H * esz;   // byte offset of row 32 inside an item (op dtype)
-    const size_t t_off32 = (size_t)Q * H;         // element offset (f32)
-    {
-      GemmProb g[2] = {};
-      g[0].A = fq16; g[0].a = fqv;
-      g[0].W = Lw.wiq; g[0].bias = Lw.biq;
-      g[0].C = w.ffn16; g[0].c = plain(N * Q, I);
-      g[0].M = N * Q; g[0].N = I; g[0].K = H;
-      g[1].A = w.hB16 + t_off16; g[1].a = tv;
-      g[1].W = Lw.wit; g[1].bias = Lw.bit;
-      g[1].C = w.ffn16 + (size_t)N * Q * I * esz; g[1].c = plain(text_rows, I);
-      g[1].M = text_rows; g[1].N = I; g[1].K = H;
-      if ((h->chain_ring & 2) && N * Q >= 512 && I % 192 == 0) g[0].tile_cfg = 10;
-      rc = launch_gemm(g, text_rows > 0 ? 2 : 1, EPI_GELU_OP, op, stream);
-      if (rc) return chk(rc, "ffn up gemm");
-    }
-    {
-      GemmProb g[2] = {};
-      g[0].A = w.ffn16; g[0].a = plain(N * Q, I);
-      g[0].W = Lw.woq; g[0].bias = Lw.boq;
-      g[0].R = fq32; g[0].r = fqv;
-      g[0].C = w.pre32; g[0].c = q_view;
-      g[0].M = N * Q; g[0].N = H; g[0].K = I;
-      g[1].A = w.ffn16 + (size_t)N * Q * I * esz; g[1].a = plain(text_rows, I);
-      g[1].W = Lw.wot; g[1].bias = Lw.bot;
-      g[1].R = w.hB32 + t_off32; g[1].r = tv;
-      g[1].C = w.pre32 + t_off32; g[1].c = tv;
-      g[1].M = text_rows; g[1].N = H; g[1].K = I;
-      g[0].tile_cfg = N * Q >= 512 && I % 128 == 0 ? 6 : 0;   // 64 weight rows x 128 activation rows, 128-deep K steps (see the QKV note)
-      if ((h->chain_ring & 4) && N * Q >= 512 && H % 96 == 0) g[0].tile_cfg = 11;
-      ffn_ln_fused = ln_fuse && !last && g[0].tile_cfg == 11;
-      if (ffn_ln_fused) {
-        // HF:573-587 for both row sets in the same launch: problem 0 = query rows (output_query.LayerNorm), problem 1 = text rows (output.LayerNorm)
-        g[0].ln_gain = Lw.lnqg; g[0].ln_bias = Lw.lnqb; g[0].ln_eps = c.ln_eps;
-        g[0].ln_y32 = w.hA32; g[0].ln_y32v = q_view; g[0].ln_y16 = w.hA16; g[0].ln_y16v = q_view; g[0].ln_counter = w.lncnt;
-        g[1].ln_gain = Lw.lntg; g[1].ln_bias = Lw.lntb; g[1].ln_eps = c.ln_eps;
-        g[1].ln_y32 = w.hA32 + t_off32; g[1].ln_y32v = tv; g[1].ln_y16 = w.hA16 + t_off16; g[1].ln_y16v = tv;
-        g[1].ln_counter = w.lncnt + (N * Q + 63) / 64;
-        rc = launch_gemm(g, text_rows > 0 ? 2 : 1, EPI_RES_LN, op, stream);
-        if (rc) return chk(rc, "ffn down gemm + ln");
-      } else {
-      rc = launch_gemm(g, text_rows > 0 ? 2 : 1, EPI_RES_F32, op, stream);
-      if (rc) return chk(rc, "ffn down gemm");
-      }
-    }
-    if (ffn_ln_fused) {
-      // the LayerNorms ran inside the down-projection's launch
-    } else if (!last && text_rows == N * L && L > 0) {
-      // query and text LayerNorm in one launch: the two row sets are the whole [N, S, H] stream
-      rc = launch_ln_rows2(w.pre32, all_rows, N * S, H, Lw.lnqg, Lw.lnqb, Lw.lntg, Lw.lntb, S, Q, c.ln_eps, w.hA32, all_rows,
-                           w.hA16, all_rows, op, stream);
-      if (rc) return chk(rc, "ffn ln");
-    } else if (!last) {
-      rc = launch_ln_rows(w.pre32, q_view, N * Q, H, Lw.lnqg, Lw.lnqb, c.ln_eps, w.hA32, q_view, w.hA16, q_view, op, stream);
-      if (rc) return chk(rc, "ffn query ln");
-      if (text_rows > 0) {
-        rc = launch_ln_rows(w.pre32 + t_off32, tv, text_rows, H, Lw.lntg, Lw.lntb, c.ln_eps, w.hA32 + t_off32, tv,
-                            w.hA16 + t_off16, tv, op, stream);
-        if (rc) return chk(rc, "ffn text ln");
-      }
-    } else {
-      // last layer: LayerNorm straight into the caller's buffers
-      if (out_full) {
-        rc = launch_ln_rows(w.pre32, q_view, N * Q, H, Lw.lnqg, Lw.lnqb, c.ln_eps, out_full, q_view, nullptr, q_view, op, stream);
-        if (rc) return chk(rc, "final query ln");
-        if (text_rows > 0) {
-          rc = launch_ln_rows(w.pre32 + t_off32, tv, text_rows, H, Lw.lntg, Lw.lntb, c.ln_eps, out_full + t_off32, tv, nullptr,
-                              tv, op, stream);
-          if (rc) return chk(rc, "final text ln");
-        }
-        if (out_query) {
-          rc = launch_copy_rows_f32(out_full, q_view, out_query, qc_rows, N * Q, H, stream);
-          if (rc) return chk(rc, "copy out_query");
-        }
-        if (out_cls) {
-          rc = launch_copy_rows_f32(out_full + t_off32, cls_view, out_cls, plain(N, H), N, H, stream);
-          if (rc) return chk(rc, "copy out_cls");
-        }
-      } else {
-        if (out_query) {
-          rc = launch_ln_rows(w.pre32, q_view, N * Q, H, Lw.lnqg, Lw.lnqb, c.ln_eps, out_query, qc_rows, nullptr, qc_rows, op,
-                              stream);
-          if (rc) return chk(rc, "final query ln");
-        }
-        if (out_cls) {
-          rc = launch_ln_rows(w.pre32 + t_off32, cls_view, N, H, Lw.lntg, Lw.lntb, c.ln_eps, out_cls, plain(N, H), nullptr,
-                              plain(N, H), op, stream);
-          if (rc) return chk(rc, "final cls ln");
-        }
-      }
-    }
-  }
-  return MRA_OK;
+  lane.out_query = out_query;
+  lane.out_full = out_full;
+  lane.out_cls = out_cls;
+  return run_lanes(&lane, 1, input_ids, attention_mask, items, L, workspace, as_stream(stream_));
 }
 
 // Lower median of the p_max histogram of one cross layer, at the centre of its bin (-1 for an empty histogram)
@@ -936,10 +966,8 @@ int forward_probe(mra_qformer* h, const int64_t* input_ids, const int64_t* atten
   const size_t hist_bytes = (size_t)h->ncross * 256 * sizeof(int);
   HIP_TRY(hipMemsetAsync(h->auto_hist, 0, hist_bytes, stream));
   h->cross_precise = 0;
-  h->probe_fold = true;
-  int rc = forward_run(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+  int rc = forward_run(h, true, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
                        workspace_bytes, stream_);
-  h->probe_fold = false;
   if (rc) return rc;   // the probe stays pending
   HIP_TRY(hipMemcpyAsync(h->auto_hist_host, h->auto_hist, hist_bytes, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
@@ -954,8 +982,8 @@ int forward_probe(mra_qformer* h, const int64_t* input_ids, const int64_t* atten
   h->cross_precise = h->auto_resolved;
   // resolved to op: the probe's outputs are op's own bits when op runs the same form here (the folded form with in-register factors or the
   // rescale pass: same bits); the K/V-cache form (Kv < 2048 in cross mode 0, or mode 1) and the streaming kernels are re-run
-  if (h->auto_resolved == 0 && use_fold(h, kv) && !fold_streams(h, kv)) return MRA_OK;
-  return forward_run(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+  if (h->auto_resolved == 0 && cross_plan(h, kv, false, false).form == CrossPlan::FOLD) return MRA_OK;
+  return forward_run(h, false, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
                      workspace_bytes, stream_);
 }
 }  // namespace
@@ -967,15 +995,17 @@ int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t*
   if (h && h->cross_auto && h->auto_stale && h->ncross > 0 && items > 0)
     return forward_probe(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
                          workspace_bytes, stream_);
-  return forward_run(h, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+  return forward_run(h, false, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
                      workspace_bytes, stream_);
 }
 
 size_t mra_qformer_pair_workspace_bytes(mra_qformer* h0, mra_qformer* h1, int32_t items, int32_t L, int32_t kv0, int32_t kv1) {
   if (!h0 || !h1 || items <= 0 || L < 0 || kv0 <= 0 || kv1 <= 0) return 0;
-  return layout_pair(h0, h1, nullptr, items, L, kv0, kv1).bytes;
+  Lane lanes[2] = {make_lane(h0, nullptr, kv0, h0->cross_precise, false), make_lane(h1, nullptr, kv1, h1->cross_precise, false)};
+  return layout_lanes(lanes, 2, nullptr, items, L);
 }
 
+// Pair forward: the layer chains of two Q-Formers of equal shape in ONE launch sequence (run_lanes with two lanes).
 int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
                              const void* enc1, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0, float* out_cls0,
                              float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream_) {
@@ -999,187 +1029,22 @@ int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* in
   if (L > c.max_pos || L > h1->cfg.max_pos) return fail(MRA_EINVAL, "L exceeds max_pos");
   if (!enc0 || !enc1 || (L > 0 && !input_ids)) return fail(MRA_EINVAL, "null input");
   if ((out_cls0 || out_cls1) && L < 1) return fail(MRA_EINVAL, "out_cls needs L >= 1");
+  Lane lanes[2] = {};
   for (int l = 0; l < 2; ++l) {
     if (!outq[l] && !outc[l]) return fail(MRA_EINVAL, "no output requested for a lane");
     if (hs[l]->cross_precise) return fail(MRA_ESTATE, "pair forward runs the operand-dtype score chain: use mra_qformer_forward for split precision");
     if (hs[l]->cross_auto && (hs[l]->auto_stale || hs[l]->auto_resolved != 0))
       return fail(MRA_ESTATE, "pair forward runs the operand-dtype score chain: auto precision must have resolved to op (use mra_qformer_forward)");
-    if (hs[l]->ncross > 0 && use_fold(hs[l], kvs[l]) && fold_streams(hs[l], kvs[l])) return fail(MRA_ESTATE, "pair forward: the streaming fold kernels are not supported");
-    char names[256];
-    const int miss = mra_qformer_missing(hs[l], names, sizeof(names));
-    int tolerated = 0;
-    for (const char* opt : {"ln.weight", "ln.bias", "llm_proj.weight", "llm_proj.bias"}) {
-      auto it = hs[l]->params.find(opt);
-      if (it != hs[l]->params.end() && !it->second.loaded) ++tolerated;
-    }
-    if (miss > tolerated) return fail(MRA_ESTATE, std::string("parameters not loaded: ") + names);
+    lanes[l] = make_lane(hs[l], encs[l], kvs[l], false, false);
+    if (lanes[l].plan.form == CrossPlan::FOLD_STREAM) return fail(MRA_ESTATE, "pair forward: the streaming fold kernels are not supported");
+    if (int rc = check_loaded(hs[l])) return rc;
+    lanes[l].out_query = outq[l];
+    lanes[l].out_cls = outc[l];
   }
   const size_t need = mra_qformer_pair_workspace_bytes(h0, h1, items, L, kv0, kv1);
   if (!workspace || workspace_bytes < need) return fail(MRA_ENOMEM, "workspace too small: need " + std::to_string(need) + " bytes");
   if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(MRA_EINVAL, "workspace must be 256-byte aligned");
-
-  hipStream_t stream = as_stream(stream_);
-  const int N = items, Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter;
-  const int op = h0->op();
-  PairWork pw = layout_pair(h0, h1, (char*)workspace, N, L, kv0, kv1);
-  Work* w = pw.w;
-  const long long SH = (long long)S * H;
-  const size_t esz = 2;
-  const RowView all_rows = plain(N * S, H), all2 = plain(2 * N * S, H);
-  const RowView q_view = items_view(SH, Q, H);
-  const RowView t_view = items_view(SH, L > 0 ? L : 1, H);
-  const RowView cls_view = items_view(SH, 1, H);
-  const RowView qc_rows = plain(N * Q, H), qc2 = plain(2 * N * Q, H);
-  int rc;
-  bool fold[2];
-  for (int l = 0; l < 2; ++l) {
-    rc = launch_embed_ln((const long long*)input_ids, N, L, Q, H, hs[l]->cfg.vocab, hs[l]->query, 0, hs[l]->word, hs[l]->pos, hs[l]->embg, hs[l]->embb, c.ln_eps,
-                         w[l].hA32, w[l].hA16, nullptr, op, stream);
-    if (rc) return chk(rc, "embed_ln");
-    fold[l] = hs[l]->ncross > 0 && use_fold(hs[l], kvs[l]);
-    if (fold[l]) {
-      if (!fold_kmajor(hs[l])) {
-        const int kvp = fold_kvp(kvs[l]);
-        rc = launch_transpose_pad(encs[l], w[l].encT, kvs[l], hs[l]->cfg.enc_width, kvp, (long long)kvs[l] * hs[l]->cfg.enc_width, (long long)hs[l]->cfg.enc_width * kvp, N, op, stream);
-        if (rc) return chk(rc, "enc transpose");
-      }
-      if ((rc = mra_qformer_prepare(hs[l], stream_))) return rc;
-    } else if (hs[l]->ncross > 0) {
-      rc = kv_project(hs[l], encs[l], N, kvs[l], w[l].kv16, stream);
-      if (rc) return chk(rc, "kv projection gemm");
-    }
-  }
-  const long long* mask2 = nullptr;
-  if (attention_mask) {   // the two lanes share the prompt: their mask rows one after the other for the 2 N-item attention launch
-    HIP_TRY(hipMemcpyAsync(pw.mask2, attention_mask, (size_t)N * S * 8, hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(pw.mask2 + (size_t)N * S, attention_mask, (size_t)N * S * 8, hipMemcpyDeviceToDevice, stream));
-    mask2 = pw.mask2;
-  }
-  const bool ring = N * S >= 1024;
-  for (int i = 0; i < c.layers; ++i) {
-    const LayerW* Lw[2] = {&h0->layers[i], &h1->layers[i]};
-    const bool last = i == c.layers - 1;
-    // 1. Q | K | V of both lanes: two problems, one launch
-    {
-      GemmProb p[2] = {};
-      for (int l = 0; l < 2; ++l) {
-        p[l].A = w[l].hA16; p[l].a = all_rows; p[l].W = Lw[l]->wqkv; p[l].bias = Lw[l]->bqkv;
-        p[l].C = w[l].qkv16; p[l].c = plain(N * S, 3 * H); p[l].M = N * S; p[l].N = 3 * H; p[l].K = H;
-        p[l].tile_cfg = ring ? (((hs[l]->chain_ring & 1) && (3 * H) % 144 == 0) ? 9 : 2) : 0;
-      }
-      if ((rc = launch_gemm(p, 2, EPI_OP, op, stream))) return chk(rc, "qkv gemm (pair)");
-    }
-    // 2. self-attention of all 2 N items
-    {
-      AttnArgs a{};
-      a.Q = w[0].qkv16; a.K = w[0].qkv16 + (size_t)H * esz; a.V = w[0].qkv16 + (size_t)2 * H * esz; a.O = w[0].ctx16;
-      a.q_item_stride = (long long)S * 3 * H; a.q_ld = 3 * H;
-      a.k_item_stride = (long long)S * 3 * H; a.k_head_stride = 64; a.k_ld = 3 * H;
-      a.v_item_stride = (long long)S * 3 * H; a.v_head_stride = 64; a.v_ld = 3 * H;
-      a.o_item_stride = SH; a.o_ld = H;
-      a.mask = mask2; a.mask_ld = S;
-      a.items = 2 * N; a.heads = c.heads; a.q_rows = S; a.kv_len = S; a.scale = 0.125f; a.nsplit = 1; a.part = nullptr;
-      if ((rc = launch_attention(a, op, stream))) return chk(rc, "self attention (pair)");
-    }
-    // 3. output projections + residual (two problems), 4. LayerNorm of both lanes in one launch
-    {
-      GemmProb p[2] = {};
-      for (int l = 0; l < 2; ++l) {
-        p[l].A = w[l].ctx16; p[l].a = all_rows; p[l].W = Lw[l]->wo; p[l].bias = Lw[l]->bo; p[l].R = w[l].hA32; p[l].r = all_rows;
-        p[l].C = w[l].pre32; p[l].c = all_rows; p[l].M = N * S; p[l].N = H; p[l].K = H;
-        if ((hs[l]->chain_ring & 4) && ring && H % 96 == 0) p[l].tile_cfg = 11;
-      }
-      if ((rc = launch_gemm(p, 2, EPI_RES_F32, op, stream))) return chk(rc, "attn out gemm (pair)");
-      rc = launch_ln_rows4(w[0].pre32, all2, 2 * N * S, H, Lw[0]->ln1g, Lw[0]->ln1b, nullptr, nullptr, N * S, Lw[1]->ln1g, Lw[1]->ln1b, nullptr, nullptr, 1, 1,
-                           c.ln_eps, w[0].hB32, all2, w[0].hB16, all2, op, stream);
-      if (rc) return chk(rc, "attn ln (pair)");
-    }
-    const bool cross = Lw[0]->cross_index >= 0;
-    if (cross) {
-      // 5. cross query projections (two problems), 6. each lane's own cross-attention, 7. output projections + residual, 8. LayerNorm
-      GemmProb p[2] = {};
-      for (int l = 0; l < 2; ++l) {
-        p[l].A = w[l].hB16; p[l].a = q_view; p[l].W = Lw[l]->wcq; p[l].bias = Lw[l]->bcq;
-        p[l].C = w[l].qc16; p[l].c = qc_rows; p[l].M = N * Q; p[l].N = H; p[l].K = H;
-      }
-      if ((rc = launch_gemm(p, 2, EPI_OP, op, stream))) return chk(rc, "cross q gemm (pair)");
-      for (int l = 0; l < 2; ++l)
-        if ((rc = cross_core(hs[l], w[l], *Lw[l], encs[l], N, kvs[l], fold[l], false, false, stream))) return rc;
-      GemmProb o[2] = {};
-      for (int l = 0; l < 2; ++l) {
-        o[l].A = w[l].ctx16; o[l].a = qc_rows; o[l].W = Lw[l]->wco; o[l].bias = Lw[l]->bco; o[l].R = w[l].hB32; o[l].r = q_view;
-        o[l].C = w[l].pre32; o[l].c = qc_rows; o[l].M = N * Q; o[l].N = H; o[l].K = H;
-      }
-      if ((rc = launch_gemm(o, 2, EPI_RES_F32, op, stream))) return chk(rc, "cross out gemm (pair)");
-      // pre32 of lane l holds its compact [N*Q][H] rows at its own base: two launches would be needed for one row view; the rows of the two
-      // lanes are N*S*H apart, so address them as items of Q rows with an item stride that jumps lanes: view (item = lane): stride N*S*H, rpi N*Q
-      const RowView pre_v = items_view((long long)N * S * H, N * Q, H);
-      rc = launch_ln_rows4(w[0].pre32, pre_v, 2 * N * Q, H, Lw[0]->lncg, Lw[0]->lncb, nullptr, nullptr, N * Q, Lw[1]->lncg, Lw[1]->lncb, nullptr, nullptr, 1, 1,
-                           c.ln_eps, w[0].hC32, qc2, w[0].hC16, qc2, op, stream);
-      if (rc) return chk(rc, "cross ln (pair)");
-    }
-    // 9-14. feed-forwards: per lane a query problem and a text problem -> four problems per launch
-    int text_rows = 0;
-    RowView tv = t_view;
-    if (L > 0) {
-      if (!last) text_rows = N * L;
-      else if (outc[0] || outc[1]) { text_rows = N; tv = cls_view; }
-    }
-    const size_t t_off16 = (size_t)Q * H * esz, t_off32 = (size_t)Q * H;
-    const int ng = text_rows > 0 ? 4 : 2;
-    {
-      GemmProb g[4] = {};
-      for (int l = 0; l < 2; ++l) {
-        GemmProb& q = g[l];                 // query problems first (they decide the tile), then the text problems
-        q.A = cross ? (const void*)w[l].hC16 : (const void*)w[l].hB16; q.a = cross ? qc_rows : q_view;
-        q.W = Lw[l]->wiq; q.bias = Lw[l]->biq; q.C = w[l].ffn16; q.c = plain(N * Q, I); q.M = N * Q; q.N = I; q.K = H;
-        GemmProb& t = g[2 + l];
-        t.A = w[l].hB16 + t_off16; t.a = tv; t.W = Lw[l]->wit; t.bias = Lw[l]->bit;
-        t.C = w[l].ffn16 + (size_t)N * Q * I * esz; t.c = plain(text_rows, I); t.M = text_rows; t.N = I; t.K = H;
-      }
-      if ((h0->chain_ring & 2) && N * Q >= 512 && I % 192 == 0) g[0].tile_cfg = 10;
-      if ((rc = launch_gemm(g, ng, EPI_GELU_OP, op, stream))) return chk(rc, "ffn up gemm (pair)");
-    }
-    {
-      GemmProb g[4] = {};
-      for (int l = 0; l < 2; ++l) {
-        GemmProb& q = g[l];
-        q.A = w[l].ffn16; q.a = plain(N * Q, I); q.W = Lw[l]->woq; q.bias = Lw[l]->boq;
-        q.R = cross ? w[l].hC32 : w[l].hB32; q.r = cross ? qc_rows : q_view;
-        q.C = w[l].pre32; q.c = q_view; q.M = N * Q; q.N = H; q.K = I;
-        GemmProb& t = g[2 + l];
-        t.A = w[l].ffn16 + (size_t)N * Q * I * esz; t.a = plain(text_rows, I); t.W = Lw[l]->wot; t.bias = Lw[l]->bot;
-        t.R = w[l].hB32 + t_off32; t.r = tv; t.C = w[l].pre32 + t_off32; t.c = tv; t.M = text_rows; t.N = H; t.K = I;
-      }
-      g[0].tile_cfg = N * Q >= 512 && I % 128 == 0 ? 6 : 0;
-      if ((h0->chain_ring & 4) && N * Q >= 512 && H % 96 == 0) g[0].tile_cfg = 11;
-      if ((rc = launch_gemm(g, ng, EPI_RES_F32, op, stream))) return chk(rc, "ffn down gemm (pair)");
-    }
-    if (!last) {
-      if (text_rows == N * L && L > 0) {
-        // query / text LayerNorms of both lanes: four parameter sets, one launch over the 2 N S rows
-        rc = launch_ln_rows4(w[0].pre32, all2, 2 * N * S, H, Lw[0]->lnqg, Lw[0]->lnqb, Lw[0]->lntg, Lw[0]->lntb, N * S, Lw[1]->lnqg, Lw[1]->lnqb, Lw[1]->lntg,
-                             Lw[1]->lntb, S, Q, c.ln_eps, w[0].hA32, all2, w[0].hA16, all2, op, stream);
-        if (rc) return chk(rc, "ffn ln (pair)");
-      } else {   // L == 0: query rows only (the whole stream)
-        rc = launch_ln_rows4(w[0].pre32, all2, 2 * N * S, H, Lw[0]->lnqg, Lw[0]->lnqb, nullptr, nullptr, N * S, Lw[1]->lnqg, Lw[1]->lnqb, nullptr, nullptr, 1, 1,
-                             c.ln_eps, w[0].hA32, all2, w[0].hA16, all2, op, stream);
-        if (rc) return chk(rc, "ffn query ln (pair)");
-      }
-    } else {
-      for (int l = 0; l < 2; ++l) {   // last layer: LayerNorm straight into the caller's buffers
-        if (outq[l]) {
-          rc = launch_ln_rows(w[l].pre32, q_view, N * Q, H, Lw[l]->lnqg, Lw[l]->lnqb, c.ln_eps, outq[l], qc_rows, nullptr, qc_rows, op, stream);
-          if (rc) return chk(rc, "final query ln (pair)");
-        }
-        if (outc[l]) {
-          rc = launch_ln_rows(w[l].pre32 + t_off32, cls_view, N, H, Lw[l]->lntg, Lw[l]->lntb, c.ln_eps, outc[l], plain(N, H), nullptr, plain(N, H), op, stream);
-          if (rc) return chk(rc, "final cls ln (pair)");
-        }
-      }
-    }
-  }
-  return MRA_OK;
+  return run_lanes(lanes, 2, input_ids, attention_mask, items, L, workspace, as_stream(stream_));
 }
 
 int mra_qformer_set_kv_events(mra_qformer* h, void* ev_start, void* ev_stop) {
@@ -1236,7 +1101,7 @@ int mra_qformer_set_cross_precision(mra_qformer* h, int32_t mode) {
   if (mode >= 1) {
     const mra_cfg& c = h->cfg;
     if (h->ncross == 0) return fail(MRA_EINVAL, "no cross-attention layers");
-    if (c.heads * c.n_query != 384 || h->sc_tile != 5 || !h->split_softmax)
+    if (!cross_plan(h, 1, true, false).softpart)   // (the form of a split-precision plan does not depend on kv)
       return fail(MRA_EINVAL, "split precision needs heads * n_query == 384 (the 176 x 384 scores tile)");
     if (!h->arena_p || (mode == 2 && !h->auto_hist)) {   // allocations happen on the handle's device
       int dev = 0;

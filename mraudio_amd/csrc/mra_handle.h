@@ -91,12 +91,8 @@ struct mra_qformer {
   // folded cross-attention (mra_qformer_set_cross_mode): per cross layer the key weight regrouped as [heads][E][64]
   char* arena_f = nullptr;
   bool fold_stale = true;
-  bool split_softmax = true;                      // scores GEMM writes exp2(s - tile max) + tile statistics (false: fp32 rows + row softmax)
-  bool inreg_rescale = true;                      // split softmax: the P . enc GEMM applies the row factors to its P~ fragments (false: a rescale pass over P; cross mode 5)
-  int sc_tile = 5;                                // scores: 5 = the 176 x 384 tile
-  bool pv_kmajor = true;                          // P . enc reads the encoder tokens themselves (K-major weights, no enc^T copy)
-  int pv_tile = 5;                                // P . enc: 5 = the 176 x 384 loader-wave tile (one workgroup per CU at E = 1408)
-  int fold_tile = 2;                              // GemmProb::tile_cfg of the two batched GEMMs (2 = 128 x 128, 4 = 128 x 384)
+  bool inreg_rescale = true;                      // the P . enc GEMM applies the softmax row factors to its P~ fragments (false: a rescale pass over P; cross mode 5)
+  int fold_tile = 2;                              // GemmProb::tile_cfg of the two batched GEMMs where the 176 x 384 tiles do not apply (2 = 128 x 128, 4 = 128 x 384)
   bool fold_stream = false;                       // folded path on the streaming kernels of fold_stream.hip (mra_qformer_set_cross_mode 4)
   int cross_mode = 0;                             // 0 automatic, 1 K/V cache, 2 folded
   // split-precision cross-attention (mra_qformer_set_cross_precision): hidden state, W_cq, Q, W_k and Q' of the score chain as operand-dtype
@@ -119,7 +115,6 @@ struct mra_qformer {
   // per-layer median p_max >= auto_tau_milli / 1000 resolves to split (cross_precise = 1), otherwise to op (cross_precise = 0)
   bool cross_auto = false;
   bool auto_stale = true;                         // a probe is pending (set wherever precise_stale is)
-  bool probe_fold = false;                        // inside the probing forward: folded form (in-register factors where they exist), probe kernels
   int auto_resolved = -1;                         // 0 op, 1 split, -1 never probed
   int auto_probes = 0;                            // probes run since create
   int auto_tau_milli = 500;                       // mra_qformer_set_option "auto_split_pmax_milli"
@@ -150,24 +145,35 @@ struct mra_qformer {
 };
 
 namespace mra_host {
-// folded cross-attention pays once the encoder sequence is long (fewer flops at any Kv, but five launches per layer)
-inline bool use_fold(const mra_qformer* h, int kv) { return h->cross_precise || h->probe_fold || h->cross_mode == 2 || (h->cross_mode == 0 && kv >= 2048); }
 // padded score-row length: whole 128- and 176-row tiles of the scores GEMM, and a multiple of 128 (K of P . enc)
-// P . enc on the 176 x 384 tile with K-major weights: no transposed copy of the encoder tokens is needed
-inline bool fold_kmajor(const mra_qformer* h) {
-  return h->pv_kmajor && h->pv_tile == 5 && h->cfg.heads * h->cfg.n_query == 384 && h->cfg.enc_width % 176 == 0;
-}
-// split softmax without the rescale pass: needs the 176-column score tiles and the K-major 176 x 384 P . enc tile
-inline bool fold_inreg_rescale(const mra_qformer* h) { return (h->inreg_rescale || h->probe_fold) && h->split_softmax && h->sc_tile == 5 && fold_kmajor(h); }
 inline int fold_kvp(int kv) { return (std::max((kv + 127) / 128 * 128, (kv + 175) / 176 * 176) + 127) / 128 * 128; }
-// the streaming kernels (fold_stream.hip): f16 operands, 384 (head, query) rows, E a multiple of 176
-inline bool fold_streams(const mra_qformer* h, int kv) {
-  return !h->cross_precise && !h->probe_fold && h->fold_stream && mra::fold_stream_supported(h->cfg.heads * h->cfg.n_query, h->cfg.enc_width, kv, fold_kvp(kv), h->op());
-}
 // split-precision cross-attention: bytes of one cross layer's prepared weights, W_cq [H][3H] then W_k [heads][E][192] (operand dtype)
 inline size_t precise_wk_off(const mra_qformer* h) { return align_up((size_t)h->cfg.hidden * 3 * h->cfg.hidden * 2); }
 inline size_t precise_layer_bytes(const mra_qformer* h) {
   return precise_wk_off(h) + align_up((size_t)h->cfg.heads * h->cfg.enc_width * 192 * 2);
+}
+// attention over the packed Q | K | V rows [items][S][3H] of a layer's self-attention; the context leaves as [items][S][H]
+inline AttnArgs self_attn_args(const mra_cfg& c, const void* qkv16, void* ctx16, const long long* mask, int items, int S, float* lse = nullptr) {
+  const int H = c.hidden;
+  AttnArgs a{};
+  a.Q = qkv16; a.K = (const char*)qkv16 + (size_t)H * 2; a.V = (const char*)qkv16 + (size_t)2 * H * 2; a.O = ctx16;
+  a.q_item_stride = a.k_item_stride = a.v_item_stride = (long long)S * 3 * H; a.q_ld = a.k_ld = a.v_ld = 3 * H;
+  a.k_head_stride = a.v_head_stride = 64; a.o_item_stride = (long long)S * H; a.o_ld = H;
+  a.mask = mask; a.mask_ld = S;
+  a.items = items; a.heads = c.heads; a.q_rows = S; a.kv_len = S; a.scale = 0.125f; a.nsplit = 1; a.lse = lse;
+  return a;
+}
+// cross-attention core of cross layer ci over the head-major K/V cache [ncross][k | v][items][heads][kv][64]: Q and the context [items][32][H]
+inline AttnArgs kv_cross_attn_args(const mra_cfg& c, const void* q16, const char* kv16, int ci, void* ctx16, int items, int kv, int nsplit,
+                                   float* part, float* lse = nullptr) {
+  const int H = c.hidden, Q = c.n_query;
+  const size_t per_sel = (size_t)items * c.heads * kv * 64 * 2;
+  AttnArgs a{};
+  a.Q = q16; a.K = kv16 + (size_t)(ci * 2 + 0) * per_sel; a.V = kv16 + (size_t)(ci * 2 + 1) * per_sel; a.O = ctx16;
+  a.q_item_stride = a.o_item_stride = (long long)Q * H; a.q_ld = a.o_ld = H;
+  a.k_item_stride = a.v_item_stride = (long long)c.heads * kv * 64; a.k_head_stride = a.v_head_stride = (long long)kv * 64; a.k_ld = a.v_ld = 64;
+  a.items = items; a.heads = c.heads; a.q_rows = Q; a.kv_len = kv; a.scale = 0.125f; a.nsplit = nsplit; a.part = part; a.lse = lse;
+  return a;
 }
 // K/V of every cross layer in ONE GEMM: [items*kv, E] x [ncross*2*H, E]^T, scattered head-major.
 int kv_project(const mra_qformer* h, const void* enc, int N, int kv, void* kv_cache, hipStream_t stream);

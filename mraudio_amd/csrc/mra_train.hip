@@ -356,28 +356,16 @@ int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const in
     char* nxt16 = i + 1 < c.layers ? t.layer[i + 1].hin16 : t.out16;
     if ((rc = X.gemm(b.hin16, all_rows, W.wqkv, W.bqkv, b.qkv16, plain(N * S, 3 * H), nullptr, all_rows, N * S, 3 * H, H, EPI_OP)))
       return chk(rc, "qkv gemm");
-    {
-      AttnArgs a{};
-      a.Q = b.qkv16; a.K = b.qkv16 + (size_t)H * 2; a.V = b.qkv16 + (size_t)2 * H * 2; a.O = b.ctx16;
-      a.q_item_stride = a.k_item_stride = a.v_item_stride = (long long)S * 3 * H; a.q_ld = a.k_ld = a.v_ld = 3 * H;
-      a.k_head_stride = a.v_head_stride = 64; a.o_item_stride = SH; a.o_ld = H;
-      a.mask = (const long long*)attention_mask; a.mask_ld = S;
-      a.items = N; a.heads = c.heads; a.q_rows = S; a.kv_len = S; a.scale = 0.125f; a.nsplit = 1; a.lse = b.lse_s;
-      if ((rc = launch_attention(a, op, stream))) return chk(rc, "self attention");
-    }
+    if ((rc = launch_attention(self_attn_args(c, b.qkv16, b.ctx16, (const long long*)attention_mask, N, S, b.lse_s), op, stream)))
+      return chk(rc, "self attention");
     if ((rc = X.gemm(b.ctx16, all_rows, W.wo, W.bo, b.pre1, all_rows, b.hin32, all_rows, N * S, H, H, EPI_RES_F32))) return chk(rc, "attn out gemm");
     if ((rc = launch_ln_rows(b.pre1, all_rows, N * S, H, W.ln1g, W.ln1b, c.ln_eps, b.h1_32, all_rows, b.h1_16, all_rows, op, stream)))
       return chk(rc, "attn ln");
     const void* fq16 = b.h1_16; const float* fq32 = b.h1_32; RowView fqv = q_view;
     if (W.cross_index >= 0) {
       if ((rc = X.gemm(b.h1_16, q_view, W.wcq, W.bcq, b.qc16, qc_rows, nullptr, qc_rows, N * Q, H, H, EPI_OP))) return chk(rc, "cross q gemm");
-      AttnArgs a{};
-      const size_t per_sel = (size_t)N * c.heads * kv * 64;
-      a.Q = b.qc16; a.K = t.kv16 + (size_t)(W.cross_index * 2) * per_sel * 2; a.V = t.kv16 + (size_t)(W.cross_index * 2 + 1) * per_sel * 2;
-      a.O = b.cctx16; a.q_item_stride = a.o_item_stride = (long long)Q * H; a.q_ld = a.o_ld = H;
-      a.k_item_stride = a.v_item_stride = (long long)c.heads * kv * 64; a.k_head_stride = a.v_head_stride = (long long)kv * 64; a.k_ld = a.v_ld = 64;
-      a.items = N; a.heads = c.heads; a.q_rows = Q; a.kv_len = kv; a.scale = 0.125f; a.nsplit = t.nsplit; a.part = t.part; a.lse = b.lse_c;
-      if ((rc = launch_attention(a, op, stream))) return chk(rc, "cross attention");
+      if ((rc = launch_attention(kv_cross_attn_args(c, b.qc16, t.kv16, W.cross_index, b.cctx16, N, kv, t.nsplit, t.part, b.lse_c), op, stream)))
+        return chk(rc, "cross attention");
       if ((rc = X.gemm(b.cctx16, qc_rows, W.wco, W.bco, b.pre2, qc_rows, b.h1_32, q_view, N * Q, H, H, EPI_RES_F32))) return chk(rc, "cross out gemm");
       if ((rc = launch_ln_rows(b.pre2, qc_rows, N * Q, H, W.lncg, W.lncb, c.ln_eps, b.hc32, qc_rows, b.hc16, qc_rows, op, stream))) return chk(rc, "cross ln");
       fq16 = b.hc16; fq32 = b.hc32; fqv = qc_rows;
