@@ -371,10 +371,9 @@ int mra_beats_set_option(mra_beats* h, const char* name, int32_t value);
 
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------
  * Number of GEMM launches of one main loop ("family") with one epilogue since the library was loaded; read-only, the only
- * process-wide state of the library.  Families (csrc/kernels.h GemmFamily): 0 / 1 two-buffer 64x64 / 128x128, 3 loader-wave 256x256,
- * 4 eight-phase 256x256, 5 / 6 loader-wave 128x384 / 176x384 (folded cross-attention), 7 / 10 128-deep 64x128 / 64x64,
- * 8 eight-phase 128x512 tail tile, 9 eight-phase full + tail tiles in one launch.  Epilogues (GemmEpi): 0 op-dtype, 1 GELU,
- * 2 fp32 residual, 3 fp32, 4 K/V cache, 5 softmax partials, 6 / 7 GELU forward + tape / GELU backward, 8 op-dtype residual.
+ * process-wide state of the library.  `family` is a GemmFamily and `epilogue` a GemmEpi of csrc/kernels.h (the numbers mraudio_amd/_lib.py
+ * repeats as GF_* and EPI_*): families 0 .. 13 -- the two-buffer, loader-wave, eight-phase, 128-deep and ring main loops, one per tile --
+ * and epilogues 0 .. 13.
  * Returns -1 for an unknown family / epilogue.  Used by the parity tests to state which kernel produced the numbers checked. */
 int64_t mra_debug_gemm_launches(int32_t family, int32_t epilogue);
 

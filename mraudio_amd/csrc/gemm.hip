@@ -24,6 +24,7 @@
 // tests/native/gemm_experiments.inc, outside the product tree and the shipped library; verdicts in DESIGN.md section 8.
 #include <atomic>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <set>
 #include <type_traits>
@@ -1552,7 +1553,7 @@ inline int counted(int family, int epi, int rc) {
 }
 
 #ifdef MRA_GEMM_EXPERIMENTS
-int g_force_cfg = -1;
+int g_force_tile = GT_AUTO;
 int g_variant = 5;  // 5 (default): warp-specialised 256x256, two-buffer small tiles (128-deep for K >= 2048);
                     // 1: two-buffer loop everywhere; other values: gemm_experiments.inc (experiment builds only)
 unsigned long long* g_dbg = nullptr;
@@ -1560,7 +1561,7 @@ int g_p8 = 1;       // the eight-phase kernel for the 256 x 256 tile when K / 64
 int g_order = 0;
 #else
 // the shipped library: no switches, the defaults are constants
-constexpr int g_force_cfg = -1, g_variant = 5, g_p8 = 1, g_order = 0;
+constexpr int g_force_tile = GT_AUTO, g_variant = 5, g_p8 = 1, g_order = 0;
 constexpr unsigned long long* g_dbg = nullptr;
 #endif
 
@@ -1579,206 +1580,223 @@ bool ensure_lds(const void* fn, size_t lds) {
 }
 
 template <typename KFN>
-int launch_k(KFN kfn, const GemmArgs& a, int threads, size_t lds, hipStream_t stream) {
+int launch_k(KFN kfn, const GemmArgs& a, int threads, size_t lds, hipStream_t stream, int grid = 0) {   // grid 0: one workgroup per tile
   if (lds > 64 * 1024 && !ensure_lds((const void*)kfn, lds)) return -3;
-  hipLaunchKernelGGL(kfn, dim3(a.total_tiles), dim3(threads), lds, stream, a);
+  hipLaunchKernelGGL(kfn, dim3(grid ? grid : a.total_tiles), dim3(threads), lds, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-#define MRA_EPI_SWITCH(KERNEL_EXPR)                         \
-  switch (epi) {                                            \
-    case EPI_OP: { constexpr int E = EPI_OP; return KERNEL_EXPR; }           \
-    case EPI_GELU_OP: { constexpr int E = EPI_GELU_OP; return KERNEL_EXPR; } \
-    case EPI_RES_F32: { constexpr int E = EPI_RES_F32; return KERNEL_EXPR; } \
-    case EPI_F32: { constexpr int E = EPI_F32; return KERNEL_EXPR; }         \
-    case EPI_KV: { constexpr int E = EPI_KV; return KERNEL_EXPR; }           \
-    case EPI_GELU_BOTH: { constexpr int E = EPI_GELU_BOTH; return KERNEL_EXPR; } \
-    case EPI_GELU_BWD: { constexpr int E = EPI_GELU_BWD; return KERNEL_EXPR; }   \
-    case EPI_RES_OP: { constexpr int E = EPI_RES_OP; return KERNEL_EXPR; }       \
-    default: return -2;                                     \
-  }
-
-template <typename T, int TN, int TM, int WGN, int WGM>
-int launch_v1(const GemmArgs& a, int epi, hipStream_t stream) {
-  constexpr size_t lds = 2 * (TN + TM) * 128;
-  MRA_EPI_SWITCH((launch_k(gemm_kernel<T, TN, TM, WGN, WGM, E>, a, WGN * WGM * 64, lds, stream)))
+// The epilogues a kernel family is instantiated for, named once: with_epi turns the runtime `epi` into a compile-time constant of the list
+// (-2: the list has no such epilogue) and epi_mask feeds the tile table, so "has this epilogue" is answered before the launch.
+template <int... E> using Epis = std::integer_sequence<int, E...>;
+template <int... E> constexpr unsigned epi_mask(Epis<E...>) { return (0u | ... | (1u << E)); }
+constexpr bool has_epi(unsigned mask, int epi) { return epi >= 0 && epi < 16 && (mask >> epi & 1); }
+template <int... E, typename F>
+int with_epi(Epis<E...>, int epi, F&& f) {
+  int rc = -2;
+  (void)((epi == E && ((rc = f(std::integral_constant<int, E>{})), true)) || ...);
+  return rc;
 }
+using EpiDirect = Epis<EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_GELU_BOTH, EPI_GELU_BWD, EPI_RES_OP>;   // two-buffer, 128-deep and 256 x 256 loader-wave loops
+#ifdef MRA_GEMM_EXPERIMENTS
+using EpiV1_256 = EpiDirect;   // gemm_force_variant(1)
+#else
+using EpiV1_256 = Epis<>;      // the shipped dispatcher never resolves GT_256 to the two-buffer loop
+#endif
+using EpiP8 = Epis<EPI_OP, EPI_GELU_OP, EPI_KV, EPI_RES_OP, EPI_RES_OP_STAT, EPI_RES_F32, EPI_RES_F32_STAT, EPI_LNF_OP, EPI_LNF_GELU_OP, EPI_F32>;
+using EpiP8Persist = Epis<EPI_OP, EPI_GELU_OP, EPI_LNF_OP, EPI_LNF_GELU_OP, EPI_KV>;   // the staged epilogues; the direct ones run one workgroup per tile
+using EpiP8Tail = Epis<EPI_RES_OP, EPI_RES_F32, EPI_F32>;
+using EpiP8Mixed = Epis<EPI_OP, EPI_RES_OP, EPI_RES_OP_STAT, EPI_RES_F32, EPI_RES_F32_STAT, EPI_F32>;   // EPI_OP: the ViT's un-padded QKV (N = 4224)
+using EpiWs128 = Epis<EPI_OP, EPI_F32>;
+using EpiWs176 = Epis<EPI_F32, EPI_SOFTPART, EPI_OP>;   // K-major weights (w_ld): EPI_OP only
+using EpiRing16 = Epis<EPI_OP, EPI_GELU_OP>;           // 144 x 128, 192 x 128: a staged fp32 tile does not fit beside the group reduction in the ring's LDS
+using EpiRing96 = Epis<EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_RES_LN>;   // EPI_RES_LN: the residual projections' tile only
 
-template <typename T>
-int launch_ws(const GemmArgs& a, int epi, hipStream_t stream) {
-  constexpr size_t lds = 2 * (256 + 256) * 128;
-  MRA_EPI_SWITCH((launch_k(gemm_ws_kernel<T, E>, a, 768, lds, stream)))
-}
-
-template <typename T>
-int launch_p8(const GemmArgs& a, int epi, hipStream_t stream, bool tail = false) {
-  constexpr size_t lds = 2 * (256 + 256) * 128 + 8 * 256;   // two K-tile buffers; the staged epilogues keep the tile's bias values behind the 128 KB tile image
-  if (tail) {   // 128 x 512 tile: 2 x 80 KB
-    constexpr size_t ldst = 2 * (128 + 512) * 128;
-    switch (epi) {
-      case EPI_RES_OP: return launch_k(gemm_p8_kernel<T, EPI_RES_OP, true>, a, 512, ldst, stream);
-      case EPI_RES_OP_STAT: return launch_k(gemm_p8_kernel<T, EPI_RES_OP_STAT, true>, a, 512, ldst, stream);
-      case EPI_RES_F32: return launch_k(gemm_p8_kernel<T, EPI_RES_F32, true>, a, 512, ldst, stream);
-      case EPI_RES_F32_STAT: return launch_k(gemm_p8_kernel<T, EPI_RES_F32_STAT, true>, a, 512, ldst, stream);
-      case EPI_F32: return launch_k(gemm_p8_kernel<T, EPI_F32, true>, a, 512, ldst, stream);
-      default: return -2;
-    }
-  }
-  if (a.p[0].persist && a.ngroups == 1 && a.p[0].batch <= 1) {   // one workgroup per CU (the grid must be a multiple of the 8 XCDs for the remap to hold)
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 8 && a.total_tiles > cus) {
-      const int grid = cus & ~7;
-      auto go = [&](auto kfn) {
-        if (!ensure_lds((const void*)kfn, lds)) return -3;
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, stream, a);
-        return hipGetLastError() == hipSuccess ? 0 : -4;
-      };
-      switch (epi) {
-        case EPI_OP: return go(gemm_p8_persist_kernel<T, EPI_OP>);
-        case EPI_GELU_OP: return go(gemm_p8_persist_kernel<T, EPI_GELU_OP>);
-        case EPI_LNF_OP: return go(gemm_p8_persist_kernel<T, EPI_LNF_OP>);
-        case EPI_LNF_GELU_OP: return go(gemm_p8_persist_kernel<T, EPI_LNF_GELU_OP>);
-        case EPI_KV: return go(gemm_p8_persist_kernel<T, EPI_KV>);
-        default: break;   // the direct epilogues: one workgroup per tile
-      }
-    }
-  }
-  switch (epi) {
-    case EPI_OP: return launch_k(gemm_p8_kernel<T, EPI_OP>, a, 512, lds, stream);
-    case EPI_GELU_OP: return launch_k(gemm_p8_kernel<T, EPI_GELU_OP>, a, 512, lds, stream);
-    case EPI_KV: return launch_k(gemm_p8_kernel<T, EPI_KV>, a, 512, lds, stream);
-    case EPI_RES_OP: return launch_k(gemm_p8_kernel<T, EPI_RES_OP>, a, 512, lds, stream);
-    case EPI_RES_OP_STAT: return launch_k(gemm_p8_kernel<T, EPI_RES_OP_STAT>, a, 512, lds, stream);
-    case EPI_RES_F32: return launch_k(gemm_p8_kernel<T, EPI_RES_F32>, a, 512, lds, stream);
-    case EPI_RES_F32_STAT: return launch_k(gemm_p8_kernel<T, EPI_RES_F32_STAT>, a, 512, lds, stream);
-    case EPI_LNF_OP: return launch_k(gemm_p8_kernel<T, EPI_LNF_OP>, a, 512, lds, stream);
-    case EPI_LNF_GELU_OP: return launch_k(gemm_p8_kernel<T, EPI_LNF_GELU_OP>, a, 512, lds, stream);
-    case EPI_F32: return launch_k(gemm_p8_kernel<T, EPI_F32>, a, 512, lds, stream);
-    default: return -100;
-  }
-}
-
-template <typename T>
-int launch_ws_fold(const GemmArgs& a, int epi, hipStream_t stream) {   // 128 (weight rows) x 384 (activation rows)
-  constexpr size_t lds = 2 * (128 + 384) * 128;
-  switch (epi) {
-    case EPI_OP: return launch_k(gemm_ws_kernel<T, EPI_OP, false, 128, 384>, a, 768, lds, stream);
-    case EPI_F32: return launch_k(gemm_ws_kernel<T, EPI_F32, false, 128, 384>, a, 768, lds, stream);
-    default: return -2;
-  }
-}
-
-template <typename T>
-int launch_ws_pv(const GemmArgs& a, int epi, hipStream_t stream) {   // 176 (weight rows) x 384 (activation rows), 1 x 8 waves
-  constexpr size_t lds = 2 * (176 + 384) * 128;
-  if (a.p[0].w_ld > 0) {   // K-major weights (P . enc straight from the encoder tokens)
-    if (epi != EPI_OP) return -2;
-    if (a.p[0].pscale) {
-      if (a.p[0].M > 384 || a.p[0].ps_ntiles <= 0) return -1;   // one row tile: the factor slice is indexed by the row inside the tile
-      return launch_k(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true, true>, a, 768, lds + 4 * 2048, stream);
-    }
-    return launch_k(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true>, a, 768, lds, stream);
-  }
-  // the slab (weight-side rows) is read by this workgroup only: non-temporal loads (7.40 -> 7.17 ms / step)
-  if (epi == EPI_F32) return launch_k(gemm_ws_kernel<T, EPI_F32, false, 176, 384, 8, true>, a, 768, lds, stream);
-  if (epi == EPI_SOFTPART) return launch_k(gemm_ws_kernel<T, EPI_SOFTPART, false, 176, 384, 8, true>, a, 768, lds, stream);
-  if (epi == EPI_OP) return launch_k(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true>, a, 768, lds, stream);
-  return -2;
-}
-
-template <typename T, int TN, int TM, int WGN, int WGM>
-int launch_k128(const GemmArgs& a, int epi, hipStream_t stream) {
-  constexpr size_t lds = 2 * (TN + TM) * 256;
-  MRA_EPI_SWITCH((launch_k(gemm_k128_kernel<T, TN, TM, WGN, WGM, E>, a, WGN * WGM * 64, lds, stream)))
-}
-
-// the ring tiles (GemmProb::tile_cfg 9 / 10 / 11): 144 x 128, 192 x 128, 96 x 64 on 2 x 4 waves.  An epilogue whose staged tile does not fit
-// beside the group reduction in the ring's LDS (fp32 outputs of the two large tiles) is refused.
 template <int TN, int TM, int WGN, int WGM, int STAGES, int EPI>
 constexpr bool ring_fits() {
   constexpr int osz = (EPI == EPI_RES_F32 || EPI == EPI_F32 || EPI == EPI_RES_LN) ? 4 : 2;
-  return WGN * WGM * (TN / WGN / 16) * (TM / WGM / 16) * 1024 + TM * (TN * osz + 16) <= STAGES * (TN + TM) * 128;
+  return WGN * WGM * (TN / WGN / 16) * (TM / WGM / 16) * 1024 + TM * (TN * osz + 16) <= STAGES * (TN + TM) * 128 && STAGES * (TN + TM) * 128 <= 160 * 1024;
 }
-template <typename T, int TN, int TM, int WGN, int WGM, int STAGES, int EPI>
-int launch_ring_epi(const GemmArgs& a, hipStream_t stream) {
-  if constexpr (ring_fits<TN, TM, WGN, WGM, STAGES, EPI>()) {
-    return launch_k(gemm_ring_kernel<T, TN, TM, WGN, WGM, STAGES, EPI>, a, 2 * WGN * WGM * 64, (size_t)STAGES * (TN + TM) * 128, stream);
-  } else {
-    return -2;
-  }
-}
-template <typename T, int TN, int TM, int WGN, int WGM, int STAGES>
-int launch_ring(const GemmArgs& a, int epi, hipStream_t stream) {
-  static_assert((size_t)STAGES * (TN + TM) * 128 <= 160 * 1024, "ring must fit the LDS");
-  switch (epi) {
-    case EPI_OP: return launch_ring_epi<T, TN, TM, WGN, WGM, STAGES, EPI_OP>(a, stream);
-    case EPI_GELU_OP: return launch_ring_epi<T, TN, TM, WGN, WGM, STAGES, EPI_GELU_OP>(a, stream);
-    case EPI_RES_F32: return launch_ring_epi<T, TN, TM, WGN, WGM, STAGES, EPI_RES_F32>(a, stream);
-    case EPI_F32: return launch_ring_epi<T, TN, TM, WGN, WGM, STAGES, EPI_F32>(a, stream);
-    case EPI_RES_LN:
-      if constexpr (TN == 96) return launch_ring_epi<T, TN, TM, WGN, WGM, STAGES, EPI_RES_LN>(a, stream);   // the residual projections' tile only
-      else return -2;
-    default: return -2;
-  }
-}
+template <int TN, int TM, int WGN, int WGM, int STAGES, int... E>
+constexpr bool ring_fits(Epis<E...>) { return (ring_fits<TN, TM, WGN, WGM, STAGES, E>() && ...); }
+static_assert(ring_fits<144, 128, 1, 4, 4>(EpiRing16{}) && !ring_fits<144, 128, 1, 4, 4, EPI_F32>(), "ring 144 x 128");
+static_assert(ring_fits<192, 128, 2, 2, 4>(EpiRing16{}) && !ring_fits<192, 128, 2, 2, 4, EPI_F32>(), "ring 192 x 128");
+static_assert(ring_fits<96, 64, 2, 2, 7>(EpiRing96{}), "ring 96 x 64");
+
+// One row per kernel family (indexed by GemmFamily), i.e. per GemmTile and, where a tile resolves to one of several main loops (pick_family),
+// per alternative: everything the host side knows about a tile.
+enum : unsigned {
+  T_RAGGED = 1, T_MASK = 2, T_BATCH = 4, T_GROUPS = 8,   // n_ragged / n_mask / batch > 1 / more than one problem allowed
+  T_WLD = 16, T_KWRAP = 32,                              // K-major weights (and pscale) / w_kwrap allowed
+  T_F32_16B = 64,                                        // fp32 outputs leave as 16-byte pieces too
+  T_PLAIN = T_RAGGED | T_MASK | T_BATCH | T_GROUPS,
+};
+struct TileDesc {
+  int tile;          // GemmTile this family serves
+  int tn, tm;        // weight rows, activation rows per tile
+  int threads, lds;  // block size, dynamic LDS bytes
+  int kstep;         // K must be a multiple of this
+  unsigned allow;    // T_*
+  unsigned epis;     // bit per GemmEpi
+};
+constexpr TileDesc kTiles[GEMM_FAMILIES] = {
+    /* GF_V1_64        */ {GT_64, 64, 64, 256, 2 * (64 + 64) * 128, 64, T_PLAIN, epi_mask(EpiDirect{})},
+    /* GF_V1_128       */ {GT_128, 128, 128, 256, 2 * (128 + 128) * 128, 64, T_PLAIN, epi_mask(EpiDirect{})},
+    /* GF_V1_256       */ {GT_256, 256, 256, 512, 2 * (256 + 256) * 128, 64, T_PLAIN, epi_mask(EpiV1_256{})},
+    /* GF_WS_256       */ {GT_256, 256, 256, 768, 2 * (256 + 256) * 128, 64, T_PLAIN, epi_mask(EpiDirect{})},
+    /* GF_P8_256       */ {GT_256, 256, 256, 512, 2 * (256 + 256) * 128 + 8 * 256, 128, T_PLAIN, epi_mask(EpiP8{})},   // the staged epilogues keep the tile's bias values behind the 128 KB tile image
+    /* GF_WS_128x384   */ {GT_WS_128x384, 128, 384, 768, 2 * (128 + 384) * 128, 64, T_PLAIN | T_KWRAP, epi_mask(EpiWs128{})},
+    /* GF_WS_176x384   */ {GT_WS_176x384, 176, 384, 768, 2 * (176 + 384) * 128, 64, T_PLAIN | T_KWRAP | T_WLD, epi_mask(EpiWs176{})},   // + 8 KB of row factors with pscale
+    /* GF_K128_64x128  */ {GT_K128_64x128, 64, 128, 256, 2 * (64 + 128) * 256, 128, T_PLAIN, epi_mask(EpiDirect{})},
+    /* GF_P8_TAIL      */ {GT_P8_TAIL, 128, 512, 512, 2 * (128 + 512) * 128, 128, T_GROUPS, epi_mask(EpiP8Tail{})},     // N = 128 exactly
+    /* GF_P8_MIXED     */ {GT_P8_MIXED, 256, 256, 512, 2 * (128 + 512) * 128, 128, 0, epi_mask(EpiP8Mixed{})},          // N = 256 k + 128 >= 384; the last column tile is 128 x 512
+    /* GF_K128_64x64   */ {GT_64, 64, 64, 256, 2 * (64 + 64) * 256, 128, T_PLAIN, epi_mask(EpiDirect{})},
+    /* GF_RING_144x128 */ {GT_RING_144x128, 144, 128, 512, 4 * (144 + 128) * 128, 64, T_GROUPS | T_F32_16B, epi_mask(EpiRing16{})},   // 1 x 4 waves per group: a wave holds all 144 weight rows x 32 activation rows
+    /* GF_RING_192x128 */ {GT_RING_192x128, 192, 128, 512, 4 * (192 + 128) * 128, 64, T_GROUPS | T_F32_16B, epi_mask(EpiRing16{})},
+    /* GF_RING_96x64   */ {GT_RING_96x64, 96, 64, 512, 7 * (96 + 64) * 128, 64, T_GROUPS | T_F32_16B, epi_mask(EpiRing96{})},
+};
 
 #ifdef MRA_GEMM_EXPERIMENTS
 #include "gemm_experiments.inc"
 #endif
 
 template <typename T>
-int launch_t(const GemmArgs& a, int cfg, int epi, hipStream_t stream) {
-  if (cfg == 8) return counted(GF_RING_144x128, epi, launch_ring<T, 144, 128, 1, 4, 4>(a, epi, stream));   // a wave: all 144 weight rows x 32 activation rows
-  if (cfg == 9) return counted(GF_RING_192x128, epi, launch_ring<T, 192, 128, 2, 2, 4>(a, epi, stream));
-  if (cfg == 10) return counted(GF_RING_96x64, epi, launch_ring<T, 96, 64, 2, 2, 7>(a, epi, stream));
-  if (cfg == 3) return counted(GF_WS_128x384, epi, launch_ws_fold<T>(a, epi, stream));
-  if (cfg == 4) return counted(GF_WS_176x384, epi, launch_ws_pv<T>(a, epi, stream));
-  if (cfg == 5) return counted(GF_K128_64x128, epi, launch_k128<T, 64, 128, 2, 2>(a, epi, stream));   // 64 weight rows x 128 activation rows, 128-deep steps
-  if (cfg == 6) return counted(GF_P8_TAIL, epi, launch_p8<T>(a, epi, stream, true));              // 128 weight rows x 512 activation rows, eight phases
-  if (cfg == 7) {                                                        // N = 256 k + 128: full tiles + one 128 x 512 tail tile per pair of row tiles
-    constexpr size_t ldst = 2 * (128 + 512) * 128;
-    switch (epi) {
-      case EPI_OP: return counted(GF_P8_MIXED, epi, launch_k(gemm_p8_mixed_kernel<T, EPI_OP>, a, 512, ldst, stream));   // the ViT's un-padded QKV (N = 4224)
-      case EPI_RES_OP: return counted(GF_P8_MIXED, epi, launch_k(gemm_p8_mixed_kernel<T, EPI_RES_OP>, a, 512, ldst, stream));
-      case EPI_RES_OP_STAT: return counted(GF_P8_MIXED, epi, launch_k(gemm_p8_mixed_kernel<T, EPI_RES_OP_STAT>, a, 512, ldst, stream));
-      case EPI_RES_F32: return counted(GF_P8_MIXED, epi, launch_k(gemm_p8_mixed_kernel<T, EPI_RES_F32>, a, 512, ldst, stream));
-      case EPI_RES_F32_STAT: return counted(GF_P8_MIXED, epi, launch_k(gemm_p8_mixed_kernel<T, EPI_RES_F32_STAT>, a, 512, ldst, stream));
-      case EPI_F32: return counted(GF_P8_MIXED, epi, launch_k(gemm_p8_mixed_kernel<T, EPI_F32>, a, 512, ldst, stream));
-      default: return -2;
-    }
-  }
-#ifdef MRA_GEMM_EXPERIMENTS
-  if (g_variant != 5 && g_variant != 1) {
-    const int rc = launch_experiment<T>(a, cfg, epi, g_variant, stream);
-    if (rc != -100) return rc;
-  }
-#endif
-  if (g_variant != 1) {
-    if (cfg == 2) {
-      bool even = true;
-      for (int g = 0; g < a.ngroups; ++g) even = even && (a.p[g].K / 64) % 2 == 0 && a.p[g].K >= 128;
-      if (g_p8 && even) {
-        const int rc = launch_p8<T>(a, epi, stream);
-        if (rc != -100) return counted(GF_P8_256, epi, rc);
+int launch_family(const GemmPlan& pl, int epi, hipStream_t stream) {
+  const GemmArgs& a = pl.args;
+  auto go = [&](auto kfn) { return launch_k(kfn, a, pl.threads, pl.lds, stream, pl.grid); };
+  switch (pl.family) {
+    case GF_V1_64: return with_epi(EpiDirect{}, epi, [&](auto e) { return go(gemm_kernel<T, 64, 64, 2, 2, e()>); });
+    case GF_V1_128: return with_epi(EpiDirect{}, epi, [&](auto e) { return go(gemm_kernel<T, 128, 128, 2, 2, e()>); });
+    case GF_V1_256: return with_epi(EpiV1_256{}, epi, [&](auto e) { return go(gemm_kernel<T, 256, 256, 2, 4, e()>); });
+    case GF_WS_256: return with_epi(EpiDirect{}, epi, [&](auto e) { return go(gemm_ws_kernel<T, e()>); });
+    case GF_P8_256:
+      if (pl.persistent) return with_epi(EpiP8Persist{}, epi, [&](auto e) { return go(gemm_p8_persist_kernel<T, e()>); });
+      return with_epi(EpiP8{}, epi, [&](auto e) { return go(gemm_p8_kernel<T, e()>); });
+    case GF_WS_128x384: return with_epi(EpiWs128{}, epi, [&](auto e) { return go(gemm_ws_kernel<T, e(), false, 128, 384>); });
+    case GF_WS_176x384:
+      if (a.p[0].w_ld > 0) {   // K-major weights (P . enc straight from the encoder tokens); EPI_OP (tile_rules)
+        if (a.p[0].pscale) return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true, true>);
+        return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true>);
       }
-      return counted(GF_WS_256, epi, launch_ws<T>(a, epi, stream));
-    }
-    if (cfg == 0) {
-      // 128-deep steps pay on the 64x64 tile once the K loop is long (FFN down-projection, K = 3072:
-      // 367 -> 460 TF/s); at K = 768 the launch is prologue/epilogue-bound and nothing changes
-      bool k128 = true;
-      for (int g = 0; g < a.ngroups; ++g) k128 = k128 && a.p[g].K % 128 == 0 && a.p[g].K >= 2048;
-      if (k128) return counted(GF_K128_64x64, epi, launch_k128<T, 64, 64, 2, 2>(a, epi, stream));
-    }
+      // the slab (weight-side rows) is read by this workgroup only: non-temporal loads (7.40 -> 7.17 ms / step)
+      return with_epi(EpiWs176{}, epi, [&](auto e) { return go(gemm_ws_kernel<T, e(), false, 176, 384, 8, true>); });
+    case GF_K128_64x128: return with_epi(EpiDirect{}, epi, [&](auto e) { return go(gemm_k128_kernel<T, 64, 128, 2, 2, e()>); });
+    case GF_P8_TAIL: return with_epi(EpiP8Tail{}, epi, [&](auto e) { return go(gemm_p8_kernel<T, e(), true>); });
+    case GF_P8_MIXED: return with_epi(EpiP8Mixed{}, epi, [&](auto e) { return go(gemm_p8_mixed_kernel<T, e()>); });
+    // 128-deep steps pay on the 64x64 tile once the K loop is long (FFN down-projection, K = 3072:
+    // 367 -> 460 TF/s); at K = 768 the launch is prologue/epilogue-bound and nothing changes
+    case GF_K128_64x64: return with_epi(EpiDirect{}, epi, [&](auto e) { return go(gemm_k128_kernel<T, 64, 64, 2, 2, e()>); });
+    case GF_RING_144x128: return with_epi(EpiRing16{}, epi, [&](auto e) { return go(gemm_ring_kernel<T, 144, 128, 1, 4, 4, e()>); });
+    case GF_RING_192x128: return with_epi(EpiRing16{}, epi, [&](auto e) { return go(gemm_ring_kernel<T, 192, 128, 2, 2, 4, e()>); });
+    case GF_RING_96x64: return with_epi(EpiRing96{}, epi, [&](auto e) { return go(gemm_ring_kernel<T, 96, 64, 2, 2, 7, e()>); });
   }
-  if (cfg == 2) return counted(GF_V1_256, epi, launch_v1<T, 256, 256, 2, 4>(a, epi, stream));
-  if (cfg == 1) return counted(GF_V1_128, epi, launch_v1<T, 128, 128, 2, 2>(a, epi, stream));
-  return counted(GF_V1_64, epi, launch_v1<T, 64, 64, 2, 2>(a, epi, stream));
+  return -2;
 }
 
-constexpr int kTile[3] = {64, 128, 256};
-constexpr int kTileN[11] = {64, 128, 256, 128, 176, 64, 128, 256, 144, 192, 96};   // weight rows per tile (config 7: 256, then 128 for the last column tile)
-constexpr int kTileM[11] = {64, 128, 256, 384, 384, 128, 512, 256, 128, 128, 64};   // activation rows per tile (config 3: explicit only, GemmProb::tile_cfg = 4)
+template <typename T>
+int launch_t(const GemmPlan& pl, int epi, hipStream_t stream) {
+#ifdef MRA_GEMM_EXPERIMENTS
+  int rc;   // an experiment's main loop in place of the plan's family (not counted)
+  if (g_variant != 5 && g_variant != 1 && pl.tile <= GT_256 && launch_experiment<T>(pl.args, pl.tile, epi, g_variant, stream, &rc)) return rc;
+#endif
+  return counted(pl.family, epi, launch_family<T>(pl, epi, stream));
+}
+
+// CU count of the current device (0: unknown), asked once per device
+int device_cus() {
+  static std::atomic<int> memo[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  int cus = memo[dev].load(std::memory_order_relaxed);
+  if (!cus && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) memo[dev].store(cus, std::memory_order_relaxed);
+  return cus;
+}
+
+// Largest of the three square tiles that still gives every CU work: 256 CUs; aim for >= 2 waves of workgroups with the 128 tile and
+// >= 1 full wave with the 256 tile.
+int pick_tile(const GemmProb* probs, int ngroups) {
+  if (g_force_tile > GT_AUTO) return g_force_tile;
+  if (probs[0].tile_cfg > GT_AUTO) return probs[0].tile_cfg;
+  for (int t : {256, 128}) {
+    long long tiles = 0;
+    bool ok = true;
+    for (int g = 0; g < ngroups; ++g) {
+      if (probs[g].N % t && !probs[g].n_ragged && !probs[g].n_mask) ok = false;
+      tiles += (long long)((probs[g].M + t - 1) / t) * ((probs[g].N + t - 1) / t) * (probs[g].batch > 1 ? probs[g].batch : 1);
+    }
+    if (ok && tiles >= (t == 256 ? 512 : 384)) return t == 256 ? GT_256 : GT_128;
+  }
+  return GT_64;
+}
+
+// The main loop behind a tile.  GT_256: eight phases when every problem has an even number of K steps and the epilogue exists there, else the
+// loader-wave kernel.  GT_64: 128-deep steps once the K loop is long.  Every other tile has one.
+int pick_family(int tile, const GemmProb* probs, int ngroups, int epi) {
+  bool even = true, deep = true;
+  for (int g = 0; g < ngroups; ++g) {
+    even = even && probs[g].K % 128 == 0;
+    deep = deep && probs[g].K % 128 == 0 && probs[g].K >= 2048;
+  }
+  if (tile == GT_256) {
+    if (g_variant == 1) return GF_V1_256;
+    return g_p8 && even && has_epi(kTiles[GF_P8_256].epis, epi) ? GF_P8_256 : GF_WS_256;
+  }
+  if (tile == GT_64 && g_variant != 1 && deep) return GF_K128_64x64;
+  for (int f = 0; f < GEMM_FAMILIES; ++f)
+    if (kTiles[f].tile == tile) return f;
+  return -1;
+}
+
+inline bool misaligned(const RowView& v, int mask) { return (v.ld & mask) || (v.item_stride & mask); }
+
+// what holds for every launch
+bool operand_rules(const GemmProb& p, int epi) {
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.K % 64 || p.batch < 0) return false;
+  if (p.a.rpi <= 0 || (epi != EPI_KV && p.c.rpi <= 0)) return false;
+  if ((epi == EPI_OP || epi == EPI_GELU_OP || epi == EPI_RES_OP) && misaligned(p.c, 7)) return false;   // 16-byte stores
+  if (p.n_ragged && (p.bias || p.n_mask)) return false;
+  if (p.n_mask && (p.N & 3)) return false;
+  return true;
+}
+
+// what an epilogue needs from the problem
+bool epilogue_rules(const GemmProb& p, int ngroups, int epi) {
+  const bool f32 = epi == EPI_RES_F32 || epi == EPI_F32;
+  if (p.n_mask && !f32 && ((epi != EPI_RES_OP && epi != EPI_OP && epi != EPI_GELU_OP) || (p.N & 63))) return false;   // the 16-bit epilogues leave in 64-column blocks
+  if (p.n_ragged && (epi == EPI_KV || epi == EPI_RES_F32)) return false;
+  switch (epi) {
+    case EPI_KV: return p.kv_tokens > 0 && p.kv_heads > 0 && p.kv_items > 0;
+    case EPI_RES_F32: return p.R && p.r.rpi > 0;
+    case EPI_RES_OP: return p.aux && !p.n_ragged;
+    case EPI_GELU_BOTH:
+    case EPI_GELU_BWD: return p.aux && !misaligned(p.c, 3) && !p.n_ragged;
+    case EPI_SOFTPART: return p.stat_m && p.stat_l && !p.bias && !(p.c.ld & 3);
+    case EPI_RES_LN:
+      return p.R && p.r.rpi > 0 && p.ln_gain && p.ln_bias && p.ln_counter && (p.ln_y32 || p.ln_y16) && p.N % 256 == 0 && p.N <= 1024 &&
+             (!p.ln_y32 || (p.ln_y32v.rpi > 0 && !misaligned(p.ln_y32v, 3))) && (!p.ln_y16 || (p.ln_y16v.rpi > 0 && !misaligned(p.ln_y16v, 3)));
+    case EPI_RES_F32_STAT:
+    case EPI_RES_OP_STAT:
+    case EPI_LNF_OP:
+    case EPI_LNF_GELU_OP:   // one plain problem
+      if (ngroups != 1 || p.batch > 1 || p.n_mask || p.n_ragged || !p.ln_y32) return false;
+      if (epi == EPI_RES_OP_STAT) return p.N % 64 == 0 && p.aux && !misaligned(p.c, 7);
+      if (epi == EPI_RES_F32_STAT) return p.R && p.r.rpi > 0 && p.N % 128 == 0 && p.ln_y16 && p.ln_y16v.rpi > 0 && !misaligned(p.ln_y16v, 7) && !misaligned(p.c, 3);
+      return p.ln_gain && !misaligned(p.c, 7);
+  }
+  return true;
+}
+
+// what the tile needs from the problem (the table), short of having the epilogue
+bool tile_rules(const TileDesc& d, int family, const GemmProb& p, int ngroups, int epi) {
+  if (p.K % d.kstep) return false;
+  if ((p.n_ragged && !(d.allow & T_RAGGED)) || (p.n_mask && !(d.allow & T_MASK)) || (p.batch > 1 && !(d.allow & T_BATCH)) || (ngroups > 1 && !(d.allow & T_GROUPS))) return false;
+  if (family == GF_P8_TAIL ? p.N != 128 : family == GF_P8_MIXED ? (p.N % 256 != 128 || p.N < 384) : (p.N % d.tn && !p.n_ragged && !p.n_mask)) return false;
+  if ((d.allow & T_F32_16B) && (epi == EPI_RES_F32 || epi == EPI_F32 || epi == EPI_RES_LN) && misaligned(p.c, 3)) return false;
+  if (p.w_ld && (!(d.allow & T_WLD) || epi != EPI_OP || (p.w_ld & 7) || p.k_rows <= 0 || p.N % d.tn)) return false;
+  if (p.w_kwrap && (!(d.allow & T_KWRAP) || p.w_kwrap < 0 || p.w_ld || 2 * p.w_kwrap * 64 != p.K)) return false;   // K = 2 passes over the weights
+  if (p.pscale && (!p.w_ld || p.M > d.tm || p.ps_ntiles <= 0 || p.K > p.ps_ntiles * d.tn + 4 * d.tn)) return false;   // one row tile: the factor slice (512 rows) is indexed by the row inside the tile
+  return true;
+}
 
 }  // namespace
 
@@ -1788,92 +1806,54 @@ long long gemm_launch_count(int family, int epi) {
   return g_launches[family][epi].load(std::memory_order_relaxed);
 }
 #ifdef MRA_GEMM_EXPERIMENTS
-void gemm_force_config(int cfg) { g_force_cfg = cfg; }
+void gemm_force_config(int tile) { g_force_tile = tile; }
 void gemm_force_variant(int v) { g_variant = v; }
 void gemm_set_tile_order(int order) { g_order = order; }
 void gemm_set_eight_phase(int on) { g_p8 = on; }
 void gemm_set_debug_buffer(unsigned long long* p) { g_dbg = p; }
 #endif
 
-int gemm_pick_config(const GemmProb* probs, int ngroups) {
-  if (g_force_cfg >= 0) return g_force_cfg;
-  if (probs[0].tile_cfg > 0) return probs[0].tile_cfg - 1;
-  // Largest tile that still gives every CU work: 256 CUs; aim for >= 2 waves of workgroups
-  // with the 64/128 tiles and >= 1 full wave with the 256 tile.
-  int best = 0;
-  for (int c = 2; c >= 0; --c) {
-    const int t = kTile[c];
-    long long tiles = 0;
-    bool ok = true;
-    for (int g = 0; g < ngroups; ++g) {
-      if (probs[g].N % t && !probs[g].n_ragged && !probs[g].n_mask) ok = false;
-      tiles += (long long)((probs[g].M + t - 1) / t) * ((probs[g].N + t - 1) / t) * (probs[g].batch > 1 ? probs[g].batch : 1);
-    }
-    if (!ok) continue;
-    const long long need = c == 2 ? 512 : (c == 1 ? 384 : 0);
-    if (tiles >= need) {
-      best = c;
-      break;
-    }
-  }
-  return best;
-}
-
-int launch_gemm(const GemmProb* probs, int ngroups, int epi, int op_dtype, hipStream_t stream) {
+int gemm_plan(const GemmProb* probs, int ngroups, int epi, int op_dtype, GemmPlan* out) {
   if (ngroups < 1 || ngroups > GEMM_MAX_GROUPS) return -1;
-  const int cfg = gemm_pick_config(probs, ngroups);
-  if (cfg < 0 || cfg > 10) return -1;
-  const int t = kTileN[cfg], tm = kTileM[cfg];
-  GemmArgs a;
+  (void)op_dtype;   // every kernel exists for both operand dtypes
+  GemmPlan& pl = *out;
+  pl.tile = pick_tile(probs, ngroups);
+  if (pl.tile >= GEMM_TILES) return -1;
+  for (int g = 0; g < ngroups; ++g)
+    if (!operand_rules(probs[g], epi) || !epilogue_rules(probs[g], ngroups, epi)) return -1;
+  pl.family = pick_family(pl.tile, probs, ngroups, epi);
+  const TileDesc& d = kTiles[pl.family];
+  GemmArgs& a = pl.args;
   a.ngroups = ngroups;
   int tiles = 0;
   for (int g = 0; g < ngroups; ++g) {
-    a.p[g] = probs[g];
-    GemmProb& p = a.p[g];
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0) return -1;
-    if (p.K % 64 || (p.N % t && !p.n_ragged && !p.n_mask && cfg != 7)) return -1;
-    if (cfg == 5 && p.K % 128) return -1;
-    if (cfg >= 8 && (p.n_ragged || p.n_mask || p.batch > 1 || p.w_ld || (epi != EPI_OP && epi != EPI_GELU_OP && epi != EPI_RES_F32 && epi != EPI_F32 && epi != EPI_RES_LN))) return -1;   // ring tiles: plain problems
-    if (cfg >= 8 && (epi == EPI_RES_F32 || epi == EPI_F32 || epi == EPI_RES_LN) && ((p.c.ld & 3) || (p.c.item_stride & 3))) return -1;   // their outputs leave as 16-byte pieces
-    if (epi == EPI_RES_LN && (cfg != 10 || !p.R || p.r.rpi <= 0 || !p.ln_gain || !p.ln_bias || !p.ln_counter || (!p.ln_y32 && !p.ln_y16) || p.N % 256 || p.N > 1024 ||
-                              (p.ln_y32 && (p.ln_y32v.rpi <= 0 || (p.ln_y32v.ld & 3) || (p.ln_y32v.item_stride & 3))) ||
-                              (p.ln_y16 && (p.ln_y16v.rpi <= 0 || (p.ln_y16v.ld & 3) || (p.ln_y16v.item_stride & 3))))) return -1;
-    if (cfg == 6 && (p.K % 128 || p.N != 128 || p.n_mask || p.n_ragged || p.batch > 1)) return -1;   // the eight-phase tail tile: one column tile, even K steps
-    if (cfg == 7 && (p.K % 128 || p.N % 256 != 128 || p.N < 384 || p.n_mask || p.n_ragged || p.batch > 1 || ngroups != 1)) return -1;
-    if (p.n_mask && ((epi != EPI_RES_F32 && epi != EPI_F32 && epi != EPI_RES_OP && epi != EPI_OP && epi != EPI_GELU_OP) || (p.N & 3) || p.n_ragged)) return -1;
-    if (p.n_mask && epi != EPI_RES_F32 && epi != EPI_F32 && (p.N & 63)) return -1;   // the 16-bit epilogues leave in 64-column blocks
-    if (p.n_ragged && (p.bias || epi == EPI_KV || epi == EPI_RES_F32)) return -1;
-    if (epi == EPI_SOFTPART && (cfg != 4 || !p.stat_m || !p.stat_l || p.bias || (p.c.ld & 3))) return -1;
-    if (p.w_ld && (cfg != 4 || epi != EPI_OP || (p.w_ld & 7) || p.k_rows <= 0 || p.N % 176)) return -1;
-    if (p.w_kwrap && (p.w_kwrap < 0 || p.w_ld || (cfg != 3 && cfg != 4) || 2 * p.w_kwrap * 64 != p.K)) return -1;   // 128 x 384 / 176 x 384 loader-wave tiles only: K = 2 passes over the weights
-    if (p.pscale && (!p.w_ld || cfg != 4 || p.M > 384 || p.ps_ntiles <= 0 || p.K > p.ps_ntiles * 176 + 4 * 176)) return -1;   // M <= the 384-row tile (slices hold 512 rows)
-    if (p.batch < 0) return -1;
-    if (p.a.rpi <= 0 || (epi != EPI_KV && p.c.rpi <= 0)) return -1;
-    if ((epi == EPI_RES_F32 || epi == EPI_RES_F32_STAT) && (!p.R || p.r.rpi <= 0)) return -1;
-    if (epi == EPI_RES_F32_STAT || epi == EPI_RES_OP_STAT || epi == EPI_LNF_OP || epi == EPI_LNF_GELU_OP) {   // eight-phase tiles only, one plain problem
-      bool even = (p.K / 64) % 2 == 0 && p.K >= 128;
-      if (!(cfg == 2 && even && g_p8 && g_variant != 1) && !(cfg == 7 && (epi == EPI_RES_F32_STAT || epi == EPI_RES_OP_STAT))) return -1;
-      if (ngroups != 1 || p.batch > 1 || p.n_mask || p.n_ragged || !p.ln_y32) return -1;
-      if (epi == EPI_RES_OP_STAT && (p.N % 64 || !p.aux || (p.c.ld & 7) || (p.c.item_stride & 7))) return -1;
-      if (epi == EPI_RES_F32_STAT && (p.N % 128 || !p.ln_y16 || p.ln_y16v.rpi <= 0 || (p.ln_y16v.ld & 7) || (p.ln_y16v.item_stride & 7) || (p.c.ld & 3) || (p.c.item_stride & 3))) return -1;
-      if ((epi == EPI_LNF_OP || epi == EPI_LNF_GELU_OP) && (!p.ln_gain || (p.c.ld & 7) || (p.c.item_stride & 7))) return -1;
-    }
-    if (epi == EPI_RES_LN && cfg != 10) return -1;
-    if (epi == EPI_KV && (p.kv_tokens <= 0 || p.kv_heads <= 0 || p.kv_items <= 0)) return -1;
-    if ((epi == EPI_OP || epi == EPI_GELU_OP || epi == EPI_RES_OP) && ((p.c.ld & 7) || (p.c.item_stride & 7))) return -1;  // 16-byte stores
-    if ((epi == EPI_RES_OP || epi == EPI_RES_OP_STAT) && (!p.aux || p.n_ragged)) return -1;
-    if ((epi == EPI_GELU_BOTH || epi == EPI_GELU_BWD) && (!p.aux || (p.c.ld & 3) || (p.c.item_stride & 3) || p.n_ragged)) return -1;
-    p.mtiles = (p.M + tm - 1) / tm;
-    p.ntiles = (p.N + t - 1) / t;
+    GemmProb& p = a.p[g] = probs[g];
+    if (!tile_rules(d, pl.family, p, ngroups, epi)) return -1;
+    p.mtiles = (p.M + d.tm - 1) / d.tm;
+    p.ntiles = (p.N + d.tn - 1) / d.tn;
     p.tile_begin = tiles;
-    if (cfg == 7) tiles += (p.mtiles + 1) / 2 * (2 * (p.N >> 8) + 1);   // per pair of row tiles: 2 k full tiles + one tail tile
+    if (pl.family == GF_P8_MIXED) tiles += (p.mtiles + 1) / 2 * (2 * (p.N >> 8) + 1);   // per pair of row tiles: 2 k full tiles + one tail tile
     else tiles += p.mtiles * p.ntiles * (p.batch > 1 ? p.batch : 1);
   }
+  if (!has_epi(d.epis, epi)) return -2;
   for (int g = ngroups; g < GEMM_MAX_GROUPS; ++g) a.p[g] = a.p[0];
   a.total_tiles = tiles;
   a.dbg = g_dbg;
   a.order = g_order ? g_order : probs[0].order;
-  return op_dtype == OP_F16 ? launch_t<f16>(a, cfg, epi, stream) : launch_t<bf16>(a, cfg, epi, stream);
+  pl.threads = d.threads;
+  pl.lds = d.lds + (a.p[0].pscale ? 4 * 2048 : 0);
+  // one workgroup per CU that walks over the tiles (the grid must be a multiple of the 8 XCDs for the remap to hold)
+  pl.persistent = pl.family == GF_P8_256 && a.p[0].persist && ngroups == 1 && a.p[0].batch <= 1 && has_epi(epi_mask(EpiP8Persist{}), epi) && pl.cus >= 8 && tiles > pl.cus;
+  pl.grid = pl.persistent ? pl.cus & ~7 : tiles;
+  return 0;
+}
+
+int launch_gemm(const GemmProb* probs, int ngroups, int epi, int op_dtype, hipStream_t stream) {
+  GemmPlan pl;
+  pl.cus = ngroups >= 1 && probs[0].persist ? device_cus() : 0;
+  const int rc = gemm_plan(probs, ngroups, epi, op_dtype, &pl);
+  if (rc) return rc;
+  return op_dtype == OP_F16 ? launch_t<f16>(pl, epi, stream) : launch_t<bf16>(pl, epi, stream);
 }
 
 }  // namespace mra

@@ -37,6 +37,23 @@ enum GemmEpi {
                     // sum go to stat_m / stat_l [row][ntiles] (176 x 384 loader-wave tile only: a wave holds whole tile rows)
 };
 
+// Tile configurations of launch_gemm (GemmProb::tile_cfg), weight rows x activation rows.  The numbers are recorded in profiles and DESIGN tables.
+enum GemmTile {
+  GT_AUTO = 0,          // the largest of 64 / 128 / 256 that divides N (or n_ragged / n_mask) and still fills the CUs
+  GT_64 = 1,            // 64 x 64 two-buffer loop; 128-deep K steps from K >= 2048 (K % 128 == 0)
+  GT_128 = 2,           // 128 x 128 two-buffer loop
+  GT_256 = 3,           // 256 x 256: eight-phase kernel when every problem has an even number of K steps, else the loader-wave kernel
+  GT_WS_128x384 = 4,    // loader-wave tile of the folded cross-attention (EPI_OP / EPI_F32; w_kwrap)
+  GT_WS_176x384 = 5,    // loader-wave tile with the compute waves in one column (N % 176 == 0 unless n_ragged; w_ld, w_kwrap, pscale, EPI_SOFTPART)
+  GT_K128_64x128 = 6,   // 128-deep K steps (K % 128 == 0): the long-K down-projections of the layer chain at ~1 k rows
+  GT_P8_TAIL = 7,       // eight-phase 128 x 512, N = 128 exactly: the half-width last column tile of N = 256 k + 128 as a launch of its own (W / bias / C / R offset to those columns)
+  GT_P8_MIXED = 8,      // N = 256 k + 128 in ONE launch: full 256 x 256 eight-phase tiles + one 128 x 512 tail tile per pair of row tiles (one problem)
+  GT_RING_144x128 = 9,  // the ring kernel's exact-fit tiles of the layer chain (plain problems, N a multiple of the tile): QKV 2048 x 2304,
+  GT_RING_192x128 = 10, // FFN-up 2 x 1024 x 3072,
+  GT_RING_96x64 = 11,   // the N = 768 projections (the only tile with EPI_RES_LN)
+  GEMM_TILES = 12
+};
+
 // Logical activation row m of a "row view" lives at base + (m / rpi) * item_stride + (m % rpi) * ld
 // (elements).  This lets the 32 query rows or the L text rows of every [S, H] item be addressed in
 // place, without gathers.
@@ -98,15 +115,7 @@ struct GemmProb {
   // 512-row factor slice by the row inside the tile).
   const float* pscale;
   int ps_ntiles;
-  int tile_cfg;    // 0 = automatic, 1 / 2 / 3 = force the 64 / 128 / 256 tile, 4 = the 128 (weight rows) x 384 (activation
-                   // rows) loader-wave tile (EPI_OP / EPI_F32 only), 5 = 176 x 384 with the compute waves in one column (EPI_OP only,
-                   // N % 176 == 0), 6 = 64 (weight rows) x 128 (activation rows) with 128-deep K steps (K % 128 == 0: the long-K down-projections of
-                   // the layer chain at ~1 k rows, where a tile's bytes per flop, not its count, sets the time), 7 = 128 (weight rows) x 512
-                   // (activation rows) on the eight-phase kernel (N = 128 exactly: the half-width last column tile of N = 256 k + 128, launched on its
-                   // own with W / bias / C / R offset to those columns; EPI_RES_F32 / EPI_F32 / EPI_RES_OP, K % 128 == 0), 8 = N = 256 k + 128 in ONE launch:
-                   // full 256 x 256 eight-phase tiles plus one 128 x 512 tail tile per pair of row tiles (same epilogues, one problem); the first problem decides;
-                   // 9 / 10 / 11 = the ring kernel's exact-fit tiles of the layer chain: 144 (weight rows) x 128 (activation rows), 192 x 128, 96 x 64 -- one
-                   // workgroup per CU at 2048 x 2304, 2 x 1024 x 3072 and 2048 x 768 (plain problems, N a multiple of the tile, EPI_OP / GELU_OP / RES_F32 / F32)
+  int tile_cfg;    // a GemmTile; in a grouped launch the first problem decides
   int order;       // tile walk: 0 = panels of 8 row tiles, rows fastest; gn > 0 = panels of gn column tiles walked down the rows, columns
                    // fastest (measured better for the ViT's N = 1408 GEMMs: all 6 column tiles of a row tile run together)
   int persist;     // eight-phase 256 x 256 kernel, staged epilogues: 1 = ONE workgroup per CU walks over the tiles (blockIdx, + gridDim, ...) instead of one
@@ -128,12 +137,23 @@ struct GemmArgs {
 
 // Returns 0 on success, <0 on bad shapes.  All problems of one launch share dtype / epilogue.
 int launch_gemm(const GemmProb* probs, int ngroups, int epi, int op_dtype, hipStream_t stream);
-// which tile config launch_gemm would pick (for tests / DESIGN.md): 0 = 64x64, 1 = 128x128, 2 = 256x256
-int gemm_pick_config(const GemmProb* probs, int ngroups);
+// Everything launch_gemm decides short of launching.  gemm_plan is host-only and makes no HIP call: validates the problems, picks the tile and
+// the kernel family, and fills the kernel argument.  Returns 0, -1 (bad problem) or -2 (the tile has no such epilogue); launch_gemm adds
+// -3 / -4 (runtime).
+struct GemmPlan {
+  int cus;          // in: CU count of the device; a persistent launch (GemmProb::persist) needs it, 0 = one workgroup per tile
+  int tile;         // GemmTile, never GT_AUTO
+  int family;       // GemmFamily
+  int threads, lds; // block size, dynamic LDS bytes
+  int persistent;   // 1: eight-phase 256 x 256 kernel as `grid` = cus & ~7 workgroups that walk over the tiles
+  int grid;
+  GemmArgs args;    // tile_begin / mtiles / ntiles of every problem, total_tiles, order
+};
+int gemm_plan(const GemmProb* probs, int ngroups, int epi, int op_dtype, GemmPlan* out);
 // Main loops ("families") launch_gemm dispatches to, and a read-only launch counter per (family, epilogue) since the library was
 // loaded (mra_debug_gemm_launches in include/mra.h): parity tests use it to state which kernel produced the numbers they checked.
 enum GemmFamily {
-  GF_V1_64 = 0, GF_V1_128 = 1, GF_V1_256 = 2,   // gemm_kernel two-buffer loop (256: experiment builds only)
+  GF_V1_64 = 0, GF_V1_128 = 1, GF_V1_256 = 2,   // gemm_kernel two-buffer loop (256: experiment builds only, gemm_force_variant(1))
   GF_WS_256 = 3,                                // gemm_ws_kernel 256 x 256 (odd number of K steps)
   GF_P8_256 = 4,                                // gemm_p8_kernel eight-phase 256 x 256
   GF_WS_128x384 = 5, GF_WS_176x384 = 6,         // loader-wave tiles of the folded cross-attention
@@ -147,7 +167,7 @@ long long gemm_launch_count(int family, int epi);
 #ifdef MRA_GEMM_EXPERIMENTS
 // Process-global A/B switches: compiled ONLY into tests/native/libmra_hip_exp.so (the experiment library of tests/native/gemm_bench and
 // kernel_check_exp); the shipped libmra_hip.so has no mutable global state besides the launch counters above.
-void gemm_force_config(int cfg);  // -1 = automatic (default)
+void gemm_force_config(int tile); // a GemmTile for every later launch, over GemmProb::tile_cfg; GT_AUTO = off (default)
 void gemm_set_debug_buffer(unsigned long long* dev_buf);  // variant 4 (stamped v1) writes 4 u64 per wave
 void gemm_set_eight_phase(int on);         // 256 x 256 launches with an even number of K steps on gemm_p8_kernel (A/B switch)
 void gemm_set_tile_order(int order);      // overrides GemmProb::order for every later launch when != 0 (A/B runs)

@@ -153,7 +153,7 @@ struct CrossPlan {
   bool kmajor;     // P . enc reads the encoder tokens themselves (K-major weights): no enc^T copy
   bool softpart;   // scores on the 176 x 384 EPI_SOFTPART tile (otherwise fp32 scores + a row softmax)
   bool inreg;      // with softpart: P . enc applies the row factors to its P~ fragments (otherwise a rescale pass over P)
-  int scores_tile, penc_tile;   // GemmProb::tile_cfg of the scores and the P . enc GEMMs
+  int scores_tile, penc_tile;   // GemmTile of the scores and the P . enc GEMMs
 };
 
 CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe) {
@@ -170,8 +170,8 @@ CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe) {
   x.kmajor = R == 384 && c.enc_width % 176 == 0;   // the 176 x 384 loader-wave tile: one workgroup per CU at E = 1408
   x.softpart = R == 384;
   x.inreg = (h->inreg_rescale || probe) && x.softpart && x.kmajor;
-  x.scores_tile = R == 384 ? 5 : 2;
-  x.penc_tile = x.kmajor ? 5 : (R == 384 ? h->fold_tile : 2);
+  x.scores_tile = R == 384 ? GT_WS_176x384 : GT_128;
+  x.penc_tile = x.kmajor ? GT_WS_176x384 : (R == 384 ? h->fold_tile : GT_128);
   return x;
 }
 
@@ -329,7 +329,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
     d.A = w.qs16; d.a = plain(N * Q, 3 * H); d.a_bs = 192;
     d.W = h->arena_p + (size_t)ci * precise_layer_bytes(h) + precise_wk_off(h); d.w_bs = (long long)E * 192;
     d.C = w.qp32; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * 4;
-    d.M = N * Q; d.N = E; d.K = 192; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? 2 : 1;
+    d.M = N * Q; d.N = E; d.K = 192; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? GT_128 : GT_64;
     rc = launch_gemm(&d, 1, EPI_F32, op, stream);
     if (rc) return chk(rc, "fold q' gemm (split precision)");
     rc = launch_split_rows(w.qp32, plain(N * R, E), N * R, E, E, 2, w.qp16, op, stream);
@@ -338,7 +338,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
     d.A = w.qc16; d.a = qc_rows; d.a_bs = 64;
     d.W = h->arena_f + (size_t)ci * H * E * esz; d.w_bs = (long long)E * 64;
     d.C = w.qp16; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * esz;
-    d.M = N * Q; d.N = E; d.K = 64; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? 2 : 1;
+    d.M = N * Q; d.N = E; d.K = 64; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? GT_128 : GT_64;
     rc = launch_gemm(&d, 1, EPI_OP, op, stream);
     if (rc) return chk(rc, "fold q' gemm");
   }
@@ -409,7 +409,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
   cx.W = (const char*)h->wkv + (size_t)(ci * 2 + 1) * H * E * esz; cx.w_bs = (long long)64 * E;
   cx.bias = h->bkv + (size_t)(ci * 2 + 1) * H; cx.bias_bs = 64;
   cx.C = w.ctx16; cx.c = qc_rows; cx.c_bs_bytes = 64 * esz;
-  cx.M = N * Q; cx.N = 64; cx.K = E; cx.batch = c.heads; cx.tile_cfg = E % 128 == 0 && N * Q >= 512 ? 6 : 1;
+  cx.M = N * Q; cx.N = 64; cx.K = E; cx.batch = c.heads; cx.tile_cfg = E % 128 == 0 && N * Q >= 512 ? GT_K128_64x128 : GT_64;
   rc = launch_gemm(&cx, 1, EPI_OP, op, stream);
   if (rc) return chk(rc, "fold context gemm");
   if (timed) (void)hipEventRecord(h->kv_ev1, stream);
@@ -713,9 +713,9 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
         // The chain GEMMs at ~1-2 k rows are bound by the operand bytes each CU pulls through its load path (~33 B / clk from L2),
         // not by tile count: 128 x 128 tiles (288 of them) move half the bytes per flop of the 1152 64 x 64 tiles the automatic
         // choice makes (headline step 6.75 -> 6.67 ms, reference item shape 2.65 -> 2.55 ms together with the down-projection below)
-        p[l].tile_cfg = N * S >= 1024 ? 2 : 0;
+        p[l].tile_cfg = N * S >= 1024 ? GT_128 : GT_AUTO;
         // ... and at ~2 k rows the ring kernel's 144 x 128 tile is exactly one workgroup per CU (2048 x 2304 = 16 x 16 tiles): 14.4 vs 17.6 us stand-alone
-        if ((lanes[l].h->chain_ring & 1) && N * S >= 1024 && (3 * H) % 144 == 0) p[l].tile_cfg = 9;
+        if ((lanes[l].h->chain_ring & 1) && N * S >= 1024 && (3 * H) % 144 == 0) p[l].tile_cfg = GT_RING_144x128;
       }
       rc = launch_gemm(p, nl, EPI_OP, op, stream);
       if (rc) return chk(rc, "qkv gemm");
@@ -732,9 +732,9 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
         p[l].R = lanes[l].w.hA32; p[l].r = all_rows;
         p[l].C = lanes[l].w.pre32; p[l].c = all_rows;
         p[l].M = N * S; p[l].N = H; p[l].K = H;
-        if ((lanes[l].h->chain_ring & 4) && N * S >= 1024 && H % 96 == 0) p[l].tile_cfg = 11;
+        if ((lanes[l].h->chain_ring & 4) && N * S >= 1024 && H % 96 == 0) p[l].tile_cfg = GT_RING_96x64;
       }
-      if (ln_fuse && p[0].tile_cfg == 11) {
+      if (ln_fuse && p[0].tile_cfg == GT_RING_96x64) {
         // HF:519-530 in one launch: the column tile of a 64-row block that finishes last normalises the block's rows
         p[0].ln_gain = Lw[0]->ln1g; p[0].ln_bias = Lw[0]->ln1b; p[0].ln_eps = c.ln_eps;
         p[0].ln_y32 = w.hB32; p[0].ln_y32v = all_rows; p[0].ln_y16 = w.hB16; p[0].ln_y16v = all_rows; p[0].ln_counter = w.lncnt;
@@ -788,7 +788,7 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
         o[l].M = N * Q; o[l].N = H; o[l].K = H;
       }
       if (ln_fuse && N * Q >= 512) {
-        o[0].tile_cfg = 11;
+        o[0].tile_cfg = GT_RING_96x64;
         o[0].ln_gain = Lw[0]->lncg; o[0].ln_bias = Lw[0]->lncb; o[0].ln_eps = c.ln_eps;
         o[0].ln_y32 = w.hC32; o[0].ln_y32v = qc_rows; o[0].ln_y16 = w.hC16; o[0].ln_y16v = qc_rows; o[0].ln_counter = w.lncnt;
         rc = launch_gemm(o, 1, EPI_RES_LN, op, stream);
@@ -826,7 +826,7 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
         t.C = v.ffn16 + (size_t)N * Q * I * esz; t.c = plain(text_rows, I);
         t.M = text_rows; t.N = I; t.K = H;
       }
-      if ((h->chain_ring & 2) && N * Q >= 512 && I % 192 == 0) g[0].tile_cfg = 10;
+      if ((h->chain_ring & 2) && N * Q >= 512 && I % 192 == 0) g[0].tile_cfg = GT_RING_192x128;
       rc = launch_gemm(g, ng, EPI_GELU_OP, op, stream);
       if (rc) return chk(rc, "ffn up gemm");
     }
@@ -848,9 +848,9 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
         t.C = v.pre32 + t_off32; t.c = tv;
         t.M = text_rows; t.N = H; t.K = I;
       }
-      g[0].tile_cfg = N * Q >= 512 && I % 128 == 0 ? 6 : 0;   // 64 weight rows x 128 activation rows, 128-deep K steps (see the QKV note)
-      if ((h->chain_ring & 4) && N * Q >= 512 && H % 96 == 0) g[0].tile_cfg = 11;
-      ffn_ln_fused = ln_fuse && !last && g[0].tile_cfg == 11;
+      g[0].tile_cfg = N * Q >= 512 && I % 128 == 0 ? GT_K128_64x128 : GT_AUTO;   // 64 weight rows x 128 activation rows, 128-deep K steps (see the QKV note)
+      if ((h->chain_ring & 4) && N * Q >= 512 && H % 96 == 0) g[0].tile_cfg = GT_RING_96x64;
+      ffn_ln_fused = ln_fuse && !last && g[0].tile_cfg == GT_RING_96x64;
       if (ffn_ln_fused) {
         // HF:573-587 for both row sets in the same launch: problem 0 = query rows (output_query.LayerNorm), problem 1 = text rows (output.LayerNorm)
         g[0].ln_gain = Lw[0]->lnqg; g[0].ln_bias = Lw[0]->lnqb; g[0].ln_eps = c.ln_eps;
@@ -1088,7 +1088,7 @@ int mra_qformer_set_cross_mode(mra_qformer* h, int32_t mode) {
   if (mode < 0 || mode > 5)
     return fail(MRA_EINVAL, "cross mode must be 0 (automatic), 1 (K/V cache), 2 (folded), 3 (folded, 128x384 loader-wave tiles), 4 (folded, streaming kernels) or 5 (folded, separate rescale pass)");
   h->cross_mode = mode >= 3 ? 2 : mode;
-  h->fold_tile = mode == 3 ? 4 : 2;
+  h->fold_tile = mode == 3 ? GT_WS_128x384 : GT_128;
   h->fold_stream = mode == 4;     // measured 13 % slower than the loader-wave GEMMs + rescale pass: opt-in
   h->inreg_rescale = mode != 5;   // 5: the round-1 form with a rescale pass over P between the two big GEMMs, kept as the measured alternative
   return MRA_OK;

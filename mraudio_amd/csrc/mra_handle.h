@@ -92,7 +92,7 @@ struct mra_qformer {
   char* arena_f = nullptr;
   bool fold_stale = true;
   bool inreg_rescale = true;                      // the P . enc GEMM applies the softmax row factors to its P~ fragments (false: a rescale pass over P; cross mode 5)
-  int fold_tile = 2;                              // GemmProb::tile_cfg of the two batched GEMMs where the 176 x 384 tiles do not apply (2 = 128 x 128, 4 = 128 x 384)
+  int fold_tile = mra::GT_128;                    // GemmTile of the two batched GEMMs where the 176 x 384 tiles do not apply (GT_128 or GT_WS_128x384)
   bool fold_stream = false;                       // folded path on the streaming kernels of fold_stream.hip (mra_qformer_set_cross_mode 4)
   int cross_mode = 0;                             // 0 automatic, 1 K/V cache, 2 folded
   // split-precision cross-attention (mra_qformer_set_cross_precision): hidden state, W_cq, Q, W_k and Q' of the score chain as operand-dtype

@@ -162,12 +162,12 @@ struct Ctx {
     p.M = M; p.N = N; p.K = K; p.tile_cfg = ring_tile(N, epi);
     return launch_gemm(&p, 1, epi, op, stream);
   }
-  // mra_qformer_set_option("train_ring"): the ring kernel's exact-fit tiles where it has the epilogue (GemmProb::tile_cfg, 0 = automatic)
+  // mra_qformer_set_option("train_ring"): the ring kernel's exact-fit tiles where it has the epilogue
   int ring_tile(int N, int epi) const {
     const int mask = h->train_ring;
-    if ((mask & 1) && epi == EPI_OP && N == 3 * h->cfg.hidden && N % 144 == 0) return 9;
-    if ((mask & 4) && (epi == EPI_OP || epi == EPI_RES_F32) && N == h->cfg.hidden && N % 96 == 0) return 11;
-    return 0;
+    if ((mask & 1) && epi == EPI_OP && N == 3 * h->cfg.hidden && N % 144 == 0) return GT_RING_144x128;
+    if ((mask & 4) && (epi == EPI_OP || epi == EPI_RES_F32) && N == h->cfg.hidden && N % 96 == 0) return GT_RING_96x64;
+    return GT_AUTO;
   }
   static GemmProb prob(const void* A, RowView av, const void* W, const float* bias, void* C, RowView cv, const float* R, RowView rv, int M, int N,
                        int K, void* aux = nullptr) {

@@ -9,7 +9,7 @@
 //   im2col -> patch GEMM (+ bias + position embedding in the epilogue) -> [CLS] rows
 //   39 x { LN -> QKV GEMM -> attention core -> projection GEMM + residual -> LN -> fc1 GEMM + GELU -> fc2 GEMM + residual }
 // 97 % of the flops are the four GEMMs per block at M = frames x 257 rows: the eight-phase 256 x 256 kernel of gemm.hip (QKV, fc1;
-// the N = 1408 ones as full tiles plus a 128 x 512 tail tile per pair of row tiles, GemmProb::tile_cfg 8) with bias / GELU /
+// the N = 1408 ones as full tiles plus a 128 x 512 tail tile per pair of row tiles, GT_P8_MIXED) with bias / GELU /
 // residual fused: the residual GEMMs START their accumulators at bias + residual, so their epilogue only stores.  The fp32
 // residual stream is updated in place and IS the output.  LayerNorms: folded into the GEMMs on either side (default with the fp32 stream,
 // see vit_fold_weight_kernel below) or separate launches that write the f16 operand of the next GEMM (f16 stream; ln_fold 0).
@@ -560,8 +560,8 @@ struct mra_vit {
   void* wpatch = nullptr;
   std::vector<VitLayer> layers;
   bool tail_tile = true;   // N = dim GEMMs: full 256-wide tiles + a 128 x 512 tail tile per pair of row tiles (false: a masked sixth 256-wide column tile)
-  int proj_tile = 3;   // GemmProb::tile_cfg of the N = dim GEMMs: 256 x 256 with a masked last column tile (1408 = 5.5 tiles); the exact-fit
-                       // 176 x 384 tile (tile_cfg 5) measured 1 % slower (615 vs 609 ms per 1024 frames): both sit on the fp32 epilogue
+  int proj_tile = GT_256;   // GemmTile of the N = dim GEMMs: 256 x 256 with a masked last column tile (1408 = 5.5 tiles); the exact-fit
+                       // 176 x 384 tile (GT_WS_176x384) measured 1 % slower (615 vs 609 ms per 1024 frames): both sit on the fp32 epilogue
   // LayerNorms folded into the QKV / fc1 GEMMs (dim = 256 k + 128): mra_vit_set_option("ln_fold", 0 / 1)
   int ln_fold = 1;
   int gemm_persist = 1;   // QKV / fc1 on the eight-phase kernel as one persistent workgroup per CU (GemmProb::persist): 0 never, 1 always, 2 up to 64 rounds of
@@ -575,7 +575,7 @@ struct mra_vit {
   bool fold_ready = false;   // W diag(gain) etc. are up to date with the loaded parameters
   int op() const { return cfg.op_dtype == MRA_BF16 ? OP_BF16 : OP_F16; }
   bool can_fold() const {   // either residual dtype
-    return proj_tile == 3 && tail_tile && cfg.dim % 256 == 128 && cfg.dim > 128 && cfg.dim <= 2048 && cfg.mlp % 128 == 0;
+    return proj_tile == GT_256 && tail_tile && cfg.dim % 256 == 128 && cfg.dim > 128 && cfg.dim <= 2048 && cfg.mlp % 128 == 0;
   }
 };
 
@@ -856,7 +856,7 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
       GemmProb p{};
       p.A = fold ? x16 : a16; p.a = plain((int)M, D); p.W = fold ? L.wqkv_f : L.wqkv; p.bias = fold ? L.bf_qkv : L.bqkv;
       p.C = big; p.c = plain((int)M, h->nqkv); p.M = (int)M; p.N = h->nqkv; p.K = D;
-      if (fold) { p.ln_gain = L.cs_qkv; p.ln_y32 = reinterpret_cast<float*>(rstat); p.tile_cfg = 3; }
+      if (fold) { p.ln_gain = L.cs_qkv; p.ln_y32 = reinterpret_cast<float*>(rstat); p.tile_cfg = GT_256; }
       p.persist = persist((M + 255) / 256 * (h->nqkv / 256));
       rc = launch_gemm(&p, 1, fold ? EPI_LNF_OP : EPI_OP, op, st);
       if (rc) return chk(rc, "vit qkv gemm");
@@ -872,16 +872,16 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
       if (op == OP_F16) hipLaunchKernelGGL((vit_attn_kernel<f16, 0>), dim3(n * c.heads), dim3(ATT_WAVES * 64), attn_lds, st, (const f16*)big, (f16*)a16, S, c.heads, hd, sl2);
       else hipLaunchKernelGGL((vit_attn_kernel<bf16, 0>), dim3(n * c.heads), dim3(ATT_WAVES * 64), attn_lds, st, (const bf16*)big, (bf16*)a16, S, c.heads, hd, sl2);
     }
-    // x += A W^T + b for the two N = dim GEMMs.  dim = 1408 is 5.5 tiles of 256: GemmProb::tile_cfg 8 runs the five full column tiles
+    // x += A W^T + b for the two N = dim GEMMs.  dim = 1408 is 5.5 tiles of 256: GT_P8_MIXED runs the five full column tiles
     // of two row tiles and then their last 128 columns as one 128 x 512 tile, all in one launch (a masked sixth 256-wide tile wastes 9 %)
     auto residual_gemm = [&](const void* A, int K, const void* W, const float* bias, bool stat) {
       GemmProb p{};
       p.A = A; p.a = plain((int)M, K); p.W = W; p.bias = bias;
       p.R = out; p.r = plain((int)M, D); p.C = x; p.c = plain((int)M, D); p.aux = x;
-      p.M = (int)M; p.N = D; p.K = K; p.tile_cfg = h->proj_tile; p.n_mask = h->proj_tile == 3; p.order = 8;
+      p.M = (int)M; p.N = D; p.K = K; p.tile_cfg = h->proj_tile; p.n_mask = h->proj_tile == GT_256; p.order = 8;
       int epi = r16 ? EPI_RES_OP : EPI_RES_F32;
-      const bool split = h->proj_tile == 3 && h->tail_tile && D % 256 == 128 && D > 128 && K % 128 == 0;
-      if (split) { p.tile_cfg = 8; p.n_mask = 0; p.order = 0; }
+      const bool split = h->proj_tile == GT_256 && h->tail_tile && D % 256 == 128 && D > 128 && K % 128 == 0;
+      if (split) { p.tile_cfg = GT_P8_MIXED; p.n_mask = 0; p.order = 0; }
       if (stat) {   // the rows' op-dtype copy and group statistics for the folded LayerNorm behind this GEMM (can_fold() implies split)
         p.ln_y32 = reinterpret_cast<float*>(groups);
         if (r16) epi = EPI_RES_OP_STAT;
@@ -901,7 +901,7 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
       GemmProb p{};
       p.A = fold ? x16 : a16; p.a = plain((int)M, D); p.W = fold ? L.wfc1_f : L.wfc1; p.bias = fold ? L.bf_fc1 : L.bfc1;
       p.C = big; p.c = plain((int)M, I); p.M = (int)M; p.N = I; p.K = D;
-      if (fold) { p.ln_gain = L.cs_fc1; p.ln_y32 = reinterpret_cast<float*>(rstat); p.tile_cfg = 3; }
+      if (fold) { p.ln_gain = L.cs_fc1; p.ln_y32 = reinterpret_cast<float*>(rstat); p.tile_cfg = GT_256; }
       p.persist = persist((M + 255) / 256 * (I / 256));
       rc = launch_gemm(&p, 1, fold ? EPI_LNF_GELU_OP : EPI_GELU_OP, op, st);
       if (rc) return chk(rc, "vit fc1 gemm");

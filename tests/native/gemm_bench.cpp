@@ -24,7 +24,7 @@ using namespace mra;
 
 struct Shape {
   const char* name;
-  int M, N, K, epi, cfg;
+  int M, N, K, epi, tile;   // GemmTile
 };
 
 #include <cstring>
@@ -76,12 +76,12 @@ static void fold_ab(int rounds) {
   // the loader-wave formulation
   GemmProb sc{};
   sc.A = Q; sc.a = RowView{0, R, E}; sc.a_bs = (long long)R * E; sc.W = X; sc.w_bs = (long long)kv * E;
-  sc.M = R; sc.N = kv; sc.K = E; sc.batch = items; sc.n_ragged = 1; sc.tile_cfg = 5;
+  sc.M = R; sc.N = kv; sc.K = E; sc.batch = items; sc.n_ragged = 1; sc.tile_cfg = GT_WS_176x384;
   sc.C = P; sc.c = RowView{0, R, kvp}; sc.c_bs_bytes = (long long)R * kvp * 2; sc.alpha = a.alpha; sc.stat_m = M; sc.stat_l = L;
   GemmProb pv{};
   pv.A = P; pv.a = RowView{0, R, kvp}; pv.a_bs = (long long)R * kvp; pv.W = X; pv.w_bs = (long long)kv * E; pv.w_ld = E; pv.k_rows = kv;
-  pv.C = U; pv.c = RowView{0, R, E}; pv.c_bs_bytes = (long long)R * E * 2; pv.M = R; pv.N = E; pv.K = kvp; pv.batch = items; pv.tile_cfg = 5;
-  gemm_force_config(-1); gemm_force_variant(5);
+  pv.C = U; pv.c = RowView{0, R, E}; pv.c_bs_bytes = (long long)R * E * 2; pv.M = R; pv.N = E; pv.K = kvp; pv.batch = items; pv.tile_cfg = GT_WS_176x384;
+  gemm_force_config(GT_AUTO); gemm_force_variant(5);
   const double o_s = timed([&] { launch_gemm(&sc, 1, EPI_SOFTPART, OP_F16, 0); });
   const double o_r = timed([&] { launch_softmax_rescale(P, kvp, M, L, items * R, nt, 176, kvp, OP_F16, 0); });
   const double o_p = timed([&] { launch_gemm(&pv, 1, EPI_OP, OP_F16, 0); });
@@ -100,12 +100,12 @@ static void fold_ab(int rounds) {
 // tile orders of the 256 x 256 loader-wave kernel on the big shapes (K/V projection, the ViT's four GEMMs over 1024 frames)
 static void order_ab(int rounds) {
   const Shape shapes[] = {
-      {"kvproj video 32x8224", 32 * 8224, 9216, 1408, EPI_KV, -1},
-      {"vit qkv 263168x1408->4608", 1024 * 257, 4608, 1408, EPI_OP, -1},
-      {"vit fc1 263168x1408->6144", 1024 * 257, 6144, 1408, EPI_GELU_OP, -1},
-      {"  same shape, plain epilogue", 1024 * 257, 6144, 1408, EPI_OP, -1},
-      {"vit fc2 263168x6144->1408", 1024 * 257, 1408, 6144, EPI_F32, 3},
-      {"vit proj 263168x1408->1408", 1024 * 257, 1408, 1408, EPI_F32, 3},
+      {"kvproj video 32x8224", 32 * 8224, 9216, 1408, EPI_KV, GT_AUTO},
+      {"vit qkv 263168x1408->4608", 1024 * 257, 4608, 1408, EPI_OP, GT_AUTO},
+      {"vit fc1 263168x1408->6144", 1024 * 257, 6144, 1408, EPI_GELU_OP, GT_AUTO},
+      {"  same shape, plain epilogue", 1024 * 257, 6144, 1408, EPI_OP, GT_AUTO},
+      {"vit fc2 263168x6144->1408", 1024 * 257, 1408, 6144, EPI_F32, GT_256},
+      {"vit proj 263168x1408->1408", 1024 * 257, 1408, 1408, EPI_F32, GT_256},
   };
   const size_t nA = (size_t)1024 * 257 * 6144, nW = (size_t)9216 * 1408, nC = (size_t)1024 * 257 * 9216;
   std::mt19937 rng(1);
@@ -124,7 +124,7 @@ static void order_ab(int rounds) {
   for (auto& s : shapes) {
     GemmProb p{};
     p.A = A; p.a = RowView{0, s.M, s.K}; p.W = W; p.bias = bias; p.C = C; p.c = RowView{0, s.M, s.N};
-    p.M = s.M; p.N = s.N; p.K = s.K; p.tile_cfg = s.cfg > 0 ? s.cfg : 0; p.n_mask = s.N % 256 != 0;
+    p.M = s.M; p.N = s.N; p.K = s.K; p.tile_cfg = s.tile; p.n_mask = s.N % 256 != 0;
     if (s.epi == EPI_KV) { p.kv_tokens = s.M / 32; p.kv_items = 32; p.kv_heads = 12; }
     printf("%-30s", s.name);
     for (int o : orders) {
@@ -185,7 +185,7 @@ static void splitk_ab(int rounds) {
       GemmProb p{};
       p.A = A; p.a = RowView{0, rows, K}; p.W = W; p.bias = bias; p.R = R; p.r = RowView{0, rows, N}; p.C = C; p.c = RowView{0, rows, N};
       p.M = rows; p.N = N; p.K = K;
-      if (K == 3072) p.tile_cfg = 6;
+      if (K == 3072) p.tile_cfg = GT_K128_64x128;
       const double whole = timed([&] { launch_gemm(&p, 1, EPI_RES_F32, OP_F16, 0); });
       // halves: A row stride K, but only K / 2 columns are walked -> RowView.ld = K with p.K = K / 2; W needs its own row stride: use two
       // weight matrices of K / 2 columns (same bytes walked)
@@ -194,17 +194,17 @@ static void splitk_ab(int rounds) {
         q[s] = GemmProb{};
         q[s].A = A + s * (K / 2); q[s].a = RowView{0, rows, K}; q[s].W = W + (size_t)s * N * (K / 2); q[s].C = C + (size_t)(1 + s) * rows * N; q[s].c = RowView{0, rows, N};
         q[s].M = rows; q[s].N = N; q[s].K = K / 2;
-        if (K == 3072) q[s].tile_cfg = 6;
+        if (K == 3072) q[s].tile_cfg = GT_K128_64x128;
       }
       const double halves = timed([&] { launch_gemm(q, 2, EPI_F32, OP_F16, 0); });
-      q[0].tile_cfg = q[1].tile_cfg = 0;
+      q[0].tile_cfg = q[1].tile_cfg = GT_AUTO;
       const double halves_auto = timed([&] { launch_gemm(q, 2, EPI_F32, OP_F16, 0); });
       printf("rows %d K %d: whole %.1f us   two halves %.1f us (auto tile %.1f us)\n", rows, K, whole, halves, halves_auto);
     }
   }
 }
 
-// the layer chain's GEMM shapes on every small-tile configuration (GemmProb::tile_cfg 1 = 64 x 64, 2 = 128 x 128, 6 = 64 x 128 x 128-deep)
+// the layer chain's GEMM shapes on every small-tile configuration (GT_64, GT_128, GT_K128_64x128 and the ring tiles; printed by GemmTile number)
 static void chain_ab(int rounds) {
   struct S { const char* name; int M, N, K, epi, groups; };
   const S shapes[] = {{"qkv 2048x768->2304", 2048, 2304, 768, EPI_OP, 1},          {"attn-out 2048x768->768", 2048, 768, 768, EPI_RES_F32, 1},
@@ -224,16 +224,16 @@ static void chain_ab(int rounds) {
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   for (auto& sh : shapes) {
     printf("%-30s", sh.name);
-    for (int cfg : {1, 2, 6, 9, 10, 11}) {
+    for (int tile : {GT_64, GT_128, GT_K128_64x128, GT_RING_144x128, GT_RING_192x128, GT_RING_96x64}) {
       GemmProb q[2];
       for (int g = 0; g < sh.groups; ++g) {
         q[g] = GemmProb{};
         q[g].A = A + (size_t)g * 1024 * sh.K; q[g].a = RowView{0, sh.M, sh.K}; q[g].W = W + (size_t)g * h.size(); q[g].bias = bias;
         q[g].R = R; q[g].r = RowView{0, sh.M, sh.N}; q[g].C = (char*)C + (size_t)g * 2048 * 3072 * 2; q[g].c = RowView{0, sh.M, sh.N};
-        q[g].M = sh.M; q[g].N = sh.N; q[g].K = sh.K; q[g].tile_cfg = cfg;
+        q[g].M = sh.M; q[g].N = sh.N; q[g].K = sh.K; q[g].tile_cfg = tile;
       }
-      if (cfg == 6 && sh.K % 128) { printf("  cfg6   n/a"); continue; }
-      if ((cfg == 9 && sh.N % 144) || (cfg == 10 && sh.N % 192) || (cfg == 11 && sh.N % 96)) { printf("  cfg%-2d  n/a   ", cfg); continue; }
+      if (tile == GT_K128_64x128 && sh.K % 128) { printf("  tile6   n/a"); continue; }
+      if ((tile == GT_RING_144x128 && sh.N % 144) || (tile == GT_RING_192x128 && sh.N % 192) || (tile == GT_RING_96x64 && sh.N % 96)) { printf("  tile%-2d  n/a   ", tile); continue; }
       double best = 1e30;
       bool ok = true;
       for (int r = 0; r < rounds && ok; ++r) {
@@ -246,7 +246,7 @@ static void chain_ab(int rounds) {
         CK(hipEventElapsedTime(&ms, e0, e1));
         best = std::min(best, (double)ms / 20 * 1e3);
       }
-      if (ok) printf("  cfg%d %5.1f us", cfg, best); else printf("  cfg%d refused", cfg);
+      if (ok) printf("  tile%d %5.1f us", tile, best); else printf("  tile%d refused", tile);
     }
     printf("\n");
   }
@@ -269,7 +269,7 @@ static void ring_stamp() {
   const size_t nent = (size_t)256 * 8 * 16;
   CK(hipMalloc((void**)&dbg, nent * 8));
   GemmProb p{};
-  p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = C; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.tile_cfg = 9;
+  p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = C; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.tile_cfg = GT_RING_144x128;
   for (int rep = 0; rep < 3; ++rep) {
     CK(hipMemset(dbg, 0, nent * 8));
     gemm_set_debug_buffer(dbg);
@@ -317,7 +317,7 @@ static void qkv_pad_ab(int rounds) {
     for (int N : {4608, 4224}) {
       GemmProb p{};
       p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = C; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K;
-      p.tile_cfg = N == 4224 ? 8 : 0;
+      p.tile_cfg = N == 4224 ? GT_P8_MIXED : GT_AUTO;
       double best = 1e30;
       for (int r = 0; r < rounds; ++r) {
         if (launch_gemm(&p, 1, EPI_OP, OP_F16, 0)) { printf("launch failed\n"); return; }
@@ -350,10 +350,10 @@ static void race_screen(int rounds) {
   for (size_t off = 0; off < nW; off += h.size()) CK(hipMemcpy(W + off, h.data(), std::min(h.size(), nW - off) * 2, hipMemcpyHostToDevice));
   CK(hipMalloc((void**)&bias, 16384 * 4)); CK(hipMemset(bias, 0, 16384 * 4));
   CK(hipMalloc((void**)&R, (size_t)M * 1408 * 4)); CK(hipMemset(R, 0, (size_t)M * 1408 * 4));
-  struct S { const char* name; int N, K, epi, cfg; size_t out_bytes; };
-  const S shapes[] = {{"kvproj 263168x1408->9216 EPI_KV", 9216, 1408, EPI_KV, 0, (size_t)M * 9216 * 2},
-                      {"fc1 263168x1408->6144 EPI_GELU_OP", 6144, 1408, EPI_GELU_OP, 0, (size_t)M * 6144 * 2},
-                      {"fc2 263168x6144->1408 EPI_RES_F32, full + tail tiles", 1408, 6144, EPI_RES_F32, 8, (size_t)M * 1408 * 4}};
+  struct S { const char* name; int N, K, epi, tile; size_t out_bytes; };
+  const S shapes[] = {{"kvproj 263168x1408->9216 EPI_KV", 9216, 1408, EPI_KV, GT_AUTO, (size_t)M * 9216 * 2},
+                      {"fc1 263168x1408->6144 EPI_GELU_OP", 6144, 1408, EPI_GELU_OP, GT_AUTO, (size_t)M * 6144 * 2},
+                      {"fc2 263168x6144->1408 EPI_RES_F32, full + tail tiles", 1408, 6144, EPI_RES_F32, GT_P8_MIXED, (size_t)M * 1408 * 4}};
   std::vector<char> ref, got;
   for (auto& sh : shapes) {
     GemmProb p{};
@@ -365,7 +365,7 @@ static void race_screen(int rounds) {
     gemm_set_eight_phase(0);
     GemmProb q = p;
     q.C = C0;
-    if (sh.cfg == 8) { q.tile_cfg = 3; q.n_mask = 1; }
+    if (sh.tile == GT_P8_MIXED) { q.tile_cfg = GT_256; q.n_mask = 1; }
     CK(hipMemset(C0, 0, sh.out_bytes));
     if (launch_gemm(&q, 1, sh.epi, OP_F16, 0)) { printf("reference launch failed\n"); return; }
     CK(hipDeviceSynchronize());
@@ -376,7 +376,7 @@ static void race_screen(int rounds) {
     for (int r = 0; r < rounds; ++r) {
       GemmProb e = p;
       e.C = C1;
-      if (sh.cfg == 8) e.tile_cfg = 8;
+      if (sh.tile == GT_P8_MIXED) e.tile_cfg = GT_P8_MIXED;
       CK(hipMemset(C1, 0, sh.out_bytes));
       if (launch_gemm(&e, 1, sh.epi, OP_F16, 0)) { printf("eight-phase launch failed\n"); return; }
       CK(hipDeviceSynchronize());
@@ -429,22 +429,22 @@ static void vit_epi_ab(int rounds) {
       CK(hipEventElapsedTime(&ms, e0, e1));
       best = std::min(best, (double)ms / 5 * 1e3);
     }
-    const double tiles = tile_cfg == 8 ? 129.0 * 11 : 257.0 * (N / 256);
+    const double tiles = tile_cfg == GT_P8_MIXED ? 129.0 * 11 : 257.0 * (N / 256);
     printf("%-44s N %4d K %4d  %7.1f us  %6.1f TF/s  %5.1f us per round of 256 tiles\n", name, N, K, best, 2.0 * M * N * K / best * 1e-6, best / (tiles / 256));
   };
   for (int K : {1408, 2816, 6144}) {
-    run("N = dim, mixed tiles: EPI_OP (f16 store)", D, K, EPI_OP, 8);
-    run("N = dim, mixed tiles: EPI_F32", D, K, EPI_F32, 8);
-    run("N = dim, mixed tiles: EPI_RES_F32", D, K, EPI_RES_F32, 8);
-    run("N = dim, mixed tiles: EPI_RES_F32_STAT", D, K, EPI_RES_F32_STAT, 8);
-    run("N = dim, mixed tiles: EPI_RES_OP", D, K, EPI_RES_OP, 8);
+    run("N = dim, mixed tiles: EPI_OP (f16 store)", D, K, EPI_OP, GT_P8_MIXED);
+    run("N = dim, mixed tiles: EPI_F32", D, K, EPI_F32, GT_P8_MIXED);
+    run("N = dim, mixed tiles: EPI_RES_F32", D, K, EPI_RES_F32, GT_P8_MIXED);
+    run("N = dim, mixed tiles: EPI_RES_F32_STAT", D, K, EPI_RES_F32_STAT, GT_P8_MIXED);
+    run("N = dim, mixed tiles: EPI_RES_OP", D, K, EPI_RES_OP, GT_P8_MIXED);
   }
   for (int K : {1408, 2816}) {
-    run("fc1: EPI_OP", I, K, EPI_OP, 3);
-    run("fc1: EPI_GELU_OP", I, K, EPI_GELU_OP, 3);
-    run("fc1: EPI_LNF_GELU_OP", I, K, EPI_LNF_GELU_OP, 3);
-    run("qkv: EPI_OP", 4608, K, EPI_OP, 3);
-    run("qkv: EPI_LNF_OP", 4608, K, EPI_LNF_OP, 3);
+    run("fc1: EPI_OP", I, K, EPI_OP, GT_256);
+    run("fc1: EPI_GELU_OP", I, K, EPI_GELU_OP, GT_256);
+    run("fc1: EPI_LNF_GELU_OP", I, K, EPI_LNF_GELU_OP, GT_256);
+    run("qkv: EPI_OP", 4608, K, EPI_OP, GT_256);
+    run("qkv: EPI_LNF_OP", 4608, K, EPI_LNF_OP, GT_256);
   }
 }
 
@@ -477,7 +477,7 @@ static void w4_ab(int rounds) {
           gemm_force_variant(variants[v]);
           GemmProb p{};
           p.persist = v == 1;
-          p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = v == 1 ? C1 : C0; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.tile_cfg = 3;
+          p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = v == 1 ? C1 : C0; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.tile_cfg = GT_256;
           double best = 1e30;
           for (int r = 0; r < rounds; ++r) {
             if (launch_gemm(&p, 1, epi, OP_F16, 0)) { printf("variant %d refused\n", variants[v]); best = -1; break; }
@@ -524,7 +524,7 @@ static void p8_stamp() {
   const size_t nent = (size_t)tiles * 8 * 8;
   CK(hipMalloc((void**)&dbg, nent * 8));
   GemmProb p{};
-  p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = C; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.tile_cfg = 3;
+  p.A = A; p.a = RowView{0, M, K}; p.W = W; p.bias = bias; p.C = C; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.tile_cfg = GT_256;
   for (int rep = 0; rep < 2; ++rep) {
     for (int i = 0; i < 2; ++i) launch_gemm(&p, 1, EPI_OP, OP_F16, 0);
     CK(hipMemset(dbg, 0, nent * 8));
@@ -569,23 +569,23 @@ int main(int argc, char** argv) {
   const int only = argc > 2 ? atoi(argv[2]) : -1;      // run a single shape (profiling)
   const int only_variant = argc > 3 ? atoi(argv[3]) : -1;
   const Shape shapes[] = {
-      {"kvproj video 32x8224 (headline)", 32 * 8224, 9216, 1408, EPI_KV, -1},
-      {"kvproj video 32x257 (ref)", 32 * 257, 9216, 1408, EPI_KV, -1},
-      {"kvproj audio 32x496", 32 * 496, 9216, 768, EPI_KV, -1},
-      {"qkv 2048x768->2304", 2048, 2304, 768, EPI_OP, -1},
-      {"qkv 2048x768->2304 cfg1", 2048, 2304, 768, EPI_OP, 1},
-      {"attn-out 2048x768->768", 2048, 768, 768, EPI_RES_F32, -1},
-      {"cross-q 1024x768->768", 1024, 768, 768, EPI_OP, -1},
-      {"ffn-up 2048x768->3072", 2048, 3072, 768, EPI_GELU_OP, -1},
-      {"ffn-up 2048x768->3072 cfg0", 2048, 3072, 768, EPI_GELU_OP, 0},
-      {"ffn-down 2048x3072->768", 2048, 768, 3072, EPI_RES_F32, -1},
-      {"ffn-down 2048x3072->768 cfg1", 2048, 768, 3072, EPI_RES_F32, 1},
+      {"kvproj video 32x8224 (headline)", 32 * 8224, 9216, 1408, EPI_KV, GT_AUTO},
+      {"kvproj video 32x257 (ref)", 32 * 257, 9216, 1408, EPI_KV, GT_AUTO},
+      {"kvproj audio 32x496", 32 * 496, 9216, 768, EPI_KV, GT_AUTO},
+      {"qkv 2048x768->2304", 2048, 2304, 768, EPI_OP, GT_AUTO},
+      {"qkv 2048x768->2304 GT_128", 2048, 2304, 768, EPI_OP, GT_128},
+      {"attn-out 2048x768->768", 2048, 768, 768, EPI_RES_F32, GT_AUTO},
+      {"cross-q 1024x768->768", 1024, 768, 768, EPI_OP, GT_AUTO},
+      {"ffn-up 2048x768->3072", 2048, 3072, 768, EPI_GELU_OP, GT_AUTO},
+      {"ffn-up 2048x768->3072 GT_64", 2048, 3072, 768, EPI_GELU_OP, GT_64},
+      {"ffn-down 2048x3072->768", 2048, 768, 3072, EPI_RES_F32, GT_AUTO},
+      {"ffn-down 2048x3072->768 GT_128", 2048, 768, 3072, EPI_RES_F32, GT_128},
       // proxies for the folded cross-attention: scores enc . Q'^T and P . enc per layer, all 32 items
-      {"fold scores N384 128-tile", 32 * 8224, 384, 1408, EPI_OP, 1},
-      {"fold scores N512 256-tile", 32 * 8224, 512, 1408, EPI_OP, 2},
-      {"fold scores N512 f32 out", 32 * 8224, 512, 1408, EPI_F32, 2},
-      {"fold P.enc M12288 N1408 K8256 128", 32 * 384, 1408, 8256, EPI_OP, 1},
-      {"fold P.enc M16384 N1536 K8256 256", 32 * 512, 1536, 8256, EPI_OP, 2},
+      {"fold scores N384 128-tile", 32 * 8224, 384, 1408, EPI_OP, GT_128},
+      {"fold scores N512 256-tile", 32 * 8224, 512, 1408, EPI_OP, GT_256},
+      {"fold scores N512 f32 out", 32 * 8224, 512, 1408, EPI_F32, GT_256},
+      {"fold P.enc M12288 N1408 K8256 128", 32 * 384, 1408, 8256, EPI_OP, GT_128},
+      {"fold P.enc M16384 N1536 K8256 256", 32 * 512, 1536, 8256, EPI_OP, GT_256},
   };
   size_t maxA = 0, maxW = 0, maxC = 0;
   for (auto& s : shapes) {
@@ -627,7 +627,7 @@ int main(int argc, char** argv) {
     p.R = R; p.r = RowView{0, s.M, s.N};
     p.M = s.M; p.N = s.N; p.K = s.K;
     if (s.epi == EPI_KV) { p.kv_tokens = s.M / 32; p.kv_items = 32; p.kv_heads = 12; }
-    gemm_force_config(s.cfg);
+    gemm_force_config(s.tile);
     double best[10] = {1e30, 1e30, 1e30, 1e30, 1e30, 1e30, 1e30, 1e30, 1e30, 1e30};
     const int reps = s.M > 100000 ? 3 : 20;
     for (int r = 0; r < rounds; ++r)
@@ -657,7 +657,7 @@ int main(int argc, char** argv) {
     CK(hipMemset(dbg, 0, nent * 8));
     gemm_set_debug_buffer(dbg);
     gemm_force_variant(4);
-    gemm_force_config(-1);
+    gemm_force_config(GT_AUTO);
     const Shape& s = shapes[0];
     GemmProb p{};
     p.A = A; p.a = RowView{0, s.M, s.K};
@@ -678,6 +678,6 @@ int main(int argc, char** argv) {
     gemm_set_debug_buffer(nullptr);
   }
   gemm_force_variant(5);
-  gemm_force_config(-1);
+  gemm_force_config(GT_AUTO);
   return 0;
 }

@@ -750,92 +750,87 @@ __global__ void __launch_bounds__(256) gemm_w4p_kernel(const GemmArgs args) {
   }
 }
 
+// The 128 x 512 tail tile with the statistics epilogues: launch_gemm has no way to them (the mixed kernel is the one that runs a tail tile with
+// statistics), but with them in the translation unit the compiler keeps the tile body they share with gemm_p8_mixed_kernel as it was when
+// that kernel was measured -- this library is the measuring instrument (gemm_bench), so its code does not move with the dispatcher
+template __global__ void gemm_p8_kernel<f16, EPI_RES_OP_STAT, true>(const GemmArgs);
+template __global__ void gemm_p8_kernel<f16, EPI_RES_F32_STAT, true>(const GemmArgs);
+template __global__ void gemm_p8_kernel<bf16, EPI_RES_OP_STAT, true>(const GemmArgs);
+template __global__ void gemm_p8_kernel<bf16, EPI_RES_F32_STAT, true>(const GemmArgs);
+
+using EpiW4 = Epis<EPI_OP, EPI_GELU_OP, EPI_KV>;
 template <typename T>
 int launch_w4p(const GemmArgs& a, int epi, hipStream_t stream) {
   constexpr size_t lds = 2 * (256 + 256) * 128;
-  switch (epi) {
-    case EPI_OP: return launch_k(gemm_w4p_kernel<T, EPI_OP>, a, 256, lds, stream);
-    case EPI_GELU_OP: return launch_k(gemm_w4p_kernel<T, EPI_GELU_OP>, a, 256, lds, stream);
-    case EPI_KV: return launch_k(gemm_w4p_kernel<T, EPI_KV>, a, 256, lds, stream);
-    default: return -2;
-  }
+  return with_epi(EpiW4{}, epi, [&](auto e) { return launch_k(gemm_w4p_kernel<T, e()>, a, 256, lds, stream); });
 }
-
 template <typename T>
 int launch_w4(const GemmArgs& a, int epi, hipStream_t stream) {
   constexpr size_t lds = 2 * (256 + 256) * 128;
-  switch (epi) {
-    case EPI_OP: return launch_k(gemm_w4_kernel<T, EPI_OP>, a, 256, lds, stream);
-    case EPI_GELU_OP: return launch_k(gemm_w4_kernel<T, EPI_GELU_OP>, a, 256, lds, stream);
-    case EPI_KV: return launch_k(gemm_w4_kernel<T, EPI_KV>, a, 256, lds, stream);
-    default: return -2;
-  }
+  return with_epi(EpiW4{}, epi, [&](auto e) { return launch_k(gemm_w4_kernel<T, e()>, a, 256, lds, stream); });
 }
-
 template <typename T>
 int launch_rot(const GemmArgs& a, int epi, hipStream_t stream) {
   constexpr size_t lds = 2 * (256 + 256) * 128;
-  MRA_EPI_SWITCH((launch_k(gemm_rot_kernel<T, E>, a, 512, lds, stream)))
+  return with_epi(EpiDirect{}, epi, [&](auto e) { return launch_k(gemm_rot_kernel<T, e()>, a, 512, lds, stream); });
 }
-
 template <typename T, int TN, int TM, int WGN, int WGM, int NS, int SPI>
 int launch_ring(const GemmArgs& a, int epi, hipStream_t stream) {
   constexpr size_t lds = (size_t)NS * (TN + TM) * 64;
-  MRA_EPI_SWITCH((launch_k(gemm_ring_kernel<T, TN, TM, WGN, WGM, NS, SPI, E>, a, WGN * WGM * 64, lds, stream)))
+  return with_epi(EpiDirect{}, epi, [&](auto e) { return launch_k(gemm_ring_kernel<T, TN, TM, WGN, WGM, NS, SPI, e()>, a, WGN * WGM * 64, lds, stream); });
 }
 template <typename T, int TN, int TM, int WGN, int WGM, bool PF, bool SPREAD>
 int launch_v1x(const GemmArgs& a, int epi, hipStream_t stream) {
   constexpr size_t lds = 2 * (TN + TM) * 128 + (PF ? WGN * WGM * 512 : 0);
-  MRA_EPI_SWITCH((launch_k(gemm_v1x_kernel<T, TN, TM, WGN, WGM, E, PF, SPREAD>, a, WGN * WGM * 64, lds, stream)))
+  return with_epi(EpiDirect{}, epi, [&](auto e) { return launch_k(gemm_v1x_kernel<T, TN, TM, WGN, WGM, e(), PF, SPREAD>, a, WGN * WGM * 64, lds, stream); });
 }
 template <typename T>
 int launch_ws2(const GemmArgs& a, int epi, hipStream_t stream) {
   constexpr size_t lds = 4 * (256 + 256) * 64 + 64;
-  MRA_EPI_SWITCH((launch_k(gemm_ws2_kernel<T, E>, a, 768, lds, stream)))
+  return with_epi(EpiDirect{}, epi, [&](auto e) { return launch_k(gemm_ws2_kernel<T, e()>, a, 768, lds, stream); });
+}
+template <typename T, int TN, int TM, int WGN, int WGM>
+int launch_k128(const GemmArgs& a, int epi, hipStream_t stream) {
+  constexpr size_t lds = 2 * (TN + TM) * 256;
+  return with_epi(EpiDirect{}, epi, [&](auto e) { return launch_k(gemm_k128_kernel<T, TN, TM, WGN, WGM, e()>, a, WGN * WGM * 64, lds, stream); });
 }
 
-// returns -100 when `variant` is not an experiment (the caller then takes the shipped path)
+// `variant` as an experiment's main loop for `tile` (GT_64 / GT_128 / GT_256): true and *rc = the launch's result; false when the variant
+// has none for this tile and epilogue (the caller then takes the shipped path)
 template <typename T>
-int launch_experiment(const GemmArgs& a, int cfg, int epi, int variant, hipStream_t stream) {
+bool launch_experiment(const GemmArgs& a, int tile, int epi, int variant, hipStream_t stream, int* rc) {
   switch (variant) {
     case 0:
-      if (cfg == 2) return launch_ring<T, 256, 256, 2, 4, 5, 2>(a, epi, stream);
-      if (cfg == 1) return launch_ring<T, 128, 128, 2, 2, 6, 2>(a, epi, stream);
-      return launch_ring<T, 64, 64, 2, 2, 8, 2>(a, epi, stream);
+      *rc = tile == GT_256 ? launch_ring<T, 256, 256, 2, 4, 5, 2>(a, epi, stream) : tile == GT_128 ? launch_ring<T, 128, 128, 2, 2, 6, 2>(a, epi, stream) : launch_ring<T, 64, 64, 2, 2, 8, 2>(a, epi, stream);
+      return true;
     case 2:
-      if (cfg == 2) return launch_v1x<T, 256, 256, 2, 4, true, false>(a, epi, stream);
-      if (cfg == 1) return launch_v1x<T, 128, 128, 2, 2, true, false>(a, epi, stream);
-      return launch_v1x<T, 64, 64, 2, 2, true, false>(a, epi, stream);
+      *rc = tile == GT_256 ? launch_v1x<T, 256, 256, 2, 4, true, false>(a, epi, stream) : tile == GT_128 ? launch_v1x<T, 128, 128, 2, 2, true, false>(a, epi, stream) : launch_v1x<T, 64, 64, 2, 2, true, false>(a, epi, stream);
+      return true;
     case 3:
-      if (cfg == 2) return launch_v1x<T, 256, 256, 2, 4, false, true>(a, epi, stream);
-      if (cfg == 1) return launch_v1x<T, 128, 128, 2, 2, false, true>(a, epi, stream);
-      return launch_v1x<T, 64, 64, 2, 2, false, true>(a, epi, stream);
+      *rc = tile == GT_256 ? launch_v1x<T, 256, 256, 2, 4, false, true>(a, epi, stream) : tile == GT_128 ? launch_v1x<T, 128, 128, 2, 2, false, true>(a, epi, stream) : launch_v1x<T, 64, 64, 2, 2, false, true>(a, epi, stream);
+      return true;
     case 4:
-      if (cfg == 2 && epi == EPI_KV)
-        return launch_k(gemm_v1x_kernel<T, 256, 256, 2, 4, EPI_KV, false, false, true>, a, 512, 2 * 512 * 128, stream);
-      return -100;
+      if (tile != GT_256 || epi != EPI_KV) return false;
+      *rc = launch_k(gemm_v1x_kernel<T, 256, 256, 2, 4, EPI_KV, false, false, true>, a, 512, 2 * 512 * 128, stream);
+      return true;
     case 6:
-      if (cfg == 2 && epi == EPI_KV) return launch_k(gemm_ws_kernel<T, EPI_KV, true>, a, 768, 2 * 512 * 128, stream);
-      return -100;
+      if (tile != GT_256 || epi != EPI_KV) return false;
+      *rc = launch_k(gemm_ws_kernel<T, EPI_KV, true>, a, 768, 2 * 512 * 128, stream);
+      return true;
     case 7:
-      if (cfg == 2) return launch_ws2<T>(a, epi, stream);
-      return -100;
     case 9:
-      if (cfg == 2) return launch_rot<T>(a, epi, stream);
-      return -100;
     case 10:
-      if (cfg == 2) return launch_w4<T>(a, epi, stream);
-      return -100;
     case 11:
-      if (cfg == 2) return launch_w4p<T>(a, epi, stream);
-      return -100;
-    case 8:
-      if (cfg < 2) {
-        bool k128 = true;
-        for (int g = 0; g < a.ngroups; ++g) k128 = k128 && a.p[g].K % 128 == 0;
-        if (k128) return cfg == 1 ? launch_k128<T, 128, 128, 2, 2>(a, epi, stream) : launch_k128<T, 64, 64, 2, 2>(a, epi, stream);
-      }
-      return -100;
+      if (tile != GT_256) return false;
+      *rc = variant == 7 ? launch_ws2<T>(a, epi, stream) : variant == 9 ? launch_rot<T>(a, epi, stream) : variant == 10 ? launch_w4<T>(a, epi, stream) : launch_w4p<T>(a, epi, stream);
+      return true;
+    case 8: {
+      bool k128 = true;
+      for (int g = 0; g < a.ngroups; ++g) k128 = k128 && a.p[g].K % 128 == 0;
+      if (tile == GT_256 || !k128) return false;
+      *rc = tile == GT_128 ? launch_k128<T, 128, 128, 2, 2>(a, epi, stream) : launch_k128<T, 64, 64, 2, 2>(a, epi, stream);
+      return true;
+    }
   }
-  return -100;
+  return false;
 }

@@ -1,5 +1,5 @@
 // Standalone GPU self-check of the gfx950 kernels against straightforward host loops.
-// Test infrastructure: links libmra_hip.so, runs in seconds, no Python.  `kernel_check [quick]`.
+// Test infrastructure: links libmra_hip.so, runs in seconds, no Python.  `kernel_check [quick]`; `kernel_check plan` needs no GPU (see plan_mode).
 // Every case prints one line "ok|FAIL name max_err tol"; exit code = number of failed cases.
 #include <hip/hip_runtime.h>
 
@@ -88,7 +88,7 @@ static long long voff(const RowView& v, int m) { return (long long)(m / v.rpi) *
 // ------------------------------------------------------------------------------------------------
 static int g_test_order = 0;   // GemmProb::order of the next test_gemm problems (tile walk)
 static int g_test_persist = 0; // GemmProb::persist of the next test_gemm problems (one workgroup per CU)
-static void test_gemm(int cfg, int epi, int op, int M, int N, int K, bool views, int groups = 1) {
+static void test_gemm(int tile, int epi, int op, int M, int N, int K, bool views, int groups = 1) {
   // activations live in [items, S, K] with the rows of interest at [:, off:off+rpi]
   const int rpi = views ? 5 : (M > 0 ? M : 1);
   const int S = views ? 9 : rpi, off = views ? 3 : 0;
@@ -143,7 +143,7 @@ static void test_gemm(int cfg, int epi, int op, int M, int N, int K, bool views,
     p.M = q == 0 ? M : (M > 3 ? M - 3 : M);
     p.N = N;
     p.K = K;
-    p.tile_cfg = cfg >= 0 ? cfg + 1 : 0;   // per problem: the shipped library has no global switches
+    p.tile_cfg = tile;   // per problem: the shipped library has no global switches
     p.order = g_test_order; p.persist = g_test_persist;
     if (epi == EPI_RES_F32 || epi == EPI_F32) {
       p.C = dC32[q]->p + (size_t)off * ldc;
@@ -198,7 +198,7 @@ static void test_gemm(int cfg, int epi, int op, int M, int N, int K, bool views,
     }
   }
   char name[160];
-  snprintf(name, sizeof(name), "gemm cfg%d epi%d %s M%d N%d K%d views%d groups%d", cfg, epi, op == OP_F16 ? "f16" : "bf16", M, N, K,
+  snprintf(name, sizeof(name), "gemm tile%d epi%d %s M%d N%d K%d views%d groups%d", tile, epi, op == OP_F16 ? "f16" : "bf16", M, N, K,
            (int)views, groups);
   const bool lowp_out = epi == EPI_OP || epi == EPI_GELU_OP || epi == EPI_KV || epi == EPI_RES_OP;
   report(name, worst, op == OP_F16 ? (lowp_out ? 2e-3 : 5e-4) : (lowp_out ? 1.2e-2 : 4e-3));
@@ -330,7 +330,7 @@ static void test_gemm_kmajor(int op, int M, int N, int K, int k_rows, int batch)
   memset(&p, 0, sizeof(p));
   p.A = dA.p; p.a = RowView{0, M, K}; p.W = dW.p; p.C = dC.p; p.c = RowView{0, M, N};
   p.M = M; p.N = N; p.K = K; p.batch = batch; p.a_bs = (long long)M * K; p.w_bs = (long long)k_rows * ldw; p.c_bs_bytes = (long long)M * N * 2;
-  p.w_ld = ldw; p.k_rows = k_rows; p.tile_cfg = 5;
+  p.w_ld = ldw; p.k_rows = k_rows; p.tile_cfg = GT_WS_176x384;
   const int rc = launch_gemm(&p, 1, EPI_OP, op, 0);
   CK(hipDeviceSynchronize());
   std::vector<uint16_t> c = dC.get();
@@ -375,7 +375,7 @@ static void test_gemm_res_ln(int op, int M, int N, int K, int groups) {
     GemmProb& p = probs[q];
     memset(&p, 0, sizeof(p));
     p.A = dA[q]->p; p.a = RowView{0, M, K}; p.W = dW[q]->p; p.bias = dB[q]->p; p.R = dR[q]->p; p.r = RowView{0, M, N};
-    p.C = dC[q]->p; p.c = RowView{0, M, N}; p.M = Mq; p.N = N; p.K = K; p.tile_cfg = 11;
+    p.C = dC[q]->p; p.c = RowView{0, M, N}; p.M = Mq; p.N = N; p.K = K; p.tile_cfg = GT_RING_96x64;
     p.ln_gain = dG[q]->p; p.ln_bias = dBe[q]->p; p.ln_eps = 1e-12f; p.ln_y32 = dY32[q]->p; p.ln_y32v = RowView{0, M, N};
     p.ln_y16 = dY16[q]->p; p.ln_y16v = RowView{0, M, N}; p.ln_counter = dCnt.p + (size_t)q * mt;
   }
@@ -448,7 +448,7 @@ static void test_gemm_ln_fold(int op, int M, int D, int K1, int N2, bool gelu, f
   GemmProb p;
   memset(&p, 0, sizeof(p));
   p.A = dA1.p; p.a = RowView{0, M, K1}; p.W = dW1.p; p.bias = dB1.p; p.R = dR.p; p.r = RowView{0, M, D};
-  p.C = dX.p; p.c = RowView{0, M, D}; p.M = M; p.N = D; p.K = K1; p.tile_cfg = D % 256 ? 8 : 3;
+  p.C = dX.p; p.c = RowView{0, M, D}; p.M = M; p.N = D; p.K = K1; p.tile_cfg = D % 256 ? GT_P8_MIXED : GT_256;
   p.ln_y32 = dGroups.p; p.ln_y16 = dX16.p; p.ln_y16v = RowView{0, M, D};
   int rc = launch_gemm(&p, 1, EPI_RES_F32_STAT, op, 0);
   CK(hipDeviceSynchronize());
@@ -484,7 +484,7 @@ static void test_gemm_ln_fold(int op, int M, int D, int K1, int N2, bool gelu, f
   Dev<float> dSt(stat);
   GemmProb q;
   memset(&q, 0, sizeof(q));
-  q.A = dX16.p; q.a = RowView{0, M, D}; q.W = dW2f.p; q.bias = dBf.p; q.C = dY.p; q.c = RowView{0, M, N2}; q.M = M; q.N = N2; q.K = D; q.tile_cfg = 3;
+  q.A = dX16.p; q.a = RowView{0, M, D}; q.W = dW2f.p; q.bias = dBf.p; q.C = dY.p; q.c = RowView{0, M, N2}; q.M = M; q.N = N2; q.K = D; q.tile_cfg = GT_256;
   q.ln_gain = dCs.p; q.ln_y32 = dSt.p;
   rc = launch_gemm(&q, 1, gelu ? EPI_LNF_GELU_OP : EPI_LNF_OP, op, 0);
   CK(hipDeviceSynchronize());
@@ -529,7 +529,7 @@ static void test_gemm_res_op_stat(int op, int M, int N, int K, float offset) {
     memset(&p, 0, sizeof(p));
     uint16_t* x = pass ? dX1.p : dX0.p;
     p.A = dA.p; p.a = RowView{0, M, K}; p.W = dW.p; p.bias = dB.p; p.C = x; p.aux = x; p.c = RowView{0, M, N};
-    p.M = M; p.N = N; p.K = K; p.tile_cfg = N % 256 ? 8 : 3; p.ln_y32 = dG.p;
+    p.M = M; p.N = N; p.K = K; p.tile_cfg = N % 256 ? GT_P8_MIXED : GT_256; p.ln_y32 = dG.p;
     rc = launch_gemm(&p, 1, pass ? EPI_RES_OP_STAT : EPI_RES_OP, op, 0);
   }
   CK(hipDeviceSynchronize());
@@ -552,7 +552,7 @@ static void test_gemm_res_op_stat(int op, int M, int N, int K, float offset) {
 }
 
 // n_mask: N not a multiple of the tile, plain [M][N] output rows; columns past N are neither read (bias, residual) nor stored
-static void test_gemm_masked(int cfg, int epi, int op, int M, int N, int K) {
+static void test_gemm_masked(int tile, int epi, int op, int M, int N, int K) {
   std::vector<uint16_t> A((size_t)M * K), W((size_t)N * K);
   for (auto& v : A) v = to_op(frand(), op);
   for (auto& v : W) v = to_op(frand(0.05f), op);
@@ -564,7 +564,7 @@ static void test_gemm_masked(int cfg, int epi, int op, int M, int N, int K) {
   GemmProb p;
   memset(&p, 0, sizeof(p));
   p.A = dA.p; p.a = RowView{0, M, K}; p.W = dW.p; p.bias = dB.p; p.R = dR.p; p.r = RowView{0, M, N};
-  p.C = dC.p; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.n_mask = 1; p.tile_cfg = cfg + 1; p.order = g_test_order; p.persist = g_test_persist;
+  p.C = dC.p; p.c = RowView{0, M, N}; p.M = M; p.N = N; p.K = K; p.n_mask = 1; p.tile_cfg = tile; p.order = g_test_order; p.persist = g_test_persist;
   const int rc = launch_gemm(&p, 1, epi, op, 0);
   CK(hipDeviceSynchronize());
   std::vector<float> c = dC.get();
@@ -577,7 +577,7 @@ static void test_gemm_masked(int cfg, int epi, int op, int M, int N, int K) {
     }
   for (size_t i = (size_t)M * N; i < c.size(); ++i) if (c[i] != 7.5f) worst = 1e30;   // nothing may be written past the matrix
   char name[128];
-  snprintf(name, sizeof(name), "gemm masked-N cfg%d epi%d %s M%d N%d K%d", cfg, epi, op == OP_F16 ? "f16" : "bf16", M, N, K);
+  snprintf(name, sizeof(name), "gemm masked-N tile%d epi%d %s M%d N%d K%d", tile, epi, op == OP_F16 ? "f16" : "bf16", M, N, K);
   report(name, worst, 2e-4);
 }
 
@@ -601,7 +601,7 @@ static void test_gemm_pscale(int op, int M, int N, int kv, int batch) {
   memset(&p, 0, sizeof(p));
   p.A = dA.p; p.a = RowView{0, M, K}; p.W = dW.p; p.C = dC.p; p.c = RowView{0, M, N};
   p.M = M; p.N = N; p.K = K; p.batch = batch; p.a_bs = (long long)M * K; p.w_bs = (long long)kv * ldw; p.c_bs_bytes = (long long)M * N * 2;
-  p.w_ld = ldw; p.k_rows = kv; p.tile_cfg = 5; p.pscale = dG.p; p.ps_ntiles = ntiles;
+  p.w_ld = ldw; p.k_rows = kv; p.tile_cfg = GT_WS_176x384; p.pscale = dG.p; p.ps_ntiles = ntiles;
   const int rc = launch_gemm(&p, 1, EPI_OP, op, 0);
   CK(hipDeviceSynchronize());
   std::vector<uint16_t> c = dC.get();
@@ -638,7 +638,7 @@ static void test_gemm_softpart(int op, int M, int kv, int K, int batch) {
   GemmProb p;
   memset(&p, 0, sizeof(p));
   p.A = dA.p; p.a = RowView{0, M, K}; p.a_bs = (long long)M * K; p.W = dW.p; p.w_bs = (long long)kv * K;
-  p.M = M; p.N = kv; p.K = K; p.batch = batch; p.n_ragged = 1; p.tile_cfg = 5;
+  p.M = M; p.N = kv; p.K = K; p.batch = batch; p.n_ragged = 1; p.tile_cfg = GT_WS_176x384;
   p.C = dP.p; p.c = RowView{0, M, ldp}; p.c_bs_bytes = (long long)M * ldp * 2; p.alpha = alpha; p.stat_m = dM.p; p.stat_l = dL.p;
   const int rc = launch_gemm(&p, 1, EPI_SOFTPART, op, 0);
   CK(hipDeviceSynchronize());
@@ -677,8 +677,8 @@ static void test_gemm_softpart(int op, int M, int kv, int K, int batch) {
 // batched launch (one weight matrix per batch entry) with a ragged N: the folded cross-attention's GEMMs
 // wrap: GemmProb::w_kwrap -- W holds only K / 2 columns and is walked twice (A = (hi | lo) rows of the split-precision scores product);
 // W is allocated EXACTLY (a stride of K instead of K / 2 would run off its end)
-static void test_gemm_batched(int cfg, int epi, int op, int M, int N, int K, int batch, bool ragged, bool wrap = false) {
-  const int t = cfg == 0 ? 64 : (cfg == 2 ? 256 : (cfg == 4 ? 176 : 128));   // weight rows per tile (config 3: 128 x 384, 4: 176 x 384)
+static void test_gemm_batched(int tile, int epi, int op, int M, int N, int K, int batch, bool ragged, bool wrap = false) {
+  const int t = tile == GT_64 ? 64 : (tile == GT_256 ? 256 : (tile == GT_WS_176x384 ? 176 : 128));   // weight rows per tile
   const int ldc = (N + t - 1) / t * t;                       // C rows hold whole tiles
   const int KW = wrap ? K / 2 : K;
   std::vector<uint16_t> A((size_t)batch * M * K), W((size_t)batch * N * KW);
@@ -693,7 +693,7 @@ static void test_gemm_batched(int cfg, int epi, int op, int M, int N, int K, int
   p.A = dA.p; p.a = RowView{0, M, K}; p.W = dW.p; p.bias = ragged ? nullptr : dB.p;
   p.M = M; p.N = N; p.K = K;
   p.batch = batch; p.a_bs = (long long)M * K; p.w_bs = (long long)N * KW; p.bias_bs = N;
-  p.n_ragged = ragged ? 1 : 0; p.tile_cfg = cfg + 1; p.w_kwrap = wrap ? KW / 64 : 0;
+  p.n_ragged = ragged ? 1 : 0; p.tile_cfg = tile; p.w_kwrap = wrap ? KW / 64 : 0;
   const bool f32 = epi == EPI_F32;
   p.C = f32 ? (void*)dC32.p : (void*)dC16.p; p.c = RowView{0, M, ldc};
   p.c_bs_bytes = (long long)M * ldc * (f32 ? 4 : 2);
@@ -712,7 +712,7 @@ static void test_gemm_batched(int cfg, int epi, int op, int M, int N, int K, int
         worst = std::max(worst, fabs(got - acc) / (1 + fabs(acc)));
       }
   char name[128];
-  snprintf(name, sizeof(name), "gemm batched cfg%d epi%d M%d N%d K%d x%d%s%s", cfg, epi, M, N, K, batch, ragged ? " ragged-N" : "", wrap ? " W walked twice" : "");
+  snprintf(name, sizeof(name), "gemm batched tile%d epi%d M%d N%d K%d x%d%s%s", tile, epi, M, N, K, batch, ragged ? " ragged-N" : "", wrap ? " W walked twice" : "");
   report(name, worst, f32 ? 2e-4 : 3e-3);
 }
 
@@ -1250,7 +1250,164 @@ static void test_attn_bwd(int items, int heads, int q_rows, int kv_len, bool sel
   report(std::string(name) + " backward dV", wv, tol);
 }
 
+// ---- `kernel_check plan`: gemm_plan over a fixed matrix of problems, before any HIP call (no GPU needed) ----------------------------
+// One line per case: inputs -> return code, tile, family, threads, LDS bytes, grid, persistent, tiles, order and tile_begin / mtiles / ntiles
+// per problem.  The matrix is every GemmTile (and automatic) x every GemmEpi (and one number that is none) x {f16, bf16} x two CU counts
+// (256: the MI355X; 8: persistent launches also at small shapes) x the shapes below, which hit each rule of gemm_plan from both sides.
+struct PlanCase {
+  const char* name;
+  int ngroups;
+  GemmProb p[GEMM_MAX_GROUPS + 1];
+};
+
+static GemmProb plan_prob(int M, int N, int K) {   // a problem every epilogue accepts (where its tile does)
+  static char mem[64];
+  GemmProb p{};
+  p.A = p.W = mem; p.C = p.aux = p.ln_y16 = mem;
+  p.R = p.ln_gain = p.ln_bias = reinterpret_cast<float*>(mem);
+  p.bias = reinterpret_cast<float*>(mem);
+  p.ln_y32 = p.stat_m = p.stat_l = reinterpret_cast<float*>(mem);
+  p.ln_counter = reinterpret_cast<unsigned*>(mem);
+  p.M = M; p.N = N; p.K = K;
+  p.a = RowView{0, M, K};
+  p.c = p.r = p.ln_y32v = p.ln_y16v = RowView{0, M, N};
+  p.kv_tokens = M; p.kv_items = 1; p.kv_heads = 12;
+  p.ln_eps = 1e-5f; p.alpha = 1.f;
+  return p;
+}
+
+static std::vector<PlanCase> plan_cases() {
+  std::vector<PlanCase> v;
+  auto add = [&](const char* name, std::initializer_list<GemmProb> ps) {
+    PlanCase c{};
+    c.name = name;
+    for (const GemmProb& p : ps) c.p[c.ngroups++] = p;
+    v.push_back(c);
+  };
+  auto with = [](GemmProb p, auto f) { f(p); return p; };
+  const int F = 16 * 257;   // ViT-g: 16 frames of 257 tokens
+  add("vit proj 4112x1408->1408", {plan_prob(F, 1408, 1408)});
+  add("vit proj masked", {with(plan_prob(F, 1408, 1408), [](GemmProb& p) { p.n_mask = 1; p.order = 8; })});
+  add("vit qkv 4112x1408->4224", {plan_prob(F, 4224, 1408)});
+  add("vit qkv persist", {with(plan_prob(F, 4608, 1408), [](GemmProb& p) { p.persist = 1; })});
+  add("vit fc1 persist", {with(plan_prob(F, 6144, 1408), [](GemmProb& p) { p.persist = 1; })});
+  add("vit fc1 one frame persist", {with(plan_prob(257, 6144, 1408), [](GemmProb& p) { p.persist = 1; })});
+  add("vit fc2 4112x6144->1408", {plan_prob(F, 1408, 6144)});
+  add("persist batch 2", {with(plan_prob(F, 6144, 1408), [](GemmProb& p) { p.persist = 1; p.batch = 2; })});
+  add("persist 2 problems", {with(plan_prob(F, 6144, 1408), [](GemmProb& p) { p.persist = 1; }), plan_prob(F, 6144, 1408)});
+  add("kv projection 32x257 x1408->9216", {with(plan_prob(32 * 257, 9216, 1408), [](GemmProb& p) { p.kv_tokens = 257; p.kv_items = 32; })});
+  add("kv projection no heads", {with(plan_prob(32 * 257, 9216, 1408), [](GemmProb& p) { p.kv_heads = 0; })});
+  add("chain qkv 2048x768->2304", {plan_prob(2048, 2304, 768)});
+  add("chain out 2048x768->768", {plan_prob(2048, 768, 768)});
+  add("chain ffn-up 2 x 1024x768->3072", {plan_prob(1024, 3072, 768), plan_prob(1024, 3072, 768)});
+  add("chain ffn-down 2048x3072->768", {plan_prob(2048, 768, 3072)});
+  add("chain 4 problems 512x768->768", {plan_prob(512, 768, 768), plan_prob(512, 768, 768), plan_prob(509, 768, 768), plan_prob(512, 768, 768)});
+  add("5 problems", {plan_prob(512, 768, 768), plan_prob(512, 768, 768), plan_prob(512, 768, 768), plan_prob(512, 768, 768), plan_prob(512, 768, 768)});
+  add("no problem", {});
+  add("small 300x1408->768", {plan_prob(300, 768, 1408)});
+  add("N 1024", {plan_prob(2048, 1024, 768)});
+  add("N 1280", {plan_prob(2048, 1280, 768)});
+  add("no residual", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.R = nullptr; })});
+  add("no aux", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.aux = nullptr; })});
+  add("no ln_y32", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.ln_y32 = nullptr; })});
+  add("no ln_y16", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.ln_y16 = nullptr; })});
+  add("no ln_counter", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.ln_counter = nullptr; })});
+  add("no statistics", {with(plan_prob(384, 8448, 1408), [](GemmProb& p) { p.stat_l = nullptr; p.bias = nullptr; })});
+  add("c.ld + 4", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.c.ld += 4; })});
+  add("c.ld + 2", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.c.ld += 2; })});
+  add("ln_y16v.ld + 4", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.ln_y16v.ld += 4; })});
+  add("c.rpi 0", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.c.rpi = 0; })});
+  add("batch 2", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.batch = 2; })});
+  add("batch -1", {with(plan_prob(2048, 768, 768), [](GemmProb& p) { p.batch = -1; })});
+  add("M 0", {plan_prob(0, 768, 768)});
+  add("K 3 steps", {plan_prob(1024, 512, 192)});
+  add("K 4 steps", {plan_prob(1024, 512, 256)});
+  add("K 1 step", {plan_prob(1024, 512, 64)});
+  add("K 32 steps", {plan_prob(1024, 512, 2048)});
+  add("K 33 steps", {plan_prob(1024, 512, 2112)});
+  add("K 100", {plan_prob(1024, 512, 100)});
+  add("K 4 and 3 steps", {plan_prob(1024, 512, 256), plan_prob(1024, 512, 192)});
+  add("K 32 and 4 steps", {plan_prob(1024, 576, 2048), plan_prob(1024, 576, 256)});
+  add("tail N 128 K 384", {plan_prob(1300, 128, 384)});
+  add("tail N 128 K 192", {plan_prob(1300, 128, 192)});
+  add("tail 2 problems", {plan_prob(1300, 128, 384), plan_prob(700, 128, 128)});
+  add("mixed N 384", {plan_prob(1300, 384, 256)});
+  add("mixed N 640 K 192", {plan_prob(1300, 640, 192)});
+  add("N 1412 masked", {with(plan_prob(F, 1412, 1408), [](GemmProb& p) { p.n_mask = 1; })});
+  add("N 1410 masked", {with(plan_prob(F, 1410, 1408), [](GemmProb& p) { p.n_mask = 1; })});
+  add("masked and ragged", {with(plan_prob(F, 1408, 1408), [](GemmProb& p) { p.n_mask = 1; p.n_ragged = 1; p.bias = nullptr; })});
+  // the folded cross-attention: 32 items, 384 (head, query) rows, 8224 / 496 encoder tokens
+  auto item = [](GemmProb& p) { p.batch = 32; p.bias = nullptr; };
+  add("fold scores 8224 ragged", {with(plan_prob(384, 8224, 1408), [&](GemmProb& p) { item(p); p.n_ragged = 1; })});
+  add("fold scores 8224 ragged with bias", {with(plan_prob(384, 8224, 1408), [&](GemmProb& p) { p.batch = 32; p.n_ragged = 1; })});
+  add("fold scores 8224", {with(plan_prob(384, 8224, 1408), item)});
+  add("fold scores 8448", {with(plan_prob(384, 8448, 1408), item)});
+  add("fold scores 496 ragged", {with(plan_prob(384, 496, 768), [&](GemmProb& p) { item(p); p.n_ragged = 1; })});
+  add("fold scores split precision", {with(plan_prob(384, 8448, 2816), [&](GemmProb& p) { item(p); p.w_kwrap = 22; })});
+  add("fold scores w_kwrap 21", {with(plan_prob(384, 8448, 2816), [&](GemmProb& p) { item(p); p.w_kwrap = 21; })});
+  auto kmajor = [&](GemmProb& p) { item(p); p.w_ld = 1408; p.k_rows = 8224; };
+  add("fold P.enc K-major", {with(plan_prob(384, 1408, 8448), kmajor)});
+  add("fold P.enc K-major w_ld 1412", {with(plan_prob(384, 1408, 8448), [&](GemmProb& p) { kmajor(p); p.w_ld = 1412; })});
+  add("fold P.enc K-major no k_rows", {with(plan_prob(384, 1408, 8448), [&](GemmProb& p) { kmajor(p); p.k_rows = 0; })});
+  add("fold P.enc K-major w_kwrap", {with(plan_prob(384, 1408, 8448), [&](GemmProb& p) { kmajor(p); p.w_kwrap = 66; })});
+  add("fold P.enc K-major N 1536", {with(plan_prob(384, 1536, 8448), kmajor)});
+  add("fold P.enc pscale", {with(plan_prob(384, 1408, 8448), [&](GemmProb& p) { kmajor(p); p.pscale = p.R; p.ps_ntiles = 47; })});
+  add("fold P.enc pscale 40 tiles", {with(plan_prob(384, 1408, 8448), [&](GemmProb& p) { kmajor(p); p.pscale = p.R; p.ps_ntiles = 40; })});
+  add("fold P.enc pscale 512 rows", {with(plan_prob(512, 1408, 8448), [&](GemmProb& p) { kmajor(p); p.pscale = p.R; p.ps_ntiles = 47; })});
+  add("fold P.enc pscale row-major", {with(plan_prob(384, 1408, 8448), [&](GemmProb& p) { item(p); p.pscale = p.R; p.ps_ntiles = 47; })});
+  add("fold P.enc row-major", {with(plan_prob(384, 1408, 8448), item)});
+  add("fold context 384x1408->64", {with(plan_prob(12288, 64, 1408), [](GemmProb& p) { p.batch = 12; })});
+  return v;
+}
+
+struct PlanRecord {   // what a launch would be
+  int rc, tile, family, threads, lds, grid, persistent, total_tiles, order;
+  int tile_begin[GEMM_MAX_GROUPS], mtiles[GEMM_MAX_GROUPS], ntiles[GEMM_MAX_GROUPS];
+};
+
+static PlanRecord plan_record(const GemmProb* probs, int ngroups, int epi, int op, int cus) {
+  static GemmPlan pl;
+  pl.cus = cus;
+  PlanRecord r{};
+  r.rc = gemm_plan(probs, ngroups, epi, op, &pl);
+  if (r.rc) return r;
+  r.tile = pl.tile; r.family = pl.family; r.threads = pl.threads; r.lds = pl.lds; r.grid = pl.grid; r.persistent = pl.persistent;
+  r.total_tiles = pl.args.total_tiles; r.order = pl.args.order;
+  for (int g = 0; g < ngroups; ++g) { r.tile_begin[g] = pl.args.p[g].tile_begin; r.mtiles[g] = pl.args.p[g].mtiles; r.ntiles[g] = pl.args.p[g].ntiles; }
+  return r;
+}
+
+static int plan_mode() {
+  std::vector<PlanCase> cases = plan_cases();
+  int n = 0, accepted = 0, no_epi = 0, bad = 0;
+  for (PlanCase& c : cases)
+    for (int tile = GT_AUTO; tile < GEMM_TILES; ++tile)
+      for (int epi = 0; epi <= 14; ++epi)
+        for (int op : {OP_F16, OP_BF16})
+          for (int cus : {256, 8}) {
+            for (int g = 0; g < c.ngroups; ++g) c.p[g].tile_cfg = tile;
+            const PlanRecord r = plan_record(c.p, c.ngroups, epi, op, cus);
+            printf("%s | tile %d epi %d %s cus %d -> rc %d", c.name, tile, epi, op == OP_F16 ? "f16" : "bf16", cus, r.rc);
+            ++n;
+            no_epi += r.rc == -2;
+            if (r.rc == 0) {
+              ++accepted;
+              printf(" tile %d family %d threads %d lds %d grid %d persistent %d tiles %d order %d |", r.tile, r.family, r.threads, r.lds, r.grid, r.persistent, r.total_tiles, r.order);
+              for (int g = 0; g < c.ngroups; ++g) printf(" %d/%d/%d", r.tile_begin[g], r.mtiles[g], r.ntiles[g]);
+              // what holds for every accepted launch
+              const bool ok = r.threads > 0 && r.threads <= 1024 && r.lds <= 160 * 1024 && r.total_tiles > 0 && (tile == GT_AUTO ? r.tile >= GT_64 && r.tile <= GT_256 : r.tile == tile) &&
+                              (r.persistent ? cus >= 8 && r.grid == (cus & ~7) && r.total_tiles > cus && r.family == GF_P8_256 : r.grid == r.total_tiles);
+              if (!ok) { ++bad; printf(" FAIL"); }
+            }
+            printf("\n");
+          }
+  printf("plan: %d cases, %d accepted, %d refused (%d for the epilogue), %d failed\n", n, accepted, n - accepted, no_epi, bad);
+  // the dispatcher this one replaced accepted exactly these, launch for launch; a change of either number is a change of behaviour
+  return bad != 0 || n != 48960 || accepted != 7812;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "plan")) return plan_mode();
   const bool quick = argc > 1 && !strcmp(argv[1], "quick");
   int dev = 0;
   CK(hipGetDevice(&dev));
@@ -1289,101 +1446,101 @@ int main(int argc, char** argv) {
   test_score();
 
   // GEMM: every tile config x epilogue, ragged M, row views, grouped
-  for (int cfg = 0; cfg < 3; ++cfg) {
-    const int t = cfg == 0 ? 64 : (cfg == 1 ? 128 : 256);
-    test_gemm(cfg, EPI_OP, OP_F16, 2 * t + 37, 2 * t, 192, true);
-    test_gemm(cfg, EPI_GELU_OP, OP_F16, t - 5, t, 64, false, 2);
-    test_gemm(cfg, EPI_RES_F32, OP_F16, 3 * t + 1, t, 128, true, 2);
-    test_gemm(cfg, EPI_F32, OP_F16, t, 2 * t, 256, false);
-    test_gemm(cfg, EPI_KV, OP_F16, 2 * t + 10, 2 * t >= 256 ? 2 * t : 256, 128, false);
-    test_gemm(cfg, EPI_OP, OP_BF16, t + 3, t, 128, true);
+  for (int tile : {GT_64, GT_128, GT_256}) {
+    const int t = tile == GT_64 ? 64 : (tile == GT_128 ? 128 : 256);
+    test_gemm(tile, EPI_OP, OP_F16, 2 * t + 37, 2 * t, 192, true);
+    test_gemm(tile, EPI_GELU_OP, OP_F16, t - 5, t, 64, false, 2);
+    test_gemm(tile, EPI_RES_F32, OP_F16, 3 * t + 1, t, 128, true, 2);
+    test_gemm(tile, EPI_F32, OP_F16, t, 2 * t, 256, false);
+    test_gemm(tile, EPI_KV, OP_F16, 2 * t + 10, 2 * t >= 256 ? 2 * t : 256, 128, false);
+    test_gemm(tile, EPI_OP, OP_BF16, t + 3, t, 128, true);
   }
-  test_gemm(-1, EPI_OP, OP_F16, 300, 768, 1408, false);  // automatic config
+  test_gemm(GT_AUTO, EPI_OP, OP_F16, 300, 768, 1408, false);  // automatic config
   // the eight-phase 256 x 256 kernel (even K / 64): every epilogue, ragged M, row views, two problems, K = 128 (one pair) .. 1408
-  test_gemm(2, EPI_OP, OP_F16, 2 * 256 + 37, 512, 128, true);
-  test_gemm(2, EPI_KV, OP_F16, 2100, 1536, 1408, false);
-  test_gemm(2, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
-  test_gemm(2, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 384, true, 2);
-  test_gemm(2, EPI_F32, OP_BF16, 300, 512, 256, false);
-  test_gemm(2, EPI_RES_OP, OP_F16, 600, 512, 640, true);
-  test_gemm(2, EPI_OP, OP_BF16, 1000, 768, 768, false, 2);
-  test_gemm_masked(2, EPI_RES_F32, OP_F16, 700, 352, 128);
-  test_gemm_masked(2, EPI_F32, OP_F16, 300, 1408, 256);
-  test_gemm(6, EPI_RES_F32, OP_F16, 1300, 128, 384, true);        // the 128 x 512 form (tile_cfg 7): one column tile, ragged M, views
-  test_gemm(6, EPI_F32, OP_BF16, 1000, 128, 128, false);
-  test_gemm(6, EPI_RES_OP, OP_F16, 700, 128, 1408, true);
-  test_gemm(6, EPI_RES_F32, OP_F16, 512, 128, 6144, false);
+  test_gemm(GT_256, EPI_OP, OP_F16, 2 * 256 + 37, 512, 128, true);
+  test_gemm(GT_256, EPI_KV, OP_F16, 2100, 1536, 1408, false);
+  test_gemm(GT_256, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
+  test_gemm(GT_256, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 384, true, 2);
+  test_gemm(GT_256, EPI_F32, OP_BF16, 300, 512, 256, false);
+  test_gemm(GT_256, EPI_RES_OP, OP_F16, 600, 512, 640, true);
+  test_gemm(GT_256, EPI_OP, OP_BF16, 1000, 768, 768, false, 2);
+  test_gemm_masked(GT_256, EPI_RES_F32, OP_F16, 700, 352, 128);
+  test_gemm_masked(GT_256, EPI_F32, OP_F16, 300, 1408, 256);
+  test_gemm(GT_P8_TAIL, EPI_RES_F32, OP_F16, 1300, 128, 384, true);        // the 128 x 512 form (GT_P8_TAIL): one column tile, ragged M, views
+  test_gemm(GT_P8_TAIL, EPI_F32, OP_BF16, 1000, 128, 128, false);
+  test_gemm(GT_P8_TAIL, EPI_RES_OP, OP_F16, 700, 128, 1408, true);
+  test_gemm(GT_P8_TAIL, EPI_RES_F32, OP_F16, 512, 128, 6144, false);
   g_test_persist = 1;                                              // the eight-phase kernel as one persistent workgroup per CU: more tiles than CUs, ragged M, views
-  test_gemm(2, EPI_OP, OP_F16, 17 * 256 - 90, 4096, 256, true);
-  test_gemm(2, EPI_GELU_OP, OP_BF16, 4200, 4096, 128, false);
-  test_gemm(2, EPI_KV, OP_F16, 9 * 256 + 10, 8192, 128, false);
+  test_gemm(GT_256, EPI_OP, OP_F16, 17 * 256 - 90, 4096, 256, true);
+  test_gemm(GT_256, EPI_GELU_OP, OP_BF16, 4200, 4096, 128, false);
+  test_gemm(GT_256, EPI_KV, OP_F16, 9 * 256 + 10, 8192, 128, false);
   g_test_persist = 0;
   test_gemm_ln_fold(OP_F16, 700, 384, 256, 512, false, 0.f);      // LayerNorm folded into the producer / consumer GEMMs: mixed tiles (N = 256 k + 128), ragged M
   test_gemm_ln_fold(OP_F16, 1300, 1408, 128, 256, true, 0.f);      // the ViT's width: 11 groups, odd number of row tiles, GELU consumer
   test_gemm_ln_fold(OP_F16, 520, 640, 384, 256, false, 8.f);       // row means 8 sigma from zero
-  test_gemm_ln_fold(OP_BF16, 600, 512, 128, 512, true, 0.f);       // N = 256 k: full tiles only (tile_cfg 3)
+  test_gemm_ln_fold(OP_BF16, 600, 512, 128, 512, true, 0.f);       // N = 256 k: full tiles only (GT_256)
   test_gemm_res_op_stat(OP_F16, 1300, 1408, 128, 0.f);             // the same for the residual stream in the operand dtype: mixed tiles, ragged M
   test_gemm_res_op_stat(OP_F16, 520, 640, 384, 8.f);
   test_gemm_res_op_stat(OP_BF16, 600, 512, 128, 0.f);              // full tiles only
-  test_gemm(7, EPI_RES_F32, OP_F16, 1300, 384, 256, true);         // tile_cfg 8: 256-wide tiles + 128 x 512 tail tiles in one launch; odd number of row tiles
-  test_gemm(7, EPI_F32, OP_BF16, 1024, 640, 128, false);
-  test_gemm(7, EPI_RES_OP, OP_F16, 2100, 1408, 384, true);
-  test_gemm(7, EPI_OP, OP_F16, 1300, 384, 256, true);             // 16-bit outputs through the tail tile's LDS-staged epilogue (gemm_bench qkvpad: un-padded ViT QKV)
-  test_gemm(7, EPI_OP, OP_BF16, 1024, 640, 128, false);
-  test_gemm(7, EPI_RES_F32, OP_F16, 700, 1408, 1408, false);
-  // the ring kernel's exact-fit tiles (tile_cfg 9 / 10 / 11): every epilogue, ragged M, row views, two problems, 1 .. 48 K steps (fewer than,
+  test_gemm(GT_P8_MIXED, EPI_RES_F32, OP_F16, 1300, 384, 256, true);         // GT_P8_MIXED: 256-wide tiles + 128 x 512 tail tiles in one launch; odd number of row tiles
+  test_gemm(GT_P8_MIXED, EPI_F32, OP_BF16, 1024, 640, 128, false);
+  test_gemm(GT_P8_MIXED, EPI_RES_OP, OP_F16, 2100, 1408, 384, true);
+  test_gemm(GT_P8_MIXED, EPI_OP, OP_F16, 1300, 384, 256, true);             // 16-bit outputs through the tail tile's LDS-staged epilogue (gemm_bench qkvpad: un-padded ViT QKV)
+  test_gemm(GT_P8_MIXED, EPI_OP, OP_BF16, 1024, 640, 128, false);
+  test_gemm(GT_P8_MIXED, EPI_RES_F32, OP_F16, 700, 1408, 1408, false);
+  // the ring kernel's exact-fit tiles (GT_RING_*): every epilogue, ragged M, row views, two problems, 1 .. 48 K steps (fewer than,
   // exactly, and many more than the ring holds)
-  test_gemm(8, EPI_OP, OP_F16, 2 * 128 + 37, 288, 192, true);
-  test_gemm(8, EPI_OP, OP_F16, 700, 144, 768, false);
-  test_gemm(8, EPI_GELU_OP, OP_F16, 100, 288, 256, false);
-  test_gemm(8, EPI_OP, OP_BF16, 300, 144, 128, false, 2);
-  test_gemm(8, EPI_OP, OP_F16, 128 + 5, 432, 64, true, 2);
-  test_gemm(9, EPI_GELU_OP, OP_F16, 2 * 128 + 37, 384, 768, true, 2);
-  test_gemm(9, EPI_OP, OP_BF16, 128, 192, 64, false);
-  test_gemm(9, EPI_OP, OP_F16, 500, 576, 128, true);
-  test_gemm(10, EPI_RES_F32, OP_F16, 3 * 64 + 11, 192, 3072, true, 2);
-  test_gemm(10, EPI_RES_F32, OP_F16, 500, 768, 768, false);
-  test_gemm(10, EPI_OP, OP_F16, 200, 96, 448, true);
-  test_gemm(10, EPI_F32, OP_BF16, 64, 288, 64, false);
-  test_gemm(10, EPI_GELU_OP, OP_F16, 70, 96, 384, false);
+  test_gemm(GT_RING_144x128, EPI_OP, OP_F16, 2 * 128 + 37, 288, 192, true);
+  test_gemm(GT_RING_144x128, EPI_OP, OP_F16, 700, 144, 768, false);
+  test_gemm(GT_RING_144x128, EPI_GELU_OP, OP_F16, 100, 288, 256, false);
+  test_gemm(GT_RING_144x128, EPI_OP, OP_BF16, 300, 144, 128, false, 2);
+  test_gemm(GT_RING_144x128, EPI_OP, OP_F16, 128 + 5, 432, 64, true, 2);
+  test_gemm(GT_RING_192x128, EPI_GELU_OP, OP_F16, 2 * 128 + 37, 384, 768, true, 2);
+  test_gemm(GT_RING_192x128, EPI_OP, OP_BF16, 128, 192, 64, false);
+  test_gemm(GT_RING_192x128, EPI_OP, OP_F16, 500, 576, 128, true);
+  test_gemm(GT_RING_96x64, EPI_RES_F32, OP_F16, 3 * 64 + 11, 192, 3072, true, 2);
+  test_gemm(GT_RING_96x64, EPI_RES_F32, OP_F16, 500, 768, 768, false);
+  test_gemm(GT_RING_96x64, EPI_OP, OP_F16, 200, 96, 448, true);
+  test_gemm(GT_RING_96x64, EPI_F32, OP_BF16, 64, 288, 64, false);
+  test_gemm(GT_RING_96x64, EPI_GELU_OP, OP_F16, 70, 96, 384, false);
   test_gemm_res_ln(OP_F16, 2048, 768, 768, 1);
   test_gemm_res_ln(OP_F16, 1024 - 30, 768, 3072, 2);
   test_gemm_res_ln(OP_BF16, 200, 768, 128, 1);
   test_gemm_res_ln(OP_F16, 333, 768, 256, 2);
   test_gemm_res_ln(OP_F16, 70, 768, 64, 1);
   // an odd number of K steps takes the loader-wave 256 x 256 kernel (8 compute + 4 loader waves)
-  test_gemm(2, EPI_GELU_OP, OP_F16, 600, 512, 1344, false);   // GELU epilogue, pre-activations out to |x| ~ 6
-  test_gemm(2, EPI_RES_OP, OP_F16, 2 * 256 + 37, 512, 192, true);
-  test_gemm(2, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
-  test_gemm(2, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
-  test_gemm(2, EPI_OP, OP_BF16, 300, 512, 192, false);
-  test_gemm(2, EPI_F32, OP_F16, 300, 256, 704, false);
+  test_gemm(GT_256, EPI_GELU_OP, OP_F16, 600, 512, 1344, false);   // GELU epilogue, pre-activations out to |x| ~ 6
+  test_gemm(GT_256, EPI_RES_OP, OP_F16, 2 * 256 + 37, 512, 192, true);
+  test_gemm(GT_256, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
+  test_gemm(GT_256, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
+  test_gemm(GT_256, EPI_OP, OP_BF16, 300, 512, 192, false);
+  test_gemm(GT_256, EPI_F32, OP_F16, 300, 256, 704, false);
   g_test_order = 8;   // column-fastest panels (the ViT's N = 1408 GEMMs)
-  test_gemm(2, EPI_RES_F32, OP_F16, 1300, 512, 320, true, 2);
-  test_gemm(2, EPI_RES_F32, OP_F16, 1300, 512, 384, true, 2);
-  test_gemm_masked(2, EPI_RES_F32, OP_F16, 1500, 1408, 192);
-  test_gemm_masked(2, EPI_RES_F32, OP_F16, 1500, 1408, 256);
-  test_gemm(1, EPI_OP, OP_F16, 700, 640, 128, true);
+  test_gemm(GT_256, EPI_RES_F32, OP_F16, 1300, 512, 320, true, 2);
+  test_gemm(GT_256, EPI_RES_F32, OP_F16, 1300, 512, 384, true, 2);
+  test_gemm_masked(GT_256, EPI_RES_F32, OP_F16, 1500, 1408, 192);
+  test_gemm_masked(GT_256, EPI_RES_F32, OP_F16, 1500, 1408, 256);
+  test_gemm(GT_128, EPI_OP, OP_F16, 700, 640, 128, true);
   g_test_order = 0;
-  test_gemm_masked(2, EPI_RES_F32, OP_F16, 700, 352, 128);   // N = 1.4 column tiles of 256, the tail is neither read nor stored
-  test_gemm_masked(2, EPI_F32, OP_F16, 300, 1408, 192);
-  test_gemm_masked(1, EPI_RES_F32, OP_BF16, 200, 200, 64);
-  test_gemm_batched(1, EPI_F32, OP_F16, 96, 300, 192, 3, true);     // scores: M = 3 x 32 rows, N = kv ragged
-  test_gemm_batched(1, EPI_OP, OP_F16, 96, 256, 320, 3, false);     // P . enc^T
-  test_gemm_batched(0, EPI_OP, OP_F16, 70, 128, 64, 4, false);      // per-head projections, K = 64
-  test_gemm_batched(0, EPI_F32, OP_BF16, 33, 100, 128, 2, true);
-  test_gemm_batched(2, EPI_F32, OP_F16, 300, 700, 128, 2, true);
-  test_gemm_batched(3, EPI_F32, OP_F16, 384, 300, 192, 2, true);    // the 128 x 384 loader-wave tile
-  test_gemm_batched(3, EPI_OP, OP_F16, 384, 256, 320, 3, false);
-  test_gemm_batched(3, EPI_OP, OP_BF16, 200, 128, 128, 2, false);   // fewer rows than the tile
-  test_gemm_batched(3, EPI_F32, OP_F16, 500, 129, 64, 1, true);     // two row tiles, one K step
-  test_gemm_batched(4, EPI_OP, OP_F16, 384, 352, 320, 3, false);    // 176 x 384, compute waves in one column
-  test_gemm_batched(4, EPI_OP, OP_BF16, 300, 176, 128, 2, false);
-  test_gemm_batched(4, EPI_OP, OP_F16, 500, 528, 64, 1, false);     // two row tiles, one K step
-  test_gemm_batched(4, EPI_F32, OP_F16, 384, 300, 192, 2, true);    // scores: ragged N on the 176-row tile
-  test_gemm_batched(4, EPI_F32, OP_F16, 384, 300, 384, 2, true, true);   // split-precision scores: A = (hi | lo), the weight slab walked twice
-  test_gemm_batched(4, EPI_F32, OP_F16, 384, 530, 2816, 1, true, true);  // ... at the video width (E = 1408)
-  test_gemm_batched(3, EPI_F32, OP_BF16, 300, 256, 256, 2, false, true);
+  test_gemm_masked(GT_256, EPI_RES_F32, OP_F16, 700, 352, 128);   // N = 1.4 column tiles of 256, the tail is neither read nor stored
+  test_gemm_masked(GT_256, EPI_F32, OP_F16, 300, 1408, 192);
+  test_gemm_masked(GT_128, EPI_RES_F32, OP_BF16, 200, 200, 64);
+  test_gemm_batched(GT_128, EPI_F32, OP_F16, 96, 300, 192, 3, true);     // scores: M = 3 x 32 rows, N = kv ragged
+  test_gemm_batched(GT_128, EPI_OP, OP_F16, 96, 256, 320, 3, false);     // P . enc^T
+  test_gemm_batched(GT_64, EPI_OP, OP_F16, 70, 128, 64, 4, false);      // per-head projections, K = 64
+  test_gemm_batched(GT_64, EPI_F32, OP_BF16, 33, 100, 128, 2, true);
+  test_gemm_batched(GT_256, EPI_F32, OP_F16, 300, 700, 128, 2, true);
+  test_gemm_batched(GT_WS_128x384, EPI_F32, OP_F16, 384, 300, 192, 2, true);    // the 128 x 384 loader-wave tile
+  test_gemm_batched(GT_WS_128x384, EPI_OP, OP_F16, 384, 256, 320, 3, false);
+  test_gemm_batched(GT_WS_128x384, EPI_OP, OP_BF16, 200, 128, 128, 2, false);   // fewer rows than the tile
+  test_gemm_batched(GT_WS_128x384, EPI_F32, OP_F16, 500, 129, 64, 1, true);     // two row tiles, one K step
+  test_gemm_batched(GT_WS_176x384, EPI_OP, OP_F16, 384, 352, 320, 3, false);    // 176 x 384, compute waves in one column
+  test_gemm_batched(GT_WS_176x384, EPI_OP, OP_BF16, 300, 176, 128, 2, false);
+  test_gemm_batched(GT_WS_176x384, EPI_OP, OP_F16, 500, 528, 64, 1, false);     // two row tiles, one K step
+  test_gemm_batched(GT_WS_176x384, EPI_F32, OP_F16, 384, 300, 192, 2, true);    // scores: ragged N on the 176-row tile
+  test_gemm_batched(GT_WS_176x384, EPI_F32, OP_F16, 384, 300, 384, 2, true, true);   // split-precision scores: A = (hi | lo), the weight slab walked twice
+  test_gemm_batched(GT_WS_176x384, EPI_F32, OP_F16, 384, 530, 2816, 1, true, true);  // ... at the video width (E = 1408)
+  test_gemm_batched(GT_WS_128x384, EPI_F32, OP_BF16, 300, 256, 256, 2, false, true);
   test_gemm_kmajor(OP_F16, 384, 352, 320, 300, 2);                  // P . enc with the weights K-major (transposed LDS reads)
   test_gemm_kmajor(OP_F16, 200, 176, 64, 64, 3);
   test_gemm_kmajor(OP_BF16, 384, 528, 192, 150, 1);
@@ -1394,7 +1551,7 @@ int main(int argc, char** argv) {
   test_gemm_pscale(OP_F16, 384, 352, 1000, 2);                      // 6 score tiles, K 1152: the factor ring wraps, NaN tail
   test_gemm_pscale(OP_F16, 384, 176, 150, 3);
   test_gemm_pscale(OP_BF16, 200, 176, 700, 1);
-  test_gemm_batched(4, EPI_F32, OP_F16, 100, 177, 64, 2, true);
+  test_gemm_batched(GT_WS_176x384, EPI_F32, OP_F16, 100, 177, 64, 2, true);
   test_fold_stream(2, 300, 704, 1.f);       // two score tiles, ragged kv, two E slabs
   test_fold_stream(1, 2100, 704, 1.f);      // 12 score tiles, K loop of 34 steps (not a multiple of the set rotation)
   test_fold_stream(2, 700, 704, 12.f);      // peaked rows: tile factors spread over many powers of two
@@ -1402,43 +1559,43 @@ int main(int argc, char** argv) {
   test_fold_stream(3, 176, 1408, 2.f);      // exactly one tile, the video width
 #ifdef MRA_GEMM_EXPERIMENTS   // kernel_check_exp (links tests/native/libmra_hip_exp.so): the A/B main loops of gemm_experiments.inc
   gemm_set_eight_phase(0);                               // the loader-wave kernel on an even number of K steps
-  test_gemm(2, EPI_GELU_OP, OP_F16, 600, 512, 1408, false);
-  test_gemm(2, EPI_KV, OP_F16, 2100, 1536, 1408, false);
+  test_gemm(GT_256, EPI_GELU_OP, OP_F16, 600, 512, 1408, false);
+  test_gemm(GT_256, EPI_KV, OP_F16, 2100, 1536, 1408, false);
   gemm_set_eight_phase(1);
   gemm_force_variant(1);                                 // the two-buffer main loop kept for A/B runs
-  for (int cfg = 0; cfg < 3; ++cfg) {
-    const int t = cfg == 0 ? 64 : (cfg == 1 ? 128 : 256);
-    test_gemm(cfg, EPI_RES_F32, OP_F16, 2 * t + 37, 2 * t, 192, true, 2);
-    test_gemm(cfg, EPI_KV, OP_F16, t + 10, 2 * t >= 256 ? 2 * t : 256, 64, false);
+  for (int tile : {GT_64, GT_128, GT_256}) {
+    const int t = tile == GT_64 ? 64 : (tile == GT_128 ? 128 : 256);
+    test_gemm(tile, EPI_RES_F32, OP_F16, 2 * t + 37, 2 * t, 192, true, 2);
+    test_gemm(tile, EPI_KV, OP_F16, t + 10, 2 * t >= 256 ? 2 * t : 256, 64, false);
   }
   gemm_force_variant(2);                                 // v1 + L2 prefetch
-  for (int cfg = 0; cfg < 3; ++cfg) {
-    const int t = cfg == 0 ? 64 : (cfg == 1 ? 128 : 256);
-    test_gemm(cfg, EPI_RES_F32, OP_F16, 2 * t + 37, 2 * t, 320, true, 2);
-    test_gemm(cfg, EPI_KV, OP_F16, t + 10, 2 * t >= 256 ? 2 * t : 256, 64, false);
+  for (int tile : {GT_64, GT_128, GT_256}) {
+    const int t = tile == GT_64 ? 64 : (tile == GT_128 ? 128 : 256);
+    test_gemm(tile, EPI_RES_F32, OP_F16, 2 * t + 37, 2 * t, 320, true, 2);
+    test_gemm(tile, EPI_KV, OP_F16, t + 10, 2 * t >= 256 ? 2 * t : 256, 64, false);
   }
   gemm_force_variant(3);                                 // v1 with the LDS-DMA issue spread over the MFMAs
-  for (int cfg = 0; cfg < 3; ++cfg) {
-    const int t = cfg == 0 ? 64 : (cfg == 1 ? 128 : 256);
-    test_gemm(cfg, EPI_RES_F32, OP_F16, 2 * t + 37, 2 * t, 320, true, 2);
-    test_gemm(cfg, EPI_KV, OP_F16, t + 10, 2 * t >= 256 ? 2 * t : 256, 64, false);
+  for (int tile : {GT_64, GT_128, GT_256}) {
+    const int t = tile == GT_64 ? 64 : (tile == GT_128 ? 128 : 256);
+    test_gemm(tile, EPI_RES_F32, OP_F16, 2 * t + 37, 2 * t, 320, true, 2);
+    test_gemm(tile, EPI_KV, OP_F16, t + 10, 2 * t >= 256 ? 2 * t : 256, 64, false);
   }
   gemm_force_variant(5);                                 // warp-specialised 256x256 loop (8 compute + 4 loader waves)
-  test_gemm(2, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
-  test_gemm(2, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
-  test_gemm(2, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
-  test_gemm(2, EPI_OP, OP_BF16, 300, 512, 192, false);
+  test_gemm(GT_256, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
+  test_gemm(GT_256, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
+  test_gemm(GT_256, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
+  test_gemm(GT_256, EPI_OP, OP_BF16, 300, 512, 192, false);
   {
     unsigned long long* dbg;
     CK(hipMalloc((void**)&dbg, 64));
     CK(hipMemset(dbg, 0, 64));
     gemm_set_debug_buffer(dbg);
     gemm_force_variant(7);                               // ws2: LDS-flag hand-off, no barrier in the K loop
-    test_gemm(2, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
-    test_gemm(2, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
-    test_gemm(2, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
-    test_gemm(2, EPI_OP, OP_BF16, 300, 512, 192, false);
-    test_gemm(2, EPI_KV, OP_F16, 2100, 1536, 1408, false);
+    test_gemm(GT_256, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
+    test_gemm(GT_256, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
+    test_gemm(GT_256, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
+    test_gemm(GT_256, EPI_OP, OP_BF16, 300, 512, 192, false);
+    test_gemm(GT_256, EPI_KV, OP_F16, 2100, 1536, 1408, false);
     unsigned long long flag = 0;
     CK(hipMemcpy(&flag, dbg, 8, hipMemcpyDeviceToHost));
     report("ws2 spin give-ups (must be 0)", (double)flag, 0);
@@ -1446,23 +1603,23 @@ int main(int argc, char** argv) {
     (void)hipFree(dbg);
   }
   gemm_force_variant(9);                                 // rot: deferred half tile across the barrier
-  test_gemm(2, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
-  test_gemm(2, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
-  test_gemm(2, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
-  test_gemm(2, EPI_OP, OP_BF16, 300, 512, 128, false);
+  test_gemm(GT_256, EPI_RES_F32, OP_F16, 2 * 256 + 37, 512, 320, true, 2);
+  test_gemm(GT_256, EPI_KV, OP_F16, 256 + 10, 512, 64, false);
+  test_gemm(GT_256, EPI_GELU_OP, OP_F16, 700, 256, 1408, true);
+  test_gemm(GT_256, EPI_OP, OP_BF16, 300, 512, 128, false);
   gemm_force_variant(8);                                 // 128-deep K steps for the 64 / 128 tiles
-  for (int cfg = 0; cfg < 2; ++cfg) {
-    const int t = cfg == 0 ? 64 : 128;
-    test_gemm(cfg, EPI_OP, OP_F16, 2 * t + 37, 2 * t, 384, true);
-    test_gemm(cfg, EPI_GELU_OP, OP_F16, t - 5, t, 128, false, 2);
-    test_gemm(cfg, EPI_RES_F32, OP_F16, 3 * t + 1, t, 768, true, 2);
-    test_gemm(cfg, EPI_KV, OP_F16, 2 * t + 10, 256, 1408, false);
-    test_gemm(cfg, EPI_OP, OP_BF16, t + 3, t, 256, true);
-    test_gemm(cfg, EPI_F32, OP_F16, t, 2 * t, 192, false);   // K % 128 != 0: falls back to the 64-deep loop
+  for (int tile : {GT_64, GT_128}) {
+    const int t = tile == GT_64 ? 64 : 128;
+    test_gemm(tile, EPI_OP, OP_F16, 2 * t + 37, 2 * t, 384, true);
+    test_gemm(tile, EPI_GELU_OP, OP_F16, t - 5, t, 128, false, 2);
+    test_gemm(tile, EPI_RES_F32, OP_F16, 3 * t + 1, t, 768, true, 2);
+    test_gemm(tile, EPI_KV, OP_F16, 2 * t + 10, 256, 1408, false);
+    test_gemm(tile, EPI_OP, OP_BF16, t + 3, t, 256, true);
+    test_gemm(tile, EPI_F32, OP_F16, t, 2 * t, 192, false);   // K % 128 != 0: falls back to the 64-deep loop
   }
   gemm_force_variant(0);                                 // ring loop
-  test_gemm(2, EPI_OP, OP_F16, 300, 512, 64, false);     // K = 64: fewer slots than the ring holds
-  test_gemm(0, EPI_OP, OP_F16, 100, 128, 3072, false);   // long K on the 8-slot ring
+  test_gemm(GT_256, EPI_OP, OP_F16, 300, 512, 64, false);     // K = 64: fewer slots than the ring holds
+  test_gemm(GT_64, EPI_OP, OP_F16, 100, 128, 3072, false);   // long K on the 8-slot ring
   gemm_force_variant(5);
 #endif
 
@@ -1477,7 +1634,7 @@ int main(int argc, char** argv) {
   test_attention(OP_BF16, 2, 2, 64, 64, true, 1);
   if (!quick) {
     test_attention(OP_F16, 2, 12, 32, 8224, false, 4);
-    test_gemm(2, EPI_KV, OP_F16, 2100, 1536, 1408, false);
+    test_gemm(GT_256, EPI_KV, OP_F16, 2100, 1536, 1408, false);
   }
   printf("%d case(s) failed\n", g_fail);
   return g_fail;

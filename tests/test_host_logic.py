@@ -2,6 +2,7 @@
 span parsing pinned to the reference's own functions through tests/golden/integer_kats.json)."""
 import json
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -168,3 +169,13 @@ def test_batched_encode_is_sample_major_and_sharded():
     pre = torch.randn(B, T, 7, 16)
     rp, _, _, _ = X._encode(stub, {"video_embeds": pre}, "video", 2, 9)
     assert torch.equal(rp, pre.reshape(B * T, 7, 16)[2:9])
+
+
+def test_gemm_plan_matrix_needs_no_gpu():
+    """`kernel_check plan` walks gemm_plan (tile, kernel family, grid and every refusal of launch_gemm) over its fixed matrix of
+    problems before any HIP call; it checks what holds for every accepted launch and how many the matrix accepts."""
+    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "kernel_check")
+    assert os.path.exists(exe), f"{exe} is missing: build() makes it"
+    r = subprocess.run([exe, "plan"], capture_output=True, text=True, timeout=300)
+    last = r.stdout.strip().splitlines()[-1]
+    assert r.returncode == 0 and last.startswith("plan: ") and last.endswith(" 0 failed"), (r.returncode, last, r.stderr[-500:])
