@@ -369,6 +369,24 @@ double mra_beats_flops(mra_beats* h, int32_t n, int32_t frames);
 /* Per-handle options.  "gemm_persist" (default 1): the QKV / fc1 GEMMs as one persistent workgroup per CU (as mra_vit_set_option). */
 int mra_beats_set_option(mra_beats* h, const char* name, int32_t value);
 
+/* ---- audio front end: waveform -> normalised filterbank (row A1, the input side of the audio half) ------------------
+ * replaces: LAVIS BeatsAudioProcessor.__call__ -> torchaudio.compliance.kaldi.fbank (call sites evaluate.py:24,
+ * utils/trainer.py:46), the host-side producer of the [T, frame_length, 128] tensors mra_beats_forward consumes.  The arithmetic
+ * is that of mraudio_amd/processors/audio_processors.py (kaldi_fbank with BEATs' arguments, then (x - 15.41663) / (2 * 6.55582));
+ * those arguments are constants of the kernel, so there is no configuration struct.  fp32 throughout.
+ * mra_fbank_create builds the window / transform / mel tables on the host in float64 and uploads them: the only allocation. */
+typedef struct mra_fbank mra_fbank;
+int mra_fbank_create(mra_fbank** out);
+void mra_fbank_destroy(mra_fbank* h);
+/* wave fp32 [total_samples] (device; mono, 16 kHz, in [-1, 1]); segs int64 [n_seg][2] (device): first sample and number of
+ * samples of each temporal position, clipped to [0, total_samples) inside the kernel; out [n_seg, frame_length, 128] (device,
+ * MRA_F32 or MRA_F16): frame t of a segment is its 400 samples at 160 t (snip_edges), rows past its last frame are written as
+ * zero.  One launch; no allocation, no synchronisation, no host read of segs.  n_seg == 0 is a no-op. */
+int mra_fbank_forward(mra_fbank* h, const float* wave, int64_t total_samples, const int64_t* segs, int32_t n_seg, int32_t frame_length,
+                      void* out, int32_t out_dtype, void* stream);
+/* executed flops of one forward (2 per MAC: the dense 400 x 512 transform, the power spectrum, the sparse mel sums) */
+double mra_fbank_flops(mra_fbank* h, int32_t n_seg, int32_t frame_length);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------
  * Number of GEMM launches of one main loop ("family") with one epilogue since the library was loaded; read-only, the only
  * process-wide state of the library.  `family` is a GemmFamily and `epilogue` a GemmEpi of csrc/kernels.h (the numbers mraudio_amd/_lib.py

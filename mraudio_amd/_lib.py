@@ -108,6 +108,10 @@ PROTOTYPES = {
     "mra_beats_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mra_beats_flops": (C.c_double, [C.c_void_p, C.c_int32, C.c_int32]),
     "mra_beats_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
+    "mra_fbank_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "mra_fbank_destroy": (None, [C.c_void_p]),
+    "mra_fbank_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mra_fbank_flops": (C.c_double, [C.c_void_p, C.c_int32, C.c_int32]),
     "mra_debug_gemm_launches": (C.c_int64, [C.c_int32, C.c_int32]),
 }
 

@@ -14,7 +14,9 @@ What differs, on purpose: the reference hands the projected query
 formats the span as the same ``"[[start, end]]"`` string, so ``evaluate.py``-shaped callers
 (``moment_str_to_list(post_process(out))``, ``evaluate.py:48``) run unchanged.  The ViT-g / BEATs
 encoders (row A1) are pluggable modules (``audio_encoder="beats"`` builds the HIP BEATs encoder, ``models/beats.py``); pre-computed encoder outputs can be passed
-as ``samples["video_embeds"] [B,T,Kv,1408]`` / ``samples["audio_embeds"] [B,T,Kv,768]``.
+as ``samples["video_embeds"] [B,T,Kv,1408]`` / ``samples["audio_embeds"] [B,T,Kv,768]``.  With ``audio_processor=`` a device
+``BeatsAudioProcessor``, audio may also enter as raw 16 kHz waveforms, ``samples["audio_wave"]`` (a list of B tensors or ``[B, samples]``,
+``samples["audio"]`` absent): the filterbank is computed on the GPU (``csrc/fbank.hip``) and T is the processor's ``n_frames``.
 
 All arithmetic between the encoder output and the span runs in ``libmra_hip.so``: modality
 LayerNorm + reorder (``:265,281-285``), Q-Former (``:286-293``), slice + llm_proj (``:303-306``),
@@ -118,7 +120,7 @@ class XInstructBLIP(nn.Module):
                  compat_repeat: bool = True, score_alpha: float = 0.5, fuse_weights: Optional[Sequence[float]] = None,
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
-                 cross_precision: str = "op"):
+                 cross_precision: str = "op", audio_processor=None):
         super().__init__()
         self.model_path, self.audio_path = model_path, audio_path
         self.modalities = list(modalities) if modalities is not None else ["audio", "video"]  # reference :71
@@ -149,6 +151,9 @@ class XInstructBLIP(nn.Module):
             from .beats import BeatsEncoder
             audio_encoder = BeatsEncoder(checkpoint_path=audio_path, backend="hip", device=self._device)
         self.audio_encoder = audio_encoder
+        # a device BeatsAudioProcessor (processors/audio_processors.py): samples["audio_wave"] becomes the step's filterbank on the GPU
+        # (mra_fbank_forward) and goes to audio_encoder without leaving it; its n_frames is T
+        self.audio_processor = audio_processor
         self.llm_hidden_size = llm_hidden_size   # Vicuna-7B: 4096 (reference :167)
         self.llm_model = None                    # stock causal LM, attached by attach_llm (row N2)
         self.llm_tokenizer = None
@@ -296,6 +301,10 @@ class XInstructBLIP(nn.Module):
         return [{"params": decay, "weight_decay": weight_decay, "lr_scale": lr_scale},
                 {"params": no_decay, "weight_decay": 0, "lr_scale": lr_scale}]
 
+    def _present(self, samples, m: str) -> bool:
+        """Whether ``samples`` carries modality ``m``: its encoder input, pre-computed encoder outputs, or (audio) raw waveforms."""
+        return m in samples or f"{m}_embeds" in samples or (m == "audio" and "audio_wave" in samples)
+
     def _clip_world(self):
         return parallel.world(self.process_group) if self.clip_parallel else (0, 1)
 
@@ -358,6 +367,20 @@ class XInstructBLIP(nn.Module):
         encoder = getattr(self, f"{modality}_encoder")
         if encoder is None:
             raise MraError(f"no {modality}_encoder was given and samples has no '{key}'")
+        if modality == "audio" and modality not in samples and "audio_wave" in samples:
+            # raw waveforms (a list of B tensors, or [B, samples]): the filterbank of this rank's items only, f16, computed on the device
+            proc = self.audio_processor
+            if proc is None or getattr(proc, "device", None) is None:
+                raise MraError("samples['audio_wave'] needs XInstructBLIP(audio_processor=BeatsAudioProcessor(..., device=<cuda device>))")
+            waves = samples["audio_wave"]
+            waves = list(waves.unbind(0)) if isinstance(waves, torch.Tensor) else list(waves)
+            bs, num = len(waves), int(proc.n_frames)
+            frames = proc.flat(waves, lo, hi, out_dtype=torch.float16)
+            outs = []
+            with torch.no_grad():
+                for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
+                    outs.append(encoder(frames[c0: c0 + self.encode_chunk]))
+            return (outs[0] if len(outs) == 1 else torch.cat(outs)), None, bs, num
         data = samples[modality]
         if modality == "video":      # [B, 3, T, H, W] -> sample-major frames [B*T, 3, H, W]
             bs, num = int(data.shape[0]), int(data.shape[2])
@@ -519,10 +542,13 @@ class XInstructBLIP(nn.Module):
         embeds, index = {}, {}
         bs = num = None
         for m in self.modalities:
-            if m not in samples and f"{m}_embeds" not in samples:
+            if not self._present(samples, m):
                 continue
             src = samples.get(f"{m}_embeds", samples.get(m))
-            n_items = int(src.shape[0]) * int(src.shape[2] if (m == "video" and f"{m}_embeds" not in samples) else src.shape[1])
+            if src is None:      # audio as raw waveforms: B clips x the processor's temporal positions
+                n_items = len(samples["audio_wave"]) * int(getattr(self.audio_processor, "n_frames", 0))
+            else:
+                n_items = int(src.shape[0]) * int(src.shape[2] if (m == "video" and f"{m}_embeds" not in samples) else src.shape[1])
             lo, hi = parallel.shard_range(n_items, rank, ws)
             embeds[m], _, bs, num = self._encode(samples, m, lo, hi)     # this rank's block only: the encoder is sharded too
         if bs is None:
@@ -653,7 +679,7 @@ class XInstructBLIP(nn.Module):
         loss is differentiable w.r.t. every Q-Former parameter (forward + backward on the HIP extension; the
         few-KB scorer and the loss run as torch ops so autograd can seed the backward); otherwise it is a
         forward-only value, as the reference's frozen Q-Formers would give."""
-        if samples is None or samples == {} or not any(m in samples or f"{m}_embeds" in samples for m in self.modalities):
+        if samples is None or samples == {} or not any(self._present(samples, m) for m in self.modalities):
             return {"loss": torch.tensor(0.0)}
         if not getattr(self, "train_qformers", False):
             out = self.encode_fuse(samples)
@@ -670,7 +696,7 @@ class XInstructBLIP(nn.Module):
         cur = torch.cuda.current_stream(self._device)
         use_streams = bool(getattr(self, "train_streams", False))
         for m in self.modalities:
-            if m not in samples and f"{m}_embeds" not in samples:
+            if not self._present(samples, m):
                 continue
             qf: QFormer = getattr(self, f"{m}_Qformer")
             side = self._side_stream(m) if use_streams else cur

@@ -12,11 +12,15 @@ normalisation ``(x - 15.41663) / (2 * 6.55582)``.  Neither package can be import
 audio fixtures: **parity unpinned**; ``tests/test_audio_processor.py`` checks the implementation against a direct
 (DFT-by-definition) restatement and against analytic properties.  Decoding the audio track of an ``.mp4`` is IO outside
 the path: pass ``reader(path) -> (waveform float tensor [samples] in [-1, 1], sample_rate)``.
+
+``BeatsAudioProcessor(device=None)`` is this host arithmetic in float64 and stays the definition.  With a CUDA ``device`` the
+same filterbank is computed on the GPU by ``mra_fbank_forward`` (``csrc/fbank.hip``: fp32 throughout, one launch for all
+temporal positions of all clips) and stays there for the encoder; ``tests/test_gpu_fbank.py`` holds it to the host processor.
 """
 from __future__ import annotations
 
 import math
-from typing import Callable, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -71,9 +75,86 @@ def kaldi_fbank(waveform: torch.Tensor, num_mel_bins: int = 128, sample_frequenc
 
 class BeatsAudioProcessor:
     def __init__(self, model_name: str = "iter3", sampling_rate: int = 16000, n_frames: int = 2, is_eval: bool = False,
-                 frame_length: int = 512, reader: Optional[Callable[[str], Tuple[torch.Tensor, int]]] = None):
+                 frame_length: int = 512, reader: Optional[Callable[[str], Tuple[torch.Tensor, int]]] = None,
+                 device=None, out_dtype: torch.dtype = torch.float32):
         self.model_name, self.sampling_rate, self.n_frames, self.is_eval, self.frame_length = model_name, sampling_rate, n_frames, is_eval, frame_length
         self.reader = reader
+        self.device = torch.device(device) if device is not None else None
+        self.out_dtype = out_dtype
+        self._handle = None
+        if self.device is not None:
+            if self.device.type != "cuda":
+                raise ValueError("device: None (the float64 host processor) or a CUDA device (the HIP front end)")
+            if int(sampling_rate) != 16000:
+                raise ValueError("the HIP front end is built for BEATs' 16 kHz input")
+            if out_dtype not in (torch.float32, torch.float16):
+                raise ValueError("out_dtype: torch.float32 or torch.float16")
+
+    def __del__(self):
+        try:
+            if self._handle:
+                self._lib.lib().mra_fbank_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    def _fbank(self):
+        """The ``mra_fbank`` handle of this processor's device (tables built and uploaded on first use)."""
+        if self._handle is None:
+            import ctypes as C
+
+            from .. import _lib
+            self._lib = _lib
+            h = C.c_void_p()
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().mra_fbank_create(C.byref(h)), "mra_fbank_create")
+            self._handle = h
+        return self._handle
+
+    def segments(self, n_samples: int) -> List[Tuple[int, int]]:
+        """(first sample, number of samples) of the ``n_frames`` temporal positions: equal windows over the clip."""
+        edges = torch.linspace(0, n_samples, self.n_frames + 1).long().tolist()
+        return [(a, b - a) for a, b in zip(edges[:-1], edges[1:])]
+
+    def flat(self, waves: Sequence[torch.Tensor], lo: Optional[int] = None, hi: Optional[int] = None,
+             out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """Items ``[lo, hi)`` of the sample-major ``B * n_frames`` positions of ``waves`` (16 kHz mono, [-1, 1]) as
+        ``[hi - lo, frame_length, 128]`` on the device: one concatenated sample buffer, one segment table, ONE launch."""
+        if self.device is None:
+            raise RuntimeError("flat() / batch() run on the HIP front end: construct the processor with a CUDA device")
+        h = self._fbank()
+        lib = self._lib
+        T = self.n_frames
+        lo, hi = (0 if lo is None else int(lo)), (len(waves) * T if hi is None else int(hi))
+        dt = self.out_dtype if out_dtype is None else out_dtype
+        out = torch.empty(max(hi - lo, 0), self.frame_length, 128, dtype=dt, device=self.device)
+        if hi <= lo:
+            return out
+        clips = range(lo // T, (hi - 1) // T + 1)          # only the clips that own an item of the block are uploaded
+        parts, segs, base = [], [], 0
+        for r in clips:
+            w = torch.as_tensor(waves[r]).reshape(-1)
+            parts.append(w.to(device=self.device, dtype=torch.float32))
+            for i, (a, n) in enumerate(self.segments(w.numel())):
+                if lo <= r * T + i < hi:
+                    segs.append((base + a, n))
+            base += w.numel()
+        wave = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
+        if wave.numel() == 0:
+            wave = torch.zeros(1, dtype=torch.float32, device=self.device)
+        seg_t = torch.tensor(segs, dtype=torch.int64).to(self.device)
+        with torch.cuda.device(self.device):
+            lib.check(lib.lib().mra_fbank_forward(h, lib.ptr(wave), base, lib.ptr(seg_t), len(segs), self.frame_length, lib.ptr(out),
+                                                  lib.mra_dtype(dt), lib.current_stream()), "mra_fbank_forward")
+        return out
+
+    def batch(self, waves: Sequence[torch.Tensor], out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """All clips of a step in one launch: ``[B, n_frames, frame_length, 128]`` on the device."""
+        return self.flat(waves, out_dtype=out_dtype).view(len(waves), self.n_frames, self.frame_length, 128)
+
+    def flops(self, n_seg: int) -> float:
+        h = self._fbank()
+        return float(self._lib.lib().mra_fbank_flops(h, int(n_seg), int(self.frame_length)))
 
     def _resample(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
         if sr == self.sampling_rate:
@@ -95,6 +176,8 @@ class BeatsAudioProcessor:
             raise RuntimeError("no audio reader configured (decoding is not part of this build); pass reader=")
         wav, sr = self.reader(path)
         wav = self._resample(torch.as_tensor(wav, dtype=torch.float32).reshape(-1), int(sr))
+        if self.device is not None:      # the waveform is uploaded once; the filterbank is computed and stays on the device
+            return self.batch([wav])[0]
         # n_frames equal windows over the clip, one per temporal position (the video processor samples its frames the same way)
         edges = torch.linspace(0, wav.numel(), self.n_frames + 1).long().tolist()
         return torch.stack([self.features(wav[a:b]) for a, b in zip(edges[:-1], edges[1:])])
