@@ -348,35 +348,63 @@ struct mra_beats {
   int device = 0;
   char* arena = nullptr;
   size_t arena_bytes = 0;
-  std::map<std::string, int> loaded;   // required names loaded so far
+  Registry params;   // every accepted parameter name (beats_layout)
   void *wpatch = nullptr, *wproj = nullptr, *wconv = nullptr;
   float *lnpg = nullptr, *lnpb = nullptr, *bproj = nullptr, *bconv = nullptr, *lneg = nullptr, *lneb = nullptr, *E = nullptr;
   std::vector<BeatsLayer> layers;
   std::map<int, short*> buckets;       // sequence length -> device int16 table [2 S - 1] of bucket(r - S + 1)
   int gemm_persist = 1;
-  int required() const { return 10 + 18 * cfg.layers; }
 };
 
 namespace {
 
+constexpr int BEATS_CONVW = 1;   // Param::store: [o][c][k] -> f16 [o][k * 48 + c] (beats_convw_kernel); 0 = plain conversion
+
+// Lays the parameter arena out and registers every accepted name; with base == nullptr only measures.
 size_t beats_layout(mra_beats* h, char* base) {
   const mra_beats_cfg& c = h->cfg;
   const size_t D = c.dim, I = c.ffn, Em = c.embed_dim, kp = (size_t)c.patch * c.patch;
   Carver cv(base);
+  auto reg = [&](const std::string& name, void* p, int dtype, long long numel, bool required = true, int store = 0) {
+    Param pr;
+    pr.ptr = p; pr.dtype = dtype; pr.numel = numel; pr.required = required; pr.store = store;
+    h->params[name] = pr;
+  };
+  auto w16 = [&](const std::string& name, void* p, long long numel) { reg(name, p, MRA_F16, numel); };
+  auto f32 = [&](const std::string& name, float* p, long long numel, bool required = true) { reg(name, p, MRA_F32, numel, required); };
   h->wpatch = cv.take<char>(Em * kp, 2);
   h->lnpg = cv.take<float>(Em); h->lnpb = cv.take<float>(Em);
   h->wproj = cv.take<char>(D * Em, 2); h->bproj = cv.take<float>(D);
   h->wconv = cv.take<char>(D * (D / c.conv_pos_groups) * c.conv_pos, 2); h->bconv = cv.take<float>(D);
   h->lneg = cv.take<float>(D); h->lneb = cv.take<float>(D);
   h->E = cv.take<float>((size_t)c.num_buckets * c.heads);
+  w16("patch_embedding.weight", h->wpatch, Em * kp);
+  f32("layer_norm.weight", h->lnpg, Em); f32("layer_norm.bias", h->lnpb, Em);
+  w16("post_extract_proj.weight", h->wproj, D * Em); f32("post_extract_proj.bias", h->bproj, D);
+  reg("encoder.pos_conv.0.weight", h->wconv, MRA_F16, D * CG * c.conv_pos, true, BEATS_CONVW); f32("encoder.pos_conv.0.bias", h->bconv, D);
+  f32("encoder.layer_norm.weight", h->lneg, D); f32("encoder.layer_norm.bias", h->lneb, D);
+  f32("encoder.layers.0.self_attn.relative_attention_bias.weight", h->E, (long long)c.num_buckets * c.heads);
   h->layers.assign(c.layers, BeatsLayer{});
-  for (auto& L : h->layers) {
+  for (int li = 0; li < c.layers; ++li) {
+    BeatsLayer& L = h->layers[li];
+    const std::string p = "encoder.layers." + std::to_string(li) + ".";
     L.wqkv = cv.take<char>(3 * D * D, 2); L.bqkv = cv.take<float>(3 * D);
     L.wout = cv.take<char>(D * D, 2); L.bout = cv.take<float>(D);
     L.wfc1 = cv.take<char>(I * D, 2); L.bfc1 = cv.take<float>(I);
     L.wfc2 = cv.take<char>(D * I, 2); L.bfc2 = cv.take<float>(D);
     L.ln1g = cv.take<float>(D); L.ln1b = cv.take<float>(D); L.ln2g = cv.take<float>(D); L.ln2b = cv.take<float>(D);
     L.gw = cv.take<float>(8 * HD); L.gb = cv.take<float>(8); L.ga = cv.take<float>(c.heads);
+    const char* qkv[3] = {"q_proj", "k_proj", "v_proj"};
+    for (int j = 0; j < 3; ++j) {   // into the packed Q | K | V weight and bias; a checkpoint may lack k_proj.bias (it stays zero)
+      w16(p + "self_attn." + qkv[j] + ".weight", L.wqkv ? (char*)L.wqkv + j * D * D * 2 : nullptr, D * D);
+      f32(p + "self_attn." + qkv[j] + ".bias", L.bqkv ? L.bqkv + j * D : nullptr, D, j != 1);
+    }
+    w16(p + "self_attn.out_proj.weight", L.wout, D * D); f32(p + "self_attn.out_proj.bias", L.bout, D);
+    f32(p + "self_attn.grep_linear.weight", L.gw, 8 * HD); f32(p + "self_attn.grep_linear.bias", L.gb, 8); f32(p + "self_attn.grep_a", L.ga, c.heads);
+    f32(p + "self_attn_layer_norm.weight", L.ln1g, D); f32(p + "self_attn_layer_norm.bias", L.ln1b, D);
+    w16(p + "fc1.weight", L.wfc1, I * D); f32(p + "fc1.bias", L.bfc1, I);
+    w16(p + "fc2.weight", L.wfc2, D * I); f32(p + "fc2.bias", L.bfc2, D);
+    f32(p + "final_layer_norm.weight", L.ln2g, D); f32(p + "final_layer_norm.bias", L.ln2b, D);
   }
   return cv.off;
 }
@@ -436,14 +464,8 @@ int mra_beats_create(const mra_beats_cfg* cfg, mra_beats** out) {
   if (c.op_dtype != MRA_F16) return fail(MRA_EINVAL, "op_dtype must be MRA_F16");
   mra_beats* h = new mra_beats();
   h->cfg = c;
-  hipError_t e = hipGetDevice(&h->device);
-  if (e != hipSuccess) { delete h; return fail(MRA_EHIP, std::string("hipGetDevice: ") + hipGetErrorString(e)); }
-  h->arena_bytes = beats_layout(h, nullptr);
-  e = hipMalloc((void**)&h->arena, h->arena_bytes);
-  if (e != hipSuccess) { delete h; return fail(MRA_ENOMEM, std::string("hipMalloc of the BEATs parameter arena: ") + hipGetErrorString(e)); }
-  beats_layout(h, h->arena);
-  e = hipMemsetAsync(h->arena, 0, h->arena_bytes, 0);   // an absent k_proj.bias stays zero
-  if (e != hipSuccess) { (void)hipFree(h->arena); delete h; return fail(MRA_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e)); }
+  const int rc = create_arena(h, beats_layout, "BEATs");   // an absent k_proj.bias stays zero
+  if (rc) { mra_beats_destroy(h); return rc; }
   *out = h;
   return MRA_OK;
 }
@@ -459,69 +481,26 @@ int mra_beats_load(mra_beats* h, const char* name, const void* src, int32_t dtyp
   if (!h || !name || !src || (ndim > 0 && !shape)) return fail(MRA_EINVAL, "null argument");
   if (dtype < MRA_F32 || dtype > MRA_BF16) return fail(MRA_EINVAL, "bad dtype");
   const mra_beats_cfg& c = h->cfg;
-  const long long D = c.dim, I = c.ffn, Em = c.embed_dim, kp = (long long)c.patch * c.patch;
-  long long numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= shape[i];
   hipStream_t st = as_stream(stream_);
   const std::string key(name);
-  auto expect = [&](long long n) { return numel == n ? 0 : fail(MRA_EINVAL, "parameter " + key + ": expected " + std::to_string(n) + " elements, got " + std::to_string(numel)); };
-  auto f32 = [&](float* dst, long long n, long long off = 0) {
-    return launch_convert((const char*)src, dtype, dst + off, MRA_F32, n, st);
-  };
-  auto f16w = [&](void* dst, long long n) { return launch_convert(src, dtype, dst, MRA_F16, n, st); };
-  int rc = 0;
-  bool required = true;
-  if (key == "patch_embedding.weight") { if ((rc = expect(Em * kp))) return rc; rc = f16w(h->wpatch, Em * kp); }
-  else if (key == "layer_norm.weight") { if ((rc = expect(Em))) return rc; rc = f32(h->lnpg, Em); }
-  else if (key == "layer_norm.bias") { if ((rc = expect(Em))) return rc; rc = f32(h->lnpb, Em); }
-  else if (key == "post_extract_proj.weight") { if ((rc = expect(D * Em))) return rc; rc = f16w(h->wproj, D * Em); }
-  else if (key == "post_extract_proj.bias") { if ((rc = expect(D))) return rc; rc = f32(h->bproj, D); }
-  else if (key == "encoder.pos_conv.0.weight") {
-    const long long n = D * CG * c.conv_pos;
-    if ((rc = expect(n))) return rc;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (dtype == MRA_F32) hipLaunchKernelGGL(beats_convw_kernel<float>, grid, block, 0, st, (const float*)src, (f16*)h->wconv, (int)D, CG, c.conv_pos);
-    else if (dtype == MRA_F16) hipLaunchKernelGGL(beats_convw_kernel<f16>, grid, block, 0, st, (const f16*)src, (f16*)h->wconv, (int)D, CG, c.conv_pos);
-    else hipLaunchKernelGGL(beats_convw_kernel<bf16>, grid, block, 0, st, (const bf16*)src, (f16*)h->wconv, (int)D, CG, c.conv_pos);
-    rc = hipGetLastError() == hipSuccess ? 0 : -4;
-  }
-  else if (key == "encoder.pos_conv.0.weight_g" || key == "encoder.pos_conv.0.weight_v")
+  if (key == "encoder.pos_conv.0.weight_g" || key == "encoder.pos_conv.0.weight_v")
     return fail(MRA_ENAME, key + ": load the effective weight encoder.pos_conv.0.weight (weight norm folded by the caller)");
-  else if (key == "encoder.pos_conv.0.bias") { if ((rc = expect(D))) return rc; rc = f32(h->bconv, D); }
-  else if (key == "encoder.layer_norm.weight") { if ((rc = expect(D))) return rc; rc = f32(h->lneg, D); }
-  else if (key == "encoder.layer_norm.bias") { if ((rc = expect(D))) return rc; rc = f32(h->lneb, D); }
-  else if (key == "encoder.layers.0.self_attn.relative_attention_bias.weight") {
-    if ((rc = expect((long long)c.num_buckets * c.heads))) return rc;
-    rc = f32(h->E, (long long)c.num_buckets * c.heads);
+  Param* pr = find_param(h->params, key, "encoder.layers.", c.layers);
+  if (!pr) return MRA_ENAME;
+  int rc = check_numel(key, *pr, shape, ndim);
+  if (rc) return rc;
+  if (pr->store == BEATS_CONVW) {
+    const dim3 grid((unsigned)((pr->numel + 255) / 256)), block(256);
+    with_src(dtype, [&](auto ti) {
+      using TI = decltype(ti);
+      hipLaunchKernelGGL(beats_convw_kernel<TI>, grid, block, 0, st, (const TI*)src, (f16*)pr->ptr, c.dim, CG, c.conv_pos);
+    });
+    rc = hipGetLastError() == hipSuccess ? 0 : -4;
+  } else {
+    rc = launch_convert(src, dtype, pr->ptr, pr->dtype, pr->numel, st);
   }
-  else if (key.rfind("encoder.layers.", 0) == 0) {
-    const size_t p0 = 15, dot = key.find('.', p0);
-    if (dot == std::string::npos) return fail(MRA_ENAME, "unknown parameter name: " + key);
-    const int li = atoi(key.substr(p0, dot - p0).c_str());
-    if (li < 0 || li >= c.layers) return fail(MRA_ENAME, "layer index out of range: " + key);
-    BeatsLayer& L = h->layers[li];
-    const std::string sub = key.substr(dot + 1);
-    const int qkv = sub == "self_attn.q_proj.weight" ? 0 : sub == "self_attn.k_proj.weight" ? 1 : sub == "self_attn.v_proj.weight" ? 2 : -1;
-    const int qkvb = sub == "self_attn.q_proj.bias" ? 0 : sub == "self_attn.k_proj.bias" ? 1 : sub == "self_attn.v_proj.bias" ? 2 : -1;
-    if (qkv >= 0) { if ((rc = expect(D * D))) return rc; rc = launch_convert(src, dtype, (char*)L.wqkv + qkv * D * D * 2, MRA_F16, D * D, st); }
-    else if (qkvb >= 0) { if ((rc = expect(D))) return rc; rc = f32(L.bqkv, D, qkvb * D); required = qkvb != 1; }
-    else if (sub == "self_attn.out_proj.weight") { if ((rc = expect(D * D))) return rc; rc = f16w(L.wout, D * D); }
-    else if (sub == "self_attn.out_proj.bias") { if ((rc = expect(D))) return rc; rc = f32(L.bout, D); }
-    else if (sub == "self_attn.grep_linear.weight") { if ((rc = expect(8 * HD))) return rc; rc = f32(L.gw, 8 * HD); }
-    else if (sub == "self_attn.grep_linear.bias") { if ((rc = expect(8))) return rc; rc = f32(L.gb, 8); }
-    else if (sub == "self_attn.grep_a") { if ((rc = expect(c.heads))) return rc; rc = f32(L.ga, c.heads); }
-    else if (sub == "self_attn_layer_norm.weight") { if ((rc = expect(D))) return rc; rc = f32(L.ln1g, D); }
-    else if (sub == "self_attn_layer_norm.bias") { if ((rc = expect(D))) return rc; rc = f32(L.ln1b, D); }
-    else if (sub == "fc1.weight") { if ((rc = expect(I * D))) return rc; rc = f16w(L.wfc1, I * D); }
-    else if (sub == "fc1.bias") { if ((rc = expect(I))) return rc; rc = f32(L.bfc1, I); }
-    else if (sub == "fc2.weight") { if ((rc = expect(D * I))) return rc; rc = f16w(L.wfc2, D * I); }
-    else if (sub == "fc2.bias") { if ((rc = expect(D))) return rc; rc = f32(L.bfc2, D); }
-    else if (sub == "final_layer_norm.weight") { if ((rc = expect(D))) return rc; rc = f32(L.ln2g, D); }
-    else if (sub == "final_layer_norm.bias") { if ((rc = expect(D))) return rc; rc = f32(L.ln2b, D); }
-    else return fail(MRA_ENAME, "unknown parameter name: " + key);
-  } else return fail(MRA_ENAME, "unknown parameter name: " + key);
   if (rc) return chk(rc, "beats load");
-  if (required) h->loaded[key] = 1;
+  pr->loaded = true;
   return MRA_OK;
 }
 
@@ -538,7 +517,7 @@ int mra_beats_set_option(mra_beats* h, const char* name, int32_t value) {
 
 int mra_beats_missing(mra_beats* h) {
   if (!h) return -1;
-  return h->required() - (int)h->loaded.size();
+  return count_missing(h->params);
 }
 
 namespace {
@@ -600,20 +579,17 @@ int mra_beats_forward(mra_beats* h, const void* fbank, int32_t dtype, int32_t n,
   }
   const int KPt = P <= 256 ? 256 : 512;
   const size_t alds = attn_lds_bytes(KPt), clds = conv_lds_bytes(P, c.conv_pos);
-  static unsigned long long attr_done = 0;
-  if (!(attr_done >> (h->device & 63) & 1)) {
-    if (hipFuncSetAttribute((const void*)beats_attn_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds_bytes(256)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)beats_attn_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds_bytes(512)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)beats_posconv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_lds_bytes(MAX_TOKENS, 256)) != hipSuccess)
-      return fail(MRA_EHIP, "hipFuncSetAttribute(beats kernels)");
-    attr_done |= 1ull << (h->device & 63);
-  }
+  if (!ensure_lds((const void*)beats_attn_kernel<256>, attn_lds_bytes(256)) || !ensure_lds((const void*)beats_attn_kernel<512>, attn_lds_bytes(512)) ||
+      !ensure_lds((const void*)beats_posconv_kernel, conv_lds_bytes(MAX_TOKENS, 256)))
+    return fail(MRA_EHIP, "hipFuncSetAttribute(beats kernels)");
   int rc;
   {   // front end: patches -> [M, 512] -> LayerNorm -> projection -> x
     const long long total8 = M * kp / 8;
     const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
-    if (dtype == MRA_F32) hipLaunchKernelGGL(beats_patch_kernel<float>, grid, block, 0, st, (const float*)fbank, big, total8, frames, P, c.mel_bins, c.patch);
-    else hipLaunchKernelGGL(beats_patch_kernel<f16>, grid, block, 0, st, (const f16*)fbank, big, total8, frames, P, c.mel_bins, c.patch);
+    with_f32_f16(dtype, [&](auto ti) {
+      using TI = decltype(ti);
+      hipLaunchKernelGGL(beats_patch_kernel<TI>, grid, block, 0, st, (const TI*)fbank, big, total8, frames, P, c.mel_bins, c.patch);
+    });
     GemmProb p{};
     p.A = big; p.a = plain((int)M, kp); p.W = h->wpatch; p.C = x; p.c = plain((int)M, Em);
     p.M = (int)M; p.N = Em; p.K = kp;

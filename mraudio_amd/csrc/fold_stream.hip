@@ -380,19 +380,12 @@ bool fold_stream_supported(int rows, int E, int kv, int kvp, int op_dtype) {
 
 int launch_fold_stream(const FoldStreamArgs& a, hipStream_t stream) {
   if (!fold_stream_supported(ROWS, a.E, a.kv, a.kvp, OP_F16) || a.items <= 0) return -1;
-  static unsigned long long attr_done = 0;   // bit per device: hipFuncSetAttribute is not a stream operation, do it once
-  int dev = 0;
-  (void)hipGetDevice(&dev);
   const int stat_ld = fold_stream_stat_ld(a.kvp);
   const int ntiles_s = (a.kv + TN - 1) / TN;
   const int lds_s = NSLOT * SLOT, lds_p = GT_OFF + ROWS * stat_ld * 2;
   auto k_scores = fold_stream_kernel<0, MRA_FOLD_SETS_SCORES>;
   auto k_pv = fold_stream_kernel<1, MRA_FOLD_SETS_PV>;
-  if (!(attr_done >> (dev & 63) & 1)) {
-    if (hipFuncSetAttribute((const void*)k_scores, hipFuncAttributeMaxDynamicSharedMemorySize, lds_s) != hipSuccess) return -3;
-    if (hipFuncSetAttribute((const void*)k_pv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -3;
-    attr_done |= 1ull << (dev & 63);
-  }
+  if (!ensure_lds((const void*)k_scores, lds_s) || !ensure_lds((const void*)k_pv, 160 * 1024)) return -3;   // not a stream operation: once per device
   if (a.phase & 1) {
     const long long pieces = (long long)a.items * ROWS * (a.E / 8);
     hipLaunchKernelGGL(fold_pack_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, stream, (const i32x4*)a.qp, (i32x4*)a.qpb, pieces, a.E / 8);

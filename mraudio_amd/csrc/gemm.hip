@@ -1565,20 +1565,6 @@ constexpr int g_force_tile = GT_AUTO, g_variant = 5, g_p8 = 1, g_order = 0;
 constexpr unsigned long long* g_dbg = nullptr;
 #endif
 
-// hipFuncSetAttribute once per kernel and device (it is not a stream operation: keep it out of the
-// per-launch path and out of graph captures)
-bool ensure_lds(const void* fn, size_t lds) {
-  static std::mutex mu;
-  static std::set<std::pair<const void*, int>> done;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  if (done.count({fn, dev})) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-  done.insert({fn, dev});
-  return true;
-}
-
 template <typename KFN>
 int launch_k(KFN kfn, const GemmArgs& a, int threads, size_t lds, hipStream_t stream, int grid = 0) {   // grid 0: one workgroup per tile
   if (lds > 64 * 1024 && !ensure_lds((const void*)kfn, lds)) return -3;
@@ -1800,6 +1786,19 @@ bool tile_rules(const TileDesc& d, int family, const GemmProb& p, int ngroups, i
 
 }  // namespace
 
+// hipFuncSetAttribute once per kernel and device (it is not a stream operation: keep it out of the
+// per-launch path and out of graph captures)
+bool ensure_lds(const void* fn, size_t lds) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  if (done.count({fn, dev})) return true;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+  done.insert({fn, dev});
+  return true;
+}
 
 long long gemm_launch_count(int family, int epi) {
   if (family < 0 || family >= GEMM_FAMILIES || epi < 0 || epi >= 16) return -1;

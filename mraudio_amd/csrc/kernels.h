@@ -367,6 +367,10 @@ int launch_split_rows(const float* src, RowView sv, int rows, int C, int chunk, 
 int launch_split_weight(const float* W, int rows, int C, void* dst, int op_dtype, hipStream_t stream);
 int launch_split_key_weight(const float* W, int heads, int E, void* dst, int op_dtype, hipStream_t stream);
 
+// Allows kernel `fn` `lds` bytes of dynamic LDS on the current device: hipFuncSetAttribute once per (kernel, device), under a mutex (gemm.hip).
+// Not a stream operation: call it before the launch, outside any stream capture.  false: the runtime refused.
+bool ensure_lds(const void* fn, size_t lds);
+
 // ---- scorer -------------------------------------------------------------------------------------
 int launch_cosine_score(const float* z, const float* t, int t_rows, int items, int Q, int H, float eps, float* sim,
                         float* logit, hipStream_t stream);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -11,6 +12,7 @@
 
 #include "../../include/mra.h"
 #include "kernels.h"
+#include "mra_common.h"
 
 namespace mra_host {
 
@@ -39,7 +41,10 @@ struct Param {
   size_t goff = 0;       // byte offset of this parameter's f32 gradient in the flat gradient buffer
   int rows = 0, cols = 0;  // matrix shape ([out, in]) for weights, 0 otherwise
   float* copy32 = nullptr;  // f32 copy kept beside the operand-dtype one (the score-chain weights of the split-precision cross-attention)
+  int store = 0;            // encoders: 0 = convert to `dtype` at ptr, otherwise the handle's own store kind (a repacking kernel)
+  bool required = true;     // encoders: counts as missing until loaded
 };
+using Registry = std::map<std::string, Param>;
 
 struct LayerW {
   void *wqkv, *wo, *wcq, *wco, *wiq, *woq, *wit, *wot;
@@ -70,6 +75,57 @@ inline int chk(int rc, const char* what) {
   if (rc == 0) return 0;
   return fail(rc == -1 ? MRA_EINVAL : MRA_EHIP, std::string(what) + " failed (rc " + std::to_string(rc) + ")");
 }
+
+// ---- the encoder handles (mra_vit, mra_beats): parameters are registered by name while the arena is laid out (as mra_qformer's), and
+// `load` is look-up + size check + one switch over the few store kinds ----
+// A per-layer name ("<layer_prefix><i>.<rest>") with a bad index is told from a bad name; the index is read as atoi reads it.
+inline Param* find_param(Registry& reg, const std::string& key, const std::string& layer_prefix, int nlayers) {
+  auto it = reg.find(key);
+  if (it == reg.end() && key.rfind(layer_prefix, 0) == 0) {
+    const size_t p0 = layer_prefix.size(), dot = key.find('.', p0);
+    if (dot != std::string::npos) {
+      const int li = atoi(key.substr(p0, dot - p0).c_str());
+      if (li < 0 || li >= nlayers) { fail(MRA_ENAME, "layer index out of range: " + key); return nullptr; }
+      it = reg.find(layer_prefix + std::to_string(li) + key.substr(dot));
+    }
+  }
+  if (it == reg.end()) { fail(MRA_ENAME, "unknown parameter name: " + key); return nullptr; }
+  return &it->second;
+}
+inline int check_numel(const std::string& key, const Param& pr, const int64_t* shape, int ndim) {
+  long long numel = 1;
+  for (int i = 0; i < ndim; ++i) numel *= shape[i];
+  return numel == pr.numel ? 0 : fail(MRA_EINVAL, "parameter " + key + ": expected " + std::to_string(pr.numel) + " elements, got " + std::to_string(numel));
+}
+inline int count_missing(const Registry& reg) {
+  int n = 0;
+  for (auto& kv : reg) n += kv.second.required && !kv.second.loaded;
+  return n;
+}
+// device -> size pass -> hipMalloc -> layout pass -> memset (padding and optional parameters stay zero); `layout(h, base)` lays h's arena out
+// at base (nullptr: only measures) and returns its size.  On failure nothing is left allocated; the caller deletes h.
+template <typename H, typename Layout>
+int create_arena(H* h, Layout layout, const char* what) {
+  HIP_TRY(hipGetDevice(&h->device));
+  h->arena_bytes = layout(h, nullptr);
+  hipError_t e = hipMalloc((void**)&h->arena, h->arena_bytes);
+  if (e != hipSuccess) { h->arena = nullptr; return fail(MRA_ENOMEM, std::string("hipMalloc of the ") + what + " parameter arena: " + hipGetErrorString(e)); }
+  layout(h, h->arena);
+  e = hipMemsetAsync(h->arena, 0, h->arena_bytes, 0);
+  if (e != hipSuccess) { (void)hipFree(h->arena); h->arena = nullptr; return fail(MRA_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e)); }
+  return MRA_OK;
+}
+
+// f(T{}) with T the I-th of Ts (the last one for any larger I): a run-time dtype code as a compile-time element type, e.g.
+//   with_op(op, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(kernel<T>, ...); });
+template <typename T0, typename... Ts, typename F>
+auto with_type(int i, F&& f) {
+  if constexpr (sizeof...(Ts) == 0) return f(T0{});
+  else return i == 0 ? f(T0{}) : with_type<Ts...>(i - 1, f);
+}
+template <typename F> auto with_op(int op, F&& f) { return with_type<f16, bf16>(op, f); }                 // OP_F16 / OP_BF16
+template <typename F> auto with_src(int dtype, F&& f) { return with_type<float, f16, bf16>(dtype, f); }   // MRA_F32 / MRA_F16 / MRA_BF16
+template <typename F> auto with_f32_f16(int dtype, F&& f) { return with_type<float, f16>(dtype, f); }     // inputs that are f32 or f16 only
 
 }  // namespace mra_host
 

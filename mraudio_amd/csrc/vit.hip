@@ -46,10 +46,154 @@ constexpr float LOG2E = 1.4426950408889634f;
 // two transposed LDS reads (ds_read_b64_tr_b16) of V [key][d].
 // ---------------------------------------------------------------------------------------------------------
 constexpr int ATT_WAVES = 9;
+template <typename T> using V8T = typename Vec8<T>::type;
+
+// ---- K, V rows of one head -> LDS (rows past S zeroed) by a workgroup of NT threads, in two halves.  kv_fetch issues every load before
+// the first LDS write and none sits under a lane-dependent branch (a clamped row is loaded and zeroed instead): one round trip, not one
+// per chunk.  kv_to_lds fixes the rows up and stores them; the stand-alone kernel calls the halves back to back, the persistent one
+// keeps the registers in flight over a whole unit of work in between.
+template <int NT> constexpr int kv_chunks() { return (KS_PAD * 12 + NT - 1) / NT; }
+template <typename T, int NT>
+__device__ __forceinline__ void kv_fetch(const T* base, int S, int ld, int heads, int tid, V8T<T> (&kr)[kv_chunks<NT>()], V8T<T> (&vr)[kv_chunks<NT>()]) {
+#pragma unroll
+  for (int u = 0; u < kv_chunks<NT>(); ++u) {
+    const int c = min(tid + u * NT, KS_PAD * 12 - 1);
+    const int row = c / 12, ch = c - row * 12;
+    const T* p = base + (long long)min(row, S - 1) * ld + ch * 8;
+    kr[u] = *reinterpret_cast<const V8T<T>*>(p + heads * HD_PAD);
+    vr[u] = *reinterpret_cast<const V8T<T>*>(p + 2 * heads * HD_PAD);
+  }
+}
+template <typename T, int NT>
+__device__ __forceinline__ void kv_to_lds(char* Ks, char* Vs, int S, bool ones, int hd, int tid, const V8T<T> (&kr)[kv_chunks<NT>()], const V8T<T> (&vr)[kv_chunks<NT>()]) {
+#pragma unroll
+  for (int u = 0; u < kv_chunks<NT>(); ++u) {
+    const int c = tid + u * NT;
+    const int row = c / 12, ch = c - row * 12;
+    V8T<T> k = kr[u], v = vr[u];
+    if (row >= S) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { k[e] = from_f32<T>(0.f); v[e] = k[e]; }
+    }
+    if (ones && ch == (hd >> 3)) {   // the ones column (masked keys carry P = 0)
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e == (hd & 7)) v[e] = from_f32<T>(1.f);
+    }
+    if (c < KS_PAD * 12) {
+      *reinterpret_cast<V8T<T>*>(Ks + row * KV_PITCH + ch * 16) = k;
+      *reinterpret_cast<V8T<T>*>(Vs + row * KV_PITCH + ch * 16) = v;
+    }
+  }
+}
+
+// One 16-query block of a wave against the staged K / V of its (frame, head): scores, masking, softmax, P V, the row sum, the store.
+// qf = the Q fragments (B operand): lane (query lm, chunk lc) holds Q[q0 + lm][32 ks + 8 lc .. + 7].
 // The softmax is VALU-bound next to 108 MFMAs per 16-query block (72 scores per lane), so it is kept lean: the scale rides the
 // exponent's fma; with the sequence length known at compile time (SC = 257 for ViT-g/224) only key fragment 16 is masked and
 // fragment 17 (all padding) is neither multiplied nor exponentiated; and the row sum comes out of the P V MFMAs themselves:
 // V's first padding column (d = hd) is set to one when the head is staged, so O^T[hd][query] = sum of the ROUNDED P row.
+// `ones`, lm = lane & 15 and lc = lane >> 4 come from the caller, which needs them too: recomputed here, the stand-alone kernel comes out
+// ~40 instructions longer at nine fewer registers (the early per-function passes see them before the inlining does).
+template <typename T, int SC>
+__device__ __forceinline__ void vit_attn_block(const char* Ks, const char* Vs, const V8T<T> (&qf)[3], T* ctx, int S, int frame, int head, int heads, int hd,
+                                               float sl2, bool ones, int q0, int lane, int lm, int lc) {
+  using V8 = V8T<T>;
+  constexpr int NFR = SC ? (SC + 15) / 16 : KS_PAD / 16;   // key fragments with at least one valid key (compile-time S)
+  f32x4 sc[KS_PAD / 16];
+  float mx = -3.0e38f;     // of the raw scores: sl2 > 0
+#pragma unroll
+  for (int i = 0; i < KS_PAD / 16; ++i) {
+    if (i >= NFR) { sc[i] = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f}; continue; }
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      const V8 kf = *reinterpret_cast<const V8*>(Ks + (16 * i + lm) * KV_PITCH + (4 * ks + lc) * 16);
+      a = mfma16<T>(kf, qf[ks], a);
+    }
+    if (SC && 16 * i + 16 <= SC) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mx = fmaxf(mx, a[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (16 * i + 4 * lc + e >= S) a[e] = -3.0e38f;
+        mx = fmaxf(mx, a[e]);
+      }
+    }
+    sc[i] = a;
+  }
+  // Scheduling of the K-fragment reads against the MFMAs: six reads run ahead, then one read per MFMA.  Left alone
+  // the scheduler hoists every read above the first MFMA and the allocator spills (644 bytes of scratch per lane, 0.96 ms per
+  // layer); strictly one read per MFMA exposes the LDS latency on every MFMA (0.37 ms).
+  __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+#pragma unroll
+  for (int i = 0; i < 3 * NFR; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float mxs = mx * sl2;
+  float l = 0.f;
+  // O^T[d][query] = sum_keys V^T[d][key] P^T[key][query]
+  f32x4 ot[HD_PAD / 16];
+#pragma unroll
+  for (int df = 0; df < HD_PAD / 16; ++df) ot[df] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < KS_PAD / 32; ++ks) {
+    V8 pf;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      pf[e] = from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * ks][e], sl2, -mxs)));          // masked keys: exp2(-huge) = 0
+      pf[4 + e] = 2 * ks + 1 < NFR ? from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * ks + 1][e], sl2, -mxs))) : from_f32<T>(0.f);
+      if (!ones) l += (float)pf[e] + (float)pf[4 + e];
+    }
+    // V^T fragment of d block df in the same key order: transposed 4 x 16 blocks at keys 32 ks + 4 lc and 32 ks + 16 + 4 lc
+    const char* vb = Vs + (32 * ks + 4 * lc + (lm >> 2)) * KV_PITCH + (lane & 3) * 8;
+#pragma unroll
+    for (int df = 0; df < HD_PAD / 16; ++df) {
+      const i16x4 c0 = lds_read_tr4(vb + df * 32), c1 = lds_read_tr4(vb + df * 32 + 16 * KV_PITCH);
+      i16x8 v;
+      v[0] = c0[0]; v[1] = c0[1]; v[2] = c0[2]; v[3] = c0[3]; v[4] = c1[0]; v[5] = c1[1]; v[6] = c1[2]; v[7] = c1[3];
+      ot[df] = mfma16<T>(__builtin_bit_cast(V8, v), pf, ot[df]);
+    }
+  }
+  __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);     // same for the 108 transposed V reads: four fragments ahead
+#pragma unroll
+  for (int i = 0; i < (HD_PAD / 16) * (KS_PAD / 32); ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+  }
+  if (ones) {
+    // O^T[hd][query]: fragment hd / 16, row hd % 16 = 4 c + e
+    float lo = 0.f;
+#pragma unroll
+    for (int df = 0; df < HD_PAD / 16; ++df)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (df == (hd >> 4) && e == (hd & 3)) lo = ot[df][e];
+    l = __shfl(lo, ((hd & 15) >> 2) * 16 + lm);
+  } else {
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+  }
+  const float inv = 1.0f / l;
+  if (q0 + lm < S) {
+    T* crow = ctx + ((long long)frame * S + q0 + lm) * (heads * hd) + head * hd;
+#pragma unroll
+    for (int df = 0; df < HD_PAD / 16; ++df) {
+      const int d = 16 * df + 4 * lc;
+      if (d + 3 < hd) {
+        typename Vec4<T>::type o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(ot[df][e] * inv);
+        *reinterpret_cast<typename Vec4<T>::type*>(crow + d) = o;
+      }
+    }
+  }
+}
+
 template <typename T, int SC>
 __global__ void __launch_bounds__(ATT_WAVES * 64) vit_attn_kernel(const T* qkv, T* ctx, int S_rt, int heads, int hd, float sl2) {
   const int S = SC ? SC : S_rt;
@@ -61,144 +205,25 @@ __global__ void __launch_bounds__(ATT_WAVES * 64) vit_attn_kernel(const T* qkv, 
   const int frame = blockIdx.x / heads, head = blockIdx.x - frame * heads;
   const int ld = 3 * heads * HD_PAD;
   const T* base = qkv + (long long)frame * S * ld + head * HD_PAD;
-  using V8 = typename Vec8<T>::type;
-  // ---- K, V rows of this head -> LDS (rows past S zeroed).  Every load is issued before the first LDS write and none sits
-  // under a lane-dependent branch (a clamped row is loaded and zeroed instead): one round trip, not one per chunk.
+  using V8 = V8T<T>;
   {
-    constexpr int NCH = (KS_PAD * 12 + ATT_WAVES * 64 - 1) / (ATT_WAVES * 64);
-    V8 kr[NCH], vr[NCH];
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int c = min(tid + u * ATT_WAVES * 64, KS_PAD * 12 - 1);
-      const int row = c / 12, ch = c - row * 12;
-      const T* p = base + (long long)min(row, S - 1) * ld + ch * 8;
-      kr[u] = *reinterpret_cast<const V8*>(p + heads * HD_PAD);
-      vr[u] = *reinterpret_cast<const V8*>(p + 2 * heads * HD_PAD);
-    }
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int c = tid + u * ATT_WAVES * 64;
-      const int row = c / 12, ch = c - row * 12;
-      if (row >= S) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { kr[u][e] = from_f32<T>(0.f); vr[u][e] = kr[u][e]; }
-      }
-      if (ones && ch == (hd >> 3)) {   // the ones column (masked keys carry P = 0)
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (e == (hd & 7)) vr[u][e] = from_f32<T>(1.f);
-      }
-      if (c < KS_PAD * 12) {
-        *reinterpret_cast<V8*>(Ks + row * KV_PITCH + ch * 16) = kr[u];
-        *reinterpret_cast<V8*>(Vs + row * KV_PITCH + ch * 16) = vr[u];
-      }
-    }
+    constexpr int NT = ATT_WAVES * 64;
+    V8 kr[kv_chunks<NT>()], vr[kv_chunks<NT>()];
+    kv_fetch<T, NT>(base, S, ld, heads, tid, kr, vr);
+    kv_to_lds<T, NT>(Ks, Vs, S, ones, hd, tid, kr, vr);
   }
   __syncthreads();
   const int lm = lane & 15, lc = lane >> 4;
   const int nblocks = (S + 15) >> 4;
   for (int qb = wave; qb < nblocks; qb += ATT_WAVES) {
     const int q0 = qb * 16;
-    // Q fragments (B operand): lane (query lm, chunk lc) holds Q[q0 + lm][32 ks + 8 lc .. + 7]
     V8 qf[3];
     {
       const T* qp = base + (long long)min(q0 + lm, S - 1) * ld + 8 * lc;
 #pragma unroll
       for (int ks = 0; ks < 3; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 32 * ks);
     }
-    constexpr int NFR = SC ? (SC + 15) / 16 : KS_PAD / 16;   // key fragments with at least one valid key (compile-time S)
-    f32x4 sc[KS_PAD / 16];
-    float mx = -3.0e38f;     // of the raw scores: sl2 > 0
-#pragma unroll
-    for (int i = 0; i < KS_PAD / 16; ++i) {
-      if (i >= NFR) { sc[i] = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f}; continue; }
-      f32x4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 3; ++ks) {
-        const V8 kf = *reinterpret_cast<const V8*>(Ks + (16 * i + lm) * KV_PITCH + (4 * ks + lc) * 16);
-        a = mfma16<T>(kf, qf[ks], a);
-      }
-      if (SC && 16 * i + 16 <= SC) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, a[e]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (16 * i + 4 * lc + e >= S) a[e] = -3.0e38f;
-          mx = fmaxf(mx, a[e]);
-        }
-      }
-      sc[i] = a;
-    }
-    // Scheduling of the K-fragment reads against the MFMAs: six reads run ahead, then one read per MFMA.  Left alone
-    // the scheduler hoists every read above the first MFMA and the allocator spills (644 bytes of scratch per lane, 0.96 ms per
-    // layer); strictly one read per MFMA exposes the LDS latency on every MFMA (0.37 ms).
-    __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-#pragma unroll
-    for (int i = 0; i < 3 * NFR; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mxs = mx * sl2;
-    float l = 0.f;
-    // O^T[d][query] = sum_keys V^T[d][key] P^T[key][query]
-    f32x4 ot[HD_PAD / 16];
-#pragma unroll
-    for (int df = 0; df < HD_PAD / 16; ++df) ot[df] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS_PAD / 32; ++ks) {
-      V8 pf;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pf[e] = from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * ks][e], sl2, -mxs)));          // masked keys: exp2(-huge) = 0
-        pf[4 + e] = 2 * ks + 1 < NFR ? from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * ks + 1][e], sl2, -mxs))) : from_f32<T>(0.f);
-        if (!ones) l += (float)pf[e] + (float)pf[4 + e];
-      }
-      // V^T fragment of d block df in the same key order: transposed 4 x 16 blocks at keys 32 ks + 4 lc and 32 ks + 16 + 4 lc
-      const char* vb = Vs + (32 * ks + 4 * lc + (lm >> 2)) * KV_PITCH + (lane & 3) * 8;
-#pragma unroll
-      for (int df = 0; df < HD_PAD / 16; ++df) {
-        const i16x4 c0 = lds_read_tr4(vb + df * 32), c1 = lds_read_tr4(vb + df * 32 + 16 * KV_PITCH);
-        i16x8 v;
-        v[0] = c0[0]; v[1] = c0[1]; v[2] = c0[2]; v[3] = c0[3]; v[4] = c1[0]; v[5] = c1[1]; v[6] = c1[2]; v[7] = c1[3];
-        ot[df] = mfma16<T>(__builtin_bit_cast(V8, v), pf, ot[df]);
-      }
-    }
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);     // same for the 108 transposed V reads: four fragments ahead
-#pragma unroll
-    for (int i = 0; i < (HD_PAD / 16) * (KS_PAD / 32); ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-    if (ones) {
-      // O^T[hd][query]: fragment hd / 16, row hd % 16 = 4 c + e
-      float lo = 0.f;
-#pragma unroll
-      for (int df = 0; df < HD_PAD / 16; ++df)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (df == (hd >> 4) && e == (hd & 3)) lo = ot[df][e];
-      l = __shfl(lo, ((hd & 15) >> 2) * 16 + lm);
-    } else {
-      l += __shfl_xor(l, 16);
-      l += __shfl_xor(l, 32);
-    }
-    const float inv = 1.0f / l;
-    if (q0 + lm < S) {
-      T* crow = ctx + ((long long)frame * S + q0 + lm) * (heads * hd) + head * hd;
-#pragma unroll
-      for (int df = 0; df < HD_PAD / 16; ++df) {
-        const int d = 16 * df + 4 * lc;
-        if (d + 3 < hd) {
-          typename Vec4<T>::type o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(ot[df][e] * inv);
-          *reinterpret_cast<typename Vec4<T>::type*>(crow + d) = o;
-        }
-      }
-    }
+    vit_attn_block<T, SC>(Ks, Vs, qf, ctx, S, frame, head, heads, hd, sl2, ones, q0, lane, lm, lc);
   }
 }
 
@@ -224,48 +249,18 @@ __global__ void __launch_bounds__(ATTP_WAVES * 64) vit_attn_persist_kernel(const
   const int ld = 3 * heads * HD_PAD;
   using V8 = typename Vec8<T>::type;
   constexpr int NT = ATTP_WAVES * 64;
-  constexpr int NCH = (KS_PAD * 12 + NT - 1) / NT;
+  constexpr int NCH = kv_chunks<NT>();
   constexpr int NBLK = (SC + 15) / 16, BPW = (NBLK + ATTP_WAVES - 1) / ATTP_WAVES;   // query blocks; per wave at most
   auto unit_base = [&](int u) {
     const int frame = u / heads, head = u - frame * heads;
     return qkv + (long long)frame * S * ld + head * HD_PAD;
   };
   V8 kr[NCH], vr[NCH];
-  auto fetch = [&](const T* base) {     // every load issued back to back, none under a lane-dependent branch (a clamped row is loaded and zeroed later)
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int c = min(tid + u * NT, KS_PAD * 12 - 1);
-      const int row = c / 12, ch = c - row * 12;
-      const T* p = base + (long long)min(row, S - 1) * ld + ch * 8;
-      kr[u] = *reinterpret_cast<const V8*>(p + heads * HD_PAD);
-      vr[u] = *reinterpret_cast<const V8*>(p + 2 * heads * HD_PAD);
-    }
-  };
-  auto to_lds = [&]() {
-#pragma unroll
-    for (int u = 0; u < NCH; ++u) {
-      const int c = tid + u * NT;
-      const int row = c / 12, ch = c - row * 12;
-      if (row >= S) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { kr[u][e] = from_f32<T>(0.f); vr[u][e] = kr[u][e]; }
-      }
-      if (ones && ch == (hd >> 3)) {   // the ones column (masked keys carry P = 0)
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (e == (hd & 7)) vr[u][e] = from_f32<T>(1.f);
-      }
-      if (c < KS_PAD * 12) {
-        *reinterpret_cast<V8*>(Ks + row * KV_PITCH + ch * 16) = kr[u];
-        *reinterpret_cast<V8*>(Vs + row * KV_PITCH + ch * 16) = vr[u];
-      }
-    }
-  };
   const int lm = lane & 15, lc = lane >> 4;
   int u = blockIdx.x;
   if (u >= units) return;
-  fetch(unit_base(u));
-  to_lds();
+  kv_fetch<T, NT>(unit_base(u), S, ld, heads, tid, kr, vr);
+  kv_to_lds<T, NT>(Ks, Vs, S, ones, hd, tid, kr, vr);
   __syncthreads();
   for (; u < units; u += gridDim.x) {
     const T* base = unit_base(u);
@@ -284,7 +279,7 @@ __global__ void __launch_bounds__(ATTP_WAVES * 64) vit_attn_persist_kernel(const
     }
     // Unconditional (the last unit of a workgroup fetches itself again and drops it): under a branch the compiler must assume the loads may not
     // have been issued and counts the Q fragments' vmcnt without them -- i.e. waits for most of the prefetch before the first MFMA.
-    fetch(unit_base(min(un, units - 1)));
+    kv_fetch<T, NT>(unit_base(min(un, units - 1)), S, ld, heads, tid, kr, vr);
     // the Q fragments have landed once at most the 2 NCH prefetch loads behind them are outstanding
     asm volatile("s_waitcnt vmcnt(%9)"
                  : "+v"(qfs[0][0]), "+v"(qfs[0][1]), "+v"(qfs[0][2]), "+v"(qfs[1][0]), "+v"(qfs[1][1]), "+v"(qfs[1][2]), "+v"(qfs[2][0]), "+v"(qfs[2][1]), "+v"(qfs[2][2])
@@ -295,103 +290,11 @@ __global__ void __launch_bounds__(ATTP_WAVES * 64) vit_attn_persist_kernel(const
       const int qb = wave + b * ATTP_WAVES;
       if (qb >= NBLK) break;                        // wave-uniform
       const int q0 = qb * 16;
-      V8 qf[3] = {qfs[b][0], qfs[b][1], qfs[b][2]};
-    constexpr int NFR = SC ? (SC + 15) / 16 : KS_PAD / 16;   // key fragments with at least one valid key (compile-time S)
-    f32x4 sc[KS_PAD / 16];
-    float mx = -3.0e38f;     // of the raw scores: sl2 > 0
-#pragma unroll
-    for (int i = 0; i < KS_PAD / 16; ++i) {
-      if (i >= NFR) { sc[i] = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f}; continue; }
-      f32x4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 3; ++ks) {
-        const V8 kf = *reinterpret_cast<const V8*>(Ks + (16 * i + lm) * KV_PITCH + (4 * ks + lc) * 16);
-        a = mfma16<T>(kf, qf[ks], a);
-      }
-      if (SC && 16 * i + 16 <= SC) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, a[e]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (16 * i + 4 * lc + e >= S) a[e] = -3.0e38f;
-          mx = fmaxf(mx, a[e]);
-        }
-      }
-      sc[i] = a;
-    }
-    // Scheduling of the K-fragment reads against the MFMAs: six reads run ahead, then one read per MFMA.  Left alone
-    // the scheduler hoists every read above the first MFMA and the allocator spills (644 bytes of scratch per lane, 0.96 ms per
-    // layer); strictly one read per MFMA exposes the LDS latency on every MFMA (0.37 ms).
-    __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-#pragma unroll
-    for (int i = 0; i < 3 * NFR; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mxs = mx * sl2;
-    float l = 0.f;
-    // O^T[d][query] = sum_keys V^T[d][key] P^T[key][query]
-    f32x4 ot[HD_PAD / 16];
-#pragma unroll
-    for (int df = 0; df < HD_PAD / 16; ++df) ot[df] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS_PAD / 32; ++ks) {
-      V8 pf;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pf[e] = from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * ks][e], sl2, -mxs)));          // masked keys: exp2(-huge) = 0
-        pf[4 + e] = 2 * ks + 1 < NFR ? from_f32<T>(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * ks + 1][e], sl2, -mxs))) : from_f32<T>(0.f);
-        if (!ones) l += (float)pf[e] + (float)pf[4 + e];
-      }
-      // V^T fragment of d block df in the same key order: transposed 4 x 16 blocks at keys 32 ks + 4 lc and 32 ks + 16 + 4 lc
-      const char* vb = Vs + (32 * ks + 4 * lc + (lm >> 2)) * KV_PITCH + (lane & 3) * 8;
-#pragma unroll
-      for (int df = 0; df < HD_PAD / 16; ++df) {
-        const i16x4 c0 = lds_read_tr4(vb + df * 32), c1 = lds_read_tr4(vb + df * 32 + 16 * KV_PITCH);
-        i16x8 v;
-        v[0] = c0[0]; v[1] = c0[1]; v[2] = c0[2]; v[3] = c0[3]; v[4] = c1[0]; v[5] = c1[1]; v[6] = c1[2]; v[7] = c1[3];
-        ot[df] = mfma16<T>(__builtin_bit_cast(V8, v), pf, ot[df]);
-      }
-    }
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);     // same for the 108 transposed V reads: four fragments ahead
-#pragma unroll
-    for (int i = 0; i < (HD_PAD / 16) * (KS_PAD / 32); ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-    if (ones) {
-      // O^T[hd][query]: fragment hd / 16, row hd % 16 = 4 c + e
-      float lo = 0.f;
-#pragma unroll
-      for (int df = 0; df < HD_PAD / 16; ++df)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (df == (hd >> 4) && e == (hd & 3)) lo = ot[df][e];
-      l = __shfl(lo, ((hd & 15) >> 2) * 16 + lm);
-    } else {
-      l += __shfl_xor(l, 16);
-      l += __shfl_xor(l, 32);
-    }
-    const float inv = 1.0f / l;
-    if (q0 + lm < S) {
-      T* crow = ctx + ((long long)frame * S + q0 + lm) * (heads * hd) + head * hd;
-#pragma unroll
-      for (int df = 0; df < HD_PAD / 16; ++df) {
-        const int d = 16 * df + 4 * lc;
-        if (d + 3 < hd) {
-          typename Vec4<T>::type o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(ot[df][e] * inv);
-          *reinterpret_cast<typename Vec4<T>::type*>(crow + d) = o;
-        }
-      }
-    }
+      const V8 qf[3] = {qfs[b][0], qfs[b][1], qfs[b][2]};
+      vit_attn_block<T, SC>(Ks, Vs, qf, ctx, S, frame, head, heads, hd, sl2, ones, q0, lane, lm, lc);
     }
     __syncthreads();                                // every wave is done with the K / V of unit u
-    if (un < units) to_lds();
+    if (un < units) kv_to_lds<T, NT>(Ks, Vs, S, ones, hd, tid, kr, vr);
     __syncthreads();
   }
 }
@@ -438,12 +341,16 @@ __global__ void __launch_bounds__(256) vit_pack_kernel(const TI* src, T* dst, lo
   dst[idx] = from_f32<T>(sr >= 0 && c < cols_in ? (float)src[sr * cols_in + c] : 0.f);
 }
 
-template <typename TI>
-int pack_to(const void* src, void* dst, int op, long long rows_out, int cols_in, int cols_out, int mode, int heads, int hd, hipStream_t st) {
+int pack_to(const void* src, int dtype, void* dst, int op, long long rows_out, int cols_in, int cols_out, int mode, int heads, int hd, hipStream_t st) {
   const long long total = rows_out * cols_out;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (op == OP_F16) hipLaunchKernelGGL((vit_pack_kernel<TI, f16>), grid, block, 0, st, (const TI*)src, (f16*)dst, total, cols_in, cols_out, mode, heads, hd);
-  else hipLaunchKernelGGL((vit_pack_kernel<TI, bf16>), grid, block, 0, st, (const TI*)src, (bf16*)dst, total, cols_in, cols_out, mode, heads, hd);
+  with_src(dtype, [&](auto ti) {
+    with_op(op, [&](auto t) {
+      using TI = decltype(ti);
+      using T = decltype(t);
+      hipLaunchKernelGGL((vit_pack_kernel<TI, T>), grid, block, 0, st, (const TI*)src, (T*)dst, total, cols_in, cols_out, mode, heads, hd);
+    });
+  });
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -555,7 +462,7 @@ struct mra_vit {
   int S = 0, np = 0, kpad = 0, nqkv = 0;
   char* arena = nullptr;
   size_t arena_bytes = 0;
-  std::map<std::string, int> loaded;   // name -> 1 once loaded
+  Registry params;   // every accepted parameter name (vit_layout)
   float *cls = nullptr, *pos = nullptr, *bpatch = nullptr;
   void* wpatch = nullptr;
   std::vector<VitLayer> layers;
@@ -581,16 +488,35 @@ struct mra_vit {
 
 namespace {
 
+// how mra_vit_load stores a parameter (Param::store; 0 = plain conversion)
+enum VitStore {
+  VIT_PACK = 1,      // [rows][numel / rows] -> operand dtype [rows][cols], columns zero-padded (vit_pack_kernel mode 0)
+  VIT_QKV = 2,       // [3][heads][hd][cols] -> operand dtype [3][heads][96][cols], eight zero rows per head (mode 1)
+  VIT_QV_BIAS = 3,   // [heads][hd] -> f32 [heads][96]: the q (or v) third of the padded bias
+};
+
+// Lays the parameter arena out and registers every accepted name; with base == nullptr only measures.
 size_t vit_layout(mra_vit* h, char* base) {
   const mra_vit_cfg& c = h->cfg;
   const size_t D = c.dim, I = c.mlp;
   Carver cv(base);
+  auto reg = [&](const std::string& name, void* p, long long numel, int store = 0, int rows = 0, int cols = 0) {
+    Param pr;
+    pr.ptr = p; pr.dtype = store == 0 || store == VIT_QV_BIAS ? MRA_F32 : c.op_dtype; pr.numel = numel; pr.store = store; pr.rows = rows; pr.cols = cols;
+    h->params[name] = pr;
+  };
   h->cls = cv.take<float>(D);
   h->pos = cv.take<float>((size_t)h->S * D);
   h->wpatch = cv.take<char>(D * h->kpad, 2);
   h->bpatch = cv.take<float>(D);
+  reg("cls_token", h->cls, D);
+  reg("pos_embed", h->pos, (long long)h->S * D);
+  reg("patch_embed.weight", h->wpatch, D * 3 * c.patch * c.patch, VIT_PACK, (int)D, h->kpad);
+  reg("patch_embed.bias", h->bpatch, D);
   h->layers.assign(c.depth, VitLayer{});
-  for (auto& L : h->layers) {
+  for (int li = 0; li < c.depth; ++li) {
+    VitLayer& L = h->layers[li];
+    const std::string p = "blocks." + std::to_string(li) + ".";
     L.n1g = cv.take<float>(D); L.n1b = cv.take<float>(D); L.n2g = cv.take<float>(D); L.n2b = cv.take<float>(D);
     L.wqkv = cv.take<char>((size_t)h->nqkv * D, 2); L.bqkv = cv.take<float>(h->nqkv);
     L.wproj = cv.take<char>(D * D, 2); L.bproj = cv.take<float>(D);
@@ -598,6 +524,14 @@ size_t vit_layout(mra_vit* h, char* base) {
     L.wfc2 = cv.take<char>(D * I, 2); L.bfc2 = cv.take<float>(D);
     L.wqkv_f = cv.take<char>((size_t)h->nqkv * D, 2); L.cs_qkv = cv.take<float>(h->nqkv); L.bf_qkv = cv.take<float>(h->nqkv);
     L.wfc1_f = cv.take<char>(I * D, 2); L.cs_fc1 = cv.take<float>(I); L.bf_fc1 = cv.take<float>(I);
+    reg(p + "norm1.weight", L.n1g, D); reg(p + "norm1.bias", L.n1b, D);
+    reg(p + "norm2.weight", L.n2g, D); reg(p + "norm2.bias", L.n2b, D);
+    reg(p + "attn.qkv.weight", L.wqkv, 3 * D * D, VIT_QKV, h->nqkv, (int)D);
+    reg(p + "attn.q_bias", L.bqkv, D, VIT_QV_BIAS);
+    reg(p + "attn.v_bias", L.bqkv ? L.bqkv + 2 * c.heads * HD_PAD : nullptr, D, VIT_QV_BIAS);
+    reg(p + "attn.proj.weight", L.wproj, D * D, VIT_PACK, (int)D, (int)D); reg(p + "attn.proj.bias", L.bproj, D);
+    reg(p + "fc1.weight", L.wfc1, I * D, VIT_PACK, (int)I, (int)D); reg(p + "fc1.bias", L.bfc1, I);
+    reg(p + "fc2.weight", L.wfc2, D * I, VIT_PACK, (int)D, (int)I); reg(p + "fc2.bias", L.bfc2, D);
   }
   return cv.off;
 }
@@ -606,21 +540,15 @@ int fold_weights(mra_vit* h, hipStream_t st) {
   const mra_vit_cfg& c = h->cfg;
   const int D = c.dim, I = c.mlp;
   for (auto& L : h->layers) {
-    if (h->op() == OP_F16) {
-      hipLaunchKernelGGL(vit_fold_weight_kernel<f16>, dim3((h->nqkv + 3) / 4), dim3(256), 0, st, (const f16*)L.wqkv, L.n1g, L.n1b, L.bqkv, (f16*)L.wqkv_f, L.cs_qkv, L.bf_qkv, h->nqkv, D);
-      hipLaunchKernelGGL(vit_fold_weight_kernel<f16>, dim3((I + 3) / 4), dim3(256), 0, st, (const f16*)L.wfc1, L.n2g, L.n2b, L.bfc1, (f16*)L.wfc1_f, L.cs_fc1, L.bf_fc1, I, D);
-    } else {
-      hipLaunchKernelGGL(vit_fold_weight_kernel<bf16>, dim3((h->nqkv + 3) / 4), dim3(256), 0, st, (const bf16*)L.wqkv, L.n1g, L.n1b, L.bqkv, (bf16*)L.wqkv_f, L.cs_qkv, L.bf_qkv, h->nqkv, D);
-      hipLaunchKernelGGL(vit_fold_weight_kernel<bf16>, dim3((I + 3) / 4), dim3(256), 0, st, (const bf16*)L.wfc1, L.n2g, L.n2b, L.bfc1, (bf16*)L.wfc1_f, L.cs_fc1, L.bf_fc1, I, D);
-    }
+    with_op(h->op(), [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(vit_fold_weight_kernel<T>, dim3((h->nqkv + 3) / 4), dim3(256), 0, st, (const T*)L.wqkv, L.n1g, L.n1b, L.bqkv, (T*)L.wqkv_f, L.cs_qkv, L.bf_qkv, h->nqkv, D);
+      hipLaunchKernelGGL(vit_fold_weight_kernel<T>, dim3((I + 3) / 4), dim3(256), 0, st, (const T*)L.wfc1, L.n2g, L.n2b, L.bfc1, (T*)L.wfc1_f, L.cs_fc1, L.bf_fc1, I, D);
+    });
   }
   if (hipGetLastError() != hipSuccess) return -4;
   h->fold_ready = true;
   return 0;
-}
-
-int copy_f32(const void* src, int dtype, float* dst, long long n, hipStream_t st) {
-  return launch_convert(src, dtype, dst, MRA_F32, n, st);
 }
 
 }  // namespace
@@ -647,13 +575,9 @@ int mra_vit_create(const mra_vit_cfg* cfg, mra_vit** out) {
   if (h->S > KS_PAD) { delete h; return fail(MRA_EINVAL, "more than 288 tokens per frame are not supported"); }
   h->kpad = (3 * c.patch * c.patch + 63) / 64 * 64;
   h->nqkv = 3 * c.heads * HD_PAD;
-  HIP_TRY(hipGetDevice(&h->device));
-  HIP_TRY(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device));
-  h->arena_bytes = vit_layout(h, nullptr);
-  const hipError_t e = hipMalloc((void**)&h->arena, h->arena_bytes);
-  if (e != hipSuccess) { delete h; return fail(MRA_ENOMEM, std::string("hipMalloc of the ViT parameter arena: ") + hipGetErrorString(e)); }
-  vit_layout(h, h->arena);
-  HIP_TRY(hipMemsetAsync(h->arena, 0, h->arena_bytes, 0));   // the key-bias third of bqkv and all padding stay zero
+  int rc = create_arena(h, vit_layout, "ViT");   // the key-bias third of bqkv and all padding stay zero
+  if (!rc && hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) rc = fail(MRA_EHIP, "hipDeviceGetAttribute");
+  if (rc) { mra_vit_destroy(h); return rc; }
   *out = h;
   return MRA_OK;
 }
@@ -668,53 +592,24 @@ int mra_vit_load(mra_vit* h, const char* name, const void* src, int32_t dtype, c
   if (!h || !name || !src || (ndim > 0 && !shape)) return fail(MRA_EINVAL, "null argument");
   if (dtype < MRA_F32 || dtype > MRA_BF16) return fail(MRA_EINVAL, "bad dtype");
   const mra_vit_cfg& c = h->cfg;
-  const long long D = c.dim, I = c.mlp, hd = c.dim / c.heads;
-  long long numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= shape[i];
+  const int hd = c.dim / c.heads;
   hipStream_t st = as_stream(stream_);
   const std::string key(name);
-  auto expect = [&](long long n) { return numel == n ? 0 : fail(MRA_EINVAL, "parameter " + key + ": expected " + std::to_string(n) + " elements, got " + std::to_string(numel)); };
-  auto pack = [&](void* dst, long long rows_out, int cols_in, int cols_out, int mode) {
-    switch (dtype) {
-      case MRA_F32: return pack_to<float>(src, dst, h->op(), rows_out, cols_in, cols_out, mode, c.heads, (int)hd, st);
-      case MRA_F16: return pack_to<f16>(src, dst, h->op(), rows_out, cols_in, cols_out, mode, c.heads, (int)hd, st);
-      default: return pack_to<bf16>(src, dst, h->op(), rows_out, cols_in, cols_out, mode, c.heads, (int)hd, st);
-    }
-  };
-  int rc = 0;
-  if (key == "cls_token") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, h->cls, D, st); }
-  else if (key == "pos_embed") { if ((rc = expect((long long)h->S * D))) return rc; rc = copy_f32(src, dtype, h->pos, (long long)h->S * D, st); }
-  else if (key == "patch_embed.weight") { if ((rc = expect(D * 3 * c.patch * c.patch))) return rc; rc = pack(h->wpatch, D, 3 * c.patch * c.patch, h->kpad, 0); }
-  else if (key == "patch_embed.bias") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, h->bpatch, D, st); }
-  else if (key.rfind("blocks.", 0) == 0) {
-    const size_t dot = key.find('.', 7);
-    if (dot == std::string::npos) return fail(MRA_ENAME, "unknown parameter name: " + key);
-    const int li = atoi(key.substr(7, dot - 7).c_str());
-    if (li < 0 || li >= c.depth) return fail(MRA_ENAME, "layer index out of range: " + key);
-    VitLayer& L = h->layers[li];
-    const std::string sub = key.substr(dot + 1);
-    if (sub == "norm1.weight") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, L.n1g, D, st); }
-    else if (sub == "norm1.bias") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, L.n1b, D, st); }
-    else if (sub == "norm2.weight") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, L.n2g, D, st); }
-    else if (sub == "norm2.bias") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, L.n2b, D, st); }
-    else if (sub == "attn.qkv.weight") { if ((rc = expect(3 * D * D))) return rc; rc = pack(L.wqkv, h->nqkv, (int)D, (int)D, 1); }
-    else if (sub == "attn.q_bias" || sub == "attn.v_bias") {
-      if ((rc = expect(D))) return rc;
-      // [heads][hd] -> the q (or v) third of the padded bias [3][heads][96], as f32: one padded row-set of width 1
-      float* dst = L.bqkv + (sub == "attn.q_bias" ? 0 : 2) * c.heads * HD_PAD;
+  Param* pr = find_param(h->params, key, "blocks.", c.depth);
+  if (!pr) return MRA_ENAME;
+  int rc = check_numel(key, *pr, shape, ndim);
+  if (rc) return rc;
+  switch (pr->store) {
+    case VIT_PACK: rc = pack_to(src, dtype, pr->ptr, h->op(), pr->rows, (int)(pr->numel / pr->rows), pr->cols, 0, c.heads, hd, st); break;
+    case VIT_QKV: rc = pack_to(src, dtype, pr->ptr, h->op(), pr->rows, pr->cols, pr->cols, 1, c.heads, hd, st); break;
+    case VIT_QV_BIAS:   // one padded row-set of width 1
       for (int hh = 0; hh < c.heads && !rc; ++hh)
-        rc = launch_convert((const char*)src + (size_t)hh * hd * (dtype == MRA_F32 ? 4 : 2), dtype, dst + hh * HD_PAD, MRA_F32, hd, st);
-    }
-    else if (sub == "attn.proj.weight") { if ((rc = expect(D * D))) return rc; rc = pack(L.wproj, D, (int)D, (int)D, 0); }
-    else if (sub == "attn.proj.bias") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, L.bproj, D, st); }
-    else if (sub == "fc1.weight") { if ((rc = expect(I * D))) return rc; rc = pack(L.wfc1, I, (int)D, (int)D, 0); }
-    else if (sub == "fc1.bias") { if ((rc = expect(I))) return rc; rc = copy_f32(src, dtype, L.bfc1, I, st); }
-    else if (sub == "fc2.weight") { if ((rc = expect(D * I))) return rc; rc = pack(L.wfc2, D, (int)I, (int)I, 0); }
-    else if (sub == "fc2.bias") { if ((rc = expect(D))) return rc; rc = copy_f32(src, dtype, L.bfc2, D, st); }
-    else return fail(MRA_ENAME, "unknown parameter name: " + key);
-  } else return fail(MRA_ENAME, "unknown parameter name: " + key);
+        rc = launch_convert((const char*)src + (size_t)hh * hd * (dtype == MRA_F32 ? 4 : 2), dtype, (float*)pr->ptr + hh * HD_PAD, MRA_F32, hd, st);
+      break;
+    default: rc = launch_convert(src, dtype, pr->ptr, pr->dtype, pr->numel, st);
+  }
   if (rc) return chk(rc, "vit load");
-  h->loaded[key] = 1;
+  pr->loaded = true;
   h->fold_ready = false;
   return MRA_OK;
 }
@@ -742,7 +637,7 @@ int mra_vit_set_option(mra_vit* h, const char* name, int32_t value) {
 
 int mra_vit_missing(mra_vit* h) {
   if (!h) return -1;
-  return 4 + 13 * h->cfg.depth - (int)h->loaded.size();
+  return count_missing(h->params);
 }
 
 namespace {
@@ -789,13 +684,13 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
   {   // patches -> x[:, 1:, :] = patch GEMM + bias + pos[1:]; x[:, 0, :] = cls + pos[0]
     const long long total = (long long)n * h->np * h->np * h->kpad;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (dtype == MRA_F32) {
-      if (op == OP_F16) hipLaunchKernelGGL((vit_im2col_kernel<float, f16>), grid, block, 0, st, (const float*)frames, (f16*)big, total, c.img, c.patch, h->np, h->kpad);
-      else hipLaunchKernelGGL((vit_im2col_kernel<float, bf16>), grid, block, 0, st, (const float*)frames, (bf16*)big, total, c.img, c.patch, h->np, h->kpad);
-    } else {
-      if (op == OP_F16) hipLaunchKernelGGL((vit_im2col_kernel<f16, f16>), grid, block, 0, st, (const f16*)frames, (f16*)big, total, c.img, c.patch, h->np, h->kpad);
-      else hipLaunchKernelGGL((vit_im2col_kernel<f16, bf16>), grid, block, 0, st, (const f16*)frames, (bf16*)big, total, c.img, c.patch, h->np, h->kpad);
-    }
+    with_f32_f16(dtype, [&](auto ti) {
+      with_op(op, [&](auto t) {
+        using TI = decltype(ti);
+        using T = decltype(t);
+        hipLaunchKernelGGL((vit_im2col_kernel<TI, T>), grid, block, 0, st, (const TI*)frames, (T*)big, total, c.img, c.patch, h->np, h->kpad);
+      });
+    });
     GemmProb p{};
     const int P2 = h->np * h->np;
     p.A = big; p.a = plain(n * P2, h->kpad);
@@ -811,17 +706,9 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
   const int xdt = r16 ? c.op_dtype : MRA_F32;       // dtype code of the residual stream for the LayerNorm kernel
   void* x = r16 ? out_ : (void*)out;
   const size_t attn_lds = 2 * KS_PAD * KV_PITCH;
-  static unsigned long long attr_done = 0;
-  if (!(attr_done >> (h->device & 63) & 1)) {
-    if (hipFuncSetAttribute((const void*)vit_attn_kernel<f16, 257>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vit_attn_kernel<bf16, 257>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vit_attn_kernel<f16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vit_attn_kernel<bf16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vit_attn_persist_kernel<f16, 257>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vit_attn_persist_kernel<bf16, 257>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds) != hipSuccess)
-      return fail(MRA_EHIP, "hipFuncSetAttribute(vit_attn_kernel)");
-    attr_done |= 1ull << (h->device & 63);
-  }
+  for (const void* k : {(const void*)vit_attn_kernel<f16, 257>, (const void*)vit_attn_kernel<bf16, 257>, (const void*)vit_attn_kernel<f16, 0>,
+                        (const void*)vit_attn_kernel<bf16, 0>, (const void*)vit_attn_persist_kernel<f16, 257>, (const void*)vit_attn_persist_kernel<bf16, 257>})
+    if (!ensure_lds(k, attn_lds)) return fail(MRA_EHIP, "hipFuncSetAttribute(vit_attn_kernel)");
   const float sl2 = LOG2E / sqrtf((float)hd);
   // folded LayerNorms (see vit_fold_weight_kernel): x16 = the op-dtype copy of the residual rows, groups = their 128-column statistics as the
   // residual GEMMs leave them, rstat = (mean, rstd) per row for the QKV / fc1 epilogues
@@ -833,14 +720,12 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
   if (fold) {
     if (!h->fold_ready && (rc = fold_weights(h, st))) return chk(rc, "vit LayerNorm fold of the weights");
     const dim3 grid((unsigned)((M + 3) / 4)), block(256);
-    if (r16) {
-      x16 = (char*)x;   // the stream is the operand
-      if (op == OP_F16) hipLaunchKernelGGL(vit_row_stats16_kernel<f16>, grid, block, 0, st, (const f16*)x, M, D, c.ln_eps, rstat);
-      else hipLaunchKernelGGL(vit_row_stats16_kernel<bf16>, grid, block, 0, st, (const bf16*)x, M, D, c.ln_eps, rstat);
-    } else {
-      if (op == OP_F16) hipLaunchKernelGGL(vit_row_stats_kernel<f16>, grid, block, 0, st, out, M, D, c.ln_eps, rstat, (f16*)x16);
-      else hipLaunchKernelGGL(vit_row_stats_kernel<bf16>, grid, block, 0, st, out, M, D, c.ln_eps, rstat, (bf16*)x16);
-    }
+    if (r16) x16 = (char*)x;   // the stream is the operand
+    with_op(op, [&](auto t) {
+      using T = decltype(t);
+      if (r16) hipLaunchKernelGGL(vit_row_stats16_kernel<T>, grid, block, 0, st, (const T*)x, M, D, c.ln_eps, rstat);
+      else hipLaunchKernelGGL(vit_row_stats_kernel<T>, grid, block, 0, st, out, M, D, c.ln_eps, rstat, (T*)x16);
+    });
   }
   auto persist = [&](long long tiles) { return h->gemm_persist == 1 || (h->gemm_persist == 2 && h->cus > 0 && tiles <= 64LL * h->cus) ? 1 : 0; };
   auto row_stats = [&]() {
@@ -861,17 +746,16 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
       rc = launch_gemm(&p, 1, fold ? EPI_LNF_OP : EPI_OP, op, st);
       if (rc) return chk(rc, "vit qkv gemm");
     }
-    if (S == 257 && h->attn_persist && h->cus > 0) {   // one persistent workgroup per CU, the next unit's K / V prefetched
-      const int units = n * c.heads, grid = std::min(units, h->cus);
-      if (op == OP_F16) hipLaunchKernelGGL((vit_attn_persist_kernel<f16, 257>), dim3(grid), dim3(ATTP_WAVES * 64), attn_lds, st, (const f16*)big, (f16*)a16, units, c.heads, hd, sl2);
-      else hipLaunchKernelGGL((vit_attn_persist_kernel<bf16, 257>), dim3(grid), dim3(ATTP_WAVES * 64), attn_lds, st, (const bf16*)big, (bf16*)a16, units, c.heads, hd, sl2);
-    } else if (S == 257) {   // ViT-g/224: the sequence length as a compile-time constant
-      if (op == OP_F16) hipLaunchKernelGGL((vit_attn_kernel<f16, 257>), dim3(n * c.heads), dim3(ATT_WAVES * 64), attn_lds, st, (const f16*)big, (f16*)a16, S, c.heads, hd, sl2);
-      else hipLaunchKernelGGL((vit_attn_kernel<bf16, 257>), dim3(n * c.heads), dim3(ATT_WAVES * 64), attn_lds, st, (const bf16*)big, (bf16*)a16, S, c.heads, hd, sl2);
-    } else {
-      if (op == OP_F16) hipLaunchKernelGGL((vit_attn_kernel<f16, 0>), dim3(n * c.heads), dim3(ATT_WAVES * 64), attn_lds, st, (const f16*)big, (f16*)a16, S, c.heads, hd, sl2);
-      else hipLaunchKernelGGL((vit_attn_kernel<bf16, 0>), dim3(n * c.heads), dim3(ATT_WAVES * 64), attn_lds, st, (const bf16*)big, (bf16*)a16, S, c.heads, hd, sl2);
-    }
+    with_op(op, [&](auto t) {
+      using T = decltype(t);
+      auto attn = [&](auto kernel, int grid, int waves, int s_or_units) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), attn_lds, st, (const T*)big, (T*)a16, s_or_units, c.heads, hd, sl2);
+      };
+      const int units = n * c.heads;
+      if (S == 257 && h->attn_persist && h->cus > 0) attn(vit_attn_persist_kernel<T, 257>, std::min(units, h->cus), ATTP_WAVES, units);   // one persistent workgroup per CU, the next unit's K / V prefetched
+      else if (S == 257) attn(vit_attn_kernel<T, 257>, units, ATT_WAVES, S);   // ViT-g/224: the sequence length as a compile-time constant
+      else attn(vit_attn_kernel<T, 0>, units, ATT_WAVES, S);
+    });
     // x += A W^T + b for the two N = dim GEMMs.  dim = 1408 is 5.5 tiles of 256: GT_P8_MIXED runs the five full column tiles
     // of two row tiles and then their last 128 columns as one 128 x 512 tile, all in one launch (a masked sixth 256-wide tile wastes 9 %)
     auto residual_gemm = [&](const void* A, int K, const void* W, const float* bias, bool stat) {

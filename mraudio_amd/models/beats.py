@@ -31,6 +31,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._hip import HipEncoder
+
 
 @dataclass
 class BEATsConfig:
@@ -283,21 +285,20 @@ class BEATs(nn.Module):
 _OPTIONAL = (".self_attn.k_proj.bias",)
 
 
-class HipBEATs(BEATs):
+class HipBEATs(HipEncoder, BEATs):
     """The same encoder on the HIP extension (``mra_beats_*``, ``mraudio_amd/csrc/beats.hip``): this module is the parameter
     container (state_dict keys unchanged); ``forward`` runs ALL given chunks as one batched pass of hand-written gfx950 kernels
     -- f16 MFMA operands, fp32 accumulation, residual stream, LayerNorm statistics and softmax -- and returns fp32
     ``[n, P, 768]``.  The positional convolution's weight norm is folded into the effective weight when the weights are
     loaded (the encoder is frozen).  No CPU path."""
 
+    _PREFIX = "mra_beats"   # options (``set_option``): ``"gemm_persist"`` 0 / 1
+
     def __init__(self, cfg: Optional[BEATsConfig] = None, device=None, **kw):
         super().__init__(cfg, **kw)
         import ctypes as C
 
         from .. import _lib
-        self._lib, self._C = _lib, C
-        self._device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self._handle = C.c_void_p()
         c = self.cfg
         hc = _lib.mra_beats_cfg()
         _lib.lib().mra_beats_cfg_default(C.byref(hc))
@@ -306,53 +307,13 @@ class HipBEATs(BEATs):
         hc.conv_pos, hc.conv_pos_groups, hc.num_buckets, hc.max_distance = c.conv_pos, c.conv_pos_groups, c.num_buckets, c.max_distance
         hc.ln_eps, hc.deep_norm_alpha = c.layer_norm_eps, float(c.deep_norm_alpha)
         hc.gate_from = _lib.MRA_BEATS_GATE_Q if c.gate_from == "q" else _lib.MRA_BEATS_GATE_INPUT
-        with torch.cuda.device(self._device):
-            _lib.check(_lib.lib().mra_beats_create(C.byref(hc), C.byref(self._handle)), "mra_beats_create")
-        self._dirty, self._ws = True, None
-        self.to(self._device)
+        self._create(hc, device)
 
-    def set_option(self, name: str, value: int) -> None:
-        """Per-handle switch of the HIP encoder (``mra_beats_set_option``): ``"gemm_persist"`` 0 / 1."""
-        self._lib.check(self._lib.lib().mra_beats_set_option(self._handle, name.encode(), int(value)), f"mra_beats_set_option({name})")
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._dirty = True
-        return out
-
-    def load_state_dict(self, *a, **kw):
-        res = super().load_state_dict(*a, **kw)
-        self._dirty = True
-        return res
-
-    def __del__(self):
-        try:
-            if self._handle:
-                self._lib.lib().mra_beats_destroy(self._handle)
-                self._handle = self._C.c_void_p()
-        except Exception:
-            pass
-
-    @torch.no_grad()
-    def sync_weights(self) -> None:
-        ver = sum(p._version for p in self.parameters())
-        if ver != getattr(self, "_ver", None):
-            self._ver, self._dirty = ver, True
-        if not self._dirty:
-            return
-        lib, C = self._lib, self._C
+    def _upload_tensors(self) -> dict:
         sd = dict(self.state_dict())
-        conv = self.encoder.pos_conv[0]
         del sd["encoder.pos_conv.0.weight_g"], sd["encoder.pos_conv.0.weight_v"]
-        sd["encoder.pos_conv.0.weight"] = conv.effective_weight().float()   # the weight norm, folded (frozen encoder)
-        with torch.cuda.device(self._device):
-            for k, v in sd.items():
-                t = v.detach().to(self._device)
-                t = (t if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else t.float()).contiguous()
-                shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-                lib.check(lib.lib().mra_beats_load(self._handle, k.encode(), lib.ptr(t), lib.mra_dtype(t.dtype), shape, t.dim(), lib.current_stream()),
-                          f"mra_beats_load({k})")
-        self._dirty = False
+        sd["encoder.pos_conv.0.weight"] = self.encoder.pos_conv[0].effective_weight().float()   # the weight norm, folded (frozen encoder)
+        return sd
 
     @torch.no_grad()
     def forward(self, fbank):
@@ -369,14 +330,11 @@ class HipBEATs(BEATs):
         if n == 0:
             return out
         with torch.cuda.device(self._device):
-            nbytes = (int(lib.lib().mra_beats_workspace_bytes(self._handle, n, frames)) + 255) // 256 * 256
+            nbytes = int(lib.lib().mra_beats_workspace_bytes(self._handle, n, frames))
             if nbytes == 0:
                 lib.check(-1, "mra_beats_workspace_bytes")
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-            lib.check(lib.lib().mra_beats_forward(self._handle, lib.ptr(x), lib.mra_dtype(x.dtype), n, frames, lib.ptr(out), lib.ptr(self._ws),
-                                                  self._ws.numel(), lib.current_stream()), "mra_beats_forward")
+            ws = self._workspace(nbytes)
+            self._call("forward", lib.ptr(x), lib.mra_dtype(x.dtype), n, frames, lib.ptr(out), lib.ptr(ws), ws.numel(), lib.current_stream())
         return out
 
     def flops(self, n: int, frames: int) -> float:

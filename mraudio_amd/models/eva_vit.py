@@ -16,6 +16,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._hip import HipEncoder
+
 
 class _Attention(nn.Module):
     def __init__(self, dim: int, heads: int):
@@ -132,7 +134,7 @@ class EvaViTg(nn.Module):
         return float(len(self.blocks) * per_block + 2 * (n - 1) * 3 * 14 * 14 * d)
 
 
-class HipEvaViTg(EvaViTg):
+class HipEvaViTg(HipEncoder, EvaViTg):
     """The same encoder on the HIP extension (``mra_vit_*``, ``mraudio_amd/csrc/vit.hip``): this module is the parameter
     container (state_dict keys unchanged); ``forward`` runs ALL given frames as one batched pass of hand-written gfx950
     kernels -- the four GEMMs per block on the eight-phase MFMA kernels with bias / GELU / residual fused, a 96-padded
@@ -141,14 +143,11 @@ class HipEvaViTg(EvaViTg):
     LayerNorms of a block are folded into the GEMMs around them (``ln_fold``, ``mra_vit_set_option``; ``ln_fold=False`` runs them
     as separate launches).  No CPU path."""
 
+    _PREFIX = "mra_vit"     # options (``set_option``): ``"ln_fold"`` 0 / 1, ``"gemm_persist"`` 0 / 1 / 2, ``"attn_persist"`` 0 / 1
+
     def __init__(self, *args, op_dtype: torch.dtype = torch.float16, residual: str = "fp32", device=None, ln_fold: bool = True, **kw):
         super().__init__(*args, **kw)
-        import ctypes as C
-
         from .. import _lib
-        self._lib, self._C = _lib, C
-        self._device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self._handle = C.c_void_p()
         blk = self.blocks[0]
         cfg = _lib.mra_vit_cfg(self.num_features, blk.attn.heads, blk.fc1.out_features, len(self.blocks), self.patch_embed.kernel_size[0],
                                self.patch_embed.kernel_size[0] * int(round((self.pos_embed.shape[1] - 1) ** 0.5)), 1e-6,
@@ -157,50 +156,9 @@ class HipEvaViTg(EvaViTg):
         if residual not in ("fp32", "op"):
             raise ValueError("residual must be 'fp32' (default) or 'op' (the operand dtype: the reference's precision='fp16' semantics)")
         self._out_dtype = torch.float32 if residual == "fp32" else op_dtype
-        with torch.cuda.device(self._device):
-            _lib.check(_lib.lib().mra_vit_create(C.byref(cfg), C.byref(self._handle)), "mra_vit_create")
-        self._dirty, self._ws = True, None
-        self.to(self._device)
+        self._create(cfg, device)
         if not ln_fold:
             self.set_option("ln_fold", 0)
-
-    def set_option(self, name: str, value: int) -> None:
-        """Per-handle switch of the HIP encoder (``mra_vit_set_option``): ``"ln_fold"`` 0 / 1."""
-        self._lib.check(self._lib.lib().mra_vit_set_option(self._handle, name.encode(), int(value)), f"mra_vit_set_option({name})")
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._dirty = True
-        return out
-
-    def load_state_dict(self, *a, **kw):
-        res = super().load_state_dict(*a, **kw)
-        self._dirty = True
-        return res
-
-    def __del__(self):
-        try:
-            if self._handle:
-                self._lib.lib().mra_vit_destroy(self._handle)
-                self._handle = self._C.c_void_p()
-        except Exception:
-            pass
-
-    def sync_weights(self) -> None:
-        ver = sum(p._version for p in self.parameters())
-        if ver != getattr(self, "_ver", None):
-            self._ver, self._dirty = ver, True
-        if not self._dirty:
-            return
-        lib, C = self._lib, self._C
-        with torch.cuda.device(self._device):
-            for k, v in self.state_dict().items():
-                t = v.detach().to(self._device)
-                t = (t if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else t.float()).contiguous()
-                shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-                lib.check(lib.lib().mra_vit_load(self._handle, k.encode(), lib.ptr(t), lib.mra_dtype(t.dtype), shape, t.dim(), lib.current_stream()),
-                          f"mra_vit_load({k})")
-        self._dirty = False
 
     @torch.no_grad()
     def forward(self, x):
@@ -215,12 +173,8 @@ class HipEvaViTg(EvaViTg):
         if n == 0:
             return out
         with torch.cuda.device(self._device):
-            nbytes = (int(lib.lib().mra_vit_workspace_bytes(self._handle, n)) + 255) // 256 * 256
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-            lib.check(lib.lib().mra_vit_forward(self._handle, lib.ptr(x), lib.mra_dtype(x.dtype), n, lib.ptr(out), lib.ptr(self._ws), self._ws.numel(),
-                                                lib.current_stream()), "mra_vit_forward")
+            ws = self._workspace(int(lib.lib().mra_vit_workspace_bytes(self._handle, n)))
+            self._call("forward", lib.ptr(x), lib.mra_dtype(x.dtype), n, lib.ptr(out), lib.ptr(ws), ws.numel(), lib.current_stream())
         return out
 
     def flops(self, frames: int) -> float:
