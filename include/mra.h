@@ -395,6 +395,33 @@ double mra_fbank_flops(mra_fbank* h, int32_t n_seg, int32_t frame_length);
  * Returns -1 for an unknown family / epilogue.  Used by the parity tests to state which kernel produced the numbers checked. */
 int64_t mra_debug_gemm_launches(int32_t family, int32_t epilogue);
 
+/* One stage of an encoder on its own, through the SAME launch code as the forward (kernel selection, LDS and bucket table included), for the
+ * per-kernel tests against float64 (tests/test_gpu_encoder_cores.py).  Buffers are device pointers in the kernels' own layouts; arguments are
+ * checked as the forwards check theirs: a null handle or pointer, a negative n, a layer or token count out of range -> MRA_EINVAL before any
+ * launch; n == 0 is a no-op; no allocation beyond the forward's (the bucket table of a new token count, cached per handle).
+ *
+ * mra_debug_vit_attention: the attention core of one ViT block over n frames of S = (img / patch)^2 + 1 tokens.  No parameter needs to be loaded.
+ *   qkv [n * S][3][heads][96]  operand dtype: q, k, v of a token, each head padded from hd = dim / heads to 96 columns; columns hd .. 95 of
+ *                              every head MUST be zero (the padded QKV weight makes them so in the forward)
+ *   ctx [n * S][heads * hd]    operand dtype: softmax(q k^T / sqrt(hd)) v per (frame, head), heads side by side, unpadded
+ * Follows the handle's "attn_persist" option at S = 257.
+ *
+ * mra_debug_beats_attention: the attention core of layer `layer` over n chunks of `tokens` (1 .. 512) tokens, with the gated relative-position
+ * bias.  Needs encoder.layers.0.self_attn.relative_attention_bias.weight and the layer's self_attn.grep_linear.{weight,bias} and
+ * self_attn.grep_a loaded (MRA_ESTATE otherwise).
+ *   qkv      [n * tokens][3 * dim]  f16: q | k | v rows as the QKV GEMM writes them (q unscaled), head h at columns 64 h .. 64 h + 63 of each third
+ *   gate_src [n * tokens][dim]      f16: the layer input, read in MRA_BEATS_GATE_INPUT mode only; ignored (may be NULL) in MRA_BEATS_GATE_Q
+ *                                   mode, where the gate reads the q third of qkv
+ *   ctx      [n * tokens][dim]      f16: softmax(q k^T / 8 + G[i] E[bucket(j - i)][h]) v, heads side by side
+ *
+ * mra_debug_beats_posconv: x += GELU(grouped positional convolution of x) over n chunks of `tokens` tokens.  Needs encoder.pos_conv.0.weight
+ * (the effective weight) and encoder.pos_conv.0.bias loaded (MRA_ESTATE otherwise).
+ *   x [n * tokens][dim]  fp32, updated in place; the convolution reads x rounded to f16 */
+int mra_debug_vit_attention(mra_vit* h, const void* qkv, int32_t n, void* ctx, void* stream);
+int mra_debug_beats_attention(mra_beats* h, int32_t layer, const void* qkv, const void* gate_src, int32_t n, int32_t tokens, void* ctx,
+                              void* stream);
+int mra_debug_beats_posconv(mra_beats* h, float* x, int32_t n, int32_t tokens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,9 @@ PROTOTYPES = {
     "mra_fbank_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mra_fbank_flops": (C.c_double, [C.c_void_p, C.c_int32, C.c_int32]),
     "mra_debug_gemm_launches": (C.c_int64, [C.c_int32, C.c_int32]),
+    "mra_debug_vit_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mra_debug_beats_attention": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mra_debug_beats_posconv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 # GemmFamily / GemmEpi codes of mra_debug_gemm_launches (csrc/kernels.h)

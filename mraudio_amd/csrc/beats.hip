@@ -529,6 +529,67 @@ size_t beats_ws_parts(const mra_beats* h, size_t M, size_t* a16, size_t* big) {
   *big = align_up(M * std::max<size_t>(std::max<size_t>(3 * c.dim, c.ffn), (size_t)c.patch * c.patch) * 2);
   return *a16 + *big + align_up(M * c.dim * 2) + 4096;
 }
+// What the two stages below need before their first launch at P tokens: the int16 bucket table of this sequence length (computed once per
+// handle and length, exactly as torch computes it: the handle's one allocation after create) and the kernels' dynamic LDS.  Neither is a
+// stream operation.
+int beats_stage_prepare(mra_beats* h, int P, short** bucket = nullptr) {
+  const mra_beats_cfg& c = h->cfg;
+  auto it = h->buckets.find(P);
+  if (it == h->buckets.end()) {
+    std::vector<short> tab(2 * P - 1);
+    for (int r = 0; r < 2 * P - 1; ++r) tab[r] = (short)bucket_of(r - (P - 1), c.num_buckets, c.max_distance);
+    short* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, tab.size() * sizeof(short)));
+    const hipError_t e = hipMemcpy(dev, tab.data(), tab.size() * sizeof(short), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); return fail(MRA_EHIP, std::string("hipMemcpy of the bucket table: ") + hipGetErrorString(e)); }
+    it = h->buckets.emplace(P, dev).first;
+  }
+  if (bucket) *bucket = it->second;
+  if (!ensure_lds((const void*)beats_attn_kernel<256>, attn_lds_bytes(256)) || !ensure_lds((const void*)beats_attn_kernel<512>, attn_lds_bytes(512)) ||
+      !ensure_lds((const void*)beats_posconv_kernel, conv_lds_bytes(MAX_TOKENS, 256)))
+    return fail(MRA_EHIP, "hipFuncSetAttribute(beats kernels)");
+  return MRA_OK;
+}
+
+// x [n * P][dim] fp32 += GELU(grouped positional convolution of x), in place: the launch of mra_beats_forward and mra_debug_beats_posconv.
+int beats_posconv(mra_beats* h, float* x, int n, int P, hipStream_t st) {
+  const mra_beats_cfg& c = h->cfg;
+  const int rc = beats_stage_prepare(h, P);
+  if (rc) return rc;
+  hipLaunchKernelGGL(beats_posconv_kernel, dim3((unsigned)(n * c.conv_pos_groups)), dim3(512), conv_lds_bytes(P, c.conv_pos), st, x, (const f16*)h->wconv,
+                     h->bconv, P, c.dim, c.conv_pos, c.conv_pos_groups);
+  return MRA_OK;
+}
+
+// The attention core of layer L over n chunks of P tokens: qkv [n * P][3 dim] -> ctx [n * P][dim] (f16).  Owns the choice of the KP instantiation
+// (256 keys of LDS up to P = 256, 512 above), the gate's source (the q third of qkv for BEATs; `layer_in` [n * P][dim], the layer input, for
+// WavLM) and the bucket table: the launch of mra_beats_forward and mra_debug_beats_attention.
+int beats_attention(mra_beats* h, const BeatsLayer& L, const f16* qkv, const f16* layer_in, int n, int P, f16* ctx, hipStream_t st) {
+  const mra_beats_cfg& c = h->cfg;
+  short* bucket = nullptr;
+  const int rc = beats_stage_prepare(h, P, &bucket);
+  if (rc) return rc;
+  const int D = c.dim;
+  const int KPt = P <= 256 ? 256 : 512;
+  const size_t alds = attn_lds_bytes(KPt);
+  const f16* gsrc = c.gate_from == MRA_BEATS_GATE_Q ? qkv : layer_in;
+  const int g_ld = c.gate_from == MRA_BEATS_GATE_Q ? 3 * D : D;
+  if (KPt == 256)
+    hipLaunchKernelGGL(beats_attn_kernel<256>, dim3((unsigned)(n * c.heads)), dim3(512), alds, st, qkv, gsrc, g_ld, (const float*)h->E,
+                       (const short*)bucket, (const float*)L.gw, (const float*)L.gb, (const float*)L.ga, ctx, P, c.heads);
+  else
+    hipLaunchKernelGGL(beats_attn_kernel<512>, dim3((unsigned)(n * c.heads)), dim3(512), alds, st, qkv, gsrc, g_ld, (const float*)h->E,
+                       (const short*)bucket, (const float*)L.gw, (const float*)L.gb, (const float*)L.ga, ctx, P, c.heads);
+  return MRA_OK;
+}
+
+bool beats_loaded(const mra_beats* h, std::initializer_list<std::string> names) {
+  for (const std::string& k : names) {
+    auto it = h->params.find(k);
+    if (it == h->params.end() || !it->second.loaded) return false;
+  }
+  return true;
+}
 }  // namespace
 
 size_t mra_beats_workspace_bytes(mra_beats* h, int32_t n, int32_t frames) {
@@ -562,27 +623,8 @@ int mra_beats_forward(mra_beats* h, const void* fbank, int32_t dtype, int32_t n,
   f16* big = (f16*)((char*)workspace + a16b);
   f16* ctx = (f16*)((char*)workspace + a16b + bigb);
   float* x = (float*)out_;   // the fp32 stream IS the output (the patch GEMM's [M, 512] rows pass through it first)
-  // bucket table of this sequence length: computed here once, exactly as torch computes it
-  short* bucket;
-  {
-    auto it = h->buckets.find(P);
-    if (it == h->buckets.end()) {
-      std::vector<short> tab(2 * P - 1);
-      for (int r = 0; r < 2 * P - 1; ++r) tab[r] = (short)bucket_of(r - (P - 1), c.num_buckets, c.max_distance);
-      short* dev = nullptr;
-      HIP_TRY(hipMalloc((void**)&dev, tab.size() * sizeof(short)));
-      const hipError_t e = hipMemcpy(dev, tab.data(), tab.size() * sizeof(short), hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(dev); return fail(MRA_EHIP, std::string("hipMemcpy of the bucket table: ") + hipGetErrorString(e)); }
-      it = h->buckets.emplace(P, dev).first;
-    }
-    bucket = it->second;
-  }
-  const int KPt = P <= 256 ? 256 : 512;
-  const size_t alds = attn_lds_bytes(KPt), clds = conv_lds_bytes(P, c.conv_pos);
-  if (!ensure_lds((const void*)beats_attn_kernel<256>, attn_lds_bytes(256)) || !ensure_lds((const void*)beats_attn_kernel<512>, attn_lds_bytes(512)) ||
-      !ensure_lds((const void*)beats_posconv_kernel, conv_lds_bytes(MAX_TOKENS, 256)))
-    return fail(MRA_EHIP, "hipFuncSetAttribute(beats kernels)");
   int rc;
+  if ((rc = beats_stage_prepare(h, P))) return rc;   // the bucket table of this sequence length and the kernels' LDS, before the first launch
   {   // front end: patches -> [M, 512] -> LayerNorm -> projection -> x
     const long long total8 = M * kp / 8;
     const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
@@ -600,8 +642,7 @@ int mra_beats_forward(mra_beats* h, const void* fbank, int32_t dtype, int32_t n,
     q.M = (int)M; q.N = D; q.K = Em;
     if ((rc = launch_gemm(&q, 1, EPI_F32, OP_F16, st))) return chk(rc, "beats projection gemm");
   }
-  hipLaunchKernelGGL(beats_posconv_kernel, dim3((unsigned)(n * c.conv_pos_groups)), dim3(512), clds, st, x, (const f16*)h->wconv, h->bconv, P, D,
-                     c.conv_pos, c.conv_pos_groups);
+  if ((rc = beats_posconv(h, x, n, P, st))) return rc;
   const float alpha = c.deep_norm_alpha;
   if ((rc = ln_rows(x, M, D, h->lneg, h->lneb, c.ln_eps, alpha, x, a16, st))) return chk(rc, "beats encoder layer norm");
   for (int li = 0; li < c.layers; ++li) {
@@ -613,14 +654,7 @@ int mra_beats_forward(mra_beats* h, const void* fbank, int32_t dtype, int32_t n,
       p.M = (int)M; p.N = 3 * D; p.K = D; p.persist = h->gemm_persist;
       if ((rc = launch_gemm(&p, 1, EPI_OP, OP_F16, st))) return chk(rc, "beats qkv gemm");
     }
-    const f16* gsrc = c.gate_from == MRA_BEATS_GATE_Q ? big : a16;
-    const int g_ld = c.gate_from == MRA_BEATS_GATE_Q ? 3 * D : D;
-    if (KPt == 256)
-      hipLaunchKernelGGL(beats_attn_kernel<256>, dim3((unsigned)(n * c.heads)), dim3(512), alds, st, (const f16*)big, gsrc, g_ld, (const float*)h->E,
-                         (const short*)bucket, (const float*)L.gw, (const float*)L.gb, (const float*)L.ga, ctx, P, c.heads);
-    else
-      hipLaunchKernelGGL(beats_attn_kernel<512>, dim3((unsigned)(n * c.heads)), dim3(512), alds, st, (const f16*)big, gsrc, g_ld, (const float*)h->E,
-                         (const short*)bucket, (const float*)L.gw, (const float*)L.gb, (const float*)L.ga, ctx, P, c.heads);
+    if ((rc = beats_attention(h, L, big, a16, n, P, ctx, st))) return rc;
     auto residual_gemm = [&](const void* A, int K, const void* W, const float* bias) {
       GemmProb p{};
       p.A = A; p.a = plain((int)M, K); p.W = W; p.bias = bias;
@@ -640,6 +674,36 @@ int mra_beats_forward(mra_beats* h, const void* fbank, int32_t dtype, int32_t n,
     if ((rc = ln_rows(x, M, D, L.ln2g, L.ln2b, c.ln_eps, last ? 1.f : alpha, x, last ? nullptr : a16, st))) return chk(rc, "beats final_layer_norm");
   }
   return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "beats forward launch");
+}
+
+int mra_debug_beats_attention(mra_beats* h, int32_t layer, const void* qkv, const void* gate_src, int32_t n, int32_t tokens, void* ctx, void* stream_) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  const mra_beats_cfg& c = h->cfg;
+  if (n < 0) return fail(MRA_EINVAL, "negative chunk count");
+  if (layer < 0 || layer >= c.layers) return fail(MRA_EINVAL, "layer out of range");
+  if (tokens <= 0 || tokens > MAX_TOKENS) return fail(MRA_EINVAL, "tokens per chunk must be in [1, 512]");
+  if (n == 0) return MRA_OK;
+  if (!qkv || !ctx || (c.gate_from == MRA_BEATS_GATE_INPUT && !gate_src)) return fail(MRA_EINVAL, "null argument");
+  const std::string p = "encoder.layers." + std::to_string(layer) + ".self_attn.";
+  if (!beats_loaded(h, {"encoder.layers.0.self_attn.relative_attention_bias.weight", p + "grep_linear.weight", p + "grep_linear.bias", p + "grep_a"}))
+    return fail(MRA_ESTATE, "the bias table or the layer's gate parameters are not loaded");
+  if ((long long)n * tokens * 3 * c.dim > 0x7fffffffLL) return fail(MRA_EINVAL, "too many chunks for one call: split them");
+  const int rc = beats_attention(h, h->layers[layer], (const f16*)qkv, (const f16*)gate_src, n, tokens, (f16*)ctx, as_stream(stream_));
+  if (rc) return rc;
+  return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "beats attention launch");
+}
+
+int mra_debug_beats_posconv(mra_beats* h, float* x, int32_t n, int32_t tokens, void* stream_) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (n < 0) return fail(MRA_EINVAL, "negative chunk count");
+  if (tokens <= 0 || tokens > MAX_TOKENS) return fail(MRA_EINVAL, "tokens per chunk must be in [1, 512]");
+  if (n == 0) return MRA_OK;
+  if (!x) return fail(MRA_EINVAL, "null argument");
+  if (!beats_loaded(h, {"encoder.pos_conv.0.weight", "encoder.pos_conv.0.bias"})) return fail(MRA_ESTATE, "encoder.pos_conv.0.* is not loaded");
+  if ((long long)n * tokens * h->cfg.dim > 0x7fffffffLL) return fail(MRA_EINVAL, "too many chunks for one call: split them");
+  const int rc = beats_posconv(h, x, n, tokens, as_stream(stream_));
+  if (rc) return rc;
+  return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "beats posconv launch");
 }
 
 double mra_beats_flops(mra_beats* h, int32_t n, int32_t frames) {

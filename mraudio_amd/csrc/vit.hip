@@ -551,6 +551,30 @@ int fold_weights(mra_vit* h, hipStream_t st) {
   return 0;
 }
 
+// The attention core of one block over n frames: qkv [n * S][3][heads][96] -> ctx [n * S][heads * hd], both in the operand dtype.  The one place
+// that picks the kernel (S == 257: the compile-time length, stand-alone or persistent; otherwise the run-time length), allows it its LDS and
+// launches it: mra_vit_forward and mra_debug_vit_attention both come through here.
+int vit_attention(const mra_vit* h, const void* qkv, void* ctx, int n, hipStream_t st) {
+  const mra_vit_cfg& c = h->cfg;
+  const int S = h->S, hd = c.dim / c.heads;
+  const size_t attn_lds = 2 * KS_PAD * KV_PITCH;
+  for (const void* k : {(const void*)vit_attn_kernel<f16, 257>, (const void*)vit_attn_kernel<bf16, 257>, (const void*)vit_attn_kernel<f16, 0>,
+                        (const void*)vit_attn_kernel<bf16, 0>, (const void*)vit_attn_persist_kernel<f16, 257>, (const void*)vit_attn_persist_kernel<bf16, 257>})
+    if (!ensure_lds(k, attn_lds)) return fail(MRA_EHIP, "hipFuncSetAttribute(vit_attn_kernel)");
+  const float sl2 = LOG2E / sqrtf((float)hd);
+  with_op(h->op(), [&](auto t) {
+    using T = decltype(t);
+    auto attn = [&](auto kernel, int grid, int waves, int s_or_units) {
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), attn_lds, st, (const T*)qkv, (T*)ctx, s_or_units, c.heads, hd, sl2);
+    };
+    const int units = n * c.heads;
+    if (S == 257 && h->attn_persist && h->cus > 0) attn(vit_attn_persist_kernel<T, 257>, std::min(units, h->cus), ATTP_WAVES, units);   // one persistent workgroup per CU, the next unit's K / V prefetched
+    else if (S == 257) attn(vit_attn_kernel<T, 257>, units, ATT_WAVES, S);   // ViT-g/224: the sequence length as a compile-time constant
+    else attn(vit_attn_kernel<T, 0>, units, ATT_WAVES, S);
+  });
+  return MRA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -672,7 +696,7 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
   if (workspace_bytes < mra_vit_workspace_bytes(h, n)) return fail(MRA_ENOMEM, "workspace too small: need " + std::to_string(mra_vit_workspace_bytes(h, n)));
   if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(MRA_EINVAL, "workspace must be 256-byte aligned");
   const mra_vit_cfg& c = h->cfg;
-  const int D = c.dim, I = c.mlp, S = h->S, op = h->op(), hd = D / c.heads;
+  const int D = c.dim, I = c.mlp, S = h->S, op = h->op();
   const long long M = (long long)n * S;
   if (M > 0x7fffffffLL / 64) return fail(MRA_EINVAL, "too many frames for one call: chunk them");
   hipStream_t st = as_stream(stream_);
@@ -705,11 +729,6 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
   }
   const int xdt = r16 ? c.op_dtype : MRA_F32;       // dtype code of the residual stream for the LayerNorm kernel
   void* x = r16 ? out_ : (void*)out;
-  const size_t attn_lds = 2 * KS_PAD * KV_PITCH;
-  for (const void* k : {(const void*)vit_attn_kernel<f16, 257>, (const void*)vit_attn_kernel<bf16, 257>, (const void*)vit_attn_kernel<f16, 0>,
-                        (const void*)vit_attn_kernel<bf16, 0>, (const void*)vit_attn_persist_kernel<f16, 257>, (const void*)vit_attn_persist_kernel<bf16, 257>})
-    if (!ensure_lds(k, attn_lds)) return fail(MRA_EHIP, "hipFuncSetAttribute(vit_attn_kernel)");
-  const float sl2 = LOG2E / sqrtf((float)hd);
   // folded LayerNorms (see vit_fold_weight_kernel): x16 = the op-dtype copy of the residual rows, groups = their 128-column statistics as the
   // residual GEMMs leave them, rstat = (mean, rstd) per row for the QKV / fc1 epilogues
   const bool fold = h->ln_fold && h->can_fold();
@@ -746,16 +765,7 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
       rc = launch_gemm(&p, 1, fold ? EPI_LNF_OP : EPI_OP, op, st);
       if (rc) return chk(rc, "vit qkv gemm");
     }
-    with_op(op, [&](auto t) {
-      using T = decltype(t);
-      auto attn = [&](auto kernel, int grid, int waves, int s_or_units) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * 64), attn_lds, st, (const T*)big, (T*)a16, s_or_units, c.heads, hd, sl2);
-      };
-      const int units = n * c.heads;
-      if (S == 257 && h->attn_persist && h->cus > 0) attn(vit_attn_persist_kernel<T, 257>, std::min(units, h->cus), ATTP_WAVES, units);   // one persistent workgroup per CU, the next unit's K / V prefetched
-      else if (S == 257) attn(vit_attn_kernel<T, 257>, units, ATT_WAVES, S);   // ViT-g/224: the sequence length as a compile-time constant
-      else attn(vit_attn_kernel<T, 0>, units, ATT_WAVES, S);
-    });
+    if ((rc = vit_attention(h, big, a16, n, st))) return rc;
     // x += A W^T + b for the two N = dim GEMMs.  dim = 1408 is 5.5 tiles of 256: GT_P8_MIXED runs the five full column tiles
     // of two row tiles and then their last 128 columns as one 128 x 512 tile, all in one launch (a masked sixth 256-wide tile wastes 9 %)
     auto residual_gemm = [&](const void* A, int K, const void* W, const float* bias, bool stat) {
@@ -796,6 +806,17 @@ int mra_vit_forward(mra_vit* h, const void* frames, int32_t dtype, int32_t n, vo
     if (feeds_ln) row_stats();
   }
   return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "vit forward launch");
+}
+
+int mra_debug_vit_attention(mra_vit* h, const void* qkv, int32_t n, void* ctx, void* stream_) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (n < 0) return fail(MRA_EINVAL, "negative frame count");
+  if (n == 0) return MRA_OK;
+  if (!qkv || !ctx) return fail(MRA_EINVAL, "null argument");
+  if ((long long)n * h->S > 0x7fffffffLL / 64) return fail(MRA_EINVAL, "too many frames for one call: chunk them");
+  const int rc = vit_attention(h, qkv, ctx, n, as_stream(stream_));
+  if (rc) return rc;
+  return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "vit attention launch");
 }
 
 double mra_vit_flops(mra_vit* h, int32_t frames) {
