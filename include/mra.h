@@ -230,6 +230,31 @@ int mra_fuse_logits(const float* const* logits, const float* weights, int32_t nm
  * logits[v*clips .. (v+1)*clips) while the neighbour >= lo + alpha * (hi - lo). */
 int mra_span_from_logits(const float* logits, int32_t videos, int32_t clips, float alpha, int32_t* spans,
                          void* stream);
+/* Ranked moment proposals: per video the top_k windows of its fused clip logits under greedy temporal NMS.
+ * replaces: the ranked pred_relevant_windows list that eval/mr_eval.py:21-94 consumes in list order and that the
+ * reference's LLM decode could emit as "[[a, b], [c, d]]" (utils/utils.py:66-132).  Build-defined like the rest of
+ * A6 (the reference has no scorer); a second head beside mra_span_from_logits, which is unchanged.
+ * Definition, per video with x = logits[v*clips .. (v+1)*clips), finite:
+ *   1. hi = max x, lo = min x, thr = lo + alpha * (hi - lo) in fp32, product and sum rounded separately
+ *      (as mra_span_from_logits);
+ *   2. q[i] = llrint(clamp((double)x[i] * 2^20, +-2^40)) - llrint(clamp((double)thr * 2^20, +-2^40))  (int64);
+ *   3. P[0] = 0, P[i+1] = P[i] + q[i]  (exact);
+ *   4. candidates: every (s, e), 0 <= s <= e < clips, inclusive clip indices, with e - s + 1 <= max_len
+ *      (max_len == 0: no cap); score(s, e) = P[e+1] - P[s], the summed excess over the threshold;
+ *   5. order: higher score, then the shorter window, then the smaller s;
+ *   6. greedy NMS in that order: a candidate is dropped when for a selected window (s', e')
+ *      (double)inter > (double)nms_thd * (double)union, inter = max(0, min(e, e') - max(s, s') + 1),
+ *      union = len + len' - inter (the product is exact; nms_thd < 1 always drops an identical window);
+ *   7. rank 1 is always emitted (its score is >= 0: the argmax clip alone qualifies); later ranks only while the best
+ *      remaining score is > 0; at most top_k.
+ * Rank 1 is a maximum-sum window; it need not equal the span of mra_span_from_logits (it may bridge a short dip).
+ * windows [videos, top_k, 2] int32 (unused slots -1), scores [videos, top_k] = (float)((double)score * 2^-20)
+ * (unused slots 0), counts [videos].  clips in 1..4096, top_k in 1..64, nms_thd in [0, 1), max_len >= 0.
+ * One launch, no allocation, no synchronisation.  For non-finite logits the results are unspecified (the kernel
+ * still terminates in bounds).  Cost grows with clips^2 when max_len == 0: see DESIGN.md section 4. */
+int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, float alpha, int32_t top_k,
+                            float nms_thd, int32_t max_len, int32_t* windows, float* scores, int32_t* counts,
+                            void* stream);
 
 /* ---- training: forward with an activation tape + backward (BASELINE config 5) --------------------
  * Beyond the reference: its Q-Formers are frozen (models/xinstructblip.py:196-204) and utils/trainer.py

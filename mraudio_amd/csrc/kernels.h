@@ -377,5 +377,8 @@ int launch_cosine_score(const float* z, const float* t, int t_rows, int items, i
 int launch_fuse_logits(const float* const* logits, const float* weights, int nmod, int n, float* out,
                        hipStream_t stream);
 int launch_span(const float* logits, int videos, int clips, float alpha, int* spans, hipStream_t stream);
+// windows.hip: ranked top-k windows under temporal NMS (include/mra.h: mra_windows_from_logits); clips 1..4096, top_k 1..64
+int launch_windows(const float* logits, int videos, int clips, float alpha, int top_k, float nms_thd, int max_len, int* windows,
+                   float* scores, int* counts, hipStream_t stream);
 
 }  // namespace mra

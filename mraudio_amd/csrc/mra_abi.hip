@@ -1226,4 +1226,17 @@ int mra_span_from_logits(const float* logits, int32_t videos, int32_t clips, flo
   return chk(launch_span(logits, videos, clips, alpha, spans, as_stream(stream)), "span_from_logits");
 }
 
+int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, float alpha, int32_t top_k, float nms_thd,
+                            int32_t max_len, int32_t* windows, float* scores, int32_t* counts, void* stream) {
+  if (videos < 0) return fail(MRA_EINVAL, "negative videos");
+  if (videos == 0) return MRA_OK;
+  if (!logits || !windows || !scores || !counts) return fail(MRA_EINVAL, "null argument");
+  if (clips < 1 || clips > 4096) return fail(MRA_EINVAL, "clips must be in 1..4096");
+  if (top_k < 1 || top_k > 64) return fail(MRA_EINVAL, "top_k must be in 1..64");
+  if (!(nms_thd >= 0.f && nms_thd < 1.f)) return fail(MRA_EINVAL, "nms_thd must be in [0, 1)");
+  if (max_len < 0) return fail(MRA_EINVAL, "negative max_len (0 = no length cap)");
+  return chk(launch_windows(logits, videos, clips, alpha, top_k, nms_thd, max_len, windows, scores, counts, as_stream(stream)),
+             "windows_from_logits");
+}
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 """Inference loop of the reference's ``evaluate.py:41-59``: batches -> ``model.generate`` -> span parsing ->
 one JSON line per query, in the format ``eval/mr_eval.py`` (here ``mraudio_amd.eval.mr_eval``) scores.
 On top of the reference's record this build also writes ``pred_saliency_scores`` -- the fused per-position
-cosine logits the span was cut from -- so the highlight metrics can be computed as well.
+cosine logits the span was cut from -- so the highlight metrics can be computed as well.  With ``--top-k N`` (N > 1)
+``pred_relevant_windows`` is the ranked list of up to N ``[start_s, end_s, score]`` proposals (``model.generate_windows``).
 
     python -m mraudio_amd.evaluate --synthetic 8 --output-file out/pred.jsonl      # smoke run on the GPU
 """
@@ -20,7 +21,7 @@ from .utils.spans import moment_str_to_list, post_process
 
 @torch.no_grad()
 def run_inference(model, dataloader: Iterable[dict], output_file: Optional[str] = None, with_saliency: bool = True,
-                  device=None) -> List[dict]:
+                  device=None, top_k: int = 1) -> List[dict]:
     records: List[dict] = []
     fh = None
     if output_file:
@@ -28,13 +29,18 @@ def run_inference(model, dataloader: Iterable[dict], output_file: Optional[str] 
         fh = open(output_file, "w")
     for samples in dataloader:
         samples = prepare_sample(samples, device)
-        scores = None
-        if with_saliency and hasattr(model, "generate_with_scores"):
+        scores = windows = None
+        if top_k > 1:   # ranked proposals: [start_s, end_s, score] triples in rank order, raw_out the multi-window string
+            outputs, windows, scores = model.generate_windows(samples)
+            if not with_saliency:
+                scores = None
+        elif with_saliency and hasattr(model, "generate_with_scores"):
             outputs, scores = model.generate_with_scores(samples)
         else:
             outputs = model.generate(samples)
         for k, (qid, query, vid, raw) in enumerate(zip(samples["qid"], samples["query"], samples["vid"], outputs)):
-            rec = {"qid": qid, "query": query, "vid": vid, "pred_relevant_windows": moment_str_to_list(post_process(raw)), "raw_out": raw}
+            pred = windows[k] if windows is not None else moment_str_to_list(post_process(raw))
+            rec = {"qid": qid, "query": query, "vid": vid, "pred_relevant_windows": pred, "raw_out": raw}
             if scores is not None:
                 rec["pred_saliency_scores"] = [float(x) for x in scores[k]]
             records.append(rec)
@@ -75,6 +81,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],
                     help="precision of the Q-Formers' cross-attention score chain: op (f16 / bf16 operands), split (~22-bit hi + lo pairs, "
                          "+28 %% of the step) or auto (measured on the first batch after the weights are loaded: split for sharply attending weights)")
+    ap.add_argument("--top-k", type=int, default=1, help="ranked proposals per query: N > 1 writes up to N [start_s, end_s, score] windows in rank order "
+                                                         "(top windows by summed excess over the span threshold under temporal NMS); 1 = the single span")
+    ap.add_argument("--nms-thd", type=float, default=0.25, help="temporal IoU above which a proposal is suppressed by a higher-ranked one, in [0, 1)")
+    ap.add_argument("--max-window", type=int, default=0, help="longest proposal in clips (0 = no cap)")
     return ap
 
 
@@ -87,14 +97,14 @@ def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
     n_frms = 60 if args.dataset == "QVH" else 20
     model = XInstructBLIP(args.model_path, args.audio_encoder, device=args.device, checkpoint=args.checkpoint, checkpoint_strict=not args.partial_checkpoint,
-                          cross_precision=args.cross_precision)
+                          cross_precision=args.cross_precision, top_k=args.top_k, nms_thd=args.nms_thd, max_window=args.max_window)
     print(f"weights: {model.weights_source}")
     if args.synthetic:
         ds = SyntheticMRDataset(args.synthetic, T=n_frms)
     else:
         ds = MRDataset(args.video_folder, args.annotation_file, None, None, model=args.model, embeds_root=args.embeds_folder)
     dl = DataLoader(ds, shuffle=False, batch_size=args.batch_size, num_workers=args.num_workers, collate_fn=collate_fn)
-    recs = run_inference(model, dl, args.output_file, device=torch.device(args.device))
+    recs = run_inference(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k)
     print(f"wrote {len(recs)} predictions to {args.output_file}")
 
 

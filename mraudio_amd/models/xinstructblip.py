@@ -120,7 +120,7 @@ class XInstructBLIP(nn.Module):
                  compat_repeat: bool = True, score_alpha: float = 0.5, fuse_weights: Optional[Sequence[float]] = None,
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
-                 cross_precision: str = "op", audio_processor=None):
+                 cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0):
         super().__init__()
         self.model_path, self.audio_path = model_path, audio_path
         self.modalities = list(modalities) if modalities is not None else ["audio", "video"]  # reference :71
@@ -129,6 +129,9 @@ class XInstructBLIP(nn.Module):
         self.num_query_token = 32        # reference :120
         self.compat_repeat = compat_repeat
         self.score_alpha = score_alpha
+        # ranked proposals (scorer.windows_from_logits): with top_k > 1 fuse_score also returns the top_k windows under temporal NMS
+        # (threshold nms_thd, window length capped at max_window clips, 0 = none); 1 = the single span only, no extra launch
+        self.top_k, self.nms_thd, self.max_window = int(top_k), float(nms_thd), int(max_window)
         self.fuse_weights = fuse_weights
         self.process_group = process_group
         # True: the clips of one batch are sharded over the ranks (inference, every rank is given the same
@@ -507,6 +510,9 @@ class XInstructBLIP(nn.Module):
             raise MraError("no features for any of the model's modalities")
         out["fused"] = scorer.fuse_logits([out["logit"][m] for m in mods], self.fuse_weights)
         out["spans"] = scorer.spans_from_logits(out["fused"], bs, num, self.score_alpha)
+        if self.top_k > 1:   # on the gathered logits: every rank of a sharded run ranks the same windows
+            out["windows"], out["window_scores"], out["window_counts"] = scorer.windows_from_logits(
+                out["fused"], bs, num, self.score_alpha, self.top_k, self.nms_thd, self.max_window)
         out["bs"], out["num"] = bs, num
         return out
 
@@ -584,6 +590,22 @@ class XInstructBLIP(nn.Module):
         ts = [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
         scores = out["fused"].view(out["bs"], out["num"]).float().cpu().tolist()
         return [o.strip() for o in scorer.spans_to_text(spans, ts)], scores
+
+    @torch.no_grad()
+    def generate_windows(self, samples):
+        """Ranked proposals (needs ``top_k > 1``): ``(texts, records, saliency)`` with per sample the
+        ``"[[a, b], [c, d]]"`` string, the ``[start_s, end_s, score]`` triples in rank order (the
+        ``pred_relevant_windows`` that ``eval/mr_eval.py:21-94`` scores) and the fused logits ``[T]``."""
+        if self.top_k <= 1:
+            raise MraError("generate_windows needs a model built with top_k > 1")
+        out = self.encode_fuse(samples)
+        ts = samples.get("timestamps")
+        if ts is None:
+            ts = [list(range(out["num"]))] * out["bs"]
+        ts = [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
+        win, sc, cnt = out["windows"].cpu(), out["window_scores"].cpu(), out["window_counts"].cpu()
+        saliency = out["fused"].view(out["bs"], out["num"]).float().cpu().tolist()
+        return scorer.windows_to_text(win, cnt, ts), scorer.windows_to_records(win, sc, cnt, ts), saliency
 
     # ---- row N2: the reference's own decode, for callers that attach a stock LLM ----------------------------
     def attach_llm(self, llm_model: nn.Module, llm_tokenizer, enumerate_inputs: bool = False, interleave_seconds: bool = True) -> None:

@@ -5,6 +5,12 @@ The reference has no scorer: it prompts a 7B LLM with the projected query embedd
 star replaces that stage; the definition (and its CPU checker) is ``oracle/qformer_ref.py``:
 ``sim[n, q] = cos(z[n, q], t[n])``, ``logit[n] = max_q sim[n, q]``, weighted sum over modalities,
 span = grow around the first argmax while the neighbour's logit >= lo + alpha * (hi - lo).
+
+A second, opt-in head ranks several windows per video (``windows_from_logits``): the top-k windows by summed
+excess over the same threshold under greedy temporal NMS, the ranked ``pred_relevant_windows`` list that
+``eval/mr_eval.py:21-94`` scores.  Its definition is in ``include/mra.h`` (``mra_windows_from_logits``) and, as a
+brute-force host reference, in ``tests/window_cases.py``.  Rank 1 is a maximum-sum window: it may bridge a short
+dip and need not equal the span of ``spans_from_logits``.
 """
 from __future__ import annotations
 
@@ -64,3 +70,43 @@ def spans_to_text(spans: Sequence[Sequence[int]], timestamps: Sequence[Sequence[
     and ``post_process`` / ``moment_str_to_list`` parse (``evaluate.py:48``); seconds come from
     ``samples["timestamps"]`` (``utils/mr_dataset.py:44``)."""
     return [f"[[{int(ts[int(s)])}, {int(ts[int(e)])}]]" for (s, e), ts in zip(spans, timestamps)]
+
+
+def windows_from_logits(logits: torch.Tensor, videos: int, clips: int, alpha: float = 0.5, top_k: int = 10,
+                        nms_thd: float = 0.25, max_len: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """logits [videos * clips] fp32 -> (windows int32 [videos, top_k, 2] inclusive clip indices, unused slots -1;
+    scores fp32 [videos, top_k], unused slots 0; counts int32 [videos]), ranked per video.  ``max_len`` caps the
+    window length in clips (0 = none); the cost grows with ``clips * max_len``."""
+    x = logits.to(torch.float32).contiguous()
+    if x.numel() != videos * clips:
+        raise MraError(f"windows_from_logits: {x.numel()} logits for {videos} x {clips}")
+    windows = torch.empty(videos, int(top_k), 2, dtype=torch.int32, device=x.device)
+    scores = torch.empty(videos, int(top_k), dtype=torch.float32, device=x.device)
+    counts = torch.empty(videos, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().mra_windows_from_logits(ptr(x), videos, clips, float(alpha), int(top_k), float(nms_thd), int(max_len),
+                                            ptr(windows), ptr(scores), ptr(counts), current_stream()),
+              "mra_windows_from_logits")
+    return windows, scores, counts
+
+
+def _rows(t) -> list:
+    return t.cpu().tolist() if torch.is_tensor(t) else [list(r) if isinstance(r, (list, tuple)) else r for r in t]
+
+
+def windows_to_records(windows, scores, counts, timestamps: Sequence[Sequence[int]]) -> List[List[list]]:
+    """Per video ``[[ts[s], ts[e], score], ...]`` in rank order: the ``pred_relevant_windows`` triples of
+    ``eval/mr_eval.py``; seconds as in ``spans_to_text``."""
+    out = []
+    for win, sc, n, ts in zip(_rows(windows), _rows(scores), _rows(counts), timestamps):
+        out.append([[int(ts[int(win[k][0])]), int(ts[int(win[k][1])]), float(sc[k])] for k in range(int(n))])
+    return out
+
+
+def windows_to_text(windows, counts, timestamps: Sequence[Sequence[int]]) -> List[str]:
+    """Ranked windows -> the ``"[[a, b], [c, d]]"`` strings (integer seconds) that ``post_process`` /
+    ``moment_str_to_list`` parse."""
+    out = []
+    for win, n, ts in zip(_rows(windows), _rows(counts), timestamps):
+        out.append("[" + ", ".join(f"[{int(ts[int(win[k][0])])}, {int(ts[int(win[k][1])])}]" for k in range(int(n))) + "]")
+    return out
