@@ -140,6 +140,28 @@ int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* in
                              const void* enc1, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0, float* out_cls0,
                              float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-prompt forward: `prompts` prompts per encoder item over ONE shared K/V cache.
+ * replaces: model.{modality}_Qformer.bert(...) (models/xinstructblip.py:286-293) as evaluate.py:42-44 calls it once per (vid, query)
+ * annotation line -- P lines of one video become one call with prompts = P, and the encoder rows of the video are given once.
+ *   input_ids      [enc_items * prompts, L]       int64   row i * prompts + p: encoder item i, prompt slot p; prompts differ freely per row
+ *   attention_mask [enc_items * prompts, 32 + L]  int64   same row order, or NULL (all ones)
+ *   enc            [enc_items, kv, E]             operand dtype, as mra_modality_ln writes it; the learned query tokens are the loaded parameter
+ *   out_query      [enc_items * prompts, 32, H]   fp32 (may be NULL)
+ *   out_cls        [enc_items * prompts, H]       fp32 (may be NULL; needs L >= 1)
+ * The layer chain runs on enc_items * prompts items; the K/V projection runs once on enc_items items and the cross core of chain item n
+ * reads the K/V of item n / prompts.  Always the K/V-cache form in operand precision, whatever mra_qformer_set_cross_mode says: per cross
+ * layer and encoder item the projection costs 4 Kv E 768 flops (call it 1), the folded form 0.5 per prompt, the flash core over a cache
+ * 4 384 Kv 64 = 0.023 per prompt at E = 1408 -- so P prompts cost 0.5 P folded, 1.023 P with a cache re-projected per replica and
+ * 1 + 0.023 P here (fewer flops from P = 3; arithmetic, not a measurement).  The cross core follows mra_qformer_set_option "multi_core".
+ * Precision as mra_qformer_forward_pair: MRA_ESTATE while split precision is in force or automatic precision is unresolved or resolved to
+ * split.  Argument checks as mra_qformer_forward, plus prompts >= 1; enc_items == 0 is a no-op; no allocation, no synchronisation;
+ * prompts == 1 is the K/V-cache mra_qformer_forward launch for launch.  Workspace: mra_qformer_multi_workspace_bytes (0 for a NULL
+ * handle or a non-positive size), 256-byte aligned. */
+size_t mra_qformer_multi_workspace_bytes(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv);
+int mra_qformer_forward_multi(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
+                              int32_t enc_items, int32_t prompts, int32_t L, int32_t kv,
+                              float* out_query, float* out_cls, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Optional instrumentation for bench.py: when both events (hipEvent_t passed as void*) are non-NULL,
  * every following mra_qformer_forward records ev_start right before and ev_stop right after its
  * K/V-projection launch, on the launch stream.  (NULL, NULL) switches it off. */
@@ -199,7 +221,11 @@ int mra_qformer_cross_precision_report(mra_qformer* h, int32_t* resolved, int32_
  *                 bit 0 QKV (144 x 128), bit 1 FFN-up (192 x 128), bit 2 the residual projections (96 x 64), bit 3 (with bit 2) their LayerNorm inside the same
  *                 launch (the last-arriving column tile of a 64-row block normalises it).  DESIGN.md section 8.
  *   "train_ring"  the same mask (bits 0 and 2) for the GEMMs of mra_qformer_forward_train / mra_qformer_backward; default 4.
- *   "auto_split_pmax_milli"  tau of the automatic cross-attention precision in thousandths, 0..1000 (default 500); applies from the next probe. */
+ *   "auto_split_pmax_milli"  tau of the automatic cross-attention precision in thousandths, 0..1000 (default 500); applies from the next probe.
+ *   "multi_core"  the cross core of mra_qformer_forward_multi with prompts > 1: 0 the core of mra_qformer_forward, each chain item taking the
+ *                 K/V of its encoder item; 1 the shared-stream core (one workgroup per encoder item, head and 4 prompt slots, the K/V tiles
+ *                 staged once into a workgroup-shared LDS ring).  Default 1 (faster at P >= 4 on both shapes of tools/bench_multi_query.py, by 0.2 - 2.3 %;
+ *                 0 is 6 % ahead at P = 2, Kv 8224).  mra_qformer_multi_workspace_bytes follows it. */
 int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value);
 /* Derives what the folded path needs from the loaded weights (W_k of every cross layer regrouped per head) on
  * `stream`, if a load made it stale.  mra_qformer_forward does this itself; a caller that runs SEVERAL forwards of one
@@ -441,8 +467,19 @@ int64_t mra_debug_gemm_launches(int32_t family, int32_t epilogue);
  *
  * mra_debug_beats_posconv: x += GELU(grouped positional convolution of x) over n chunks of `tokens` tokens.  Needs encoder.pos_conv.0.weight
  * (the effective weight) and encoder.pos_conv.0.bias loaded (MRA_ESTATE otherwise).
- *   x [n * tokens][dim]  fp32, updated in place; the convolution reads x rounded to f16 */
+ *   x [n * tokens][dim]  fp32, updated in place; the convolution reads x rounded to f16
+ *
+ * mra_debug_shared_kv_attention: the cross core of mra_qformer_forward_multi on its own, through the forward's launch code (grid split of long
+ * KV included).  No handle, no parameters.
+ *   q   [enc_items * prompts][32][heads * 64]  operand dtype (MRA_F16 / MRA_BF16): row i * prompts + p = encoder item i, prompt slot p
+ *   k,v [enc_items][heads][kv][64]             operand dtype: one layer of the K/V cache's layout
+ *   ctx [enc_items * prompts][32][heads * 64]  operand dtype: softmax(q k^T / 8) v of chain item n over the K/V of item n / prompts
+ *   core 0: attn_kernel with kv_share, 1: the shared-stream core.  workspace (16-byte aligned) holds the grid-split partials:
+ *   mra_debug_shared_kv_workspace_bytes (0 where the core does not split).  enc_items == 0 is a no-op. */
 int mra_debug_vit_attention(mra_vit* h, const void* qkv, int32_t n, void* ctx, void* stream);
+size_t mra_debug_shared_kv_workspace_bytes(int32_t enc_items, int32_t prompts, int32_t heads, int32_t kv, int32_t core);
+int mra_debug_shared_kv_attention(const void* q, const void* k, const void* v, int32_t dtype, int32_t enc_items, int32_t prompts,
+                                  int32_t heads, int32_t kv, int32_t core, void* ctx, void* workspace, size_t workspace_bytes, void* stream);
 int mra_debug_beats_attention(mra_beats* h, int32_t layer, const void* qkv, const void* gate_src, int32_t n, int32_t tokens, void* ctx,
                               void* stream);
 int mra_debug_beats_posconv(mra_beats* h, float* x, int32_t n, int32_t tokens, void* stream);

@@ -62,6 +62,9 @@ PROTOTYPES = {
     "mra_qformer_pair_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mra_qformer_forward_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mra_qformer_multi_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mra_qformer_forward_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mra_qformer_set_kv_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mra_qformer_set_kv_done_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mra_qformer_set_cross_mode": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -116,6 +119,9 @@ PROTOTYPES = {
     "mra_fbank_flops": (C.c_double, [C.c_void_p, C.c_int32, C.c_int32]),
     "mra_debug_gemm_launches": (C.c_int64, [C.c_int32, C.c_int32]),
     "mra_debug_vit_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mra_debug_shared_kv_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mra_debug_shared_kv_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mra_debug_beats_attention": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mra_debug_beats_posconv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }

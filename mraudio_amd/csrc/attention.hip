@@ -19,6 +19,8 @@
 // Long KV (cross attention): the 4 waves of a workgroup take interleaved tiles of one unit and
 // merge through LDS; optionally the KV range is also split over workgroups (partials merged by
 // attn_combine_kernel) so that 384 (item, head) units still fill 256 CUs.
+// Several prompts per clip (AttnArgs::kv_share > 1): attn_kernel takes the K/V of item n / kv_share; attn_shared_kernel below is the
+// core built for that case, one workgroup-shared K/V ring under the query blocks of 4 prompts.
 #include "kernels.h"
 #include "mra_common.h"
 
@@ -26,12 +28,20 @@ namespace mra {
 
 namespace {
 
+typedef int i32x4v __attribute__((ext_vector_type(4)));
+
 constexpr int KVT = 32;                 // tokens per tile
 constexpr int TILE_B = KVT * 128;       // bytes per K (or V) tile
 constexpr int WAVE_LDS = 4 * TILE_B;    // 2 buffers x (K + V)
 constexpr int OPAD = 68;                // padded row of the f32 O scratch
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int PART_STRIDE = 32 * 64 + 64;  // floats per partial: O[32][64], m[32], l[32]
+// shared-stream core: a stage is SH_TPS tiles of K and V, the ring holds SH_STAGES stages (one barrier per stage)
+constexpr int SH_TPS = 2;
+constexpr int SH_STAGES = 3;
+constexpr int SH_STAGE_B = SH_TPS * 2 * TILE_B;        // [tile][K tile | V tile]
+constexpr int SH_PARK_B = (32 * OPAD + 64) * 4;        // one wave's O scratch + m + l
+constexpr int SH_LDS = SH_STAGES * SH_STAGE_B > 4 * SH_PARK_B ? SH_STAGES * SH_STAGE_B : 4 * SH_PARK_B;
 
 template <typename T, bool MASKED, int SPLITW>
 __global__ void __launch_bounds__(256) attn_kernel(const AttnArgs a) {
@@ -69,8 +79,9 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnArgs a) {
   const int mask_pad = ntiles_all * KVT;
   float* wmask = reinterpret_cast<float*>(smem + 4 * WAVE_LDS) + wave * mask_pad;
 
-  const T* Kb = (const T*)a.K + (long long)item * a.k_item_stride + (long long)head * a.k_head_stride;
-  const T* Vb = (const T*)a.V + (long long)item * a.v_item_stride + (long long)head * a.v_head_stride;
+  const int kv_item = item / a.kv_share;   // several prompts of one clip read one K/V stream (kv_share 1: every item its own)
+  const T* Kb = (const T*)a.K + (long long)kv_item * a.k_item_stride + (long long)head * a.k_head_stride;
+  const T* Vb = (const T*)a.V + (long long)kv_item * a.v_item_stride + (long long)head * a.v_head_stride;
 
   // ---- additive mask in log2 units (self attention only) ----
   if (MASKED) {
@@ -364,6 +375,252 @@ int launch_t(const AttnArgs& a, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// Several prompts over one K/V stream.  Workgroup = (K/V item, head, group of 4 prompt slots, grid split); wave w owns the 32 queries of
+// slot 4 group + w exactly as a wave of attn_kernel<T, false, 1> owns its unit (Q fragments in registers, own online softmax, no cross-wave
+// merge).  The K/V tiles are staged once per workgroup: every wave fetches rows 8 w .. 8 w + 7 of each K and V tile of a stage by LDS-DMA
+// (same K / V swizzles on the source address), all four read the whole stage.  Ring of SH_STAGES stages with one stage in flight across
+// the barrier:
+//   iteration s:  s_waitcnt vmcnt(own loads of stage s + 1 may stay in flight)   -> this wave's part of stage s has landed
+//                 s_barrier                                                       -> every wave's part has, and every wave is done with s - 1
+//                 issue stage s + 2 into the buffer of stage s - 1
+//                 read + compute stage s
+// The barrier is the raw one: __syncthreads() would drain the DMA in flight (vmcnt(0)).  Every LDS read of the loop is inline asm with its
+// own lgkmcnt(0), so no read is pending when a wave arrives at the next barrier and hipcc has no LDS load to order behind the DMA.
+// The spare waves of the last group (kv_share % 4 != 0) repeat the last slot: same loads, same barriers, no store.
+template <typename T>
+__global__ void __launch_bounds__(256) attn_shared_kernel(const AttnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int groups = (a.kv_share + 3) >> 2;
+  const int ntiles_all = (a.kv_len + KVT - 1) / KVT;
+  const int nstages_all = (ntiles_all + SH_TPS - 1) / SH_TPS;
+
+  int b = blockIdx.x;
+  const int gs = b % a.nsplit; b /= a.nsplit;
+  const int grp = b % groups; b /= groups;
+  const int head = b % a.heads;
+  const int kv_item = b / a.heads;
+  const int slot = grp * 4 + wave;
+  const bool active = slot < a.kv_share;
+  const int item = kv_item * a.kv_share + min(slot, a.kv_share - 1);
+
+  const int sps = (nstages_all + a.nsplit - 1) / a.nsplit;  // stages per grid split
+  const int sb = gs * sps;
+  const int se = min(sb + sps, nstages_all);
+
+  const T* Kb = (const T*)a.K + (long long)kv_item * a.k_item_stride + (long long)head * a.k_head_stride;
+  const T* Vb = (const T*)a.V + (long long)kv_item * a.v_item_stride + (long long)head * a.v_head_stride;
+
+  // ---- Q fragments (as attn_kernel) ----
+  typename Vec8<T>::type qf[4];
+  {
+    const int qr = min(lane & 31, a.q_rows - 1);
+    const T* qp = (const T*)a.Q + (long long)item * a.q_item_stride + (long long)qr * a.q_ld + head * 64 + 8 * (lane >> 5);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const typename Vec8<T>::type*>(qp + 16 * s);
+  }
+  // the Q loads retire here, ahead of the first DMA: the counted waits below then count DMA only
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+  // ---- this wave's quarter of a stage: rows 8 wave + (lane >> 3) of every tile, physical chunk lane & 7 ----
+  const int row = 8 * wave + (lane >> 3), sc = lane & 7;
+  const int kc = sc ^ ((row >> 1) & 7);
+  const int vc = sc ^ (((row >> 1) & 1) << 2);
+  auto issue = [&](int buf, int s) {
+    char* st = smem + buf * SH_STAGE_B + wave * 1024;
+#pragma unroll
+    for (int j = 0; j < SH_TPS; ++j) {
+      const int tok = min((s * SH_TPS + j) * KVT + row, a.kv_len - 1);
+      glds16((const char*)(Kb + (long long)tok * a.k_ld) + kc * 16, st + j * 2 * TILE_B);
+      glds16((const char*)(Vb + (long long)tok * a.v_ld) + vc * 16, st + j * 2 * TILE_B + TILE_B);
+    }
+  };
+
+  // ---- fragment read addresses (as attn_kernel) ----
+  unsigned koff[4];
+  {
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) koff[s] = r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) << 4);
+  }
+  unsigned vlane[2];
+  {
+    const int g = lane >> 4, i = lane & 15, q4 = i >> 2, p = i & 3, h = lane >> 5;
+    const int vrow = 4 * h + q4;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int c = 4 * mt + 2 * (g & 1) + (p >> 1);
+      const int pc = c ^ (((q4 >> 1) & 1) << 2);
+      vlane[mt] = vrow * 128 + pc * 16 + (p & 1) * 8;
+    }
+  }
+  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+
+  const float sl2 = a.scale * LOG2E;
+  float m_run = -1e30f, l_run = 0.f;
+  f32x16 ot[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { ot[0][i] = 0.f; ot[1][i] = 0.f; }
+  const int h4 = 4 * (lane >> 5);
+
+  if (sb < se) issue(0, sb);
+  if (sb + 1 < se) issue(1, sb + 1);
+  int buf = 0;
+  for (int s = sb; s < se; ++s) {
+    if (s + 1 < se) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SH_TPS) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (s + 2 < se) issue(buf >= 1 ? buf - 1 : SH_STAGES - 1, s + 2);   // (buf + 2) % 3: the buffer stage s - 1 was read from
+
+#pragma unroll
+    for (int j = 0; j < SH_TPS; ++j) {
+      const int t = s * SH_TPS + j;
+      if (t >= ntiles_all) break;   // workgroup-uniform: the last stage of an odd tile count
+      const unsigned kbase = smem_lds + buf * SH_STAGE_B + j * 2 * TILE_B;
+
+      // S^T = K * Q^T
+      i32x4v k0, k1, k2, k3;
+      asm volatile(
+          "ds_read_b128 %0, %4\n\t"
+          "ds_read_b128 %1, %5\n\t"
+          "ds_read_b128 %2, %6\n\t"
+          "ds_read_b128 %3, %7\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(k0), "=&v"(k1), "=&v"(k2), "=&v"(k3)
+          : "v"(kbase + koff[0]), "v"(kbase + koff[1]), "v"(kbase + koff[2]), "v"(kbase + koff[3])
+          : "memory");
+      f32x16 st;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) st[i] = 0.f;
+      st = mfma32<T>(__builtin_bit_cast(typename Vec8<T>::type, k0), qf[0], st);
+      st = mfma32<T>(__builtin_bit_cast(typename Vec8<T>::type, k1), qf[1], st);
+      st = mfma32<T>(__builtin_bit_cast(typename Vec8<T>::type, k2), qf[2], st);
+      st = mfma32<T>(__builtin_bit_cast(typename Vec8<T>::type, k3), qf[3], st);
+
+      // scores in log2 units, tail mask (as attn_kernel without an additive mask)
+      const int tok0 = t * KVT;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = 4 * g4 + e;
+          float y = st[i] * sl2;
+          if (tok0 + 8 * g4 + h4 + e >= a.kv_len) y = -INFINITY;
+          st[i] = y;
+          mx = fmaxf(mx, y);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run, mx);
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      m_run = m_new;
+      float psum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float p = __builtin_amdgcn_exp2f(st[i] - m_new);
+        st[i] = p;
+        psum += p;
+      }
+      l_run = l_run * alpha + psum;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { ot[0][i] *= alpha; ot[1][i] *= alpha; }
+
+      typename Vec8<T>::type pf[2];
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) pf[s2][e] = from_f32<T>(st[8 * s2 + e]);
+
+      // O^T += V^T * P^T
+      {
+        const unsigned vaddr0 = kbase + TILE_B + vlane[0];
+        const unsigned vaddr1 = kbase + TILE_B + vlane[1];
+        i16x4 r00, r01, r02, r03, r10, r11, r12, r13;
+        asm volatile(
+            "ds_read_b64_tr_b16 %0, %8\n\t"
+            "ds_read_b64_tr_b16 %1, %8 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %2, %8 offset:2048\n\t"
+            "ds_read_b64_tr_b16 %3, %8 offset:3072\n\t"
+            "ds_read_b64_tr_b16 %4, %9\n\t"
+            "ds_read_b64_tr_b16 %5, %9 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %6, %9 offset:2048\n\t"
+            "ds_read_b64_tr_b16 %7, %9 offset:3072\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(r00), "=&v"(r01), "=&v"(r02), "=&v"(r03), "=&v"(r10), "=&v"(r11), "=&v"(r12), "=&v"(r13)
+            : "v"(vaddr0), "v"(vaddr1)
+            : "memory");
+        auto cat = [](i16x4 lo, i16x4 hi) {
+          i16x8 v8;
+          v8[0] = lo[0]; v8[1] = lo[1]; v8[2] = lo[2]; v8[3] = lo[3];
+          v8[4] = hi[0]; v8[5] = hi[1]; v8[6] = hi[2]; v8[7] = hi[3];
+          return __builtin_bit_cast(typename Vec8<T>::type, v8);
+        };
+        ot[0] = mfma32<T>(cat(r00, r01), pf[0], ot[0]);
+        ot[0] = mfma32<T>(cat(r02, r03), pf[1], ot[0]);
+        ot[1] = mfma32<T>(cat(r10, r11), pf[0], ot[1]);
+        ot[1] = mfma32<T>(cat(r12, r13), pf[1], ot[1]);
+      }
+    }
+    buf = buf + 1 == SH_STAGES ? 0 : buf + 1;
+  }
+
+  // ---- each wave finishes its own slot: O^T -> [q][d] through its own LDS region (the ring is idle behind the barrier) ----
+  __syncthreads();
+  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  float* ow = reinterpret_cast<float*>(smem + wave * SH_PARK_B);
+  float* mw = ow + 32 * OPAD;
+  float* lw = mw + 32;
+  {
+    const int q = lane & 31;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        f32x4 v = {ot[mt][4 * g4], ot[mt][4 * g4 + 1], ot[mt][4 * g4 + 2], ot[mt][4 * g4 + 3]};
+        *reinterpret_cast<f32x4*>(ow + q * OPAD + 32 * mt + 8 * g4 + h4) = v;
+      }
+    if (lane < 32) { mw[q] = m_run; lw[q] = l_tot; }
+  }
+  __syncthreads();
+  if (!active) return;
+  const long long unit = (long long)item * a.heads + head;
+  for (int idx = lane; idx < 256; idx += 64) {
+    const int q = idx >> 3, dc = idx & 7;
+    const float M = mw[q], L = lw[q];
+    const f32x4 x0 = *reinterpret_cast<const f32x4*>(ow + q * OPAD + 8 * dc);
+    const f32x4 x1 = *reinterpret_cast<const f32x4*>(ow + q * OPAD + 8 * dc + 4);
+    if (a.nsplit > 1) {
+      float* pp = a.part + (unit * a.nsplit + gs) * PART_STRIDE;
+      *reinterpret_cast<f32x4*>(pp + q * 64 + 8 * dc) = x0;
+      *reinterpret_cast<f32x4*>(pp + q * 64 + 8 * dc + 4) = x1;
+      if (dc == 0) { pp[32 * 64 + q] = M; pp[32 * 64 + 32 + q] = L; }
+    } else if (q < a.q_rows) {
+      const float inv = 1.0f / L;
+      typename Vec8<T>::type r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { r[e] = from_f32<T>(x0[e] * inv); r[4 + e] = from_f32<T>(x1[e] * inv); }
+      T* op = (T*)a.O + (long long)item * a.o_item_stride + (long long)q * a.o_ld + head * 64 + 8 * dc;
+      *reinterpret_cast<typename Vec8<T>::type*>(op) = r;
+    }
+  }
+}
+
+template <typename T>
+int launch_shared_t(const AttnArgs& a, hipStream_t stream) {
+  const int groups = (a.kv_share + 3) / 4;
+  const long long wgs = (long long)(a.items / a.kv_share) * a.heads * groups * a.nsplit;
+  if (wgs > 0x7fffffffLL) return -1;
+  hipLaunchKernelGGL(attn_shared_kernel<T>, dim3((unsigned)wgs), dim3(256), SH_LDS, stream, a);
+  if (a.nsplit > 1) hipLaunchKernelGGL(attn_combine_kernel<T>, dim3(a.items * a.heads), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 }  // namespace
 
 size_t attn_partial_bytes(int items, int heads, int q_rows, int nsplit) {
@@ -387,11 +644,38 @@ int attn_pick_split(int items, int heads, int q_rows, int kv_len) {
   return best;
 }
 
-int launch_attention(const AttnArgs& a, int op_dtype, hipStream_t stream) {
+int launch_attention(const AttnArgs& args, int op_dtype, hipStream_t stream) {
+  AttnArgs a = args;
+  if (a.kv_share < 1) a.kv_share = 1;   // (a zero-filled AttnArgs means what it always meant)
   if (a.items <= 0 || a.heads <= 0 || a.q_rows <= 0 || a.kv_len <= 0 || a.nsplit < 1) return -1;
   if (a.nsplit > 1 && !a.part) return -1;
   if ((a.q_ld | a.o_ld | a.k_ld | a.v_ld) & 7) return -1;  // 16-byte rows
+  if (a.items % a.kv_share) return -1;
   return op_dtype == OP_F16 ? launch_t<f16>(a, stream) : launch_t<bf16>(a, stream);
+}
+
+int attn_shared_pick_split(int kv_items, int kv_share, int heads, int kv_len) {
+  const int units = kv_items * heads * ((kv_share + 3) / 4);
+  const int ntiles = (kv_len + KVT - 1) / KVT;
+  const int nstages = (ntiles + SH_TPS - 1) / SH_TPS;
+  if (ntiles < 64) return 1;   // the threshold of attn_pick_split: below it a second launch costs more than the idle CUs
+  // three 48 KB workgroups fit a CU: split until 512 workgroups, each with >= 8 stages (16 tiles) behind its prologue
+  int best = 1;
+  for (int s = 1; s <= 16; ++s) {
+    if (nstages / s < 8) break;
+    best = s;
+    if ((long long)units * s >= 512) break;
+  }
+  return best;
+}
+
+int launch_attention_shared(const AttnArgs& args, int op_dtype, hipStream_t stream) {
+  AttnArgs a = args;
+  if (a.items <= 0 || a.heads <= 0 || a.q_rows <= 0 || a.q_rows > 32 || a.kv_len <= 0 || a.nsplit < 1 || a.kv_share < 1) return -1;
+  if (a.items % a.kv_share || a.mask || a.lse) return -1;
+  if (a.nsplit > 1 && !a.part) return -1;
+  if ((a.q_ld | a.o_ld | a.k_ld | a.v_ld) & 7) return -1;  // 16-byte rows
+  return op_dtype == OP_F16 ? launch_shared_t<f16>(a, stream) : launch_shared_t<bf16>(a, stream);
 }
 
 }  // namespace mra

@@ -322,10 +322,19 @@ struct AttnArgs {
   int nsplit;
   float* part;   // [items*heads*qblocks][nsplit][32*64 + 64] f32
   float* lse;    // optional [item][head][q_rows] f32: log2-sum-exp2 of the scaled, masked scores (for the backward)
+  // several prompts over one K/V stream (mra_qformer_forward_multi): item n reads the K/V of item n / kv_share; Q, O, mask, partials
+  // and lse stay per item
+  int kv_share = 1;
 };
 size_t attn_partial_bytes(int items, int heads, int q_rows, int nsplit);
 int attn_pick_split(int items, int heads, int q_rows, int kv_len);
 int launch_attention(const AttnArgs& a, int op_dtype, hipStream_t stream);
+// The shared-stream core: a workgroup is one (K/V item, head, group of up to 4 of its kv_share prompt slots); its 4 waves each own the 32
+// queries of one slot and all read the K/V tiles from ONE workgroup-shared LDS ring, so the K/V bytes leave L2 / HBM once per 4 prompts.
+// a.items = K/V items x a.kv_share, a.q_rows <= 32, no mask, no lse; a.nsplit from attn_shared_pick_split, partials as attn_partial_bytes
+// (merged by the same combine kernel).
+int attn_shared_pick_split(int kv_items, int kv_share, int heads, int kv_len);
+int launch_attention_shared(const AttnArgs& a, int op_dtype, hipStream_t stream);
 
 // ---- normalisation / embeddings / conversions -----------------------------------------------
 // y = LN(x) over H (multiple of 256, <= 1024) with gain/bias; writes f32 and/or op-dtype copies.

@@ -203,6 +203,7 @@ struct Lane {
   long long query_stride;      // ... and their item stride (0: shared)
   float *out_query, *out_full, *out_cls;
   Work w;
+  int share = 1;               // chain items per encoder item (mra_qformer_forward_multi: the prompts of a clip); K/V-cache form only
 };
 
 // the layer chain's buffers for NN items (residual streams, QKV, attention context, feed-forward intermediate), seen from item n0 on
@@ -224,8 +225,9 @@ void layout_chain(Carver& cv, Work& w, size_t NN, size_t n0, size_t S, size_t H,
   w.lncnt = cv.take<unsigned>(w.lncnt_bytes / sizeof(unsigned));
 }
 
-// one lane's cross-attention buffers for N items (K/V cache, or the folded form's Q' / P / U / statistics)
-void layout_cross(const mra_qformer* h, const CrossPlan& x, Carver& cv, Work& w, int N, int Kv) {
+// one lane's cross-attention buffers for N encoder items (K/V cache, or the folded form's Q' / P / U / statistics), each read by
+// `share` chain items
+void layout_cross(const mra_qformer* h, const CrossPlan& x, Carver& cv, Work& w, int N, int Kv, int share = 1) {
   const mra_cfg& c = h->cfg;
   const size_t H = c.hidden, Q = c.n_query, E = c.enc_width, R = (size_t)c.heads * Q, kvp = fold_kvp(Kv);
   if (x.form == CrossPlan::FOLD_STREAM) {
@@ -255,7 +257,9 @@ void layout_cross(const mra_qformer* h, const CrossPlan& x, Carver& cv, Work& w,
   } else {
     w.kv16 = cv.take<char>((size_t)h->ncross * 2 * N * Kv * H, 2);
   }
-  w.nsplit = attn_pick_split(N, c.heads, (int)Q, Kv);
+  // which core runs a shared K/V stream: attn_kernel with kv_share at share == 1 (the existing forward, launch for launch) and
+  // multi_core 0, the shared-stream core otherwise; each splits long KV by its own rule
+  w.nsplit = share > 1 && h->multi_core == 1 ? attn_shared_pick_split(N, share, c.heads, Kv) : attn_pick_split(N * share, c.heads, (int)Q, Kv);
 }
 
 // The workspace of a forward over nl lanes of N items each; with base == nullptr only measures.  Returns its bytes.  The chain buffers hold
@@ -273,7 +277,7 @@ size_t layout_lanes(Lane* lanes, int nl, char* base, int N, int L, long long** m
   }
   for (int l = 0; l < nl; ++l) {
     Work& w = lanes[l].w;
-    layout_cross(lanes[l].h, lanes[l].plan, cv, w, N, lanes[l].kv);
+    layout_cross(lanes[l].h, lanes[l].plan, cv, w, N / lanes[l].share, lanes[l].kv, lanes[l].share);
     // (the two-lane layout has always kept 64 floats of slack behind each lane's partials)
     float* part = cv.take<float>(attn_partial_bytes(N, c.heads, c.n_query, w.nsplit) / sizeof(float) + (nl > 1 ? 64 : 0));
     w.part = w.nsplit > 1 ? part : nullptr;
@@ -314,7 +318,11 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
   int rc = 0;
   if (x.form == CrossPlan::KV_CACHE) {
     // 6. cross-attention core over the head-major K/V cache
-    rc = launch_attention(kv_cross_attn_args(c, w.qc16, w.kv16, ci, w.ctx16, N, kv, w.nsplit, w.part), op, stream);
+    // (the cache holds N / share encoder items; chain item n reads the K/V of item n / share)
+    AttnArgs a = kv_cross_attn_args(c, w.qc16, w.kv16, ci, w.ctx16, N / lane.share, kv, w.nsplit, w.part);
+    a.items = N;
+    a.kv_share = lane.share;
+    rc = lane.share > 1 && h->multi_core == 1 ? launch_attention_shared(a, op, stream) : launch_attention(a, op, stream);
     return rc ? chk(rc, "cross attention") : MRA_OK;
   }
   const bool timed = ci == 0 && h->kv_ev0 && h->kv_ev1;
@@ -678,7 +686,7 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
       // K/V of every cross layer in one GEMM, scattered head-major
       const bool timed = !pair && hl->kv_ev0 && hl->kv_ev1;
       if (timed) (void)hipEventRecord(hl->kv_ev0, stream);
-      rc = kv_project(hl, x.enc, N, x.kv, x.w.kv16, stream);
+      rc = kv_project(hl, x.enc, N / x.share, x.kv, x.w.kv16, stream);
       if (rc) return chk(rc, "kv projection gemm");
       if (timed) (void)hipEventRecord(hl->kv_ev1, stream);
     }
@@ -1047,6 +1055,90 @@ int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* in
   return run_lanes(lanes, 2, input_ids, attention_mask, items, L, workspace, as_stream(stream_));
 }
 
+namespace {
+// the lane of a multi-prompt forward: always the K/V-cache form in operand precision, `prompts` chain items per encoder item
+void make_multi_lane(Lane& x, mra_qformer* h, const void* enc, int kv, int prompts) {
+  x = make_lane(h, enc, kv, false, false);
+  x.plan.form = CrossPlan::KV_CACHE;
+  x.share = prompts;
+}
+}  // namespace
+
+size_t mra_qformer_multi_workspace_bytes(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv) {
+  if (!h || enc_items <= 0 || prompts <= 0 || L < 0 || kv <= 0) return 0;
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return 0;
+  Lane x;
+  make_multi_lane(x, h, nullptr, kv, prompts);
+  return layout_lanes(&x, 1, nullptr, enc_items * prompts, L);
+}
+
+// Multi-prompt forward: `prompts` chain items per encoder item over ONE K/V projection (run_lanes with a lane whose share count is prompts).
+int mra_qformer_forward_multi(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int32_t enc_items,
+                              int32_t prompts, int32_t L, int32_t kv, float* out_query, float* out_cls, void* workspace, size_t workspace_bytes,
+                              void* stream_) {
+  if (prompts < 1) return fail(MRA_EINVAL, "prompts must be >= 1");
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (enc_items < 0 || L < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
+  if (enc_items == 0) return MRA_OK;
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return fail(MRA_EINVAL, "enc_items * prompts exceeds int32");
+  const mra_cfg& c = h->cfg;
+  if (kv == 0) return fail(MRA_EINVAL, "kv must be >= 1");
+  if (L > c.max_pos) return fail(MRA_EINVAL, "L exceeds max_pos");
+  if (!enc || (L > 0 && !input_ids)) return fail(MRA_EINVAL, "null input");
+  if (out_cls && L < 1) return fail(MRA_EINVAL, "out_cls needs L >= 1");
+  if (!out_query && !out_cls) return fail(MRA_EINVAL, "no output requested");
+  if (h->cross_precise) return fail(MRA_ESTATE, "multi forward runs the operand-dtype K/V cache: use mra_qformer_forward for split precision");
+  if (h->cross_auto && (h->auto_stale || h->auto_resolved != 0))
+    return fail(MRA_ESTATE, "multi forward runs the operand-dtype K/V cache: auto precision must have resolved to op (use mra_qformer_forward)");
+  if (int rc = check_loaded(h)) return rc;
+  Lane lane;
+  make_multi_lane(lane, h, enc, kv, prompts);
+  const size_t need = mra_qformer_multi_workspace_bytes(h, enc_items, prompts, L, kv);
+  if (!workspace || workspace_bytes < need) return fail(MRA_ENOMEM, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(MRA_EINVAL, "workspace must be 256-byte aligned");
+  lane.out_query = out_query;
+  lane.out_cls = out_cls;
+  return run_lanes(&lane, 1, input_ids, attention_mask, enc_items * prompts, L, workspace, as_stream(stream_));
+}
+
+namespace {
+int shared_kv_split(int enc_items, int prompts, int heads, int kv, int core) {
+  return core == 1 ? attn_shared_pick_split(enc_items, prompts, heads, kv) : attn_pick_split(enc_items * prompts, heads, 32, kv);
+}
+}  // namespace
+
+size_t mra_debug_shared_kv_workspace_bytes(int32_t enc_items, int32_t prompts, int32_t heads, int32_t kv, int32_t core) {
+  if (enc_items <= 0 || prompts <= 0 || heads <= 0 || kv <= 0 || core < 0 || core > 1) return 0;
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return 0;
+  return attn_partial_bytes(enc_items * prompts, heads, 32, shared_kv_split(enc_items, prompts, heads, kv, core));
+}
+
+// The cross core of the multi forward on its own, through the launch code the forward uses (launch_attention with kv_share, or
+// launch_attention_shared), split rule included.
+int mra_debug_shared_kv_attention(const void* q, const void* k, const void* v, int32_t dtype, int32_t enc_items, int32_t prompts, int32_t heads,
+                                  int32_t kv, int32_t core, void* ctx, void* workspace, size_t workspace_bytes, void* stream) {
+  if (enc_items < 0 || prompts < 1 || heads < 1 || kv < 1) return fail(MRA_EINVAL, "sizes: enc_items >= 0, prompts / heads / kv >= 1");
+  if (core < 0 || core > 1) return fail(MRA_EINVAL, "core must be 0 (kv_share) or 1 (shared stream)");
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (enc_items == 0) return MRA_OK;
+  if (!q || !k || !v || !ctx) return fail(MRA_EINVAL, "null argument");
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return fail(MRA_EINVAL, "enc_items * prompts exceeds int32");
+  const size_t need = mra_debug_shared_kv_workspace_bytes(enc_items, prompts, heads, kv, core);
+  if (need && (!workspace || workspace_bytes < need)) return fail(MRA_ENOMEM, "workspace too small: need " + std::to_string(need) + " bytes");
+  if (need && reinterpret_cast<uintptr_t>(workspace) % 16) return fail(MRA_EINVAL, "workspace must be 16-byte aligned");
+  AttnArgs a{};
+  a.Q = q; a.K = k; a.V = v; a.O = ctx;
+  a.q_item_stride = a.o_item_stride = (long long)32 * heads * 64; a.q_ld = a.o_ld = heads * 64;
+  a.k_item_stride = a.v_item_stride = (long long)heads * kv * 64; a.k_head_stride = a.v_head_stride = (long long)kv * 64; a.k_ld = a.v_ld = 64;
+  a.items = enc_items * prompts; a.heads = heads; a.q_rows = 32; a.kv_len = kv; a.scale = 0.125f;
+  a.nsplit = shared_kv_split(enc_items, prompts, heads, kv, core);
+  a.part = a.nsplit > 1 ? (float*)workspace : nullptr;
+  a.kv_share = prompts;
+  const int op = dtype == MRA_BF16 ? OP_BF16 : OP_F16;
+  const int rc = core == 1 ? launch_attention_shared(a, op, as_stream(stream)) : launch_attention(a, op, as_stream(stream));
+  return rc ? chk(rc, "shared K/V attention") : MRA_OK;
+}
+
 int mra_qformer_set_kv_events(mra_qformer* h, void* ev_start, void* ev_stop) {
   if (!h) return fail(MRA_EINVAL, "null handle");
   if ((ev_start == nullptr) != (ev_stop == nullptr)) return fail(MRA_EINVAL, "give both events or neither");
@@ -1154,6 +1246,11 @@ int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value) {
   if (key == "chain_ring") {
     if (value < 0 || value > 15) return fail(MRA_EINVAL, "chain_ring is a mask of bits 0-3");
     h->chain_ring = value;
+    return MRA_OK;
+  }
+  if (key == "multi_core") {
+    if (value < 0 || value > 1) return fail(MRA_EINVAL, "multi_core is 0 (attn_kernel with kv_share) or 1 (shared-stream core)");
+    h->multi_core = value;   // the workspace size of the multi forward follows it (grid-split partials)
     return MRA_OK;
   }
   return fail(MRA_ENAME, "unknown option: " + key);

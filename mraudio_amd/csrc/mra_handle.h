@@ -162,6 +162,12 @@ struct mra_qformer {
   int train_ring = 4;   // the same mask for the training forward / backward GEMMs (mra_qformer_set_option "train_ring"): bit 0 QKV, bit 2 every N = hidden
                         // GEMM whose epilogue the ring kernel has (projections with a residual, the data gradients).  Measured at B = 1 x T = 20 (r03x,
                         // one session): 14.6-15.2 ms per step with 0, 14.0-14.3 with 4, 14.2 with 5
+  // mra_qformer_forward_multi: the cross core that lets several prompts read one K/V stream (mra_qformer_set_option "multi_core"):
+  // 0 attn_kernel with AttnArgs::kv_share, 1 the shared-stream core (attn_shared_kernel).  The rule for the default: whichever the line of
+  // tools/bench_multi_query.py shows faster at P >= 4 on both of its shapes.  Measured (profiles/multi_query_line.json, one session): 1 at
+  // every P >= 4 -- 40 x Kv 257: 4.73 / 8.65 / 16.40 ms against 4.77 / 8.67 / 16.57 at P = 4 / 8 / 16; 32 x Kv 8224: 11.45 / 15.74 against
+  // 11.63 / 16.11 at P = 4 / 8 (0.2 - 2.3 %); at P = 2, where half of every workgroup idles, 0 is ahead (Kv 8224: 9.33 against 9.89 ms)
+  int multi_core = 1;
   int cross_precise = 0;
   float* wk32 = nullptr;
   char* arena_p = nullptr;

@@ -53,6 +53,44 @@ def run_inference(model, dataloader: Iterable[dict], output_file: Optional[str] 
     return records
 
 
+@torch.no_grad()
+def run_inference_grouped(model, dataloader: Iterable[dict], output_file: Optional[str] = None, with_saliency: bool = True,
+                          device=None, top_k: int = 1) -> List[dict]:
+    """``run_inference`` over ``VideoGroupedDataset`` batches: every video is encoded once and its queries are scored together
+    (``model.generate_multi*``).  Same record per query, written in the annotation file's original order."""
+    by_line = {}
+    for samples in dataloader:
+        samples = prepare_sample(samples, device)
+        queries = samples["text_input"]
+        scores = windows = None
+        if top_k > 1:
+            outputs, windows, scores = model.generate_multi_windows(samples, queries)
+            if not with_saliency:
+                scores = None
+        elif with_saliency:
+            outputs, scores = model.generate_multi_with_scores(samples, queries)
+        else:
+            outputs = model.generate_multi(samples, queries)
+        first = not by_line
+        for b, (lines, qids, qs, vid) in enumerate(zip(samples["index"], samples["qid"], samples["query"], samples["vid"])):
+            for k, (line, qid, query) in enumerate(zip(lines, qids, qs)):
+                raw = outputs[b][k]
+                pred = windows[b][k] if windows is not None else moment_str_to_list(post_process(raw))
+                rec = {"qid": qid, "query": query, "vid": vid, "pred_relevant_windows": pred, "raw_out": raw}
+                if scores is not None:
+                    rec["pred_saliency_scores"] = [float(x) for x in scores[b][k]]
+                by_line[int(line)] = rec
+        if first and hasattr(model, "cross_precision_report"):   # once, after the first batch
+            print(f"cross-attention precision: {format_cross_precision(model.cross_precision_report())}")
+    records = [by_line[i] for i in sorted(by_line)]
+    if output_file:
+        os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
+        with open(output_file, "w") as fh:
+            for rec in records:
+                fh.write(json.dumps(rec) + "\n")
+    return records
+
+
 def format_cross_precision(report: dict) -> str:
     """One line per model: for each modality the mode set, the precision in force and the probe's per-cross-layer median p_max."""
     parts = []
@@ -85,6 +123,9 @@ def build_parser() -> argparse.ArgumentParser:
                                                          "(top windows by summed excess over the span threshold under temporal NMS); 1 = the single span")
     ap.add_argument("--nms-thd", type=float, default=0.25, help="temporal IoU above which a proposal is suppressed by a higher-ranked one, in [0, 1)")
     ap.add_argument("--max-window", type=int, default=0, help="longest proposal in clips (0 = no cap)")
+    ap.add_argument("--group-by-video", action="store_true",
+                    help="encode every video once and score its queries together over one shared K/V cache (same records, annotation order)")
+    ap.add_argument("--max-queries-per-call", type=int, default=16, help="with --group-by-video: most queries of one video scored in one call")
     return ap
 
 
@@ -92,7 +133,7 @@ def main(argv=None) -> None:
     from torch.utils.data import DataLoader
 
     from .models.xinstructblip import XInstructBLIP
-    from .utils.mr_dataset import MRDataset, SyntheticMRDataset, collate_fn
+    from .utils.mr_dataset import MRDataset, SyntheticMRDataset, VideoGroupedDataset, collate_fn, collate_grouped
 
     args = build_parser().parse_args(argv)
     n_frms = 60 if args.dataset == "QVH" else 20
@@ -103,8 +144,13 @@ def main(argv=None) -> None:
         ds = SyntheticMRDataset(args.synthetic, T=n_frms)
     else:
         ds = MRDataset(args.video_folder, args.annotation_file, None, None, model=args.model, embeds_root=args.embeds_folder)
-    dl = DataLoader(ds, shuffle=False, batch_size=args.batch_size, num_workers=args.num_workers, collate_fn=collate_fn)
-    recs = run_inference(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k)
+    if args.group_by_video:
+        dl = DataLoader(VideoGroupedDataset(ds, args.max_queries_per_call), shuffle=False, batch_size=args.batch_size, num_workers=args.num_workers,
+                        collate_fn=collate_grouped)
+        recs = run_inference_grouped(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k)
+    else:
+        dl = DataLoader(ds, shuffle=False, batch_size=args.batch_size, num_workers=args.num_workers, collate_fn=collate_fn)
+        recs = run_inference(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k)
     print(f"wrote {len(recs)} predictions to {args.output_file}")
 
 

@@ -36,6 +36,7 @@ from torch.nn.modules.module import _IncompatibleKeys
 from .. import parallel, scorer
 from .._lib import MraError
 from ..qformer import QFormer, QFormerConfig, draw_seeded
+from ..utils.mr_dataset import bpt_index, pad_queries
 
 
 class HashTokenizer:
@@ -606,6 +607,154 @@ class XInstructBLIP(nn.Module):
         win, sc, cnt = out["windows"].cpu(), out["window_scores"].cpu(), out["window_counts"].cpu()
         saliency = out["fused"].view(out["bs"], out["num"]).float().cpu().tolist()
         return scorer.windows_to_text(win, cnt, ts), scorer.windows_to_records(win, sc, cnt, ts), saliency
+
+    # ---- several queries per video over one shared K/V cache ---------------------------------------------------
+    def _multi_pack(self, flat: Dict[str, object], logit: Dict[str, torch.Tensor], bs: int, num: int, P: int, counts: Sequence[int]) -> Dict[str, object]:
+        """Per-video views of the (b, p, t)-ordered results of ``bs * P`` scored rows, the padded prompt slots dropped."""
+        out: Dict[str, object] = {"bs": bs, "num": num, "counts": list(counts)}
+        out["fused"] = [flat["fused"].view(bs, P, num)[b, :c] for b, c in enumerate(counts)]
+        out["spans"] = [flat["spans"].view(bs, P, 2)[b, :c] for b, c in enumerate(counts)]
+        out["logit"] = {m: [x.view(bs, P, num)[b, :c] for b, c in enumerate(counts)] for m, x in logit.items()}
+        if "windows" in flat:
+            k = self.top_k
+            out["windows"] = [flat["windows"].view(bs, P, k, 2)[b, :c] for b, c in enumerate(counts)]
+            out["window_scores"] = [flat["window_scores"].view(bs, P, k)[b, :c] for b, c in enumerate(counts)]
+            out["window_counts"] = [flat["window_counts"].view(bs, P)[b, :c] for b, c in enumerate(counts)]
+        return out
+
+    def _multi_op_chain(self, qf: QFormer, ids_one: torch.Tensor, att_one: torch.Tensor, enc_one: torch.Tensor) -> bool:
+        """Whether ``qf`` runs the operand-dtype score chain (what ``forward_multi`` needs).  Automatic precision that has not been
+        resolved yet is resolved here, once, by an ordinary forward on one video and one query."""
+        mode = getattr(qf, "_cross_precision", "op")
+        if mode == "auto" and qf.cross_precision_report()["resolved"] is None:
+            qf.forward_fused(ids_one, att_one, enc_one, want_query=True)
+        return mode == "op" or (mode == "auto" and qf.cross_precision_report()["resolved"] == "op")
+
+    @torch.no_grad()
+    def encode_fuse_multi(self, samples, queries: Sequence[Sequence[str]]) -> Dict[str, object]:
+        """``encode_fuse`` for several queries per video: ``queries[b]`` is the list of prompts of video ``b`` (ragged counts are
+        padded to the largest count ``P`` by repeating the last prompt, and the padded results are dropped).  The encoders and the
+        modality LayerNorm run once per video; each modality Q-Former runs ``forward_multi`` -- ``P`` prompts per position over
+        ONE K/V projection -- on its own stream as in ``fuse_score``.  Prompts are always aligned to their own video: the
+        reference's ``ids.repeat(num, 1)`` row order (``compat_repeat``) does not exist on this path.
+
+        Returns ``fused`` (per video ``[P_b, T]``), ``spans`` (``[P_b, 2]``), with ``top_k > 1`` ``windows`` / ``window_scores`` /
+        ``window_counts``, and ``logit[m]`` (per video ``[P_b, T]``).  One query per video for the whole call is ``encode_fuse`` itself
+        (aligned prompts, the handle's cross mode).  Where split precision is in force (set, or resolved by the automatic mode) the
+        modality falls back to one ordinary forward per prompt slot, with a warning.  Not sharded: a process group of more than one
+        rank raises ``MraError``."""
+        ranks = self._clip_world()[1]
+        if ranks == 1 and callable(getattr(self.process_group, "size", None)):   # (a group handed over before torch.distributed is up)
+            ranks = int(self.process_group.size())
+        if ranks > 1:
+            raise MraError("encode_fuse_multi is not sharded over a process group: run it on one rank")
+        queries = [list(q) for q in queries]
+        if not queries or any(len(q) == 0 for q in queries):
+            raise MraError("encode_fuse_multi: every video needs at least one query")
+        padded, counts = pad_queries(queries)
+        P = max(counts)
+        if P == 1:
+            one = dict(samples)
+            one["text_input"] = [q[0] for q in queries]
+            keep, self.compat_repeat = self.compat_repeat, False
+            try:
+                res = self.encode_fuse(one)
+            finally:
+                self.compat_repeat = keep
+            if res["bs"] != len(queries):
+                raise MraError(f"encode_fuse_multi: {len(queries)} query lists for {res['bs']} videos")
+            return self._multi_pack(res, res["logit"], res["bs"], res["num"], 1, counts)
+        text = self.tokenizer([t for q in padded for t in q], padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
+        ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)      # [B * P, L], row b * P + p
+        embeds = {}
+        bs = num = None
+        for m in self.modalities:
+            if self._present(samples, m):
+                embeds[m], _, bs, num = self._encode(samples, m)
+        if bs is None:
+            raise MraError("samples holds none of the model's modalities")
+        if bs != len(queries):
+            raise MraError(f"encode_fuse_multi: {len(queries)} query lists for {bs} videos")
+        self._sync()
+        L = int(ids.shape[1])
+        # chain row (b * T + t) * P + p carries prompt p of video b
+        ids_n = ids.view(bs, 1, P, L).expand(bs, num, P, L).reshape(bs * num * P, L)
+        tm_n = tmask.view(bs, 1, P, L).expand(bs, num, P, L).reshape(bs * num * P, L)
+        att = torch.cat([torch.ones(bs * num * P, self.num_query_token, dtype=torch.long, device=self._device), tm_n], dim=1)
+        cur = torch.cuda.current_stream(self._device)
+        live = [m for m in self.modalities if m in embeds]
+        use_streams = self.overlap_modalities and len(live) > 1
+        logit: Dict[str, torch.Tensor] = {}
+        used = []
+        for m in live:
+            qf: QFormer = getattr(self, f"{m}_Qformer")
+            side = self._side_stream(m) if use_streams else cur
+            if use_streams:
+                used.append(side)
+                side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                enc = qf.modality_ln(embeds[m].to(self._device))
+                if self._multi_op_chain(qf, ids_n[0:num * P:P], att[0:num * P:P], enc[:num]):
+                    res = qf.forward_multi(ids_n, att, enc, P, want_query=True, want_cls=True)
+                    z, cls = res["query"], res["cls"]
+                else:
+                    if not getattr(self, "_multi_split_warned", False):
+                        logging.warning("encode_fuse_multi: split precision is in force for %s -- one ordinary forward per prompt slot, "
+                                        "no shared K/V cache", m)
+                        self._multi_split_warned = True
+                    per = [qf.forward_fused(ids_n[p::P], att[p::P], enc, want_query=True, want_cls=True) for p in range(P)]
+                    z = torch.stack([r["query"] for r in per], dim=1).reshape(bs * num * P, self.num_query_token, -1)
+                    cls = torch.stack([r["cls"] for r in per], dim=1).reshape(bs * num * P, -1)
+                _, lg = scorer.cosine_scores(z, cls, want_sim=False)
+                # (b, t, p) -> (b, p, t): the scorer's heads then see bs * P "videos" of num positions
+                logit[m] = lg.index_select(0, bpt_index(bs, num, P).to(lg.device))
+                if use_streams:
+                    for t in (enc, z, cls, lg, logit[m]):
+                        t.record_stream(cur)
+        for side in used:
+            cur.wait_stream(side)
+        flat: Dict[str, object] = {"fused": scorer.fuse_logits([logit[m] for m in live], self.fuse_weights)}
+        flat["spans"] = scorer.spans_from_logits(flat["fused"], bs * P, num, self.score_alpha)
+        if self.top_k > 1:
+            flat["windows"], flat["window_scores"], flat["window_counts"] = scorer.windows_from_logits(
+                flat["fused"], bs * P, num, self.score_alpha, self.top_k, self.nms_thd, self.max_window)
+        return self._multi_pack(flat, logit, bs, num, P, counts)
+
+    def _multi_timestamps(self, samples, out) -> list:
+        ts = samples.get("timestamps")
+        if ts is None:
+            ts = [list(range(out["num"]))] * out["bs"]
+        return [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
+
+    @torch.no_grad()
+    def generate_multi(self, samples, queries: Sequence[Sequence[str]]) -> List[List[str]]:
+        """``generate`` for several queries per video (``encode_fuse_multi``): per video one ``"[[start, end]]"`` string per query."""
+        out = self.encode_fuse_multi(samples, queries)
+        ts = self._multi_timestamps(samples, out)
+        return [[o.strip() for o in scorer.spans_to_text(sp.cpu().tolist(), [t] * int(sp.shape[0]))] for sp, t in zip(out["spans"], ts)]
+
+    @torch.no_grad()
+    def generate_multi_with_scores(self, samples, queries: Sequence[Sequence[str]]):
+        """``generate_multi`` plus the fused per-position logits ``[B][P_b][T]`` the spans were cut from."""
+        out = self.encode_fuse_multi(samples, queries)
+        ts = self._multi_timestamps(samples, out)
+        texts = [[o.strip() for o in scorer.spans_to_text(sp.cpu().tolist(), [t] * int(sp.shape[0]))] for sp, t in zip(out["spans"], ts)]
+        return texts, [f.float().cpu().tolist() for f in out["fused"]]
+
+    @torch.no_grad()
+    def generate_multi_windows(self, samples, queries: Sequence[Sequence[str]]):
+        """``generate_windows`` for several queries per video (needs ``top_k > 1``): ``(texts, records, saliency)``, each ``[B][P_b]``."""
+        if self.top_k <= 1:
+            raise MraError("generate_multi_windows needs a model built with top_k > 1")
+        out = self.encode_fuse_multi(samples, queries)
+        ts = self._multi_timestamps(samples, out)
+        texts, records = [], []
+        for win, sc, cnt, t in zip(out["windows"], out["window_scores"], out["window_counts"], ts):
+            tt = [t] * int(win.shape[0])
+            win, sc, cnt = win.cpu(), sc.cpu(), cnt.cpu()
+            texts.append(scorer.windows_to_text(win, cnt, tt))
+            records.append(scorer.windows_to_records(win, sc, cnt, tt))
+        return texts, records, [f.float().cpu().tolist() for f in out["fused"]]
 
     # ---- row N2: the reference's own decode, for callers that attach a stock LLM ----------------------------
     def attach_llm(self, llm_model: nn.Module, llm_tokenizer, enumerate_inputs: bool = False, interleave_seconds: bool = True) -> None:

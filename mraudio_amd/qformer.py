@@ -344,6 +344,50 @@ class QFormer(nn.Module):
                     check(lib().mra_qformer_set_kv_events(self._handle, None, None), "set_kv_events")
         return out
 
+    def forward_multi(self, input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor], enc: torch.Tensor, prompts: int,
+                      want_query: bool = True, want_cls: bool = False) -> Dict[str, torch.Tensor]:
+        """``prompts`` prompts per encoder item over one shared K/V cache (``mra_qformer_forward_multi``).  enc [N, Kv, E] in the
+        operand dtype, given once per item; row ``i * prompts + p`` of ``input_ids`` [N * prompts, L] and ``attention_mask``
+        [N * prompts, 32 + L] is prompt slot ``p`` of item ``i``.  Returns ``query`` [N * prompts, 32, H] and / or ``cls``
+        [N * prompts, H] (fp32) in the same row order.  Always the K/V-cache form in operand precision (``MraError`` while split
+        precision is in force or automatic precision has not resolved to op); ``prompts == 1`` is ``forward_fused`` under
+        ``set_cross_mode("kv_cache")``.  The cross core follows ``set_option("multi_core", 0 / 1)``."""
+        self.sync_weights()
+        cfg = self.cfg
+        P = int(prompts)
+        if P < 1:
+            raise MraError(f"prompts must be >= 1, got {prompts}")
+        if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
+            raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
+        if enc.dtype != cfg.op_dtype:
+            enc = enc.to(cfg.op_dtype)
+        enc = enc.contiguous()
+        N, Kv = int(enc.shape[0]), int(enc.shape[1])
+        L = 0 if input_ids is None else int(input_ids.shape[1])
+        dev = enc.device
+        if input_ids is not None:
+            if input_ids.shape[0] != N * P:
+                raise MraError(f"input_ids has {input_ids.shape[0]} rows, encoder_hidden_states {N} x prompts {P}")
+            input_ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != (N * P, cfg.n_query + L):
+                raise MraError(f"attention_mask must be [{N * P}, {cfg.n_query + L}], got {tuple(attention_mask.shape)}")
+            attention_mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous()
+        if N == 0:
+            return {"query": torch.empty(0, cfg.n_query, cfg.hidden, device=dev), "cls": torch.empty(0, cfg.hidden, device=dev)}
+        out: Dict[str, torch.Tensor] = {}
+        if want_query:
+            out["query"] = torch.empty(N * P, cfg.n_query, cfg.hidden, dtype=torch.float32, device=dev)
+        if want_cls:
+            out["cls"] = torch.empty(N * P, cfg.hidden, dtype=torch.float32, device=dev)
+        with torch.cuda.device(self._device):
+            nbytes = (int(lib().mra_qformer_multi_workspace_bytes(self._handle, N, P, L, Kv)) + 255) // 256 * 256
+            ws = self._workspace(nbytes)
+            check(lib().mra_qformer_forward_multi(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, P, L, Kv,
+                                                  ptr(out.get("query")), ptr(out.get("cls")), ptr(ws), nbytes, current_stream()),
+                  "mra_qformer_forward_multi")
+        return out
+
     @staticmethod
     def forward_pair(qf0: "QFormer", qf1: "QFormer", input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor], enc0: torch.Tensor,
                      enc1: torch.Tensor, want_cls: bool = True, kv_events=None):

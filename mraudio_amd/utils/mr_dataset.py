@@ -15,7 +15,7 @@ from __future__ import annotations
 import inspect
 import json
 import os
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch.utils.data import Dataset
@@ -80,6 +80,19 @@ class SyntheticMRDataset(Dataset):
     def __len__(self) -> int:
         return self.n
 
+    @property
+    def annotation(self) -> List[dict]:
+        """The annotation lines ``MRDataset`` would hold for this corpus (one query per video), without the features."""
+        out = []
+        for i in range(self.n):
+            g = torch.Generator().manual_seed(self.seed * 100003 + i)
+            s = int(torch.randint(0, self.T - 2, (1,), generator=g))
+            e = min(self.T - 1, s + 1 + int(torch.randint(1, max(2, self.T // 3), (1,), generator=g)))
+            ts = [round(k * self.duration / self.T) for k in range(self.T)]
+            out.append({"qid": i, "query": f"synthetic event number {i}", "vid": f"syn{i}", "duration": self.duration,
+                        "relevant_windows": [[ts[s], ts[e]]]})
+        return out
+
     def __getitem__(self, i: int) -> Dict[str, object]:
         g = torch.Generator().manual_seed(self.seed * 100003 + i)
         step = self.duration / self.T
@@ -101,6 +114,87 @@ def collate_fn(batch: List[dict]) -> Dict[str, object]:
     """``utils/mr_dataset.py:113-119``: tensors are stacked, everything else stays a list."""
     return {k: (torch.stack([b[k] for b in batch], dim=0) if isinstance(batch[0][k], torch.Tensor) else [b[k] for b in batch])
             for k in batch[0]}
+
+
+# ---- several queries per video (XInstructBLIP.encode_fuse_multi) ------------------------------------------------
+GROUPED_KEYS = ("qid", "query", "text_input", "text_output")
+
+
+def group_by_video(annotation: Sequence[dict], max_queries: int = 16) -> List[List[int]]:
+    """The annotation lines grouped by ``vid``: one list of line indices per video, videos in order of first appearance, lines in
+    file order; a video with more than ``max_queries`` lines is cut into consecutive chunks of at most ``max_queries``."""
+    if max_queries < 1:
+        raise ValueError("max_queries must be >= 1")
+    by_vid: Dict[object, List[int]] = {}
+    for i, ann in enumerate(annotation):
+        by_vid.setdefault(ann["vid"], []).append(i)
+    return [idx[c: c + max_queries] for idx in by_vid.values() for c in range(0, len(idx), max_queries)]
+
+
+def pad_queries(queries: Sequence[Sequence[object]]) -> Tuple[List[List[object]], List[int]]:
+    """Ragged per-video lists -> (lists padded to the largest count by repeating each list's last entry, the original counts)."""
+    counts = [len(q) for q in queries]
+    if not counts or min(counts) < 1:
+        raise ValueError("every video needs at least one query")
+    width = max(counts)
+    return [list(q) + [q[-1]] * (width - len(q)) for q in queries], counts
+
+
+def drop_padding(rows: Sequence[Sequence[object]], counts: Sequence[int]) -> List[List[object]]:
+    """Inverse of ``pad_queries`` on per-slot results: the first ``counts[b]`` entries of row ``b``."""
+    return [list(r[:c]) for r, c in zip(rows, counts)]
+
+
+def restore_order(groups: Sequence[Sequence[int]], results: Sequence[Sequence[object]]) -> List[object]:
+    """Per-group results (``results[g][k]`` belongs to annotation line ``groups[g][k]``) back in the annotation file's order."""
+    n = sum(len(g) for g in groups)
+    out: List[object] = [None] * n
+    seen = 0
+    for g, r in zip(groups, results):
+        if len(g) != len(r):
+            raise ValueError(f"group of {len(g)} lines got {len(r)} results")
+        for i, x in zip(g, r):
+            out[i] = x
+            seen += 1
+    if seen != n or len(groups) != len(results):
+        raise ValueError("results do not cover the groups")
+    return out
+
+
+def bpt_index(bs: int, num: int, prompts: int) -> torch.Tensor:
+    """Gather index that brings rows ordered (video b, position t, prompt p) -- what ``forward_multi`` scores -- to (b, p, t), the
+    order in which the scorer's span / window heads see ``bs * prompts`` videos of ``num`` positions: ``out[j] = rows[index[j]]``."""
+    return torch.arange(bs * num * prompts).view(bs, num, prompts).permute(0, 2, 1).reshape(-1)
+
+
+class VideoGroupedDataset(Dataset):
+    """``base`` (an ``MRDataset``, or anything with its ``annotation`` list and records) regrouped so that one record is one video with
+    up to ``max_queries`` of its queries: the video is loaded ONCE per group, ``qid`` / ``query`` / ``text_input`` / ``text_output``
+    are lists, and ``index`` holds the annotation line numbers (``restore_order``)."""
+
+    def __init__(self, base: Dataset, max_queries: int = 16):
+        self.base, self.max_queries = base, int(max_queries)
+        self.annotation = list(base.annotation)
+        self.groups = group_by_video(self.annotation, self.max_queries)
+
+    def __len__(self) -> int:
+        return len(self.groups)
+
+    def __getitem__(self, g: int) -> Dict[str, object]:
+        idx = self.groups[g]
+        rec = dict(self.base[idx[0]])
+        anns = [self.annotation[i] for i in idx]
+        rec["qid"] = [a["qid"] for a in anns]
+        rec["query"] = [a["query"] for a in anns]
+        rec["text_input"] = [build_prompt(a["query"]) for a in anns]
+        rec["text_output"] = [str(a["relevant_windows"]) for a in anns]
+        rec["index"] = list(idx)
+        return rec
+
+
+def collate_grouped(batch: List[dict]) -> Dict[str, object]:
+    """``collate_fn`` for ``VideoGroupedDataset`` records: tensors are stacked, the per-query lists stay one list per video."""
+    return collate_fn(batch)
 
 
 def prepare_sample(samples: dict, device=None) -> dict:
