@@ -484,6 +484,47 @@ int mra_debug_beats_attention(mra_beats* h, int32_t layer, const void* qkv, cons
                               void* stream);
 int mra_debug_beats_posconv(mra_beats* h, float* x, int32_t n, int32_t tokens, void* stream);
 
+/* The Q-Former forward's own kernels, one launch each, through the launch functions the forward calls (tests/test_gpu_qformer_kernels.py).  No
+ * handle, no parameters, no allocation; buffers are device pointers in the kernels' own layouts.  Arguments are checked before any launch: a
+ * null pointer, a bad size or a misaligned buffer -> MRA_EINVAL; zero rows / items is a no-op that returns 0.  `dtype` is the operand dtype
+ * (MRA_F16 / MRA_BF16).  A row view is a HOST triple int64 {item_stride, rows per item, row stride} in elements (csrc/kernels.h RowView:
+ * logical row m lives at (m / rpi) * item_stride + (m % rpi) * stride).
+ *
+ * mra_debug_self_attention: the masked self-attention core of a layer, built by the forward's own argument builder for hidden = heads * 64.
+ *   qkv  [items][S][3 * heads * 64]  q | k | v rows as the QKV GEMM writes them; K and V are read in place
+ *   mask [items][S] int64 (1 = attend; additive (1 - m) * -10000) or NULL = all ones (the unmasked kernels)
+ *   ctx  [items][S][heads * 64]      lse [items][heads][S] fp32 log2-sum-exp2 of the scaled, masked scores, or NULL
+ * mra_debug_ln_rows: launch_ln_rows4.  params: HOST array of 8 device pointers gain1, bias1, .. gain4, bias4 (sets 2 - 4 may be NULL pairs);
+ *   rows >= lane_rows take sets (3, 4) for (1, 2); with a second set of the pair, rows with row % period >= split take it.  Either output
+ *   may be NULL (not both).
+ * mra_debug_embed_ln: launch_embed_ln.  query [1 or items][Q][H] with query_item_stride 0 or Q * H; ids outside [0, vocab) are clamped;
+ *   h32 / h16 [items][Q + L][H] both required, pre32 (the rows before the LayerNorm) optional.
+ * mra_debug_modality_ln: launch_modality_ln with explicit width and parameters (mra_modality_ln takes them from a handle, whose enc_width
+ *   is a multiple of 64; the kernel takes any multiple of 8 up to 4096).
+ * mra_debug_softmax_rows / _fold_rowfactor / _softmax_rescale / _transpose_pad: the folded cross-attention's helpers (csrc/kernels.h states
+ *   the layouts); hist [256] int32 or NULL selects the probe variants.
+ * mra_debug_split: kind 0 launch_split_rows (src_view, chunk, parts 2 / 3), 1 launch_split_weight (rows x C), 2 launch_split_key_weight
+ *   (rows = heads, C = enc_width); src_view, chunk and parts are read by kind 0 only. */
+int mra_debug_self_attention(const void* qkv, const int64_t* mask, int32_t dtype, int32_t items, int32_t S, int32_t heads, void* ctx, float* lse,
+                             void* stream);
+int mra_debug_ln_rows(const float* x, const int64_t* x_view, int32_t rows, int32_t H, const float* const* params, int32_t lane_rows, int32_t period,
+                      int32_t split, float eps, float* y32, const int64_t* y32_view, void* y16, const int64_t* y16_view, int32_t dtype, void* stream);
+int mra_debug_embed_ln(const int64_t* ids, int32_t items, int32_t L, int32_t Q, int32_t H, int32_t vocab, const float* query, int64_t query_item_stride,
+                       const float* word, const float* pos, const float* gain, const float* bias, float eps, float* h32, void* h16, float* pre32,
+                       int32_t dtype, void* stream);
+int mra_debug_modality_ln(const void* x, int32_t x_dtype, const int64_t* item_index, int32_t items, int32_t tokens, int32_t E, const float* gain,
+                          const float* bias, float eps, void* out, int32_t dtype, void* stream);
+int mra_debug_softmax_rows(const float* S, int64_t ld_s, void* P, int64_t ld_p, int32_t rows, int32_t kv, int32_t kvp, float scale, int32_t dtype,
+                           void* stream);
+int mra_debug_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int32_t rows, int32_t R, int32_t ntiles, void* P, int64_t ld_p,
+                             int32_t tile_cols, int32_t kvp, int32_t* hist, void* stream);
+int mra_debug_softmax_rescale(void* P, int64_t ld_p, const float* stat_m, const float* stat_l, int32_t rows, int32_t ntiles, int32_t tile_cols,
+                              int32_t kvp, int32_t dtype, int32_t* hist, void* stream);
+int mra_debug_transpose_pad(const void* src, void* dst, int32_t R, int32_t C, int32_t ld_d, int64_t src_bs, int64_t dst_bs, int32_t batch, int32_t dtype,
+                            void* stream);
+int mra_debug_split(int32_t kind, const float* src, const int64_t* src_view, int32_t rows, int32_t C, int32_t chunk, int32_t parts, void* dst,
+                    int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

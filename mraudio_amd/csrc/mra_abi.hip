@@ -1336,4 +1336,163 @@ int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, 
              "windows_from_logits");
 }
 
+// ---- the Q-Former forward's own kernels, one launch each (include/mra.h; tests/test_gpu_qformer_kernels.py) ----------------------------
+// Every entry checks its arguments before any launch, allocates nothing and calls the launch function the forward calls.
+namespace {
+bool dbg_op(int32_t dtype, int* op) {
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return false;
+  *op = dtype == MRA_BF16 ? OP_BF16 : OP_F16;
+  return true;
+}
+bool dbg_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+// a host triple (item_stride, rows per item, row stride) -> RowView; rows of 16-byte multiples
+bool dbg_view(const int64_t* v, RowView* out) {
+  if (!v || v[1] <= 0 || v[1] > 0x7fffffffLL || v[2] <= 0 || v[2] > 0x7fffffffLL || v[0] < 0 || (v[0] & 3) || (v[2] & 3)) return false;
+  *out = RowView{(long long)v[0], (int)v[1], (int)v[2]};
+  return true;
+}
+}  // namespace
+
+int mra_debug_self_attention(const void* qkv, const int64_t* mask, int32_t dtype, int32_t items, int32_t S, int32_t heads, void* ctx, float* lse,
+                             void* stream) {
+  int op;
+  if (items < 0 || S < 1 || heads < 1 || heads > 16) return fail(MRA_EINVAL, "sizes: items >= 0, S >= 1, heads in 1..16");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (items == 0) return MRA_OK;
+  if (!qkv || !ctx) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(qkv, 16) || !dbg_aligned(ctx, 16)) return fail(MRA_EINVAL, "qkv and ctx must be 16-byte aligned");
+  if ((long long)items * heads * ((S + 31) / 32) > 0x7fffffffLL / 4) return fail(MRA_EINVAL, "items * heads * query blocks exceeds int32");
+  mra_cfg c{};
+  c.hidden = heads * 64;
+  c.heads = heads;
+  return chk(launch_attention(self_attn_args(c, qkv, ctx, (const long long*)mask, items, S, lse), op, as_stream(stream)), "self attention");
+}
+
+int mra_debug_ln_rows(const float* x, const int64_t* x_view, int32_t rows, int32_t H, const float* const* params, int32_t lane_rows, int32_t period,
+                      int32_t split, float eps, float* y32, const int64_t* y32_view, void* y16, const int64_t* y16_view, int32_t dtype, void* stream) {
+  int op;
+  if (rows < 0) return fail(MRA_EINVAL, "negative rows");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (H <= 0 || H % 256 || H > 1024) return fail(MRA_EINVAL, "H must be a multiple of 256, <= 1024");
+  if (period <= 0 || split < 0 || lane_rows < 0) return fail(MRA_EINVAL, "period > 0, split >= 0, lane_rows >= 0");
+  if (rows == 0) return MRA_OK;
+  if (!x || !params || (!y32 && !y16)) return fail(MRA_EINVAL, "null argument");
+  RowView xv{}, y32v{0, 1, H}, y16v{0, 1, H};
+  if (!dbg_view(x_view, &xv) || (y32 && !dbg_view(y32_view, &y32v)) || (y16 && !dbg_view(y16_view, &y16v)))
+    return fail(MRA_EINVAL, "a row view is (item_stride >= 0, rows per item > 0, row stride > 0), strides multiples of 4");
+  if (xv.ld < H || y32v.ld < H || y16v.ld < H) return fail(MRA_EINVAL, "row stride below H");
+  if (!dbg_aligned(x, 16) || !dbg_aligned(y32, 16) || !dbg_aligned(y16, 8)) return fail(MRA_EINVAL, "misaligned buffer");
+  for (int s = 0; s < 4; ++s)
+    if ((params[2 * s] == nullptr) != (params[2 * s + 1] == nullptr)) return fail(MRA_EINVAL, "a parameter set is a (gain, bias) pair");
+  if (!params[0]) return fail(MRA_EINVAL, "parameter set 1 is required");
+  if (lane_rows < rows && !params[4]) return fail(MRA_EINVAL, "rows from lane_rows on need parameter set 3");
+  for (int s = 0; s < 8; ++s)
+    if (!dbg_aligned(params[s], 16)) return fail(MRA_EINVAL, "misaligned parameter");
+  return chk(launch_ln_rows4(x, xv, rows, H, params[0], params[1], params[2], params[3], lane_rows, params[4], params[5], params[6], params[7], period,
+                             split, eps, y32, y32v, y16, y16v, op, as_stream(stream)),
+             "ln_rows");
+}
+
+int mra_debug_embed_ln(const int64_t* ids, int32_t items, int32_t L, int32_t Q, int32_t H, int32_t vocab, const float* query, int64_t query_item_stride,
+                       const float* word, const float* pos, const float* gain, const float* bias, float eps, float* h32, void* h16, float* pre32,
+                       int32_t dtype, void* stream) {
+  int op;
+  if (items < 0 || L < 0 || Q < 0 || vocab < 1) return fail(MRA_EINVAL, "sizes: items, L, Q >= 0, vocab >= 1");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (H <= 0 || H % 256 || H > 1024) return fail(MRA_EINVAL, "H must be a multiple of 256, <= 1024");
+  if (query_item_stride < 0 || (query_item_stride & 3)) return fail(MRA_EINVAL, "query_item_stride must be 0 or a multiple of 4");
+  if (items == 0 || Q + L == 0) return MRA_OK;
+  if (!gain || !bias || !h32 || !h16 || (Q > 0 && !query) || (L > 0 && (!ids || !word || !pos))) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(query, 16) || !dbg_aligned(word, 16) || !dbg_aligned(pos, 16) || !dbg_aligned(gain, 16) || !dbg_aligned(bias, 16) ||
+      !dbg_aligned(h32, 16) || !dbg_aligned(h16, 8) || !dbg_aligned(pre32, 16))
+    return fail(MRA_EINVAL, "misaligned buffer");
+  return chk(launch_embed_ln((const long long*)ids, items, L, Q, H, vocab, query, query_item_stride, word, pos, gain, bias, eps, h32, h16, pre32, op,
+                             as_stream(stream)),
+             "embed_ln");
+}
+
+int mra_debug_modality_ln(const void* x, int32_t x_dtype, const int64_t* item_index, int32_t items, int32_t tokens, int32_t E, const float* gain,
+                          const float* bias, float eps, void* out, int32_t dtype, void* stream) {
+  int op;
+  if (items < 0 || tokens < 0) return fail(MRA_EINVAL, "negative size");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (x_dtype != MRA_F32 && x_dtype != MRA_F16 && x_dtype != MRA_BF16) return fail(MRA_EINVAL, "x_dtype must be f32, f16 or bf16");
+  if (E <= 0 || E % 8 || E > 4096) return fail(MRA_EINVAL, "E must be a multiple of 8, <= 4096");
+  if (items == 0 || tokens == 0) return MRA_OK;
+  if (!x || !gain || !bias || !out) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(x, 16) || !dbg_aligned(gain, 16) || !dbg_aligned(bias, 16) || !dbg_aligned(out, 16)) return fail(MRA_EINVAL, "misaligned buffer");
+  return chk(launch_modality_ln(x, x_dtype, (const long long*)item_index, items, tokens, E, gain, bias, eps, out, op, as_stream(stream)), "modality_ln");
+}
+
+int mra_debug_softmax_rows(const float* S, int64_t ld_s, void* P, int64_t ld_p, int32_t rows, int32_t kv, int32_t kvp, float scale, int32_t dtype,
+                           void* stream) {
+  int op;
+  if (rows < 0) return fail(MRA_EINVAL, "negative rows");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (kv <= 0 || kvp < kv || (kvp & 3) || ld_s < kv || ld_p < kvp || (ld_s & 3) || (ld_p & 3))
+    return fail(MRA_EINVAL, "need 0 < kv <= kvp <= ld_p, kv <= ld_s, and kvp, ld_s, ld_p multiples of 4");
+  if (rows == 0) return MRA_OK;
+  if (!S || !P) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(S, 16) || !dbg_aligned(P, 8)) return fail(MRA_EINVAL, "misaligned buffer");
+  return chk(launch_softmax_rows(S, ld_s, P, ld_p, rows, kv, kvp, scale, op, as_stream(stream)), "softmax_rows");
+}
+
+int mra_debug_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int32_t rows, int32_t R, int32_t ntiles, void* P, int64_t ld_p,
+                             int32_t tile_cols, int32_t kvp, int32_t* hist, void* stream) {
+  if (rows < 0) return fail(MRA_EINVAL, "negative rows");
+  if (ntiles <= 0 || tile_cols <= 0 || R <= 0 || R > 512 || rows % R) return fail(MRA_EINVAL, "need ntiles, tile_cols > 0, 0 < R <= 512, rows % R == 0");
+  if ((long long)ntiles * tile_cols > kvp || ld_p < kvp) return fail(MRA_EINVAL, "need ntiles * tile_cols <= kvp <= ld_p");
+  if (rows == 0) return MRA_OK;
+  if (!stat_m || !stat_l || !factors || !P) return fail(MRA_EINVAL, "null argument");
+  return chk(launch_fold_rowfactor(stat_m, stat_l, factors, rows, R, ntiles, P, ld_p, tile_cols, kvp, as_stream(stream), hist), "fold_rowfactor");
+}
+
+int mra_debug_softmax_rescale(void* P, int64_t ld_p, const float* stat_m, const float* stat_l, int32_t rows, int32_t ntiles, int32_t tile_cols,
+                              int32_t kvp, int32_t dtype, int32_t* hist, void* stream) {
+  int op;
+  if (rows < 0) return fail(MRA_EINVAL, "negative rows");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (ntiles <= 0 || ntiles > 128 || tile_cols <= 0 || (tile_cols & 7) || kvp <= 0 || (kvp & 7) || (ld_p & 7) || ld_p < kvp)
+    return fail(MRA_EINVAL, "need 0 < ntiles <= 128, and tile_cols, kvp, ld_p positive multiples of 8 with kvp <= ld_p");
+  if (rows == 0) return MRA_OK;
+  if (!P || !stat_m || !stat_l) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(P, 16)) return fail(MRA_EINVAL, "misaligned buffer");
+  return chk(launch_softmax_rescale(P, ld_p, stat_m, stat_l, rows, ntiles, tile_cols, kvp, op, as_stream(stream), hist), "softmax_rescale");
+}
+
+int mra_debug_transpose_pad(const void* src, void* dst, int32_t R, int32_t C, int32_t ld_d, int64_t src_bs, int64_t dst_bs, int32_t batch, int32_t dtype,
+                            void* stream) {
+  int op;
+  if (batch < 0 || R < 0 || C < 0) return fail(MRA_EINVAL, "negative size");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (ld_d < R || batch > 65535) return fail(MRA_EINVAL, "need R <= ld_d and batch <= 65535");
+  if (batch == 0 || R == 0 || C == 0) return MRA_OK;
+  if (!src || !dst) return fail(MRA_EINVAL, "null argument");
+  if (src_bs < (long long)R * C || dst_bs < (long long)C * ld_d) return fail(MRA_EINVAL, "batch stride smaller than the matrix");
+  // launch_transpose_pad takes its 64 x 64 kernel (16-byte accesses) from C and ld_d alone: the forward's strides and buffers always fit it
+  if (C % 8 == 0 && ld_d % 8 == 0 && C >= 64 && ld_d >= 64 && (src_bs % 8 || dst_bs % 8 || !dbg_aligned(src, 16) || !dbg_aligned(dst, 16)))
+    return fail(MRA_EINVAL, "C, ld_d multiples of 8 and >= 64 need 16-byte aligned buffers and batch strides that are multiples of 8");
+  return chk(launch_transpose_pad(src, dst, R, C, ld_d, src_bs, dst_bs, batch, op, as_stream(stream)), "transpose_pad");
+}
+
+int mra_debug_split(int32_t kind, const float* src, const int64_t* src_view, int32_t rows, int32_t C, int32_t chunk, int32_t parts, void* dst,
+                    int32_t dtype, void* stream) {
+  int op;
+  if (kind < 0 || kind > 2) return fail(MRA_EINVAL, "kind must be 0 (rows), 1 (weight) or 2 (key weight)");
+  if (rows < 0 || C <= 0) return fail(MRA_EINVAL, "sizes: rows >= 0, C > 0");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  RowView sv{0, 1, C};
+  if (kind == 0) {
+    if (chunk <= 0 || C % chunk || chunk % 4 || (parts != 2 && parts != 3)) return fail(MRA_EINVAL, "need chunk % 4 == 0, C % chunk == 0, parts 2 or 3");
+    if (!dbg_view(src_view, &sv) || sv.ld < C) return fail(MRA_EINVAL, "bad row view");
+  }
+  if (rows == 0) return MRA_OK;
+  if (!src || !dst) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(src, 16) || !dbg_aligned(dst, 8)) return fail(MRA_EINVAL, "misaligned buffer");
+  hipStream_t st = as_stream(stream);
+  if (kind == 0) return chk(launch_split_rows(src, sv, rows, C, chunk, parts, dst, op, st), "split_rows");
+  if (kind == 1) return chk(launch_split_weight(src, rows, C, dst, op, st), "split_weight");
+  return chk(launch_split_key_weight(src, rows, C, dst, op, st), "split_key_weight");
+}
+
 }  // extern "C"
