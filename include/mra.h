@@ -323,6 +323,34 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
                          int32_t items, int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls,
                          float* grads, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-query training step: `prompts` chain items per encoder item over ONE K/V cache, forward with a tape and backward.  Defined as one
+ * mra_qformer_forward_train / mra_qformer_backward pair on enc repeated `prompts` times per item (row i * prompts + p reads encoder item i),
+ * without the repetition:
+ *   input_ids      [enc_items * prompts, L]       int64   row i * prompts + p: encoder item i, prompt slot p; prompts differ freely per row
+ *   attention_mask [enc_items * prompts, 32 + L]  int64   same row order, or NULL (all ones)
+ *   enc            [enc_items, kv, E]             operand dtype, as mra_modality_ln writes it
+ *   out_query / d_out_query  [enc_items * prompts, 32, H]  fp32 (may be NULL)
+ *   out_cls / d_out_cls      [enc_items * prompts, H]      fp32 (may be NULL; needs L >= 1)
+ * The layer chain, its tape and its gradients run on enc_items * prompts items.  The K/V projection, the K/V cache, the dK / dV tape and
+ * the dW_k / dW_v weight gradients run on enc_items items: per cross layer and encoder item the projection and its weight gradient cost
+ * 4 Kv E 768 flops each (call it 1 each) -- 2 per encoder item here, 2 prompts on a repeated enc (arithmetic, not a measurement).  dK / dV
+ * of an encoder item are summed over its prompts in registers inside the attention backward, rounded once; no atomics.
+ * The cross core of the tape forward is the core of mra_qformer_forward_train with each chain item taking the K/V of item n / prompts, and
+ * writes the log-sum-exp the backward needs, whatever mra_qformer_set_option "multi_core" says: the shared-stream core writes none and is
+ * not used here.  Long KV splits by the rule of mra_qformer_forward_train on chain items.  Precision as mra_qformer_forward_train.
+ * Argument checks worded as mra_qformer_forward_multi (prompts >= 1, enc_items == 0 is a no-op); ownership, workspace lifetime and
+ * ADD-into-grads as mra_qformer_forward_train / mra_qformer_backward.  prompts == 1 is that pair launch for launch.  The attention
+ * backward keeps fp32 dQ / lse / delta of all prompts of an encoder item in LDS: prompts above 14 (at 32 query rows, 160 KB) -> MRA_EINVAL
+ * naming the limit; split the group.  Workspace: mra_qformer_multi_train_workspace_bytes (0 for a NULL handle or a non-positive size),
+ * 256-byte aligned. */
+size_t mra_qformer_multi_train_workspace_bytes(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv);
+int mra_qformer_forward_multi_train(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
+                                    int32_t enc_items, int32_t prompts, int32_t L, int32_t kv, float* out_query, float* out_cls,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int mra_qformer_backward_multi(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
+                               int32_t enc_items, int32_t prompts, int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls,
+                               float* grads, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- introspection for the bench ------------------------------------------------------------------
  * Algorithmic flop count of one mra_qformer_forward (2 flops per MAC; formula in DESIGN.md). */
 double mra_qformer_flops(mra_qformer* h, int32_t items, int32_t L, int32_t kv, int32_t with_last_text);
@@ -483,6 +511,15 @@ int mra_debug_shared_kv_attention(const void* q, const void* k, const void* v, i
 int mra_debug_beats_attention(mra_beats* h, int32_t layer, const void* qkv, const void* gate_src, int32_t n, int32_t tokens, void* ctx,
                               void* stream);
 int mra_debug_beats_posconv(mra_beats* h, float* x, int32_t n, int32_t tokens, void* stream);
+/* mra_debug_attention_bwd: the attention backward core on its own in the cross-attention layout of mra_qformer_backward(_multi), through
+ * launch_attn_bwd.  No handle, no parameters, no mask.  `share` chain items stand behind one K/V item (1: every item its own).
+ *   q, o, d_o, dq [kv_items * share][q_rows][heads * 64]  operand dtype (MRA_F16 / MRA_BF16): row block i * share + p = K/V item i, slot p
+ *   k, v, dk, dv  [kv_items][heads][kv][64]               operand dtype; dk / dv of item i are summed over its `share` slots
+ *   lse           [kv_items * share][heads][q_rows]       fp32 log2-sum-exp2 of the scaled scores (AttnArgs::lse)
+ * MRA_EINVAL with a message for a NULL pointer, a non-positive size, a dtype that is not f16 / bf16, and a share (or q_rows) whose fp32
+ * dQ / lse / delta areas pass 160 KB of LDS: share * ceil(q_rows / 32) <= 14. */
+int mra_debug_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, int32_t dtype,
+                            int32_t kv_items, int32_t share, int32_t heads, int32_t q_rows, int32_t kv, void* dq, void* dk, void* dv, void* stream);
 
 /* The Q-Former forward's own kernels, one launch each, through the launch functions the forward calls (tests/test_gpu_qformer_kernels.py).  No
  * handle, no parameters, no allocation; buffers are device pointers in the kernels' own layouts.  Arguments are checked before any launch: a

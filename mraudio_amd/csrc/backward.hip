@@ -288,6 +288,9 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(const AttnBwdArgs a) {
 // Both orientations of the score tile are computed (S = Q K^T with the token on the lane axis feeds dV and
 // dK, S^T = K Q^T with the query on the lane axis feeds dQ): 8 extra MFMAs per tile pair instead of a
 // transpose through LDS.  dQ partials of the four waves meet in an fp32 LDS tile through ds_add_f32.
+// Shared K/V (AttnBwdArgs::kv_share = P > 1): the workgroup is one (K/V item, head) and the walk covers the query blocks of its P chain items
+// one after the other -- block b is query block b % nqb of chain item kv_item * P + b / nqb, with that item's own Q / O / dO / dQ / lse --
+// while dK / dV stay in the owning wave's registers: the sum over the prompts of a clip is the same register accumulation, written once.
 namespace bwd {
 constexpr int TILE = 32 * 128;  // bytes of one [32][64] 16-bit tile
 
@@ -325,40 +328,45 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int head = blockIdx.x % a.heads, item = blockIdx.x / a.heads;
+  const int head = blockIdx.x % a.heads, item = blockIdx.x / a.heads;   // item: the K/V item
+  const int share = a.kv_share > 1 ? a.kv_share : 1;
   const int nqb = (a.q_rows + 31) / 32, nkb = (a.kv_len + 31) / 32;
+  const int nb = share * nqb;                 // query blocks this workgroup walks; LDS rows of block b: [32 b, 32 b + 32)
+  const int item0 = item * share;             // first chain item behind this K/V item
   const int h = lane >> 5, ln = lane & 31;
 
   char* Qs = smem_raw;                                   // shared Q tile
   char* dOs = Qs + bwd::TILE;                            // shared dO tile
   char* KVs = dOs + bwd::TILE;                           // per wave: K tile, V tile
-  float* dQs = reinterpret_cast<float*>(KVs + 4 * 2 * bwd::TILE);   // [nqb*32][64]
-  float* lse_s = dQs + nqb * 32 * 64;                    // [nqb*32]
-  float* delta_s = lse_s + nqb * 32;                     // [nqb*32]
-  float* mterm_s = delta_s + nqb * 32;                   // [4][32]
+  float* dQs = reinterpret_cast<float*>(KVs + 4 * 2 * bwd::TILE);   // [nb*32][64]
+  float* lse_s = dQs + nb * 32 * 64;                     // [nb*32]
+  float* delta_s = lse_s + nb * 32;                      // [nb*32]
+  float* mterm_s = delta_s + nb * 32;                    // [4][32]
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_raw;
   const unsigned q_tile = lds0, do_tile = lds0 + bwd::TILE;
   const unsigned k_tile = lds0 + 2 * bwd::TILE + wave * 2 * bwd::TILE, v_tile = k_tile + bwd::TILE;
   const char* Kw = KVs + wave * 2 * bwd::TILE;   // this wave's K tile, V tile behind it
   const char* Vw = Kw + bwd::TILE;
 
-  const T* Qg = (const T*)a.Q + (long long)item * a.q_item_stride + head * 64;
-  const T* dOg = (const T*)a.dO + (long long)item * a.o_item_stride + head * 64;
-  const T* Og = (const T*)a.O + (long long)item * a.o_item_stride + head * 64;
+  // Q / O / dO / dQ of chain item item0 (slot s of a shared K/V item: + s item strides)
+  const T* Qg = (const T*)a.Q + (long long)item0 * a.q_item_stride + head * 64;
+  const T* dOg = (const T*)a.dO + (long long)item0 * a.o_item_stride + head * 64;
+  const T* Og = (const T*)a.O + (long long)item0 * a.o_item_stride + head * 64;
   const T* Kg = (const T*)a.K + (long long)item * a.k_item_stride + (long long)head * a.k_head_stride;
   const T* Vg = (const T*)a.V + (long long)item * a.v_item_stride + (long long)head * a.v_head_stride;
-  T* dQg = (T*)a.dQ + (long long)item * a.dq_item_stride + head * 64;
+  T* dQg = (T*)a.dQ + (long long)item0 * a.dq_item_stride + head * 64;
   T* dKg = (T*)a.dK + (long long)item * a.dk_item_stride + (long long)head * a.dk_head_stride;
   T* dVg = (T*)a.dV + (long long)item * a.dv_item_stride + (long long)head * a.dv_head_stride;
 
-  for (int i = tid; i < nqb * 32 * 64; i += 256) dQs[i] = 0.f;
+  for (int i = tid; i < nb * 32 * 64; i += 256) dQs[i] = 0.f;
   // delta[q] = sum_d dO[q][d] O[q][d]: 8 lanes per row, 16 bytes each
-  for (int base = 0; base < nqb * 32; base += 32) {
-    const int q = base + (tid >> 3), c = tid & 7;
+  for (int b = 0; b < nb; ++b) {
+    const int slot = b / nqb, q = (b - slot * nqb) * 32 + (tid >> 3), c = tid & 7;
+    const int row = b * 32 + (tid >> 3);
     float sacc = 0.f;
     if (q < a.q_rows) {
-      const V8 o = *reinterpret_cast<const V8*>(Og + (long long)q * a.o_ld + c * 8);
-      const V8 g = *reinterpret_cast<const V8*>(dOg + (long long)q * a.o_ld + c * 8);
+      const V8 o = *reinterpret_cast<const V8*>(Og + slot * a.o_item_stride + (long long)q * a.o_ld + c * 8);
+      const V8 g = *reinterpret_cast<const V8*>(dOg + slot * a.o_item_stride + (long long)q * a.o_ld + c * 8);
 #pragma unroll
       for (int j = 0; j < 8; ++j) sacc += (float)o[j] * (float)g[j];
     }
@@ -366,8 +374,8 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
     sacc += __shfl_xor(sacc, 2);
     sacc += __shfl_xor(sacc, 4);
     if (c == 0) {
-      delta_s[q] = sacc;
-      lse_s[q] = q < a.q_rows ? a.lse[((long long)item * a.heads + head) * a.q_rows + q] : 0.f;
+      delta_s[row] = sacc;
+      lse_s[row] = q < a.q_rows ? a.lse[((long long)(item0 + slot) * a.heads + head) * a.q_rows + q] : 0.f;
     }
   }
   // transposed-read lane offsets for the two 32-column halves of a tile (gemm_tn.hip)
@@ -406,19 +414,19 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
     f32x16 accK[2], accV[2];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { accK[0][i] = 0.f; accK[1][i] = 0.f; accV[0][i] = 0.f; accV[1][i] = 0.f; }
-    for (int qb = 0; qb < nqb; ++qb) {
+    for (int b = 0; b < nb; ++b) {
+      const int slot = b / nqb, q0 = (b - slot * nqb) * 32, l0 = b * 32;   // chain item item0 + slot, its rows q0 .., LDS rows l0 ..
       __syncthreads();   // everyone is done with the previous Q / dO tiles
       {
         const int row = tid >> 3, sc = tid & 7;
-        const int q = min(qb * 32 + row, a.q_rows - 1);
+        const int q = min(q0 + row, a.q_rows - 1);
         const int src = (sc ^ (((row >> 1) & 1) << 2)) * 8;
-        glds16(Qg + (long long)q * a.q_ld + src, Qs + wave * 1024);
-        glds16(dOg + (long long)q * a.o_ld + src, dOs + wave * 1024);
+        glds16(Qg + slot * a.q_item_stride + (long long)q * a.q_ld + src, Qs + wave * 1024);
+        glds16(dOg + slot * a.o_item_stride + (long long)q * a.o_ld + src, dOs + wave * 1024);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (!active) continue;
-      const int q0 = qb * 32;
       // ---- token on the lane axis: S[q][t], dP[q][t] -> P, dS -> dV, dK ------------------------------
       f32x16 s, dp;
 #pragma unroll
@@ -434,10 +442,10 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
         V8 p8[2], ds8[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int ql = (r & 3) + 8 * (r >> 2) + 4 * h;
           float p = 0.f;
-          if (tok_ok && q < a.q_rows) p = __builtin_amdgcn_exp2f(s[r] * sl2 + mt - lse_s[q]);
-          const float d = p * (dp[r] - delta_s[q]) * a.scale;
+          if (tok_ok && q0 + ql < a.q_rows) p = __builtin_amdgcn_exp2f(s[r] * sl2 + mt - lse_s[l0 + ql]);
+          const float d = p * (dp[r] - delta_s[l0 + ql]) * a.scale;
           p8[r >> 3][r & 7] = from_f32<T>(p);
           ds8[r >> 3][r & 7] = from_f32<T>(d);
         }
@@ -461,9 +469,8 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
         dp = mfma32<T>(bwd::direct_frag<T>(Vw, lane, ks), bwd::direct_frag<T>(dOs, lane, ks), dp);
       }
       {
-        const int q = q0 + ln;
-        const bool q_ok = q < a.q_rows;
-        const float lq = lse_s[q], dq = delta_s[q];
+        const bool q_ok = q0 + ln < a.q_rows;
+        const float lq = lse_s[l0 + ln], dq = delta_s[l0 + ln];
         V8 ds8[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -482,7 +489,7 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
           accQ = mfma32<T>(ds8[0], b0, accQ);
           accQ = mfma32<T>(ds8[1], b1, accQ);
           // rows q (registers), column d = 32 ct + ln
-          float* dst = dQs + (size_t)q0 * 64 + 32 * ct + ln;
+          float* dst = dQs + (size_t)l0 * 64 + 32 * ct + ln;
 #pragma unroll
           for (int r = 0; r < 16; ++r) atomicAdd(dst + ((r & 3) + 8 * (r >> 2) + 4 * h) * 64, accQ[r]);
         }
@@ -502,12 +509,14 @@ __global__ void __launch_bounds__(256) attn_bwd_mfma_kernel(const AttnBwdArgs a)
     }
   }
   __syncthreads();
-  for (int i = tid; i < a.q_rows * 8; i += 256) {
-    const int q = i >> 3, c = (i & 7) * 8;
+  for (int i = tid; i < nb * 32 * 8; i += 256) {
+    const int row = i >> 3, c = (i & 7) * 8, b = row >> 5;
+    const int slot = b / nqb, q = (b - slot * nqb) * 32 + (row & 31);
+    if (q >= a.q_rows) continue;
     V8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(dQs[q * 64 + c + j]);
-    *reinterpret_cast<V8*>(dQg + (long long)q * a.dq_ld + c) = o;
+    for (int j = 0; j < 8; ++j) o[j] = from_f32<T>(dQs[row * 64 + c + j]);
+    *reinterpret_cast<V8*>(dQg + slot * a.dq_item_stride + (long long)q * a.dq_ld + c) = o;
   }
 }
 
@@ -734,8 +743,21 @@ void attn_bwd_force_valu(int on) { g_attn_bwd_valu = on; }
 constexpr int g_attn_bwd_valu = 0;   // the shipped library: the MFMA kernel, no switch
 #endif
 
+size_t attn_bwd_mfma_lds_bytes(int q_rows, int kv_share) {
+  const size_t nb = (size_t)(kv_share > 1 ? kv_share : 1) * ((q_rows + 31) / 32);
+  return 10 * (size_t)bwd::TILE + sizeof(float) * (nb * 32 * 64 + 2 * nb * 32 + 4 * 32);
+}
+
+int attn_bwd_max_share(int q_rows) {
+  int p = 1;
+  while (attn_bwd_mfma_lds_bytes(q_rows, p + 1) <= ATTN_BWD_LDS_LIMIT) ++p;
+  return attn_bwd_mfma_lds_bytes(q_rows, 1) <= ATTN_BWD_LDS_LIMIT ? p : 0;
+}
+
 int launch_attn_bwd(const AttnBwdArgs& a, int op_dtype, hipStream_t stream) {
   if (a.items <= 0 || a.heads <= 0 || a.q_rows <= 0 || a.kv_len <= 0 || !a.lse) return -1;
+  const int share = a.kv_share > 1 ? a.kv_share : 1;
+  if (share > 1 && (a.items % share || a.mask || g_attn_bwd_valu)) return -1;   // one K/V item behind several chain items: MFMA kernel, no mask
   if (g_attn_bwd_valu) {
     const size_t lds = attn_bwd_lds_bytes(a.q_rows);
     if (lds > 160 * 1024) return -1;
@@ -747,12 +769,11 @@ int launch_attn_bwd(const AttnBwdArgs& a, int op_dtype, hipStream_t stream) {
   // 16-byte operand rows: every leading dimension / stride a multiple of 8 elements
   if ((a.q_ld | a.o_ld | a.dq_ld | a.k_ld | a.v_ld) & 7) return -1;
   if ((a.q_item_stride | a.o_item_stride | a.dq_item_stride | a.k_item_stride | a.k_head_stride | a.v_item_stride | a.v_head_stride) & 7) return -1;
-  const int nqb = (a.q_rows + 31) / 32;
-  const size_t lds = 10 * (size_t)bwd::TILE + sizeof(float) * ((size_t)nqb * 32 * 64 + 2 * nqb * 32 + 4 * 32);
-  if (lds > 160 * 1024) return -1;
+  const size_t lds = attn_bwd_mfma_lds_bytes(a.q_rows, share);
+  if (lds > ATTN_BWD_LDS_LIMIT) return -1;
   void (*kfn)(const AttnBwdArgs) = op_dtype == OP_F16 ? attn_bwd_mfma_kernel<f16> : attn_bwd_mfma_kernel<bf16>;
   if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -3;
-  hipLaunchKernelGGL(kfn, dim3(a.items * a.heads), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(kfn, dim3(a.items / share * a.heads), dim3(256), lds, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -238,8 +238,16 @@ struct AttnBwdArgs {
   const float* lse;                 // [item][head][q_rows] from the forward
   int items, heads, q_rows, kv_len;
   float scale;
+  // several chain items behind one K/V item (mra_qformer_backward_multi): with kv_share = P > 1, `items` counts chain items (a multiple of P),
+  // chain items n P .. n P + P - 1 read K / V item n and their dK / dV are summed into dK / dV item n; Q, O, dO, dQ, lse per chain item; no mask.
+  // 0 or 1: every item its own K / V.
+  int kv_share;
 };
 int launch_attn_bwd(const AttnBwdArgs& a, int op_dtype, hipStream_t stream);
+// LDS of the backward core: the fp32 dQ / lse / delta areas grow with kv_share * ceil(q_rows / 32) query blocks; launch_attn_bwd refuses (-1) past the limit
+constexpr size_t ATTN_BWD_LDS_LIMIT = 160 * 1024;
+size_t attn_bwd_mfma_lds_bytes(int q_rows, int kv_share);
+int attn_bwd_max_share(int q_rows);   // largest kv_share the LDS holds at q_rows (14 at q_rows <= 32); 0: q_rows itself is too long
 #ifdef MRA_GEMM_EXPERIMENTS
 void attn_bwd_force_valu(int on);   // A/B switch (experiment library only): the first (fp32 VALU) kernel instead of the MFMA one
 #endif

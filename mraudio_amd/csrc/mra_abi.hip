@@ -1139,6 +1139,30 @@ int mra_debug_shared_kv_attention(const void* q, const void* k, const void* v, i
   return rc ? chk(rc, "shared K/V attention") : MRA_OK;
 }
 
+// The attention backward core on its own, in the cross-attention layout mra_qformer_backward gives it (compact query-side rows, head-major K/V).
+int mra_debug_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, int32_t dtype,
+                            int32_t kv_items, int32_t share, int32_t heads, int32_t q_rows, int32_t kv, void* dq, void* dk, void* dv, void* stream) {
+  if (kv_items < 1 || share < 1 || heads < 1 || q_rows < 1 || kv < 1) return fail(MRA_EINVAL, "sizes: kv_items / share / heads / q_rows / kv >= 1");
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (!q || !k || !v || !o || !d_o || !lse || !dq || !dk || !dv) return fail(MRA_EINVAL, "null argument");
+  if ((long long)kv_items * share > 0x7fffffffLL) return fail(MRA_EINVAL, "kv_items * share exceeds int32");
+  const int limit = attn_bwd_max_share(q_rows);
+  if (share > limit)
+    return fail(MRA_EINVAL, "share " + std::to_string(share) + " exceeds " + std::to_string(limit) + ", what the backward core's LDS holds at " +
+                                std::to_string(q_rows) + " query rows");
+  AttnBwdArgs g{};
+  g.Q = q; g.K = k; g.V = v; g.O = o; g.dO = d_o; g.dQ = dq; g.dK = dk; g.dV = dv;
+  const int H = heads * 64;
+  g.q_item_stride = g.o_item_stride = g.dq_item_stride = (long long)q_rows * H; g.q_ld = g.o_ld = g.dq_ld = H;
+  g.k_item_stride = g.v_item_stride = g.dk_item_stride = g.dv_item_stride = (long long)heads * kv * 64;
+  g.k_head_stride = g.v_head_stride = g.dk_head_stride = g.dv_head_stride = (long long)kv * 64;
+  g.k_ld = g.v_ld = g.dk_ld = g.dv_ld = 64;
+  g.lse = lse; g.items = kv_items * share; g.heads = heads; g.q_rows = q_rows; g.kv_len = kv; g.scale = 0.125f;
+  g.kv_share = share;
+  const int rc = launch_attn_bwd(g, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream));
+  return rc ? chk(rc, "attention backward") : MRA_OK;
+}
+
 int mra_qformer_set_kv_events(mra_qformer* h, void* ev_start, void* ev_stop) {
   if (!h) return fail(MRA_EINVAL, "null handle");
   if ((ev_start == nullptr) != (ev_stop == nullptr)) return fail(MRA_EINVAL, "give both events or neither");

@@ -38,9 +38,12 @@ struct TrainBufs {
   size_t bytes;
 };
 
-TrainBufs layout_train(const mra_qformer* h, char* base, int N, int L, int Kv) {
+// N chain items; `share` of them (the prompts of a clip, mra_qformer_forward_multi_train) stand behind one encoder item: the K/V cache and its
+// gradient hold N / share items, everything else N.  share = 1: every item its own (mra_qformer_forward_train).
+TrainBufs layout_train(const mra_qformer* h, char* base, int N, int L, int Kv, int share) {
   const mra_cfg& c = h->cfg;
   const size_t H = c.hidden, I = c.inter, S = c.n_query + L, Q = c.n_query, heads = c.heads;
+  const size_t Ne = N / share;
   Carver cv(base);
   TrainBufs t;
   t.layer.resize(c.layers);
@@ -72,7 +75,7 @@ TrainBufs layout_train(const mra_qformer* h, char* base, int N, int L, int Kv) {
   t.emb_pre = cv.take<float>(N * S * H);
   t.out32 = cv.take<float>(N * S * H);
   t.out16 = cv.take<char>(N * S * H, 2);
-  t.kv16 = cv.take<char>((size_t)h->ncross * 2 * N * Kv * H, 2);
+  t.kv16 = cv.take<char>((size_t)h->ncross * 2 * Ne * Kv * H, 2);
   t.nsplit = attn_pick_split(N, c.heads, (int)Q, Kv);
   t.part = cv.take<float>(attn_partial_bytes(N, c.heads, (int)Q, t.nsplit) / 4 + 64);
   t.dhA = cv.take<float>(N * S * H);
@@ -88,7 +91,7 @@ TrainBufs layout_train(const mra_qformer* h, char* base, int N, int L, int Kv) {
   t.dpre2_16 = cv.take<char>(N * Q * H, 2);
   t.dcctx16 = cv.take<char>(N * Q * H, 2);
   t.dqc16 = cv.take<char>(N * Q * H, 2);
-  t.dkv16 = cv.take<char>((size_t)h->ncross * 2 * N * Kv * H, 2);
+  t.dkv16 = cv.take<char>((size_t)h->ncross * 2 * Ne * Kv * H, 2);
   t.bytes = cv.off;
   return t;
 }
@@ -324,23 +327,21 @@ int mra_qformer_enable_training(mra_qformer* h, void* stream) {
 
 size_t mra_qformer_train_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
   if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
-  return layout_train(h, nullptr, items, L, kv).bytes;
+  return layout_train(h, nullptr, items, L, kv, 1).bytes;
 }
 
-int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
-                              int32_t items, int32_t L, int32_t kv, float* out_query, float* out_cls, void* workspace,
-                              size_t workspace_bytes, void* stream_) {
-  if (!h) return fail(MRA_EINVAL, "null handle");
-  if (items <= 0 || L < 0 || kv <= 0) return fail(MRA_EINVAL, "bad sizes");
+}  // extern "C"
+
+namespace {
+// The tape forward over N chain items, `share` per encoder item (arguments checked by the two entries).  share = 1 is
+// mra_qformer_forward_train launch for launch; share > 1 projects K/V on N / share encoder items and lets chain item n read item n / share.
+int forward_train_body(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int N, int share, int L, int kv,
+                       float* out_query, float* out_cls, void* workspace, hipStream_t stream) {
   const mra_cfg& c = h->cfg;
-  if (L > c.max_pos || !enc || (L > 0 && !input_ids) || (out_cls && L < 1)) return fail(MRA_EINVAL, "bad arguments");
-  if (!workspace || workspace_bytes < mra_qformer_train_workspace_bytes(h, items, L, kv) || reinterpret_cast<uintptr_t>(workspace) % 256)
-    return fail(MRA_ENOMEM, "training workspace too small or misaligned");
-  hipStream_t stream = as_stream(stream_);
-  const int N = items, Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter;
+  const int Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter;
   const Ctx X{h, stream, h->op(), stream, {}};
   const int op = X.op;
-  TrainBufs t = layout_train(h, (char*)workspace, N, L, kv);
+  TrainBufs t = layout_train(h, (char*)workspace, N, L, kv, share);
   const long long SH = (long long)S * H;
   const RowView all_rows = plain(N * S, H), q_view = items_view(SH, Q, H), t_view = items_view(SH, L > 0 ? L : 1, H);
   const RowView qc_rows = plain(N * Q, H);
@@ -348,7 +349,7 @@ int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const in
   int rc = launch_embed_ln((const long long*)input_ids, N, L, Q, H, c.vocab, h->query, 0, h->word, h->pos, h->embg, h->embb, c.ln_eps,
                            t.layer[0].hin32, t.layer[0].hin16, t.emb_pre, op, stream);
   if (rc) return chk(rc, "embed_ln");
-  if (h->ncross > 0 && (rc = kv_project(h, enc, N, kv, t.kv16, stream))) return chk(rc, "kv projection");
+  if (h->ncross > 0 && (rc = kv_project(h, enc, N / share, kv, t.kv16, stream))) return chk(rc, "kv projection");
   for (int i = 0; i < c.layers; ++i) {
     const LayerW& W = h->layers[i];
     LayerBuf& b = t.layer[i];
@@ -364,8 +365,11 @@ int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const in
     const void* fq16 = b.h1_16; const float* fq32 = b.h1_32; RowView fqv = q_view;
     if (W.cross_index >= 0) {
       if ((rc = X.gemm(b.h1_16, q_view, W.wcq, W.bcq, b.qc16, qc_rows, nullptr, qc_rows, N * Q, H, H, EPI_OP))) return chk(rc, "cross q gemm");
-      if ((rc = launch_attention(kv_cross_attn_args(c, b.qc16, t.kv16, W.cross_index, b.cctx16, N, kv, t.nsplit, t.part, b.lse_c), op, stream)))
-        return chk(rc, "cross attention");
+      // the cache holds N / share encoder items; chain item n reads the K/V of item n / share (attn_kernel with kv_share: it writes lse)
+      AttnArgs ca = kv_cross_attn_args(c, b.qc16, t.kv16, W.cross_index, b.cctx16, N / share, kv, t.nsplit, t.part, b.lse_c);
+      ca.items = N;
+      ca.kv_share = share;
+      if ((rc = launch_attention(ca, op, stream))) return chk(rc, "cross attention");
       if ((rc = X.gemm(b.cctx16, qc_rows, W.wco, W.bco, b.pre2, qc_rows, b.h1_32, q_view, N * Q, H, H, EPI_RES_F32))) return chk(rc, "cross out gemm");
       if ((rc = launch_ln_rows(b.pre2, qc_rows, N * Q, H, W.lncg, W.lncb, c.ln_eps, b.hc32, qc_rows, b.hc16, qc_rows, op, stream))) return chk(rc, "cross ln");
       fq16 = b.hc16; fq32 = b.hc32; fqv = qc_rows;
@@ -388,18 +392,12 @@ int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const in
   return MRA_OK;
 }
 
-int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int32_t items,
-                         int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls, float* grads, void* workspace,
-                         size_t workspace_bytes, void* stream_) {
-  if (!h) return fail(MRA_EINVAL, "null handle");
-  if (items <= 0 || L < 0 || kv <= 0 || !grads || !enc) return fail(MRA_EINVAL, "bad arguments");
-  if (!d_out_query && !d_out_cls) return fail(MRA_EINVAL, "no upstream gradient");
-  if (!h->arena_t || h->transposes_stale) return fail(MRA_ESTATE, "call mra_qformer_enable_training after the last weight upload");
-  if (!workspace || workspace_bytes < mra_qformer_train_workspace_bytes(h, items, L, kv)) return fail(MRA_ENOMEM, "training workspace too small");
+// The backward over the tape of forward_train_body (arguments checked by the two entries).  share > 1: dK / dV of an encoder item are summed
+// over its prompts inside the attention backward (AttnBwdArgs::kv_share), and dW_k / dW_v run once per encoder item.
+int backward_body(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int N, int share, int L, int kv,
+                  const float* d_out_query, const float* d_out_cls, float* grads, void* workspace, hipStream_t stream) {
   const mra_cfg& c = h->cfg;
-  hipStream_t stream = as_stream(stream_);
-  const int N = items, Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter;
-  if (!h->wg_stream) return fail(MRA_ESTATE, "call mra_qformer_enable_training first");
+  const int Q = c.n_query, S = Q + L, H = c.hidden, I = c.inter, Ne = N / share;
   // Weight gradients are off the critical path (nothing in this call reads them): they run on the handle's side stream beside
   // the data-gradient chain.  fork(): the side stream waits for everything issued on `stream` so far (the dY it is about to
   // read); done(): an event on the side stream that `stream` waits for before it overwrites a scratch tensor those GEMMs read;
@@ -425,7 +423,7 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
   auto wait_for = [&](hipEvent_t e) { note(hipStreamWaitEvent(stream, e, 0)); };
   auto body = [&]() -> int {
   hipEvent_t ffn_done = nullptr, attn_done = nullptr;   // weight gradients of the previously processed layer
-  TrainBufs t = layout_train(h, (char*)workspace, N, L, kv);
+  TrainBufs t = layout_train(h, (char*)workspace, N, L, kv, share);
   const long long SH = (long long)S * H;
   const RowView all_rows = plain(N * S, H), q_view = items_view(SH, Q, H), t_view = items_view(SH, L > 0 ? L : 1, H);
   const RowView qc_rows = plain(N * Q, H);
@@ -437,7 +435,7 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
   HIP_TRY(hipMemsetAsync(dh, 0, (size_t)N * S * H * 4, stream));
   if (d_out_query && (rc = launch_copy_rows_f32(d_out_query, qc_rows, dh, q_view, N * Q, H, stream))) return chk(rc, "seed dq");
   if (d_out_cls && (rc = launch_copy_rows_f32(d_out_cls, plain(N, H), dh + t32, items_view(SH, 1, H), N, H, stream))) return chk(rc, "seed dcls");
-  if (h->ncross > 0) HIP_TRY(hipMemsetAsync(t.dkv16, 0, (size_t)h->ncross * 2 * N * kv * H * 2, stream));
+  if (h->ncross > 0) HIP_TRY(hipMemsetAsync(t.dkv16, 0, (size_t)h->ncross * 2 * Ne * kv * H * 2, stream));
   auto G = [&](const std::string& n) { return gptr(h, grads, n); };
 
   for (int i = c.layers - 1; i >= 0; --i) {
@@ -490,7 +488,7 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
       if ((rc = launch_ln_bwd(a, H, op, stream))) return chk(rc, "cross ln bwd");
       if ((rc = X.gemm(t.dpre2_16, qc_rows, W.wcoT, nullptr, t.dcctx16, qc_rows, nullptr, qc_rows, N * Q, H, H, EPI_OP))) return chk(rc, "d_cctx");
       AttnBwdArgs g{};
-      const size_t per_sel = (size_t)N * c.heads * kv * 64;
+      const size_t per_sel = (size_t)Ne * c.heads * kv * 64;
       g.Q = b.qc16; g.K = t.kv16 + (size_t)(W.cross_index * 2) * per_sel * 2; g.V = t.kv16 + (size_t)(W.cross_index * 2 + 1) * per_sel * 2;
       g.O = b.cctx16; g.dO = t.dcctx16;
       g.dQ = t.dqc16; g.dK = t.dkv16 + (size_t)(W.cross_index * 2) * per_sel * 2; g.dV = t.dkv16 + (size_t)(W.cross_index * 2 + 1) * per_sel * 2;
@@ -499,6 +497,7 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
       g.k_head_stride = g.v_head_stride = g.dk_head_stride = g.dv_head_stride = (long long)kv * 64;
       g.k_ld = g.v_ld = g.dk_ld = g.dv_ld = 64;
       g.lse = b.lse_c; g.items = N; g.heads = c.heads; g.q_rows = Q; g.kv_len = kv; g.scale = 0.125f;
+      g.kv_share = share;
       if ((rc = launch_attn_bwd(g, op, stream))) return chk(rc, "cross attention bwd");
       fork();
       if ((rc = X.wgrad(t.dpre2_16, qc_rows, 64, b.cctx16, qc_rows, N * Q, H, H, G(p + "crossattention.output.dense.weight"), G(p + "crossattention.output.dense.bias"))))
@@ -561,12 +560,12 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
     const int cl = h->layers[i].cross_index;
     if (cl < 0) continue;
     const std::string p = "bert.encoder.layer." + std::to_string(i) + ".crossattention.self.";
-    const size_t per_sel = (size_t)N * c.heads * kv * 64;
+    const size_t per_sel = (size_t)Ne * c.heads * kv * 64;
     const RowView hv = items_view((long long)c.heads * kv * 64, kv, 64);
     for (int kvsel = 0; kvsel < 2; ++kvsel) {
       const char* dY = t.dkv16 + (size_t)(cl * 2 + kvsel) * per_sel * 2;
       const std::string nm = p + (kvsel ? "value" : "key");
-      if ((rc = X.wgrad(dY, hv, (long long)kv * 64, enc, plain(N * kv, c.enc_width), N * kv, H, c.enc_width, G(nm + ".weight"), G(nm + ".bias"))))
+      if ((rc = X.wgrad(dY, hv, (long long)kv * 64, enc, plain(Ne * kv, c.enc_width), Ne * kv, H, c.enc_width, G(nm + ".weight"), G(nm + ".bias"))))
         return chk(rc, "dWkv");
     }
   }
@@ -583,6 +582,86 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
   if (rc_body) return rc_body;
   if (sync_err != hipSuccess) return fail(MRA_EHIP, std::string("side-stream synchronisation of the weight gradients: ") + hipGetErrorString(sync_err));
   return MRA_OK;
+}
+
+// argument checks the multi entries share (wording as mra_qformer_forward_multi); MRA_OK with *empty set when there is nothing to do
+int check_multi(mra_qformer* h, const int64_t* input_ids, const void* enc, int enc_items, int prompts, int L, int kv, bool want_cls, bool* empty) {
+  *empty = false;
+  if (prompts < 1) return fail(MRA_EINVAL, "prompts must be >= 1");
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (enc_items < 0 || L < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
+  if (enc_items == 0) { *empty = true; return MRA_OK; }
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return fail(MRA_EINVAL, "enc_items * prompts exceeds int32");
+  if (kv == 0) return fail(MRA_EINVAL, "kv must be >= 1");
+  if (L > h->cfg.max_pos) return fail(MRA_EINVAL, "L exceeds max_pos");
+  if (!enc || (L > 0 && !input_ids)) return fail(MRA_EINVAL, "null input");
+  if (want_cls && L < 1) return fail(MRA_EINVAL, "out_cls needs L >= 1");
+  const int limit = attn_bwd_max_share(h->cfg.n_query);
+  if (h->ncross > 0 && prompts > limit)
+    return fail(MRA_EINVAL, "prompts " + std::to_string(prompts) + " exceeds " + std::to_string(limit) +
+                                ", what the backward attention core's LDS holds at " + std::to_string(h->cfg.n_query) + " query rows: split the group");
+  return MRA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
+                              int32_t items, int32_t L, int32_t kv, float* out_query, float* out_cls, void* workspace,
+                              size_t workspace_bytes, void* stream_) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (items <= 0 || L < 0 || kv <= 0) return fail(MRA_EINVAL, "bad sizes");
+  const mra_cfg& c = h->cfg;
+  if (L > c.max_pos || !enc || (L > 0 && !input_ids) || (out_cls && L < 1)) return fail(MRA_EINVAL, "bad arguments");
+  if (!workspace || workspace_bytes < mra_qformer_train_workspace_bytes(h, items, L, kv) || reinterpret_cast<uintptr_t>(workspace) % 256)
+    return fail(MRA_ENOMEM, "training workspace too small or misaligned");
+  return forward_train_body(h, input_ids, attention_mask, enc, items, 1, L, kv, out_query, out_cls, workspace, as_stream(stream_));
+}
+
+int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int32_t items,
+                         int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls, float* grads, void* workspace,
+                         size_t workspace_bytes, void* stream_) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (items <= 0 || L < 0 || kv <= 0 || !grads || !enc) return fail(MRA_EINVAL, "bad arguments");
+  if (!d_out_query && !d_out_cls) return fail(MRA_EINVAL, "no upstream gradient");
+  if (!h->arena_t || h->transposes_stale) return fail(MRA_ESTATE, "call mra_qformer_enable_training after the last weight upload");
+  if (!workspace || workspace_bytes < mra_qformer_train_workspace_bytes(h, items, L, kv)) return fail(MRA_ENOMEM, "training workspace too small");
+  if (!h->wg_stream) return fail(MRA_ESTATE, "call mra_qformer_enable_training first");
+  return backward_body(h, input_ids, attention_mask, enc, items, 1, L, kv, d_out_query, d_out_cls, grads, workspace, as_stream(stream_));
+}
+
+size_t mra_qformer_multi_train_workspace_bytes(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv) {
+  if (!h || enc_items <= 0 || prompts <= 0 || L < 0 || kv <= 0) return 0;
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return 0;
+  return layout_train(h, nullptr, enc_items * prompts, L, kv, prompts).bytes;
+}
+
+int mra_qformer_forward_multi_train(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int32_t enc_items,
+                                    int32_t prompts, int32_t L, int32_t kv, float* out_query, float* out_cls, void* workspace,
+                                    size_t workspace_bytes, void* stream_) {
+  bool empty;
+  if (int rc = check_multi(h, input_ids, enc, enc_items, prompts, L, kv, out_cls != nullptr, &empty)) return rc;
+  if (empty) return MRA_OK;
+  if (!out_query && !out_cls) return fail(MRA_EINVAL, "no output requested");
+  const size_t need = mra_qformer_multi_train_workspace_bytes(h, enc_items, prompts, L, kv);
+  if (!workspace || workspace_bytes < need) return fail(MRA_ENOMEM, "training workspace too small: need " + std::to_string(need) + " bytes");
+  if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(MRA_EINVAL, "workspace must be 256-byte aligned");
+  return forward_train_body(h, input_ids, attention_mask, enc, enc_items * prompts, prompts, L, kv, out_query, out_cls, workspace, as_stream(stream_));
+}
+
+int mra_qformer_backward_multi(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc, int32_t enc_items,
+                               int32_t prompts, int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls, float* grads, void* workspace,
+                               size_t workspace_bytes, void* stream_) {
+  bool empty;
+  if (int rc = check_multi(h, input_ids, enc, enc_items, prompts, L, kv, d_out_cls != nullptr, &empty)) return rc;
+  if (empty) return MRA_OK;
+  if (!grads) return fail(MRA_EINVAL, "null gradient buffer");
+  if (!d_out_query && !d_out_cls) return fail(MRA_EINVAL, "no upstream gradient");
+  if (!h->arena_t || h->transposes_stale || !h->wg_stream) return fail(MRA_ESTATE, "call mra_qformer_enable_training after the last weight upload");
+  const size_t need = mra_qformer_multi_train_workspace_bytes(h, enc_items, prompts, L, kv);
+  if (!workspace || workspace_bytes < need) return fail(MRA_ENOMEM, "training workspace too small: need " + std::to_string(need) + " bytes");
+  return backward_body(h, input_ids, attention_mask, enc, enc_items * prompts, prompts, L, kv, d_out_query, d_out_cls, grads, workspace, as_stream(stream_));
 }
 
 }  // extern "C"

@@ -60,6 +60,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num-workers", type=int, default=0)
     ap.add_argument("--dataset", required=True, choices=["QVH", "Charades_STA"])
     ap.add_argument("--synthetic", type=int, default=0)
+    ap.add_argument("--synthetic-queries", type=int, default=1, help="with --synthetic: queries per synthetic video (several make --group-by-video groups)")
+    ap.add_argument("--group-by-video", action="store_true",
+                    help="train on one record per video with all its queries: the encoders, the modality LayerNorm and the K/V projection run once per "
+                         "video, the Q-Former layer chain once per query (XInstructBLIP.forward_multi); validation is unchanged")
+    ap.add_argument("--max-queries-per-call", type=int, default=8, help="with --group-by-video: most queries of one video in one Q-Former call (at most 14)")
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--warmup-steps", type=int, default=1000)
     ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],

@@ -852,6 +852,9 @@ class XInstructBLIP(nn.Module):
         forward-only value, as the reference's frozen Q-Formers would give."""
         if samples is None or samples == {} or not any(self._present(samples, m) for m in self.modalities):
             return {"loss": torch.tensor(0.0)}
+        ti = samples.get("text_input")
+        if ti is not None and len(ti) > 0 and isinstance(ti[0], (list, tuple)):   # one record per video with the list of its queries
+            return self.forward_multi(samples)
         if not getattr(self, "train_qformers", False):
             out = self.encode_fuse(samples)
             bs, num = out["bs"], out["num"]
@@ -891,6 +894,94 @@ class XInstructBLIP(nn.Module):
         w = self.fuse_weights or [1.0 / len(per_mod)] * len(per_mod)
         fused = sum(x * wt for x, wt in zip(per_mod, w))
         return {"loss": nn.functional.binary_cross_entropy_with_logits(fused.view(bs, num) * 20.0, self._targets(samples, bs, num))}
+
+    max_queries_per_call = 8      # forward_multi: most queries of one video in one Q-Former call (the backward core's LDS holds 14)
+
+    def _multi_targets(self, samples, windows: Sequence[Sequence[str]], num: int) -> List[torch.Tensor]:
+        """Per video ``[P_b, T]`` clip-membership targets: row ``p`` from the windows of the video's query ``p`` (as ``_targets``)."""
+        ts = samples.get("timestamps") or [list(range(num))] * len(windows)
+        out = []
+        for b, txts in enumerate(windows):
+            t = torch.as_tensor(ts[b], dtype=torch.float32, device=self._device)
+            rows = torch.zeros(len(txts), num, dtype=torch.float32, device=self._device)
+            for p, txt in enumerate(txts):
+                for s0, e0 in self.parse_windows(txt):
+                    rows[p] = torch.maximum(rows[p], ((t >= s0) & (t <= e0)).float())
+            out.append(rows)
+        return out
+
+    def forward_multi(self, samples, queries: Optional[Sequence[Sequence[str]]] = None, targets: Optional[Sequence[Sequence[str]]] = None):
+        """``forward`` for one record per video with several queries: ``queries[b]`` / ``targets[b]`` are the prompts and the
+        ``text_output`` strings of video ``b`` (default: the lists in ``samples["text_input"][b]`` / ``samples["text_output"][b]``).
+        The loss is the binary cross-entropy of ``20 x fused logit`` against clip membership of each query's own windows, averaged
+        over the real (video, query, position) triples -- the mean of the ``forward`` losses of one ``(video, query)`` sample each
+        when every video has ``T`` positions.  The encoders and the modality LayerNorm run once per video under ``no_grad``; each
+        modality Q-Former runs ``forward_multi_train``: ``P`` prompts per position over ONE K/V projection, one dK / dV tape and one
+        K/V weight gradient.  Ragged counts are padded by ``pad_queries``; padded slots carry no loss and no gradient.  Videos
+        with more than ``max_queries_per_call`` queries run as consecutive calls of at most that many, each call's loss weighted by
+        its share of the triples.  Prompts are always aligned to their own video (no ``compat_repeat`` on this path).  Without
+        ``enable_qformer_training()`` the loss is the forward-only value from ``encode_fuse_multi``."""
+        queries = [list(q) for q in (queries if queries is not None else samples["text_input"])]
+        if targets is None:
+            targets = samples.get("text_output") or [["[[-1, -1]]"] * len(q) for q in queries]
+        targets = [list(t) for t in targets]
+        if not queries or any(len(q) == 0 for q in queries):
+            raise MraError("forward_multi: every video needs at least one query")
+        if len(targets) != len(queries) or any(len(t) != len(q) for t, q in zip(targets, queries)):
+            raise MraError("forward_multi: targets must hold one text_output per query")
+        counts = [len(q) for q in queries]
+        bce = nn.functional.binary_cross_entropy_with_logits
+        if not getattr(self, "train_qformers", False):
+            out = self.encode_fuse_multi(samples, queries)
+            tg = self._multi_targets(samples, targets, out["num"])
+            total = sum(bce(f.float() * 20.0, t, reduction="sum") for f, t in zip(out["fused"], tg))
+            return {"loss": total / float(sum(counts) * out["num"])}
+        step = int(self.max_queries_per_call)
+        if step < 1:
+            raise MraError("max_queries_per_call must be >= 1")
+        self._sync()
+        encs: Dict[str, torch.Tensor] = {}
+        bs = num = None
+        with torch.no_grad():
+            for m in self.modalities:
+                if self._present(samples, m):
+                    raw, idx, bs, num = self._encode(samples, m)
+                    encs[m] = getattr(self, f"{m}_Qformer").modality_ln(raw, item_index=idx, items=bs * num)
+        if bs is None:
+            return {"loss": torch.tensor(0.0)}
+        if bs != len(queries):
+            raise MraError(f"forward_multi: {len(queries)} query lists for {bs} videos")
+        tg = self._multi_targets(samples, targets, num)
+        w = self.fuse_weights or [1.0 / len(encs)] * len(encs)
+        triples = float(sum(counts) * num)
+        loss = None
+        for lo in range(0, max(counts), step):
+            vids = [b for b, c in enumerate(counts) if c > lo]            # the videos that still have queries in this round
+            padded, cnt = pad_queries([queries[b][lo: lo + step] for b in vids])
+            nb, P = len(vids), max(cnt)
+            text = self.tokenizer([t for q in padded for t in q], padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
+            ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)      # [nb * P, L], row b * P + p
+            L = int(ids.shape[1])
+            # chain row (b * T + t) * P + p carries prompt p of video b
+            ids_n = ids.view(nb, 1, P, L).expand(nb, num, P, L).reshape(nb * num * P, L)
+            tm_n = tmask.view(nb, 1, P, L).expand(nb, num, P, L).reshape(nb * num * P, L)
+            att = torch.cat([torch.ones(nb * num * P, self.num_query_token, dtype=torch.long, device=self._device), tm_n], dim=1)
+            sel = None if nb == bs else torch.as_tensor(vids, device=self._device)
+            per_mod = []
+            for m, enc in encs.items():
+                if sel is not None:
+                    enc = enc.view(bs, num, *enc.shape[1:]).index_select(0, sel).reshape(nb * num, *enc.shape[1:])
+                z, cls = getattr(self, f"{m}_Qformer").forward_multi_train(ids_n, att, enc, P)
+                per_mod.append(nn.functional.cosine_similarity(z, cls[:, None, :], dim=-1, eps=1e-8).max(dim=1).values)
+            fused = sum(x * wt for x, wt in zip(per_mod, w)).view(nb, num, P).permute(0, 2, 1)      # (b, t, p) -> [nb, P, T]
+            target = torch.zeros(nb, P, num, dtype=torch.float32, device=self._device)
+            real = torch.zeros(nb, P, 1, dtype=torch.float32, device=self._device)                  # 0 on padded slots: no loss, no gradient
+            for k, b in enumerate(vids):
+                target[k, :cnt[k]] = tg[b][lo: lo + cnt[k]]
+                real[k, :cnt[k]] = 1.0
+            part = (bce(fused * 20.0, target, reduction="none") * real).sum() / triples
+            loss = part if loss is None else loss + part
+        return {"loss": loss}
 
     def flat_optimizer_params(self) -> List[nn.Parameter]:
         """Parameters for an optimizer after ``enable_qformer_training()``: one flat parameter per Q-Former (bert.* and

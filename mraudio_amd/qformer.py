@@ -546,6 +546,36 @@ class QFormer(nn.Module):
         return (q, c) if want_cls else (q, None)
 
 
+    def forward_multi_train(self, input_ids, attention_mask, enc, prompts: int, want_cls: bool = True):
+        """Training forward for ``prompts`` prompts per encoder item over one shared K/V cache (``mra_qformer_forward_multi_train``):
+        ``(out_query [N * prompts, 32, H], out_cls [N * prompts, H])`` connected to autograd, row ``i * prompts + p`` = item ``i``,
+        prompt slot ``p`` (the row order of ``forward_multi``).  enc [N, Kv, E] is given once per item.  Equal to ``forward_train`` on
+        ``enc.repeat_interleave(prompts, 0)``; the K/V projection, the dK / dV tape and the K/V weight gradients run once per item.
+        ``loss.backward()`` accumulates gradients exactly as after ``forward_train``.  ``prompts`` is limited by the LDS of the
+        attention backward (14 at 32 query tokens; ``MraError`` beyond).  The tape lives in a workspace of its own, so a second call
+        before the first one's backward gets a fresh one."""
+        self.enable_training()
+        cfg = self.cfg
+        P = int(prompts)
+        if P < 1:
+            raise MraError(f"prompts must be >= 1, got {prompts}")
+        if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
+            raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
+        enc = enc.to(cfg.op_dtype).contiguous()
+        N = int(enc.shape[0])
+        L = 0 if input_ids is None else int(input_ids.shape[1])
+        if input_ids is not None:
+            if input_ids.shape[0] != N * P:
+                raise MraError(f"input_ids has {input_ids.shape[0]} rows, encoder_hidden_states {N} x prompts {P}")
+            input_ids = input_ids.to(device=enc.device, dtype=torch.int64).contiguous()
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != (N * P, cfg.n_query + L):
+                raise MraError(f"attention_mask must be [{N * P}, {cfg.n_query + L}], got {tuple(attention_mask.shape)}")
+            attention_mask = attention_mask.to(device=enc.device, dtype=torch.int64).contiguous()
+        q, c = _QFormerMultiTrainFn.apply(self._anchor, self, input_ids, attention_mask, enc, P, want_cls)
+        return (q, c) if want_cls else (q, None)
+
+
     def _slice_of(self, name: str):
         off, numel = C.c_size_t(), C.c_int64()
         check(lib().mra_qformer_grad_offset(self._handle, name.encode(), C.byref(off), C.byref(numel)), f"grad_offset({name})")
@@ -586,7 +616,7 @@ class QFormer(nn.Module):
         self._dirty = False
         self._grads_zeroed = bool(zero_grad)
 
-    def _run_backward(self, input_ids, attention_mask, enc, N, L, Kv, d_q, d_c) -> None:
+    def _run_backward(self, input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts: int = 0, workspace=None) -> None:
         # optimizer.zero_grad(set_to_none=True) drops the views: start from a clean buffer in that case
         probe = self.bert.embeddings.LayerNorm.weight
         fp = getattr(self, "_flat_param", None)
@@ -595,9 +625,14 @@ class QFormer(nn.Module):
         if fp is not None:
             fp.grad = self._grad_flat
         with torch.cuda.device(self._device):
-            check(lib().mra_qformer_backward(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, L, Kv, ptr(d_q), ptr(d_c),
-                                             ptr(self._grad_flat), ptr(self._train_ws), self._train_ws.numel(), current_stream()),
-                  "mra_qformer_backward")
+            if prompts:      # N encoder items x `prompts` chain items over the tape of forward_multi_train
+                check(lib().mra_qformer_backward_multi(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, prompts, L, Kv, ptr(d_q),
+                                                       ptr(d_c), ptr(self._grad_flat), ptr(workspace), workspace.numel(), current_stream()),
+                      "mra_qformer_backward_multi")
+            else:
+                check(lib().mra_qformer_backward(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, L, Kv, ptr(d_q), ptr(d_c),
+                                                 ptr(self._grad_flat), ptr(self._train_ws), self._train_ws.numel(), current_stream()),
+                      "mra_qformer_backward")
         self._bind_grads()
         binder = getattr(self, "_extra_grad_binder", None)
         if binder is not None:
@@ -645,3 +680,45 @@ class _QFormerTrainFn(torch.autograd.Function):
         d_c = d_c.to(torch.float32).contiguous() if (ctx.want_cls and d_c is not None) else None
         owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c)
         return torch.zeros_like(owner._anchor), None, None, None, None, None
+
+
+class _QFormerMultiTrainFn(torch.autograd.Function):
+    """Autograd node around ``mra_qformer_forward_multi_train`` / ``mra_qformer_backward_multi``: as ``_QFormerTrainFn`` (same anchor,
+    same gradient buffer and bookkeeping), with the tape in a workspace the node holds until its backward has run."""
+
+    @staticmethod
+    def forward(ctx, anchor, owner, input_ids, attention_mask, enc, prompts, want_cls):
+        cfg = owner.cfg
+        N, Kv = int(enc.shape[0]), int(enc.shape[1])
+        L = 0 if input_ids is None else int(input_ids.shape[1])
+        dev = enc.device
+        out_q = torch.empty(N * prompts, cfg.n_query, cfg.hidden, dtype=torch.float32, device=dev)
+        out_c = torch.empty(N * prompts, cfg.hidden, dtype=torch.float32, device=dev) if want_cls else None
+        with torch.cuda.device(dev):
+            nbytes = int(lib().mra_qformer_multi_train_workspace_bytes(owner._handle, N, prompts, L, Kv))
+            ws = getattr(owner, "_multi_train_ws", None)      # free again once the node that used it last has run its backward
+            owner._multi_train_ws = None
+            if ws is None or ws.numel() < nbytes:
+                ws = None
+                ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+            check(lib().mra_qformer_forward_multi_train(owner._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, prompts, L, Kv, ptr(out_q),
+                                                        ptr(out_c), ptr(ws), ws.numel(), current_stream()),
+                  "mra_qformer_forward_multi_train")
+        ctx.owner, ctx.shape, ctx.ws = owner, (N, prompts, L, Kv), ws
+        ctx.save_for_backward(input_ids, attention_mask, enc)
+        ctx.want_cls = want_cls
+        return (out_q, out_c) if want_cls else (out_q, torch.empty(0, device=dev))
+
+    @staticmethod
+    def backward(ctx, d_q, d_c):
+        owner = ctx.owner
+        input_ids, attention_mask, enc = ctx.saved_tensors
+        N, P, L, Kv = ctx.shape
+        d_q = None if d_q is None else d_q.to(torch.float32).contiguous()
+        d_c = d_c.to(torch.float32).contiguous() if (ctx.want_cls and d_c is not None) else None
+        owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts=P, workspace=ctx.ws)
+        kept = getattr(owner, "_multi_train_ws", None)
+        if kept is None or kept.numel() < ctx.ws.numel():
+            owner._multi_train_ws = ctx.ws
+        ctx.ws = None
+        return torch.zeros_like(owner._anchor), None, None, None, None, None, None

@@ -69,43 +69,58 @@ class MRDataset(Dataset):
 class SyntheticMRDataset(Dataset):
     """Seeded stand-in corpus of pre-extracted features (no dataset exists offline): ``n`` videos of ``T``
     positions, one target window each; the target positions' features carry a common direction so a trained
-    scorer has something to find."""
+    scorer has something to find.  ``queries_per_video = Q > 1`` (opt-in) gives every video ``Q`` annotation lines: record ``j`` is
+    query ``j % Q`` of video ``j // Q``, with the video's features (those of ``Q = 1``, signal on the window of query 0) and a window of
+    its own; query 0 is the record of ``Q = 1``."""
 
     def __init__(self, n: int = 8, T: int = 20, seed: int = 0, duration: int = 40, kv_video: int = 257, kv_audio: int = 256,
-                 modalities=("video", "audio"), signal: float = 0.0):
+                 modalities=("video", "audio"), signal: float = 0.0, queries_per_video: int = 1):
         self.n, self.T, self.seed, self.duration = n, T, seed, duration
         self.kv = {"video": (kv_video, 1408), "audio": (kv_audio, 768)}
         self.modalities, self.signal = tuple(modalities), signal
+        self.queries_per_video = max(1, int(queries_per_video))
 
     def __len__(self) -> int:
-        return self.n
+        return self.n * self.queries_per_video
+
+    def _window(self, g: torch.Generator):
+        s = int(torch.randint(0, self.T - 2, (1,), generator=g))
+        return s, min(self.T - 1, s + 1 + int(torch.randint(1, max(2, self.T // 3), (1,), generator=g)))
+
+    def _line(self, j: int):
+        """(video i, query r, the video's generator after the draw of query 0's window, window of query 0, window of query r)."""
+        i, r = divmod(j, self.queries_per_video)
+        g = torch.Generator().manual_seed(self.seed * 100003 + i)
+        w0 = self._window(g)
+        wr = w0 if r == 0 else self._window(torch.Generator().manual_seed((self.seed * 100003 + i) * 131 + r))
+        return i, r, g, w0, wr
 
     @property
     def annotation(self) -> List[dict]:
-        """The annotation lines ``MRDataset`` would hold for this corpus (one query per video), without the features."""
+        """The annotation lines ``MRDataset`` would hold for this corpus (``queries_per_video`` lines per video), without the features."""
         out = []
-        for i in range(self.n):
-            g = torch.Generator().manual_seed(self.seed * 100003 + i)
-            s = int(torch.randint(0, self.T - 2, (1,), generator=g))
-            e = min(self.T - 1, s + 1 + int(torch.randint(1, max(2, self.T // 3), (1,), generator=g)))
+        for j in range(len(self)):
+            i, r, _, _, (s, e) = self._line(j)
             ts = [round(k * self.duration / self.T) for k in range(self.T)]
-            out.append({"qid": i, "query": f"synthetic event number {i}", "vid": f"syn{i}", "duration": self.duration,
+            out.append({"qid": j, "query": self._query(i, r), "vid": f"syn{i}", "duration": self.duration,
                         "relevant_windows": [[ts[s], ts[e]]]})
         return out
 
-    def __getitem__(self, i: int) -> Dict[str, object]:
-        g = torch.Generator().manual_seed(self.seed * 100003 + i)
+    @staticmethod
+    def _query(i: int, r: int) -> str:
+        return f"synthetic event number {i}" + (f", part {r}" if r else "")
+
+    def __getitem__(self, j: int) -> Dict[str, object]:
+        i, r, g, (s0, e0), (s, e) = self._line(j)
         step = self.duration / self.T
-        s = int(torch.randint(0, self.T - 2, (1,), generator=g))
-        e = min(self.T - 1, s + 1 + int(torch.randint(1, max(2, self.T // 3), (1,), generator=g)))
         ts = [round(k * step) for k in range(self.T)]
-        rec: Dict[str, object] = {"text_input": build_prompt(f"synthetic event number {i}"), "text_output": str([[ts[s], ts[e]]]),
-                                  "timestamps": ts, "duration": self.duration, "qid": i, "query": f"synthetic event number {i}", "vid": f"syn{i}"}
+        rec: Dict[str, object] = {"text_input": build_prompt(self._query(i, r)), "text_output": str([[ts[s], ts[e]]]),
+                                  "timestamps": ts, "duration": self.duration, "qid": j, "query": self._query(i, r), "vid": f"syn{i}"}
         for m in self.modalities:
             kv, width = self.kv[m]
             x = torch.randn(self.T, kv, width, generator=g)
             if self.signal:
-                x[s:e + 1] += self.signal * torch.randn(1, 1, width, generator=torch.Generator().manual_seed(self.seed + 7))
+                x[s0:e0 + 1] += self.signal * torch.randn(1, 1, width, generator=torch.Generator().manual_seed(self.seed + 7))
             rec[f"{m}_embeds"] = x
         return rec
 

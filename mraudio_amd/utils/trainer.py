@@ -17,6 +17,10 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
   * the Q-Formers are unfrozen (``model.enable_qformer_training()``; BASELINE config 5) -- with the
     reference's frozen Q-Formers and no LLM on this path nothing would be trainable;
   * validation results are gathered from all ranks before scoring (the reference scores rank 0's shard only).
+  * ``args.group_by_video`` (default off; ``finetune --group-by-video``) trains on one record per video with the lists of its queries
+    (``VideoGroupedDataset`` + ``collate_grouped``): ``model(samples)`` then runs ``XInstructBLIP.forward_multi`` -- encoders, modality
+    LayerNorm and K/V projection once per video, at most ``args.max_queries_per_call`` (8) queries per Q-Former call.  The reference
+    trains one ``(video, query)`` annotation line per sample; the grouped loss is the mean over the same lines.
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -35,7 +39,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader, DistributedSampler
 
 from ..eval.mr_eval import eval_submission
-from .mr_dataset import MRDataset, SyntheticMRDataset, collate_fn, prepare_sample
+from .mr_dataset import MRDataset, SyntheticMRDataset, VideoGroupedDataset, collate_fn, collate_grouped, prepare_sample
 from .spans import moment_str_to_list, post_process
 
 log = logging.getLogger("mraudio_amd.trainer")
@@ -102,7 +106,7 @@ class Trainer:
 
         if train_dataset is None:
             if getattr(args, "synthetic", 0):
-                train_dataset = SyntheticMRDataset(args.synthetic, T=n_frms, seed=0, signal=1.0)
+                train_dataset = SyntheticMRDataset(args.synthetic, T=n_frms, seed=0, signal=1.0, queries_per_video=getattr(args, "synthetic_queries", 1))
                 val_dataset = SyntheticMRDataset(max(2, args.synthetic // 2), T=n_frms, seed=1, signal=1.0)
             else:
                 from ..processors.alpro_processors import AlproVideoEvalProcessor_Stamps, AlproVideoTrainProcessor_Stamps
@@ -113,10 +117,23 @@ class Trainer:
                 ap_ = None if emb else BeatsAudioProcessor(model_name="iter3", sampling_rate=16000, n_frames=n_frms, is_eval=False, frame_length=512)
                 train_dataset = MRDataset(args.video_folder, args.train_annotation_file, tp, ap_, model="X-InstructBLIP", embeds_root=emb)
                 val_dataset = MRDataset(args.video_folder, args.val_annotation_file, vp, ap_, model="X-InstructBLIP", embeds_root=emb)
+        # group_by_video: one training record per video with the lists of its queries -- model(samples) then runs XInstructBLIP.forward_multi
+        # (encoders, modality LayerNorm and K/V projection once per video).  Validation keeps one record per annotation line.
+        self.group_by_video = bool(getattr(args, "group_by_video", False))
+        self.max_queries_per_call = int(getattr(args, "max_queries_per_call", 8))
+        train_collate = collate_fn
+        if self.group_by_video:
+            if self.max_queries_per_call < 1:
+                raise ValueError("max_queries_per_call must be >= 1")
+            if not isinstance(train_dataset, VideoGroupedDataset):
+                train_dataset = VideoGroupedDataset(train_dataset)
+            train_collate = collate_grouped
+            if hasattr(model, "max_queries_per_call"):
+                model.max_queries_per_call = self.max_queries_per_call
         bs, nw = getattr(args, "batch_size", 1), getattr(args, "num_workers", 0)
         self.train_sampler = DistributedSampler(train_dataset, shuffle=True, num_replicas=self.world_size, rank=self.rank)
         val_sampler = DistributedSampler(val_dataset, shuffle=False, num_replicas=self.world_size, rank=self.rank)
-        self.train_dataloader = DataLoader(train_dataset, batch_size=bs, sampler=self.train_sampler, num_workers=nw, collate_fn=collate_fn)
+        self.train_dataloader = DataLoader(train_dataset, batch_size=bs, sampler=self.train_sampler, num_workers=nw, collate_fn=train_collate)
         self.val_dataloader = DataLoader(val_dataset, batch_size=bs, sampler=val_sampler, num_workers=nw, collate_fn=collate_fn)
         self.history: List[dict] = []
 
