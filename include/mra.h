@@ -562,6 +562,53 @@ int mra_debug_transpose_pad(const void* src, void* dst, int32_t R, int32_t C, in
 int mra_debug_split(int32_t kind, const float* src, const int64_t* src_view, int32_t rows, int32_t C, int32_t chunk, int32_t parts, void* dst,
                     int32_t dtype, void* stream);
 
+/* The Q-Former training step's own kernels, one launch each, through the launch functions mra_qformer_forward_train / mra_qformer_backward
+ * call (tests/test_gpu_train_kernels.py).  Same rules as the block above: no handle, no allocation, device pointers in the kernels' own
+ * layouts, every argument checked before any launch (MRA_EINVAL with a message).  Per-job arguments are HOST arrays with one entry per job;
+ * row views are HOST triples, three int64 per view, one after the other.  The entries cannot know the size of a buffer: the caller owns
+ * every element the views, strides and sizes address.
+ *
+ * mra_debug_gemm_tn_group: launch_gemm_tn_group over njobs = 1 .. 4 weight gradients (one job reaches launch_gemm_tn, as in the training step):
+ *   dW[n][k] (+)= sum_m dY[m][n] X[m][k], db[n] += sum_m dY[m][n].  Job i: dY[i] / X[i] operand dtype, given as 64-column blocks -- block b of
+ *   dY starts at dY + b * y_block_stride[i], its row m at the row view y_views[3 i ..] (csrc/kernels.h GemmTnArgs); dW[i] fp32 [N][ldw];
+ *   db NULL, or an array whose entries may be NULL; accumulate[i] != 0: dW += (db always accumulates).
+ *   Refused: njobs outside 1 .. 4; a NULL dY / X / dW; dY or X not 16-byte aligned; a view with rows per item <= 0 or a row / item stride that
+ *   is not a multiple of 8; a block stride that is not a multiple of 8; M <= 0; N or K not a positive multiple of 64; ldw < K; and a group
+ *   whose contraction the launcher splits while one of its jobs does not accumulate.
+ * mra_debug_ln_bwd: launch_ln_bwd2 over job a and an optional job b (ptrs_b NULL: none; either job may have 0 rows).  ptrs_*: HOST array of 8
+ *   device pointers dy, x, gamma, dx, add, dx16, dgamma, dbeta (add, dx16 and the dgamma / dbeta pair may be NULL); views_*: 5 views dy, x, dx,
+ *   add, dx16 (those of NULL buffers are not read).  dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ add), g = dy gamma; dx16 = dx rounded
+ *   once; dgamma += sum_rows dy xhat, dbeta += sum_rows dy.
+ *   Refused: H outside {256, 512, 768, 1024}; negative rows; a NULL dy / x / gamma / dx of a job with rows; a view whose strides are not
+ *   multiples of 4 (8 for dx16) or whose row stride is below H; a buffer that is not 16-byte aligned; dgamma without dbeta (or the reverse);
+ *   two jobs of which only one takes dgamma.
+ * mra_debug_embed_bwd: launch_embed_bwd.  demb [items][Q + L][H] fp32; dquery [Q][H] += sum over items, dpos [L][H] likewise, dword
+ *   [vocab][H] += the rows of the ids (clamped to [0, vocab) as the forward clamps them); each output may be NULL.  items == 0 is a no-op.
+ *   Refused: H <= 0 or H % 4; Q < 0, L < 0 or Q + L == 0; vocab < 1; negative items; NULL demb; NULL ids with L > 0 and dword given.
+ * mra_debug_transpose16_batch: launch_transpose16_batch over njobs = 1 .. 64 matrices, dst[i] [C][R] = src[i] [R][C]^T (operand dtype).  The
+ *   job table is built as the training step builds it and copied (synchronously) into `scratch`, device memory of at least
+ *   mra_debug_transpose16_batch_scratch_bytes(njobs) bytes (0 for an njobs out of range), 8-byte aligned.
+ *   Refused: njobs out of range, R or C below 1, a NULL matrix, a scratch buffer that is NULL, too small or misaligned.
+ * mra_debug_gemm_gelu: one or two problems C = A W^T through launch_gemm, as Ctx::gemm2 (csrc/mra_train.hip) issues the feed-forward
+ *   up-projection and its data gradient.  backward == 0: EPI_GELU_BOTH, aux = T(acc + bias), C = T(gelu(aux)); backward != 0: EPI_GELU_BWD,
+ *   C = T(acc gelu'(aux)), aux read.  W[i] [N][K] dense; A by a_views, C and aux by c_views; bias NULL or an array with NULL entries.
+ *   tile_cfg: GT_AUTO (0), GT_64 (1), GT_128 (2), GT_256 (3) of csrc/kernels.h.
+ *   Refused: what gemm_plan refuses (M, N or K <= 0, K % 64, N no multiple of the tile, C strides no multiples of 4), a NULL A / W / C / aux,
+ *   A strides that are not multiples of 8, a row stride below the row length, a misaligned buffer (A, W, bias 16 bytes; C, aux 8). */
+int mra_debug_gemm_tn_group(int32_t njobs, const void* const* dY, const int64_t* y_views, const int64_t* y_block_stride, const void* const* X,
+                            const int64_t* x_views, const int64_t* x_block_stride, float* const* dW, float* const* db, const int32_t* M,
+                            const int32_t* N, const int32_t* K, const int32_t* ldw, const int32_t* accumulate, int32_t dtype, void* stream);
+int mra_debug_ln_bwd(const void* const* ptrs_a, const int64_t* views_a, int32_t rows_a, float eps_a, const void* const* ptrs_b, const int64_t* views_b,
+                     int32_t rows_b, float eps_b, int32_t H, int32_t dtype, void* stream);
+int mra_debug_embed_bwd(const float* demb, const int64_t* ids, int32_t items, int32_t L, int32_t Q, int32_t H, int32_t vocab, float* dquery, float* dpos,
+                        float* dword, void* stream);
+size_t mra_debug_transpose16_batch_scratch_bytes(int32_t njobs);
+int mra_debug_transpose16_batch(const void* const* src, void* const* dst, const int32_t* R, const int32_t* C, int32_t njobs, int32_t dtype, void* scratch,
+                                size_t scratch_bytes, void* stream);
+int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_views, const void* const* W, const float* const* bias, void* const* C,
+                        const int64_t* c_views, void* const* aux, const int32_t* M, const int32_t* N, const int32_t* K, int32_t backward, int32_t tile_cfg,
+                        int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

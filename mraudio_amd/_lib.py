@@ -148,12 +148,28 @@ PROTOTYPES = {
                                           C.c_void_p]),
     "mra_debug_split": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p]),
+    "mra_debug_gemm_tn_group": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
+    "mra_debug_ln_bwd": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                   C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
+    "mra_debug_embed_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "mra_debug_transpose16_batch_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "mra_debug_transpose16_batch": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mra_debug_gemm_gelu": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 # GemmFamily / GemmEpi codes of mra_debug_gemm_launches (csrc/kernels.h)
 GF_V1_64, GF_V1_128, GF_WS_256, GF_P8_256, GF_WS_128x384, GF_WS_176x384, GF_K128_64x128, GF_P8_TAIL, GF_P8_MIXED, GF_K128_64x64 = 0, 1, 3, 4, 5, 6, 7, 8, 9, 10
 EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART, EPI_RES_OP = 0, 1, 2, 3, 4, 5, 8
 EPI_RES_F32_STAT, EPI_LNF_OP, EPI_LNF_GELU_OP, EPI_RES_OP_STAT = 10, 11, 12, 13     # the ViT's folded LayerNorms (csrc/kernels.h)
+EPI_GELU_BOTH, EPI_GELU_BWD = 6, 7                                                   # the training step's feed-forward epilogues
+GT_AUTO, GT_64, GT_128, GT_256 = 0, 1, 2, 3                                          # GemmTile codes mra_debug_gemm_gelu takes
+GEMM_TN_MAX_JOBS = 4
 
 
 def gemm_launches(family: int, epi: int) -> int:

@@ -1519,4 +1519,151 @@ int mra_debug_split(int32_t kind, const float* src, const int64_t* src_view, int
   return chk(launch_split_key_weight(src, rows, C, dst, op, st), "split_key_weight");
 }
 
+// ---- the Q-Former training step's own kernels, one launch each (include/mra.h; tests/test_gpu_train_kernels.py) -------------------------
+// As above: every argument is checked before any launch, nothing is allocated, and the launch function is the one mra_train.hip calls.
+namespace {
+// a row view of 16-bit operand rows read or written in 16-byte pieces: strides multiples of 8 elements
+bool dbg_view8(const int64_t* v, RowView* out) { return dbg_view(v, out) && !(v[0] & 7) && !(v[2] & 7); }
+constexpr int DBG_TR_MAX_JOBS = 64;
+}  // namespace
+
+int mra_debug_gemm_tn_group(int32_t njobs, const void* const* dY, const int64_t* y_views, const int64_t* y_block_stride, const void* const* X,
+                            const int64_t* x_views, const int64_t* x_block_stride, float* const* dW, float* const* db, const int32_t* M,
+                            const int32_t* N, const int32_t* K, const int32_t* ldw, const int32_t* accumulate, int32_t dtype, void* stream) {
+  int op;
+  if (njobs < 1 || njobs > GEMM_TN_MAX_JOBS) return fail(MRA_EINVAL, "njobs must be 1 .. 4");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (!dY || !y_views || !y_block_stride || !X || !x_views || !x_block_stride || !dW || !M || !N || !K || !ldw || !accumulate)
+    return fail(MRA_EINVAL, "null argument array");
+  GemmTnArgs jobs[GEMM_TN_MAX_JOBS];
+  for (int i = 0; i < njobs; ++i) {
+    GemmTnArgs& a = jobs[i];
+    a = GemmTnArgs{};
+    if (!dY[i] || !X[i] || !dW[i]) return fail(MRA_EINVAL, "null dY, X or dW");
+    if (!dbg_aligned(dY[i], 16) || !dbg_aligned(X[i], 16) || !dbg_aligned(dW[i], 4) || (db && !dbg_aligned(db[i], 4)))
+      return fail(MRA_EINVAL, "dY and X must be 16-byte aligned (dW, db: 4)");
+    if (M[i] <= 0 || N[i] <= 0 || K[i] <= 0 || N[i] % 64 || K[i] % 64) return fail(MRA_EINVAL, "need M > 0 and N, K positive multiples of 64");
+    if (!dbg_view8(y_views + 3 * i, &a.yv) || !dbg_view8(x_views + 3 * i, &a.xv))
+      return fail(MRA_EINVAL, "a row view is (item_stride >= 0, rows per item > 0, row stride > 0), strides multiples of 8");
+    if (y_block_stride[i] < 0 || x_block_stride[i] < 0 || (y_block_stride[i] & 7) || (x_block_stride[i] & 7))
+      return fail(MRA_EINVAL, "block strides must be non-negative multiples of 8");
+    if (ldw[i] < K[i]) return fail(MRA_EINVAL, "ldw below K");
+    a.dY = dY[i]; a.X = X[i]; a.dW = dW[i]; a.db = db ? db[i] : nullptr;
+    a.y_block_stride = y_block_stride[i]; a.x_block_stride = x_block_stride[i];
+    a.M = M[i]; a.N = N[i]; a.K = K[i]; a.ldw = ldw[i]; a.accumulate = accumulate[i] ? 1 : 0;
+  }
+  const int rc = launch_gemm_tn_group(jobs, njobs, op, as_stream(stream));
+  // everything else the launchers refuse was refused above: what is left is the group's rule on the split contraction
+  if (rc == -1) return fail(MRA_EINVAL, "a group whose contraction is split needs every job accumulating");
+  return chk(rc, "gemm_tn group");
+}
+
+namespace {
+// ptrs: dy, x, gamma, dx, add, dx16, dgamma, dbeta; views: dy, x, dx, add, dx16 (3 each)
+const char* dbg_ln_bwd_job(const void* const* p, const int64_t* v, int32_t rows, float eps, int H, LnBwdArgs* out) {
+  LnBwdArgs& a = *out;
+  a = LnBwdArgs{};
+  a.rows = rows;
+  a.eps = eps;
+  if (!p) return rows > 0 ? "null argument" : nullptr;
+  if ((p[6] == nullptr) != (p[7] == nullptr)) return "dgamma and dbeta come as a pair";
+  a.dgamma = (float*)p[6];
+  a.dbeta = (float*)p[7];
+  if (rows == 0) return nullptr;
+  if (!v || !p[0] || !p[1] || !p[2] || !p[3]) return "null argument";
+  if (!dbg_view(v, &a.dyv) || !dbg_view(v + 3, &a.xv) || !dbg_view(v + 6, &a.dxv) || (p[4] && !dbg_view(v + 9, &a.addv)))
+    return "a row view is (item_stride >= 0, rows per item > 0, row stride > 0), strides multiples of 4";
+  if (p[5] && !dbg_view8(v + 12, &a.dx16v)) return "the dx16 view needs strides that are multiples of 8";
+  if (a.dyv.ld < H || a.xv.ld < H || a.dxv.ld < H || (p[4] && a.addv.ld < H) || (p[5] && a.dx16v.ld < H)) return "row stride below H";
+  for (int i = 0; i < 8; ++i)
+    if (!dbg_aligned(p[i], 16)) return "misaligned buffer";
+  a.dy = (const float*)p[0]; a.x = (const float*)p[1]; a.gamma = (const float*)p[2]; a.dx = (float*)p[3];
+  a.add = (const float*)p[4]; a.dx16 = (void*)p[5];
+  return nullptr;
+}
+}  // namespace
+
+int mra_debug_ln_bwd(const void* const* ptrs_a, const int64_t* views_a, int32_t rows_a, float eps_a, const void* const* ptrs_b, const int64_t* views_b,
+                     int32_t rows_b, float eps_b, int32_t H, int32_t dtype, void* stream) {
+  int op;
+  if (rows_a < 0 || rows_b < 0) return fail(MRA_EINVAL, "negative rows");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (H != 256 && H != 512 && H != 768 && H != 1024) return fail(MRA_EINVAL, "H must be 256, 512, 768 or 1024");
+  if (!ptrs_b && rows_b > 0) return fail(MRA_EINVAL, "rows_b > 0 without job b");
+  LnBwdArgs a, b;
+  if (const char* e = dbg_ln_bwd_job(ptrs_a, views_a, rows_a, eps_a, H, &a)) return fail(MRA_EINVAL, std::string("job a: ") + e);
+  if (const char* e = dbg_ln_bwd_job(ptrs_b, views_b, rows_b, eps_b, H, &b)) return fail(MRA_EINVAL, std::string("job b: ") + e);
+  if (ptrs_a && ptrs_b && (a.dgamma != nullptr) != (b.dgamma != nullptr)) return fail(MRA_EINVAL, "both jobs or neither take dgamma / dbeta");
+  return chk(launch_ln_bwd2(a, ptrs_b ? &b : nullptr, H, op, as_stream(stream)), "ln_bwd");
+}
+
+int mra_debug_embed_bwd(const float* demb, const int64_t* ids, int32_t items, int32_t L, int32_t Q, int32_t H, int32_t vocab, float* dquery, float* dpos,
+                        float* dword, void* stream) {
+  if (items < 0) return fail(MRA_EINVAL, "negative items");
+  if (H <= 0 || H % 4) return fail(MRA_EINVAL, "H must be a positive multiple of 4");
+  if (Q < 0 || L < 0 || Q + (int64_t)L == 0 || Q + (int64_t)L > 0x7fffffffLL) return fail(MRA_EINVAL, "need Q >= 0, L >= 0 and Q + L > 0");
+  if (vocab < 1) return fail(MRA_EINVAL, "vocab must be at least 1");
+  if (items == 0) return MRA_OK;
+  if (!demb) return fail(MRA_EINVAL, "null argument");
+  if (L > 0 && dword && !ids) return fail(MRA_EINVAL, "dword needs ids");
+  if (!dbg_aligned(demb, 4) || !dbg_aligned(dquery, 4) || !dbg_aligned(dpos, 4) || !dbg_aligned(dword, 4) || !dbg_aligned(ids, 8))
+    return fail(MRA_EINVAL, "misaligned buffer");
+  return chk(launch_embed_bwd(demb, (const long long*)ids, items, L, Q, H, vocab, dquery, dpos, dword, as_stream(stream)), "embed_bwd");
+}
+
+size_t mra_debug_transpose16_batch_scratch_bytes(int32_t njobs) { return njobs < 1 || njobs > DBG_TR_MAX_JOBS ? 0 : (size_t)njobs * sizeof(TrJob); }
+
+int mra_debug_transpose16_batch(const void* const* src, void* const* dst, const int32_t* R, const int32_t* C, int32_t njobs, int32_t dtype, void* scratch,
+                                size_t scratch_bytes, void* stream) {
+  int op;
+  if (njobs < 1 || njobs > DBG_TR_MAX_JOBS) return fail(MRA_EINVAL, "njobs must be 1 .. 64");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (!src || !dst || !R || !C || !scratch) return fail(MRA_EINVAL, "null argument");
+  if (scratch_bytes < mra_debug_transpose16_batch_scratch_bytes(njobs) || !dbg_aligned(scratch, 8))
+    return fail(MRA_EINVAL, "scratch smaller than mra_debug_transpose16_batch_scratch_bytes, or not 8-byte aligned");
+  TrJob jobs[DBG_TR_MAX_JOBS];
+  long long tiles = 0;
+  for (int i = 0; i < njobs; ++i) {   // the table as refresh_transposes (mra_train.hip) builds it
+    if (!src[i] || !dst[i]) return fail(MRA_EINVAL, "null matrix");
+    if (R[i] < 1 || C[i] < 1) return fail(MRA_EINVAL, "R and C must be at least 1");
+    if (!dbg_aligned(src[i], 2) || !dbg_aligned(dst[i], 2)) return fail(MRA_EINVAL, "misaligned matrix");
+    const int tx = (C[i] + 31) / 32, ty = (R[i] + 31) / 32;
+    jobs[i] = TrJob{src[i], dst[i], R[i], C[i], (int)tiles, tx};
+    tiles += (long long)tx * ty;
+    if (tiles > 0x7fffffffLL) return fail(MRA_EINVAL, "too many tiles");
+  }
+  HIP_TRY(hipMemcpy(scratch, jobs, (size_t)njobs * sizeof(TrJob), hipMemcpyHostToDevice));
+  return chk(launch_transpose16_batch((const TrJob*)scratch, njobs, (int)tiles, op, as_stream(stream)), "transpose16_batch");
+}
+
+int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_views, const void* const* W, const float* const* bias, void* const* C,
+                        const int64_t* c_views, void* const* aux, const int32_t* M, const int32_t* N, const int32_t* K, int32_t backward, int32_t tile_cfg,
+                        int32_t dtype, void* stream) {
+  int op;
+  if (nprob < 1 || nprob > 2) return fail(MRA_EINVAL, "one or two problems");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (tile_cfg != GT_AUTO && tile_cfg != GT_64 && tile_cfg != GT_128 && tile_cfg != GT_256) return fail(MRA_EINVAL, "tile_cfg must be GT_AUTO, GT_64, GT_128 or GT_256");
+  if (!A || !a_views || !W || !C || !c_views || !aux || !M || !N || !K) return fail(MRA_EINVAL, "null argument array");
+  GemmProb ps[2];
+  for (int i = 0; i < nprob; ++i) {
+    GemmProb& p = ps[i];
+    p = GemmProb{};
+    if (!A[i] || !W[i] || !C[i] || !aux[i]) return fail(MRA_EINVAL, "null A, W, C or aux");
+    if (!dbg_view8(a_views + 3 * i, &p.a)) return fail(MRA_EINVAL, "the A view needs rows per item > 0 and strides that are multiples of 8");
+    if (!dbg_view(c_views + 3 * i, &p.c)) return fail(MRA_EINVAL, "the C view needs rows per item > 0 and strides that are multiples of 4");
+    if (!dbg_aligned(A[i], 16) || !dbg_aligned(W[i], 16) || !dbg_aligned(C[i], 8) || !dbg_aligned(aux[i], 8) || (bias && !dbg_aligned(bias[i], 16)))
+      return fail(MRA_EINVAL, "misaligned buffer");
+    p.A = A[i]; p.W = W[i]; p.bias = bias ? bias[i] : nullptr; p.C = C[i]; p.aux = aux[i];
+    p.M = M[i]; p.N = N[i]; p.K = K[i];
+    if (p.M > 0 && (p.a.ld < p.K || p.c.ld < p.N)) return fail(MRA_EINVAL, "row stride below the row length");
+  }
+  ps[0].tile_cfg = tile_cfg;   // the first problem decides (Ctx::gemm2)
+  const int epi = backward ? EPI_GELU_BWD : EPI_GELU_BOTH;
+  GemmPlan pl;
+  pl.cus = 0;
+  const int rc = gemm_plan(ps, nprob, epi, op, &pl);
+  if (rc) return fail(MRA_EINVAL, rc == -2 ? "the tile has no such epilogue" : "gemm_plan refuses the problem (M, N > 0, K % 64, N % tile)");
+  return chk(launch_gemm(ps, nprob, epi, op, as_stream(stream)), "gemm gelu");
+}
+
 }  // extern "C"
