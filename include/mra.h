@@ -609,6 +609,52 @@ int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_vi
                         const int64_t* c_views, void* const* aux, const int32_t* M, const int32_t* N, const int32_t* K, int32_t backward, int32_t tile_cfg,
                         int32_t dtype, void* stream);
 
+/* The forward GEMMs, one launch each, through launch_gemm (tests/test_gpu_gemm_forward.py): the launch forms of mra_qformer_forward*,
+ * mra_kv_project and mra_llm_proj.  No handle, no allocation.  A launch is 1 .. 4 problem descriptors; the descriptor mirrors the GemmProb
+ * fields of csrc/kernels.h that those forwards set (see there for their meaning) and ADDS the byte size of every buffer handed over, so
+ * the entry can check the whole read and write footprint on the host before anything is launched.
+ *   struct_bytes   sizeof(mra_gemm_desc) as the caller sees it; a mismatch is refused, not misread
+ *   *_view         row views, HOST triples {item_stride, rows per item, row stride} in elements
+ *   *_bytes        bytes addressable from the pointer of the same name (0 with a NULL pointer)
+ * mra_debug_gemm: epilogue one of EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART, EPI_RES_LN (0 .. 5, 9); dtype MRA_F16 /
+ *   MRA_BF16.  gemm_plan runs first (it picks the tile every footprint below is computed with); then refused with MRA_EINVAL and a message:
+ *   a NULL A / W / C; A, W, C, R, bias, the LayerNorm buffers or pscale not 16-byte aligned (stat_m, stat_l, ln_counter: 4); an A view whose
+ *   strides are not multiples of 8 or a batch stride the vector accesses cannot take (a_bs, w_bs: 8 elements; c_bs_bytes: 16 bytes;
+ *   bias_bs: 4); a row stride below the row length (A: K; C, R and the LayerNorm outputs: the columns
+ *   written, i.e. ceil(N / tile) * tile with n_ragged and for EPI_SOFTPART); w_ld < N; a negative batch or stride; and ANY problem whose
+ *   footprint leaves the given sizes --
+ *     A        rows of the view x K elements, + (batch - 1) a_bs
+ *     W        [N][K] ([N][K / 2] with w_kwrap; (k_rows - 1) w_ld + N with w_ld), + (batch - 1) w_bs
+ *     bias     N floats, + (batch - 1) bias_bs
+ *     C, R     rows of the view x columns written, + (batch - 1) c_bs_bytes (R is not batched); EPI_KV: (N / (kv_heads * 64)) x kv_items x
+ *              kv_heads x kv_tokens x 64 elements, with N a multiple of kv_heads * 64 and M <= kv_items * kv_tokens
+ *     stat_*   batch x M x ntiles floats          pscale   batch x ps_ntiles x 512 floats (M <= 384)
+ *     ln_*     N floats of gain and bias, the output rows of the views, ceil(M / 64) counters; the counter ranges of two EPI_RES_LN problems
+ *              of one launch must not overlap
+ *   What the entry cannot see is device DATA: with pscale the caller keeps A zero from column ps_ntiles * 176 on, and the counters zero.
+ * mra_debug_gemm_plan: host only, no GPU needed and no pointer followed: the same checks over the same descriptors -- every refusal above --
+ *   and gemm_plan for a device of `cus` compute units, without the launch.  out[0 .. 6] = tile (GemmTile), family (GemmFamily), threads, LDS
+ *   bytes, grid, persistent flag, total tiles. */
+typedef struct mra_gemm_desc {
+  uint64_t struct_bytes;
+  const void* A; const void* W; const float* bias; void* C; const float* R;
+  int64_t a_view[3], c_view[3], r_view[3];
+  int32_t M, N, K;
+  int32_t kv_tokens, kv_items, kv_heads;
+  int32_t batch, bias_bs;
+  int64_t a_bs, w_bs, c_bs_bytes;
+  int32_t n_ragged, w_ld, k_rows, w_kwrap;
+  const float* ln_gain; const float* ln_bias; float* ln_y32; void* ln_y16; uint32_t* ln_counter;
+  int64_t ln_y32_view[3], ln_y16_view[3];
+  float ln_eps, alpha;
+  float* stat_m; float* stat_l; const float* pscale;
+  int32_t ps_ntiles, tile_cfg, persist, reserved;
+  uint64_t a_bytes, w_bytes, bias_bytes, c_bytes, r_bytes, ln_gain_bytes, ln_bias_bytes, ln_y32_bytes, ln_y16_bytes, ln_counter_bytes, stat_m_bytes,
+      stat_l_bytes, pscale_bytes;
+} mra_gemm_desc;
+int mra_debug_gemm(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, void* stream);
+int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, int32_t cus, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,29 @@ class mra_beats_cfg(C.Structure):
                 ("gate_from", C.c_int32), ("op_dtype", C.c_int32)]
 
 
+class mra_gemm_desc(C.Structure):
+    """include/mra.h mra_gemm_desc: one problem of mra_debug_gemm / mra_debug_gemm_plan (the GemmProb fields of csrc/kernels.h the forwards
+    set, plus the byte size of every buffer).  ``struct_bytes`` must be ``ctypes.sizeof(mra_gemm_desc)``."""
+    _fields_ = [
+        ("struct_bytes", C.c_uint64),
+        ("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("C", C.c_void_p), ("R", C.c_void_p),
+        ("a_view", C.c_int64 * 3), ("c_view", C.c_int64 * 3), ("r_view", C.c_int64 * 3),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("kv_tokens", C.c_int32), ("kv_items", C.c_int32), ("kv_heads", C.c_int32),
+        ("batch", C.c_int32), ("bias_bs", C.c_int32),
+        ("a_bs", C.c_int64), ("w_bs", C.c_int64), ("c_bs_bytes", C.c_int64),
+        ("n_ragged", C.c_int32), ("w_ld", C.c_int32), ("k_rows", C.c_int32), ("w_kwrap", C.c_int32),
+        ("ln_gain", C.c_void_p), ("ln_bias", C.c_void_p), ("ln_y32", C.c_void_p), ("ln_y16", C.c_void_p), ("ln_counter", C.c_void_p),
+        ("ln_y32_view", C.c_int64 * 3), ("ln_y16_view", C.c_int64 * 3),
+        ("ln_eps", C.c_float), ("alpha", C.c_float),
+        ("stat_m", C.c_void_p), ("stat_l", C.c_void_p), ("pscale", C.c_void_p),
+        ("ps_ntiles", C.c_int32), ("tile_cfg", C.c_int32), ("persist", C.c_int32), ("reserved", C.c_int32),
+        ("a_bytes", C.c_uint64), ("w_bytes", C.c_uint64), ("bias_bytes", C.c_uint64), ("c_bytes", C.c_uint64), ("r_bytes", C.c_uint64),
+        ("ln_gain_bytes", C.c_uint64), ("ln_bias_bytes", C.c_uint64), ("ln_y32_bytes", C.c_uint64), ("ln_y16_bytes", C.c_uint64),
+        ("ln_counter_bytes", C.c_uint64), ("stat_m_bytes", C.c_uint64), ("stat_l_bytes", C.c_uint64), ("pscale_bytes", C.c_uint64),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/mra.h declares (tests check this)
 PROTOTYPES = {
     "mra_cfg_default": (None, [C.POINTER(mra_cfg), C.c_int32]),
@@ -161,14 +184,21 @@ PROTOTYPES = {
     "mra_debug_gemm_gelu": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mra_debug_gemm": (C.c_int, [C.POINTER(mra_gemm_desc), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mra_debug_gemm_plan": (C.c_int, [C.POINTER(mra_gemm_desc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
 }
 
 # GemmFamily / GemmEpi codes of mra_debug_gemm_launches (csrc/kernels.h)
 GF_V1_64, GF_V1_128, GF_WS_256, GF_P8_256, GF_WS_128x384, GF_WS_176x384, GF_K128_64x128, GF_P8_TAIL, GF_P8_MIXED, GF_K128_64x64 = 0, 1, 3, 4, 5, 6, 7, 8, 9, 10
+GF_RING_144x128, GF_RING_192x128, GF_RING_96x64 = 11, 12, 13                         # gemm_ring_kernel: the layer chain's exact-fit tiles
+GEMM_FAMILIES = 14
 EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART, EPI_RES_OP = 0, 1, 2, 3, 4, 5, 8
 EPI_RES_F32_STAT, EPI_LNF_OP, EPI_LNF_GELU_OP, EPI_RES_OP_STAT = 10, 11, 12, 13     # the ViT's folded LayerNorms (csrc/kernels.h)
 EPI_GELU_BOTH, EPI_GELU_BWD = 6, 7                                                   # the training step's feed-forward epilogues
+EPI_RES_LN = 9                                                                       # EPI_RES_F32 + the LayerNorm of the finished rows (ring 96 x 64)
 GT_AUTO, GT_64, GT_128, GT_256 = 0, 1, 2, 3                                          # GemmTile codes mra_debug_gemm_gelu takes
+GT_WS_128x384, GT_WS_176x384, GT_K128_64x128, GT_P8_TAIL, GT_P8_MIXED = 4, 5, 6, 7, 8   # ... and the further ones of mra_debug_gemm
+GT_RING_144x128, GT_RING_192x128, GT_RING_96x64 = 9, 10, 11
 GEMM_TN_MAX_JOBS = 4
 
 

@@ -1666,4 +1666,178 @@ int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_vi
   return chk(launch_gemm(ps, nprob, epi, op, as_stream(stream)), "gemm gelu");
 }
 
+// ---- the forward GEMMs, one launch each (include/mra.h; tests/test_gpu_gemm_forward.py) ----------------------------------------------------
+namespace {
+typedef unsigned __int128 u128;   // footprints are products of caller-given 63-bit strides and 31-bit counts
+
+// elements from the view's base to one past column cols - 1 of the farthest of its first `rows` rows
+u128 dbg_extent(const RowView& v, long long rows, long long cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  const long long last_item = (rows - 1) / v.rpi, last_row = (rows - 1) % v.rpi;
+  u128 far = (u128)last_item * (u128)v.item_stride + (u128)last_row * (u128)v.ld;
+  if (last_item > 0) {   // a full item before the last one may reach further (item stride below rpi * ld)
+    const u128 full = (u128)(last_item - 1) * (u128)v.item_stride + (u128)(v.rpi - 1) * (u128)v.ld;
+    if (full > far) far = full;
+  }
+  return far + (u128)cols;
+}
+bool dbg_fits(u128 elements, size_t esz, u128 extra_bytes, uint64_t have) { return elements * esz + extra_bytes <= (u128)have; }
+
+// the descriptor -> GemmProb, everything that needs no tile checked; nullptr or the reason for a refusal
+const char* dbg_gemm_prob(const mra_gemm_desc& d, int epi, GemmProb* out) {
+  GemmProb& p = *out;
+  p = GemmProb{};
+  if (d.struct_bytes != sizeof(mra_gemm_desc)) return "struct_bytes is not sizeof(mra_gemm_desc)";
+  if (!d.A || !d.W || !d.C) return "null A, W or C";
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0) return "M, N and K must be positive";
+  if (d.batch < 0 || d.batch > 65535 || d.a_bs < 0 || d.w_bs < 0 || d.c_bs_bytes < 0 || d.bias_bs < 0) return "negative batch count or batch stride (batch <= 65535)";
+  if (d.n_ragged < 0 || d.n_ragged > 1 || d.persist < 0 || d.persist > 1 || d.w_ld < 0 || d.k_rows < 0 || d.w_kwrap < 0 || d.ps_ntiles < 0)
+    return "n_ragged and persist are 0 or 1; w_ld, k_rows, w_kwrap and ps_ntiles are not negative";
+  if (d.tile_cfg < GT_AUTO || d.tile_cfg >= GEMM_TILES || d.tile_cfg == GT_P8_TAIL || d.tile_cfg == GT_P8_MIXED) return "tile_cfg outside the forward's tiles";
+  if (!dbg_view8(d.a_view, &p.a)) return "the A view needs rows per item > 0 and strides that are non-negative multiples of 8";
+  if (epi == EPI_KV) p.c = RowView{0, 1, 1};
+  else if (!dbg_view(d.c_view, &p.c)) return "the C view needs rows per item > 0 and strides that are non-negative multiples of 4";
+  const bool res = epi == EPI_RES_F32 || epi == EPI_RES_LN;
+  if (res && (!d.R || !dbg_view(d.r_view, &p.r))) return "the residual needs a pointer and a view with strides that are multiples of 4";
+  if (!dbg_aligned(d.A, 16) || !dbg_aligned(d.W, 16) || !dbg_aligned(d.C, 16) || !dbg_aligned(d.bias, 16) || (res && !dbg_aligned(d.R, 16)))
+    return "A, W, C, R and bias must be 16-byte aligned";
+  if (d.batch > 1 && ((d.a_bs & 7) || (d.w_bs & 7) || (d.c_bs_bytes & 15) || (d.bias_bs & 3)))
+    return "batch strides: a_bs and w_bs multiples of 8 elements, c_bs_bytes of 16 bytes, bias_bs of 4 floats";
+  if (d.batch > 1 && (epi == EPI_KV || epi == EPI_RES_LN)) return "EPI_KV and EPI_RES_LN take no batch";
+  if (p.a.ld < d.K) return "A row stride below K";
+  if (d.w_ld && d.w_ld < d.N) return "w_ld below N";
+  p.A = d.A; p.W = d.W; p.bias = d.bias; p.C = d.C; p.R = res ? d.R : nullptr;
+  p.M = d.M; p.N = d.N; p.K = d.K;
+  p.kv_tokens = d.kv_tokens; p.kv_items = d.kv_items; p.kv_heads = d.kv_heads;
+  p.batch = d.batch; p.a_bs = d.a_bs; p.w_bs = d.w_bs; p.c_bs_bytes = d.c_bs_bytes; p.bias_bs = d.bias_bs;
+  p.n_ragged = d.n_ragged; p.w_ld = d.w_ld; p.k_rows = d.k_rows; p.w_kwrap = d.w_kwrap;
+  p.tile_cfg = d.tile_cfg; p.persist = d.persist;
+  if (epi == EPI_KV) {
+    if (d.kv_tokens <= 0 || d.kv_items <= 0 || d.kv_heads <= 0 || d.kv_heads > 1024) return "EPI_KV needs kv_tokens, kv_items and kv_heads > 0";
+    if (d.N % (d.kv_heads * 64)) return "EPI_KV: N must be a multiple of kv_heads * 64";
+    if ((long long)d.M > (long long)d.kv_items * d.kv_tokens) return "EPI_KV: M exceeds kv_items * kv_tokens";
+  }
+  if (epi == EPI_RES_LN) {
+    if (!d.ln_gain || !d.ln_bias || !d.ln_counter || (!d.ln_y32 && !d.ln_y16)) return "EPI_RES_LN needs gain, bias, counters and an output";
+    if ((d.ln_y32 && !dbg_view(d.ln_y32_view, &p.ln_y32v)) || (d.ln_y16 && !dbg_view(d.ln_y16_view, &p.ln_y16v)))
+      return "a LayerNorm output view needs rows per item > 0 and strides that are multiples of 4";
+    if (!dbg_aligned(d.ln_gain, 16) || !dbg_aligned(d.ln_bias, 16) || !dbg_aligned(d.ln_y32, 16) || !dbg_aligned(d.ln_y16, 16) || !dbg_aligned(d.ln_counter, 4))
+      return "the LayerNorm buffers must be 16-byte aligned (counters: 4)";
+    if (!(d.ln_eps >= 0.f)) return "ln_eps must not be negative";
+    p.ln_gain = d.ln_gain; p.ln_bias = d.ln_bias; p.ln_eps = d.ln_eps; p.ln_y32 = d.ln_y32; p.ln_y16 = d.ln_y16; p.ln_counter = d.ln_counter;
+  }
+  if (epi == EPI_SOFTPART) {
+    if (!d.stat_m || !d.stat_l || !dbg_aligned(d.stat_m, 4) || !dbg_aligned(d.stat_l, 4)) return "EPI_SOFTPART needs stat_m and stat_l (4-byte aligned)";
+    if (!(d.alpha > 0.f) || !(d.alpha < 3.0e38f)) return "EPI_SOFTPART needs a finite alpha > 0";
+    p.alpha = d.alpha; p.stat_m = d.stat_m; p.stat_l = d.stat_l;
+  }
+  if (d.pscale) {
+    if (!dbg_aligned(d.pscale, 16)) return "pscale must be 16-byte aligned";
+    if (d.M > 384) return "pscale needs M <= 384 (one row tile)";
+    p.pscale = d.pscale; p.ps_ntiles = d.ps_ntiles;
+  }
+  return nullptr;
+}
+
+const char* dbg_gemm_epi_ok(int epi) {
+  switch (epi) {
+    case EPI_OP: case EPI_GELU_OP: case EPI_RES_F32: case EPI_F32: case EPI_KV: case EPI_SOFTPART: case EPI_RES_LN: return nullptr;
+  }
+  return "epilogue must be EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART or EPI_RES_LN";
+}
+
+// weight rows (output columns) of a family's tile: what n_ragged and EPI_SOFTPART round the written columns up to (the kTiles table of gemm.hip)
+int dbg_tile_cols(int family) {
+  switch (family) {
+    case GF_V1_64: case GF_K128_64x128: case GF_K128_64x64: return 64;
+    case GF_V1_128: case GF_WS_128x384: case GF_P8_TAIL: return 128;
+    case GF_V1_256: case GF_WS_256: case GF_P8_256: case GF_P8_MIXED: return 256;
+    case GF_WS_176x384: return 176;
+    case GF_RING_144x128: return 144;
+    case GF_RING_192x128: return 192;
+    case GF_RING_96x64: return 96;
+  }
+  return 0;
+}
+
+// the read and write footprint of problem d under the plan's tile against the sizes the caller gave
+const char* dbg_gemm_footprint(const mra_gemm_desc& d, const GemmProb& p, const GemmPlan& pl, int g, int epi) {
+  const long long nb = d.batch > 1 ? d.batch : 1;
+  const long long ntiles = pl.args.p[g].ntiles;
+  const long long cols = (d.n_ragged || epi == EPI_SOFTPART) ? ntiles * dbg_tile_cols(pl.family) : d.N;   // columns of C a tile row writes
+  const size_t csz = (epi == EPI_RES_F32 || epi == EPI_F32 || epi == EPI_RES_LN) ? 4 : 2;
+  if ((d.n_ragged || epi == EPI_SOFTPART) && (cols < d.N || ntiles != (d.N + dbg_tile_cols(pl.family) - 1) / dbg_tile_cols(pl.family))) return "unknown tile";
+  if (!dbg_fits(dbg_extent(p.a, d.M, d.K) + (u128)(nb - 1) * (u128)d.a_bs, 2, 0, d.a_bytes)) return "A: the view, K and the batch stride leave a_bytes";
+  u128 w = d.w_ld ? (u128)(d.k_rows - 1) * (u128)d.w_ld + (u128)d.N : (u128)d.N * (u128)(d.w_kwrap ? d.K / 2 : d.K);
+  if (!dbg_fits(w + (u128)(nb - 1) * (u128)d.w_bs, 2, 0, d.w_bytes)) return "W: N, K (w_ld, k_rows, w_kwrap) and the batch stride leave w_bytes";
+  if (d.bias && !dbg_fits((u128)d.N + (u128)(nb - 1) * (u128)d.bias_bs, 4, 0, d.bias_bytes)) return "bias: N and the batch stride leave bias_bytes";
+  if (epi == EPI_KV) {
+    const u128 n = (u128)(d.N / (d.kv_heads * 64)) * (u128)d.kv_items * (u128)d.kv_heads * (u128)d.kv_tokens * 64;
+    if (!dbg_fits(n, 2, 0, d.c_bytes)) return "C: the head-major scatter leaves c_bytes";
+  } else {
+    if (p.c.ld < cols) return "C row stride below the columns written (ceil(N / tile) * tile with n_ragged and EPI_SOFTPART)";
+    if (!dbg_fits(dbg_extent(p.c, d.M, cols), csz, (u128)(nb - 1) * (u128)d.c_bs_bytes, d.c_bytes)) return "C: the view, the columns written and the batch stride leave c_bytes";
+  }
+  if (p.R) {
+    if (p.r.ld < d.N) return "R row stride below N";
+    if (!dbg_fits(dbg_extent(p.r, d.M, d.N), 4, 0, d.r_bytes)) return "R: the view leaves r_bytes";
+  }
+  if (epi == EPI_SOFTPART) {
+    const u128 n = (u128)nb * (u128)d.M * (u128)ntiles;
+    if (!dbg_fits(n, 4, 0, d.stat_m_bytes) || !dbg_fits(n, 4, 0, d.stat_l_bytes)) return "stat_m / stat_l: batch * M * ntiles floats leave their sizes";
+  }
+  if (p.pscale && !dbg_fits((u128)nb * (u128)d.ps_ntiles * 512, 4, 0, d.pscale_bytes)) return "pscale: batch * ps_ntiles * 512 floats leave pscale_bytes";
+  if (epi == EPI_RES_LN) {
+    if (!dbg_fits((u128)d.N, 4, 0, d.ln_gain_bytes) || !dbg_fits((u128)d.N, 4, 0, d.ln_bias_bytes)) return "ln_gain / ln_bias: N floats leave their sizes";
+    if (p.ln_y32 && (p.ln_y32v.ld < d.N || !dbg_fits(dbg_extent(p.ln_y32v, d.M, d.N), 4, 0, d.ln_y32_bytes))) return "ln_y32: row stride below N, or the view leaves ln_y32_bytes";
+    if (p.ln_y16 && (p.ln_y16v.ld < d.N || !dbg_fits(dbg_extent(p.ln_y16v, d.M, d.N), 2, 0, d.ln_y16_bytes))) return "ln_y16: row stride below N, or the view leaves ln_y16_bytes";
+    if (!dbg_fits((u128)((d.M + 63) / 64), 4, 0, d.ln_counter_bytes)) return "ln_counter: ceil(M / 64) counters leave ln_counter_bytes";
+  }
+  return nullptr;
+}
+
+// descriptors -> problems + plan; every refusal of mra_debug_gemm (none needs a device: mra_debug_gemm_plan makes the same).  0 or MRA_EINVAL (message set).
+int dbg_gemm_prepare(const mra_gemm_desc* probs, int32_t nprob, int32_t epi, int32_t dtype, int cus, GemmProb* ps, GemmPlan* pl, int* op) {
+  if (nprob < 1 || nprob > GEMM_MAX_GROUPS) return fail(MRA_EINVAL, "1 .. 4 problems");
+  if (!dbg_op(dtype, op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (const char* e = dbg_gemm_epi_ok(epi)) return fail(MRA_EINVAL, e);
+  if (!probs) return fail(MRA_EINVAL, "null descriptor array");
+  for (int i = 0; i < nprob; ++i)
+    if (const char* e = dbg_gemm_prob(probs[i], epi, &ps[i])) return fail(MRA_EINVAL, "problem " + std::to_string(i) + ": " + e);
+  pl->cus = cus;
+  const int rc = gemm_plan(ps, nprob, epi, *op, pl);
+  if (rc) return fail(MRA_EINVAL, rc == -2 ? "the tile has no such epilogue" : "gemm_plan refuses the launch (K % 64, N % tile, what the tile or the epilogue allows)");
+  for (int i = 0; i < nprob; ++i)
+    if (const char* e = dbg_gemm_footprint(probs[i], ps[i], *pl, i, epi)) return fail(MRA_EINVAL, "problem " + std::to_string(i) + ": " + e);
+  if (epi == EPI_RES_LN)
+    for (int i = 0; i < nprob; ++i)
+      for (int j = i + 1; j < nprob; ++j) {
+        const uintptr_t a0 = (uintptr_t)ps[i].ln_counter, a1 = a0 + 4 * (uintptr_t)((ps[i].M + 63) / 64);
+        const uintptr_t b0 = (uintptr_t)ps[j].ln_counter, b1 = b0 + 4 * (uintptr_t)((ps[j].M + 63) / 64);
+        if (a0 < b1 && b0 < a1) return fail(MRA_EINVAL, "the counter ranges of two EPI_RES_LN problems overlap");
+      }
+  return MRA_OK;
+}
+}  // namespace
+
+int mra_debug_gemm(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, void* stream) {
+  GemmProb ps[GEMM_MAX_GROUPS];
+  static thread_local GemmPlan pl;   // (a plan carries the kernel argument: ~2 KB)
+  int op;
+  if (const int rc = dbg_gemm_prepare(probs, nprob, epilogue, dtype, 0, ps, &pl, &op)) return rc;
+  return chk(launch_gemm(ps, nprob, epilogue, op, as_stream(stream)), "debug gemm");
+}
+
+int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, int32_t cus, int32_t* out) {
+  GemmProb ps[GEMM_MAX_GROUPS];
+  static thread_local GemmPlan pl;
+  int op;
+  if (!out) return fail(MRA_EINVAL, "null out");
+  if (cus < 0) return fail(MRA_EINVAL, "negative cus");
+  if (const int rc = dbg_gemm_prepare(probs, nprob, epilogue, dtype, cus, ps, &pl, &op)) return rc;
+  const int32_t r[7] = {pl.tile, pl.family, pl.threads, pl.lds, pl.grid, pl.persistent, pl.args.total_tiles};
+  for (int i = 0; i < 7; ++i) out[i] = r[i];
+  return MRA_OK;
+}
+
 }  // extern "C"

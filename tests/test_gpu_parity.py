@@ -420,7 +420,7 @@ def test_layer_chain_on_the_ring_tiles_and_with_the_layernorm_inside_the_launch(
     torch.set_num_threads(max(1, min(32, len(os.sched_getaffinity(0)))))
     with torch.no_grad():
         ref = O.qformer_forward(w, oracle_cfg(cfg), ids, att, w["query_tokens"].expand(n, -1, -1), enc.float().cpu())
-    GF_RING = (11, 12, 13)                      # GemmFamily: ring 144 x 128, 192 x 128, 96 x 64
+    GF_RING = (L.GF_RING_144x128, L.GF_RING_192x128, L.GF_RING_96x64)
     outs = {}
     for mask in (0, 7, 15):
         qf.set_option("chain_ring", mask)
