@@ -118,6 +118,27 @@ int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t*
                         int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* The same forward over RAW encoder features: `enc` [items, kv, enc_width] is what mra_modality_ln would READ (operand dtype, contiguous,
+ * no item gather), and no normalised copy is made.  The modality LayerNorm lives in the folded cross-attention instead: its gain and the
+ * centring inside the key / value weights (W' = W diag(g) with every row centred over enc_width, so W LN(x) = r (W' x) + W b and the token
+ * mean never appears), its bias inside the value bias, and the token factors r = 1 / sqrt(var + enc_ln_eps) are computed by cross layer 0's
+ * scores launch from the token rows as they stream through its LDS, applied to the score columns, and kept in the workspace for the
+ * later cross layers.  Only the folded form on the 176 x 384 tiles with in-register row factors, in operand precision:
+ *   mra_qformer_raw_features_ok(h, kv, x_dtype)   1 when a forward of h over kv tokens per item of dtype x_dtype can take raw features --
+ *       folded form (cross mode 2, or 0 with kv >= 2048; not the streaming kernels, not the separate rescale pass), heads * n_query == 384,
+ *       enc_width a multiple of 176, x_dtype the operand dtype, ln.weight and ln.bias loaded, no split precision and no pending or
+ *       split-resolved automatic precision, and mra_qformer_set_option "raw_features" not 0.  Otherwise 0: run mra_modality_ln and
+ *       mra_qformer_forward, whose results do not change.
+ *   mra_qformer_forward_raw   arguments, checks and workspace as mra_qformer_forward; MRA_ESTATE where mra_qformer_raw_features_ok says 0.
+ * The folded weights are rounded to the operand dtype AFTER centring, so a token's mean mu meets their rounding error uncancelled: against
+ * the normalised-copy path the scores err by about 2^-11 |mu| / sigma relative (f16) on top of the operand rounding both paths share.
+ * Features whose mean over enc_width is many standard deviations from zero are better served by mra_modality_ln. */
+int mra_qformer_raw_features_ok(mra_qformer* h, int32_t kv, int32_t x_dtype);
+int mra_qformer_forward_raw(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask,
+                            const float* query_embeds, int32_t query_items, const void* enc, int32_t items, int32_t L,
+                            int32_t kv, float* out_query, float* out_full, float* out_cls, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* The dominant launch of the forward on its own (what bench.py prices against the MFMA roofline):
  * K and V of every cross-attention layer, enc [items*kv, enc_width] x Wkv[n_cross*2*hidden, enc_width]^T
  * + bias, written head-major into kv_cache [n_cross][2][items][heads][kv][64] (operand dtype,
@@ -139,6 +160,12 @@ size_t mra_qformer_pair_workspace_bytes(mra_qformer* h0, mra_qformer* h1, int32_
 int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
                              const void* enc1, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0, float* out_cls0,
                              float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream);
+/* The same with RAW encoder features for the lanes whose bit is set in raw_mask (bit 0: enc0, bit 1: enc1), each as mra_qformer_forward_raw
+ * takes them (MRA_ESTATE where mra_qformer_raw_features_ok says 0 for that lane); raw_mask 0 is mra_qformer_forward_pair.  Per lane the
+ * launches and the results are those of the lane's own mra_qformer_forward / mra_qformer_forward_raw call. */
+int mra_qformer_forward_pair_raw(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
+                                 const void* enc1, int32_t raw_mask, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0,
+                                 float* out_cls0, float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Multi-prompt forward: `prompts` prompts per encoder item over ONE shared K/V cache.
  * replaces: model.{modality}_Qformer.bert(...) (models/xinstructblip.py:286-293) as evaluate.py:42-44 calls it once per (vid, query)
@@ -222,6 +249,7 @@ int mra_qformer_cross_precision_report(mra_qformer* h, int32_t* resolved, int32_
  *                 launch (the last-arriving column tile of a 64-row block normalises it).  DESIGN.md section 8.
  *   "train_ring"  the same mask (bits 0 and 2) for the GEMMs of mra_qformer_forward_train / mra_qformer_backward; default 4.
  *   "auto_split_pmax_milli"  tau of the automatic cross-attention precision in thousandths, 0..1000 (default 500); applies from the next probe.
+ *   "raw_features"  1 (default): mra_qformer_raw_features_ok may answer yes; 0: it answers no (A/B against the normalised-copy path).
  *   "multi_core"  the cross core of mra_qformer_forward_multi with prompts > 1: 0 the core of mra_qformer_forward, each chain item taking the
  *                 K/V of its encoder item; 1 the shared-stream core (one workgroup per encoder item, head and 4 prompt slots, the K/V tiles
  *                 staged once into a workgroup-shared LDS ring).  Default 1 (faster at P >= 4 on both shapes of tools/bench_multi_query.py, by 0.2 - 2.3 %;
@@ -629,6 +657,7 @@ int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_vi
  *     C, R     rows of the view x columns written, + (batch - 1) c_bs_bytes (R is not batched); EPI_KV: (N / (kv_heads * 64)) x kv_items x
  *              kv_heads x kv_tokens x 64 elements, with N a multiple of kv_heads * 64 and M <= kv_items * kv_tokens
  *     stat_*   batch x M x ntiles floats          pscale   batch x ps_ntiles x 512 floats (M <= 384)
+ *     col_scale  N floats, + (batch - 1) cs_bs (EPI_SOFTPART on the 176 x 384 tile only; cs_bs >= N with a batch)
  *     ln_*     N floats of gain and bias, the output rows of the views, ceil(M / 64) counters; the counter ranges of two EPI_RES_LN problems
  *              of one launch must not overlap
  *   What the entry cannot see is device DATA: with pscale the caller keeps A zero from column ps_ntiles * 176 on, and the counters zero.
@@ -651,6 +680,11 @@ typedef struct mra_gemm_desc {
   int32_t ps_ntiles, tile_cfg, persist, reserved;
   uint64_t a_bytes, w_bytes, bias_bytes, c_bytes, r_bytes, ln_gain_bytes, ln_bias_bytes, ln_y32_bytes, ln_y16_bytes, ln_counter_bytes, stat_m_bytes,
       stat_l_bytes, pscale_bytes;
+  /* EPI_SOFTPART on the 176 x 384 tile over RAW weight-side rows (appended; all zero = off): column n of batch entry b carries the factor
+   * col_scale[b * cs_bs + n] -- read, or with col_stats = 1 computed in the launch from the rows themselves (1 / sqrt(biased variance over K
+   * + cs_eps)) and written there for n < N.  C = T(exp2(alpha r acc - stat_m) r), stat_m over r acc, stat_l the fp32 sum of the exponentials. */
+  float* col_scale; int64_t cs_bs; int32_t col_stats; float cs_eps;
+  uint64_t col_scale_bytes;
 } mra_gemm_desc;
 int mra_debug_gemm(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, void* stream);
 int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, int32_t cus, int32_t* out);

@@ -63,6 +63,8 @@ class mra_gemm_desc(C.Structure):
         ("a_bytes", C.c_uint64), ("w_bytes", C.c_uint64), ("bias_bytes", C.c_uint64), ("c_bytes", C.c_uint64), ("r_bytes", C.c_uint64),
         ("ln_gain_bytes", C.c_uint64), ("ln_bias_bytes", C.c_uint64), ("ln_y32_bytes", C.c_uint64), ("ln_y16_bytes", C.c_uint64),
         ("ln_counter_bytes", C.c_uint64), ("stat_m_bytes", C.c_uint64), ("stat_l_bytes", C.c_uint64), ("pscale_bytes", C.c_uint64),
+        ("col_scale", C.c_void_p), ("cs_bs", C.c_int64), ("col_stats", C.c_int32), ("cs_eps", C.c_float),
+        ("col_scale_bytes", C.c_uint64),
     ]
 
 
@@ -82,9 +84,15 @@ PROTOTYPES = {
     "mra_qformer_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    "mra_qformer_raw_features_ok": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mra_qformer_forward_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
     "mra_qformer_pair_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mra_qformer_forward_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mra_qformer_forward_pair_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mra_qformer_multi_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mra_qformer_forward_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

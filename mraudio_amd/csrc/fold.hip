@@ -275,4 +275,49 @@ int launch_transpose_pad(const void* src, void* dst, int R, int C, int ld_d, lon
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+namespace {
+// One workgroup per weight row n: w'_e = w_e g_e - mean_e(w g) in fp32, rounded once; bias_out[n] = bias_in[n] + sum_e w_e b_e.
+// (Run once per weight upload, from mra_qformer_prepare.)
+template <typename T, typename TW, bool KEY>
+__global__ void __launch_bounds__(256) fold_ln_weight_kernel(const TW* W, int E, const float* gain, const float* ln_bias, const float* bias_in,
+                                                             T* dst, float* bias_out) {
+  __shared__ float red[8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = blockIdx.x;
+  const TW* w = W + (long long)n * E;
+  float s = 0.f, sb = 0.f;
+  for (int e = tid; e < E; e += 256) {
+    const float we = (float)w[e];
+    s += we * gain[e];
+    sb = __builtin_fmaf(we, ln_bias[e], sb);
+  }
+  s = wave_sum(s);
+  sb = wave_sum(sb);
+  if (lane == 0) { red[wave] = s; red[4 + wave] = sb; }
+  __syncthreads();
+  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / (float)E;
+  if (tid == 0 && bias_out) bias_out[n] = (bias_in ? bias_in[n] : 0.f) + ((red[4] + red[5]) + (red[6] + red[7]));
+  for (int e = tid; e < E; e += 256) {
+    const T o = from_f32<T>((float)w[e] * gain[e] - mean);
+    if (KEY) dst[((long long)(n >> 6) * E + e) * 64 + (n & 63)] = o;
+    else dst[(long long)n * E + e] = o;
+  }
+}
+}  // namespace
+
+int launch_fold_ln_weight(const void* W, int w32, int rows, int E, const float* gain, const float* ln_bias, const float* bias_in, void* dst,
+                          int key_layout, float* bias_out, int op_dtype, hipStream_t stream) {
+  if (rows <= 0 || E <= 0 || !W || !gain || !ln_bias || !dst || (key_layout && rows % 64)) return -1;
+#define MRA_FL(T, TW, KEY) hipLaunchKernelGGL((fold_ln_weight_kernel<T, TW, KEY>), dim3(rows), dim3(256), 0, stream, (const TW*)W, E, gain, ln_bias, bias_in, (T*)dst, bias_out)
+#define MRA_FL_T(T)                                                          \
+  do {                                                                       \
+    if (w32) { if (key_layout) MRA_FL(T, float, true); else MRA_FL(T, float, false); } \
+    else { if (key_layout) MRA_FL(T, T, true); else MRA_FL(T, T, false); }   \
+  } while (0)
+  if (op_dtype == OP_F16) MRA_FL_T(f16); else MRA_FL_T(bf16);
+#undef MRA_FL_T
+#undef MRA_FL
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 }  // namespace mra

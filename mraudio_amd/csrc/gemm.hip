@@ -299,9 +299,15 @@ __device__ __forceinline__ void accumulators_from_residual(const GemmProb& P, f3
 // EPI_SOFTPART (scores of the folded cross-attention): first half of a softmax split over column tiles.  Needs a wave
 // that holds whole tile rows (one column of compute waves): row m = lane & 15 of fragment j has its TN columns in the
 // four lanes with that lane & 15, so the tile maximum and tile sum of a row are two lane swaps away.
-template <typename T, int FN, int FM>
+// CSC (GemmProb::col_scale, raw tokens on the weight side): `sc` holds the tile's FN * 16 column factors r in LDS.  They are read from LDS
+// inside the loops (FN * 4 = 44 more live registers do not fit under the loader-wave kernels' 168-register cap).  The maximum is taken over
+// fl(r acc), the exponent is fma(fl(r acc), alpha, -max) <= 0, and C = T(p r).  stat_l is the fp32 sum of the exponentials p THEMSELVES, not of
+// what is stored: the stored T(p r) has no unscaled counterpart to sum (dividing it by r again would round a second time), its rounding
+// errors are independent of one another and of p, so the row sum the second half of the softmax divides by is off by ~u / sqrt(columns)
+// relative (5e-6 at the headline's 8224 columns, f16) -- two orders below the rounding of P~ itself.
+template <typename T, int FN, int FM, bool CSC = false>
 __device__ __forceinline__ void epilogue_softpart(const GemmProb& P, f32x4 (&acc)[FN][FM], int n0, int m_base, int tile, int batch_row0,
-                                                  int lane) {
+                                                  int lane, const float* sc = nullptr) {
   // VALU-bound (67.6 k exponentials per 176 x 384 tile, 13 k cycles per SIMD): the scale rides the exponent's fma, and the
   // column-limit compares exist only in the last, ragged tile (wave-uniform branch)
   const int lm = lane & 15, ln = (lane >> 4) * 4;
@@ -311,6 +317,15 @@ __device__ __forceinline__ void epilogue_softpart(const GemmProb& P, f32x4 (&acc
   for (int j = 0; j < FM; ++j) {
     const int m = m_base + j * 16 + lm;
     float mx = -3.0e38f;
+    if constexpr (CSC) {
+      // the factors multiply the accumulators in place (once per row fragment j: each accumulator belongs to one j)
+#pragma unroll
+      for (int i = 0; i < FN; ++i) {
+        const f32x4 r = *reinterpret_cast<const f32x4*>(sc + i * 16 + ln);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][j][e] *= r[e];
+      }
+    }
     if (full) {
 #pragma unroll
       for (int i = 0; i < FN; ++i)
@@ -333,12 +348,19 @@ __device__ __forceinline__ void epilogue_softpart(const GemmProb& P, f32x4 (&acc
     for (int i = 0; i < FN; ++i) {
       const int n = n0 + i * 16 + ln;
       typename Vec4<T>::type o;
+      f32x4 r;
+      if constexpr (CSC) r = *reinterpret_cast<const f32x4*>(sc + i * 16 + ln);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float p = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[i][j][e], alpha, -mx));
         if (!full && n + e >= P.N) p = 0.f;
-        o[e] = from_f32<T>(p);
-        l += (float)o[e];          // the sum of what the next GEMM will actually read
+        if constexpr (CSC) {
+          o[e] = from_f32<T>(p * r[e]);
+          l += p;                    // the exponentials themselves (see above)
+        } else {
+          o[e] = from_f32<T>(p);
+          l += (float)o[e];          // the sum of what the next GEMM will actually read
+        }
       }
       if (live) *reinterpret_cast<typename Vec4<T>::type*>((T*)P.C + coff + n) = o;
     }
@@ -658,7 +680,14 @@ __global__ void __launch_bounds__(WGN* WGM * 64) gemm_kernel(const GemmArgs args
 // (head, query) rows of an item against a 128-row slab of the other operand, so that operand streams once).
 // 176 x 384 with the 8 compute waves in one column (WGM = 8): P . enc of the folded path -- N = 1408 = 8 x 176, so
 // 32 items give exactly 256 workgroups, one per CU, and each streams its 176-row slab of enc^T exactly once.
-template <typename T, int EPI, bool NODMA = false, int TN = 256, int TM = 256, int WGM = 4, bool NTW = false, bool WKM = false, bool PSC = false>  // NODMA: diagnostic only (wrong results); NTW: non-temporal loads of the weight-side slab; WKM: K-major W (GemmProb::w_ld); PSC: GemmProb::pscale
+// CS (EPI_SOFTPART, GemmProb::col_scale): the weight-side rows are raw tokens and column n of the scores carries the LayerNorm factor r_n of
+// token n.  CS = 1 reads the tile's TN factors (loader wave 8, before the K loop; into LDS after it); CS = 2 computes them: every K step the
+// loader lane that staged chunk q of the weight-side rows reads it back from the landed buffer while tile kt + 1 is in flight (its own
+// bytes, behind its own vmcnt(0) and the barrier) and folds the chunk's mean and centred sum of squares into its running pair (Chan et al.:
+// no E[x^2] - mean^2 anywhere); after the loop the eight lanes of a row merge by lane swaps, r = 1 / sqrt(M2 / K + eps) goes to LDS -- into
+// the K buffer the last step did not use -- and, behind the one workgroup barrier both wave groups reach, wave 8 stores the tile's factors to
+// GemmProb::col_scale for the later layers.  A column tile belongs to one workgroup: no atomics, no waiting across workgroups.
+template <typename T, int EPI, bool NODMA = false, int TN = 256, int TM = 256, int WGM = 4, bool NTW = false, bool WKM = false, bool PSC = false, int CS = 0>  // NODMA: diagnostic only (wrong results); NTW: non-temporal loads of the weight-side slab; WKM: K-major W (GemmProb::w_ld); PSC: GemmProb::pscale
 __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
   constexpr int BK = 64, ROWB = BK * 2;
   constexpr int WGN = 8 / WGM, WTN = TN / WGN, WTM = TM / WGM, FN = WTN / 16, FM = WTM / 16;
@@ -668,6 +697,8 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
   constexpr int NCHUNK = (TN + TM) * 8, NLD = (NCHUNK + 255) / 256;  // 16-byte chunks of a K tile (W rows, then A rows) / loader lanes
   constexpr bool STAGED = (EPI == EPI_OP || EPI == EPI_GELU_OP || EPI == EPI_KV || EPI == EPI_RES_OP) && TN % 64 == 0;   // LDS-staged 16-bit epilogue
   static_assert(WTN % 16 == 0 && WTM % 16 == 0 && TN % 16 == 0 && NCHUNK % 64 == 0, "tile must split over the waves; whole waves per DMA piece");
+  static_assert(CS == 0 || (EPI == EPI_SOFTPART && !WKM && !PSC && TN * 4 <= BUF && TN <= 192), "column factors: the scores launch only; three per lane of one wave");
+  constexpr int NWS = (TN * 8 + 255) / 256;   // CS == 2: weight-side chunks per loader lane
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -736,6 +767,18 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
         }
       }
     };
+    // this batch entry's factors (batch_row0 = b * M; the offset is applied here, not in tile_of, so no other kernel carries it)
+    float* const cscale = CS != 0 ? P.col_scale + (long long)(P.batch_row0 / M) * P.cs_bs : nullptr;
+    float csv[3] = {0.f, 0.f, 0.f};   // CS == 1: the tile's factors, three per lane of wave 8 (columns past N: the last one's, never used)
+    if constexpr (CS == 1) {
+      if (wave == 8) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) csv[k] = cscale[min(n0 + min(lane + 64 * k, TN - 1), P.N - 1)];
+      }
+    }
+    float cmean[NWS], cm2[NWS];       // CS == 2: running mean and centred sum of squares of this lane's chunks (8 kt values so far)
+#pragma unroll
+    for (int i = 0; i < NWS; ++i) cmean[i] = cm2[i] = 0.f;
     stage(0, 0);
     stage_factors(0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -743,6 +786,64 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if (kt + 1 < nk && !(NODMA && kt >= 1)) { stage((kt + 1) & 1, kt + 1); stage_factors(kt + 1); }
+      if constexpr (CS == 2) {
+        // chunk q = lt + 256 i of buffer kt & 1 (this lane staged it): inline asm, so that no compiler wait on the DMA just issued sits
+        // in front of the reads
+        const unsigned cb = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem + (kt & 1) * BUF + lt * 16;
+        i32x4 raw[NWS];
+#pragma unroll
+        for (int i = 0; i < NWS; ++i)
+          if (i * 256 + wq0 < TN * 8) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(raw[i]) : "v"(cb), "n"(i * 4096) : "memory");
+        const float fk = 1.0f / (float)(kt + 1), fq = 8.0f * (float)kt * fk;   // merge weights of (8 kt values) + (8 values)
+#pragma unroll
+        for (int i = 0; i < NWS; ++i)
+          if (i * 256 + wq0 < TN * 8) {
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(raw[i])::"memory");   // (the first of these waits for all the reads, ~1 k cycles of VALU work follow)
+            const typename Vec8<T>::type v = __builtin_bit_cast(typename Vec8<T>::type, raw[i]);
+            float x[8], sum = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { x[e] = (float)v[e]; sum += x[e]; }
+            const float m8 = sum * 0.125f;
+            float q8 = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float d = x[e] - m8; q8 = __builtin_fmaf(d, d, q8); }
+            const float dl = m8 - cmean[i];
+            cmean[i] = __builtin_fmaf(dl, fk, cmean[i]);
+            cm2[i] = cm2[i] + q8 + dl * dl * fq;
+          }
+      }
+    }
+    if constexpr (CS != 0) {
+      float* scol = reinterpret_cast<float*>(smem + (nk & 1) * BUF);   // the K buffer the last step did not read: dead since barrier nk - 1
+      if constexpr (CS == 2) {
+        float cnt = 8.0f * (float)nk;   // values behind each lane's pair; equal on both sides of every swap
+#pragma unroll
+        for (int sw = 1; sw < 8; sw <<= 1) {
+#pragma unroll
+          for (int i = 0; i < NWS; ++i) {
+            const float om = __shfl_xor(cmean[i], sw), oq = __shfl_xor(cm2[i], sw);
+            const float dl = om - cmean[i];
+            cmean[i] = __builtin_fmaf(dl, 0.5f, cmean[i]);
+            cm2[i] = cm2[i] + oq + dl * dl * (0.5f * cnt);
+          }
+          cnt *= 2.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < NWS; ++i)
+          if (i * 256 + wq0 < TN * 8 && (lane & 7) == 0) scol[(lt + i * 256) >> 3] = 1.0f / __builtin_sqrtf(cm2[i] / cnt + P.cs_eps);
+      } else if (wave == 8) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (lane + 64 * k < TN) scol[lane + 64 * k] = csv[k];
+      }
+      __syncthreads();   // the factors are in LDS (the compute waves' only barrier after the K loop)
+      if constexpr (CS == 2) {
+        if (wave == 8) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k)
+            if (lane + 64 * k < TN && n0 + lane + 64 * k < P.N) cscale[n0 + lane + 64 * k] = scol[lane + 64 * k];
+        }
+      }
     }
     if constexpr (STAGED) {
       __syncthreads();  // K loop reads over
@@ -841,7 +942,12 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
   }
   if constexpr (EPI == EPI_SOFTPART) {
     static_assert(EPI != EPI_SOFTPART || WGN == 1, "the softmax-partial epilogue needs whole tile rows in one wave");
+    if constexpr (CS != 0) {
+      __syncthreads();   // the loader waves have left the tile's column factors in the K buffer the last step did not use
+      epilogue_softpart<T, FN, FM, true>(P, acc, n0, m0 + wm0, n0 / TN, P.batch_row0, lane, reinterpret_cast<const float*>(smem + (nk & 1) * BUF));
+    } else {
     epilogue_softpart<T, FN, FM>(P, acc, n0, m0 + wm0, n0 / TN, P.batch_row0, lane);
+    }
   } else if constexpr (STAGED) {
     __syncthreads();
     epilogue_lds16<T, TN, TM, FN, FM, 512, EPI>(P, acc, smem, n0, m0, wn0, wm0, tid);
@@ -1664,6 +1770,10 @@ int launch_family(const GemmPlan& pl, int epi, hipStream_t stream) {
         if (a.p[0].pscale) return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true, true>);
         return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true>);
       }
+      if (a.p[0].col_scale) {   // raw tokens on the weight side, their LayerNorm factors on the columns; EPI_SOFTPART (epilogue_rules)
+        if (a.p[0].col_stats) return go(gemm_ws_kernel<T, EPI_SOFTPART, false, 176, 384, 8, true, false, false, 2>);
+        return go(gemm_ws_kernel<T, EPI_SOFTPART, false, 176, 384, 8, true, false, false, 1>);
+      }
       // the slab (weight-side rows) is read by this workgroup only: non-temporal loads (7.40 -> 7.17 ms / step)
       return with_epi(EpiWs176{}, epi, [&](auto e) { return go(gemm_ws_kernel<T, e(), false, 176, 384, 8, true>); });
     case GF_K128_64x128: return with_epi(EpiDirect{}, epi, [&](auto e) { return go(gemm_k128_kernel<T, 64, 128, 2, 2, e()>); });
@@ -1756,7 +1866,7 @@ bool epilogue_rules(const GemmProb& p, int ngroups, int epi) {
     case EPI_RES_OP: return p.aux && !p.n_ragged;
     case EPI_GELU_BOTH:
     case EPI_GELU_BWD: return p.aux && !misaligned(p.c, 3) && !p.n_ragged;
-    case EPI_SOFTPART: return p.stat_m && p.stat_l && !p.bias && !(p.c.ld & 3);
+    case EPI_SOFTPART: return p.stat_m && p.stat_l && !p.bias && !(p.c.ld & 3) && (!p.col_stats || (p.col_scale && !p.w_kwrap && p.cs_eps >= 0.f));
     case EPI_RES_LN:
       return p.R && p.r.rpi > 0 && p.ln_gain && p.ln_bias && p.ln_counter && (p.ln_y32 || p.ln_y16) && p.N % 256 == 0 && p.N <= 1024 &&
              (!p.ln_y32 || (p.ln_y32v.rpi > 0 && !misaligned(p.ln_y32v, 3))) && (!p.ln_y16 || (p.ln_y16v.rpi > 0 && !misaligned(p.ln_y16v, 3)));
@@ -1780,6 +1890,7 @@ bool tile_rules(const TileDesc& d, int family, const GemmProb& p, int ngroups, i
   if ((d.allow & T_F32_16B) && (epi == EPI_RES_F32 || epi == EPI_F32 || epi == EPI_RES_LN) && misaligned(p.c, 3)) return false;
   if (p.w_ld && (!(d.allow & T_WLD) || epi != EPI_OP || (p.w_ld & 7) || p.k_rows <= 0 || p.N % d.tn)) return false;
   if (p.w_kwrap && (!(d.allow & T_KWRAP) || p.w_kwrap < 0 || p.w_ld || 2 * p.w_kwrap * 64 != p.K)) return false;   // K = 2 passes over the weights
+  if (p.col_scale && (epi != EPI_SOFTPART || family != GF_WS_176x384 || p.w_ld || ngroups != 1)) return false;
   if (p.pscale && (!p.w_ld || p.M > d.tm || p.ps_ntiles <= 0 || p.K > p.ps_ntiles * d.tn + 4 * d.tn)) return false;   // one row tile: the factor slice (512 rows) is indexed by the row inside the tile
   return true;
 }

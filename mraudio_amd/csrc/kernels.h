@@ -115,6 +115,16 @@ struct GemmProb {
   // 512-row factor slice by the row inside the tile).
   const float* pscale;
   int ps_ntiles;
+  // col_scale != nullptr (EPI_SOFTPART with row-major W only): the weight-side rows are RAW tokens whose LayerNorm is folded into the other
+  // operand; column n of batch entry b carries the factor r = col_scale[b * cs_bs + n] (1 / sqrt(var + eps) of token n).  The epilogue takes
+  // the tile maximum over r * acc, writes C = T(exp2(alpha * r * acc - stat_m) * r) and keeps stat_l the fp32 sum of the exponentials
+  // themselves (without r, before any rounding to T).
+  // col_stats != 0: the kernel computes the factors itself from the weight-side rows as they pass through LDS (biased variance over K,
+  // cs_eps) and WRITES col_scale[b * cs_bs + n] for n < N (no w_kwrap: one pass over the rows); otherwise col_scale is read.
+  float* col_scale;
+  long long cs_bs;
+  int col_stats;
+  float cs_eps;
   int tile_cfg;    // a GemmTile; in a grouped launch the first problem decides
   int order;       // tile walk: 0 = panels of 8 row tiles, rows fastest; gn > 0 = panels of gn column tiles walked down the rows, columns
                    // fastest (measured better for the ViT's N = 1408 GEMMs: all 6 column tiles of a row tile run together)
@@ -288,6 +298,13 @@ int launch_softmax_rescale(void* P, long long ld_p, const float* stat_m, const f
 // dst[b][c][r] = src[b][r][c] (r < R), 0 for R <= r < ld_d; src [batch][R][C], dst [batch][C][ld_d]
 int launch_transpose_pad(const void* src, void* dst, int R, int C, int ld_d, long long src_bs, long long dst_bs, int batch, int op_dtype,
                          hipStream_t stream);
+
+// The modality LayerNorm folded into a cross-attention weight (raw encoder features): row n of W [rows][E] (fp32 when w32, else the operand
+// dtype) becomes w'_e = w_e g_e - mean_e(w g), computed in fp32 and rounded once -- W LN(x) = r (W' x) + W b with no mean term, because a
+// centred row sums to zero.  key_layout: dst[(n / 64)][e][n % 64] (the per-head [heads][E][64] operand of the Q' GEMM), else dst[n][e].
+// bias_out (may be null) [rows] = bias_in[n] + sum_e w_e b_e.
+int launch_fold_ln_weight(const void* W, int w32, int rows, int E, const float* gain, const float* ln_bias, const float* bias_in, void* dst,
+                          int key_layout, float* bias_out, int op_dtype, hipStream_t stream);
 
 // ---- folded cross-attention, streaming form (fold_stream.hip) ---------------------------------------
 // scores + split-softmax statistics + P . enc of one cross layer for `items` items of 384 (head, query) rows:

@@ -153,10 +153,12 @@ struct CrossPlan {
   bool kmajor;     // P . enc reads the encoder tokens themselves (K-major weights): no enc^T copy
   bool softpart;   // scores on the 176 x 384 EPI_SOFTPART tile (otherwise fp32 scores + a row softmax)
   bool inreg;      // with softpart: P . enc applies the row factors to its P~ fragments (otherwise a rescale pass over P)
+  bool raw;        // the encoder features are RAW (no modality LayerNorm pass): its gain and centring live in the folded weights, the token
+                   // factors 1 / sqrt(var + eps) come out of cross layer 0's scores launch (FOLD with softpart && kmajor && inreg only)
   int scores_tile, penc_tile;   // GemmTile of the scores and the P . enc GEMMs
 };
 
-CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe) {
+CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe, bool raw = false) {
   const mra_cfg& c = h->cfg;
   const int R = c.heads * c.n_query;
   CrossPlan x{};
@@ -172,6 +174,7 @@ CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe) {
   x.inreg = (h->inreg_rescale || probe) && x.softpart && x.kmajor;
   x.scores_tile = R == 384 ? GT_WS_176x384 : GT_128;
   x.penc_tile = x.kmajor ? GT_WS_176x384 : (R == 384 ? h->fold_tile : GT_128);
+  x.raw = raw && x.form == CrossPlan::FOLD && x.softpart && x.kmajor && x.inreg && !precise && !probe;
   return x;
 }
 
@@ -188,6 +191,7 @@ struct Work {
   float* s32;                      // scores [N][R][kvp]
   float* stat;                     // split softmax: tile maxima [N][R][ntiles], then tile sums
   float* gfac;                     // split softmax: row factors exp2(m_tile - m_row) / L as [N][ntiles][512] for the P . enc GEMM
+  float* rt;                       // raw features: token factors 1 / sqrt(var + eps) [N][kvp], written by cross layer 0's scores launch
   float *st_m, *st_l, *ginv;       // streaming kernels: statistics [N * R][stat_ld], 1 / L [N * R]
   char* gexp;                      // tile factors f16 [N * R][stat_ld]
   int nsplit;
@@ -254,6 +258,7 @@ void layout_cross(const mra_qformer* h, const CrossPlan& x, Carver& cv, Work& w,
     if (x.inreg) w.gfac = cv.take<float>((size_t)N * ((Kv + 175) / 176) * 512);
     w.p16 = cv.take<char>((size_t)N * R * kvp, 2);
     w.u16 = cv.take<char>((size_t)N * R * E, 2);
+    if (x.raw) w.rt = cv.take<float>((size_t)N * kvp);   // last: every other buffer sits where the normalised-copy form has it
   } else {
     w.kv16 = cv.take<char>((size_t)h->ncross * 2 * N * Kv * H, 2);
   }
@@ -288,12 +293,12 @@ size_t layout_lanes(Lane* lanes, int nl, char* base, int N, int L, long long** m
 }
 
 // a lane of handle h over the encoder tokens enc (kv per item), its cross-attention planned for (precise, probe), no outputs yet
-Lane make_lane(mra_qformer* h, const void* enc, int kv, bool precise, bool probe) {
+Lane make_lane(mra_qformer* h, const void* enc, int kv, bool precise, bool probe, bool raw = false) {
   Lane x{};
   x.h = h;
   x.enc = enc;
   x.kv = kv;
-  x.plan = cross_plan(h, kv, precise, probe);
+  x.plan = cross_plan(h, kv, precise, probe, raw);
   x.query = h->query;
   return x;
 }
@@ -344,7 +349,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
     if (rc) return chk(rc, "split q'");
   } else {
     d.A = w.qc16; d.a = qc_rows; d.a_bs = 64;
-    d.W = h->arena_f + (size_t)ci * H * E * esz; d.w_bs = (long long)E * 64;
+    d.W = x.raw ? fold_raw_wk(h, ci) : h->arena_f + (size_t)ci * H * E * esz; d.w_bs = (long long)E * 64;
     d.C = w.qp16; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * esz;
     d.M = N * Q; d.N = E; d.K = 64; d.batch = c.heads; d.tile_cfg = (N * Q) % 128 == 0 && E % 128 == 0 ? GT_128 : GT_64;
     rc = launch_gemm(&d, 1, EPI_OP, op, stream);
@@ -377,6 +382,9 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
       sc.C = w.p16; sc.c = plain(R, kvp); sc.c_bs_bytes = (long long)R * kvp * esz;
       sc.alpha = 0.125f * 1.4426950408889634f;
       sc.stat_m = w.stat; sc.stat_l = w.stat + (size_t)N * R * ntiles;
+      if (x.raw) {   // raw tokens: column t carries r_t; the first cross layer computes the factors as the tokens stream through its LDS
+        sc.col_scale = w.rt; sc.cs_bs = kvp; sc.col_stats = ci == 0; sc.cs_eps = c.enc_ln_eps;
+      }
       rc = launch_gemm(&sc, 1, EPI_SOFTPART, op, stream);
       if (rc) return chk(rc, "fold scores gemm (softmax partials)");
       if (x.inreg) {
@@ -416,6 +424,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
   cx.A = w.u16; cx.a = items_view((long long)R * E, Q, E); cx.a_bs = (long long)Q * E;
   cx.W = (const char*)h->wkv + (size_t)(ci * 2 + 1) * H * E * esz; cx.w_bs = (long long)64 * E;
   cx.bias = h->bkv + (size_t)(ci * 2 + 1) * H; cx.bias_bs = 64;
+  if (x.raw) { cx.W = fold_raw_wv(h, ci); cx.bias = fold_raw_bv(h, ci); }   // U is over raw tokens: W_v' and b_v + W_v b
   cx.C = w.ctx16; cx.c = qc_rows; cx.c_bs_bytes = 64 * esz;
   cx.M = N * Q; cx.N = 64; cx.K = E; cx.batch = c.heads; cx.tile_cfg = E % 128 == 0 && N * Q >= 512 ? GT_K128_64x128 : GT_64;
   rc = launch_gemm(&cx, 1, EPI_OP, op, stream);
@@ -493,7 +502,7 @@ int mra_qformer_create(const mra_cfg* cfg, mra_qformer** out) {
   }
   layout_params(h, h->arena);
   if (h->ncross > 0) {
-    e = hipMalloc((void**)&h->arena_f, (size_t)h->ncross * c.hidden * c.enc_width * 2);
+    e = hipMalloc((void**)&h->arena_f, fold_arena_bytes(h));
     if (e != hipSuccess) {
       mra_qformer_destroy(h);
       return fail(MRA_ENOMEM, std::string("fold weight arena: ") + hipGetErrorString(e));
@@ -610,10 +619,11 @@ int mra_modality_ln(mra_qformer* h, const void* x, int32_t x_dtype, const int64_
 
 size_t mra_qformer_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
   if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
-  if (!h->cross_auto) return work_bytes(make_lane(h, nullptr, kv, h->cross_precise, false), items, L);
+  // (a raw-feature forward adds its token factors behind the other buffers: asked for whenever that form could run)
+  if (!h->cross_auto) return work_bytes(make_lane(h, nullptr, kv, h->cross_precise, false, true), items, L);
   // automatic precision: the largest of op, the probing forward's op-precision folded form and split precision, so neither the probe nor
   // its resolution ever needs a larger workspace
-  return std::max({work_bytes(make_lane(h, nullptr, kv, false, false), items, L), work_bytes(make_lane(h, nullptr, kv, false, true), items, L),
+  return std::max({work_bytes(make_lane(h, nullptr, kv, false, false, true), items, L), work_bytes(make_lane(h, nullptr, kv, false, true), items, L),
                    work_bytes(make_lane(h, nullptr, kv, true, false), items, L)});
 }
 
@@ -919,7 +929,7 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
 // mra_qformer_forward in the precision in force, or (probe) as the probing forward of the automatic precision
 int forward_run(mra_qformer* h, bool probe, const int64_t* input_ids, const int64_t* attention_mask, const float* query_embeds,
                 int32_t query_items, const void* enc, int32_t items, int32_t L, int32_t kv, float* out_query, float* out_full, float* out_cls,
-                void* workspace, size_t workspace_bytes, void* stream_) {
+                void* workspace, size_t workspace_bytes, void* stream_, bool raw = false) {
   if (!h) return fail(MRA_EINVAL, "null handle");
   if (items < 0 || L < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
   if (items == 0) return MRA_OK;
@@ -932,7 +942,8 @@ int forward_run(mra_qformer* h, bool probe, const int64_t* input_ids, const int6
     return fail(MRA_EINVAL, "query_items must be 1 or items");
   if (!out_query && !out_full && !out_cls) return fail(MRA_EINVAL, "no output requested");
   if (int rc = check_loaded(h)) return rc;
-  Lane lane = make_lane(h, enc, kv, h->cross_precise, probe);
+  Lane lane = make_lane(h, enc, kv, h->cross_precise, probe, raw);
+  if (raw && !lane.plan.raw) return fail(MRA_ESTATE, "raw features are not supported in this form: ask mra_qformer_raw_features_ok");
   // the probe needs its own form's workspace; every other forward what mra_qformer_workspace_bytes promises
   const size_t need = probe ? work_bytes(lane, items, L) : mra_qformer_workspace_bytes(h, items, L, kv);
   if (!workspace || workspace_bytes < need)
@@ -1007,16 +1018,37 @@ int mra_qformer_forward(mra_qformer* h, const int64_t* input_ids, const int64_t*
                      workspace_bytes, stream_);
 }
 
+// can a forward of h over kv tokens per item read RAW features (x_dtype) in place of mra_modality_ln's output?
+static bool raw_ok(mra_qformer* h, int kv, int x_dtype) {
+  if (!h || kv <= 0 || h->ncross == 0 || !h->raw_features || x_dtype != h->cfg.op_dtype) return false;
+  if (h->cross_precise || (h->cross_auto && (h->auto_stale || h->auto_resolved != 0))) return false;   // split precision; a pending probe
+  if (!h->params["ln.weight"].loaded || !h->params["ln.bias"].loaded) return false;
+  return cross_plan(h, kv, false, false, true).raw;
+}
+
+int mra_qformer_raw_features_ok(mra_qformer* h, int32_t kv, int32_t x_dtype) { return raw_ok(h, kv, x_dtype) ? 1 : 0; }
+
+int mra_qformer_forward_raw(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const float* query_embeds,
+                            int32_t query_items, const void* enc, int32_t items, int32_t L, int32_t kv, float* out_query, float* out_full,
+                            float* out_cls, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (!raw_ok(h, kv, h->cfg.op_dtype)) return fail(MRA_ESTATE, "raw features are not supported in this form: ask mra_qformer_raw_features_ok");
+  return forward_run(h, false, input_ids, attention_mask, query_embeds, query_items, enc, items, L, kv, out_query, out_full, out_cls, workspace,
+                     workspace_bytes, stream_, true);
+}
+
 size_t mra_qformer_pair_workspace_bytes(mra_qformer* h0, mra_qformer* h1, int32_t items, int32_t L, int32_t kv0, int32_t kv1) {
   if (!h0 || !h1 || items <= 0 || L < 0 || kv0 <= 0 || kv1 <= 0) return 0;
-  Lane lanes[2] = {make_lane(h0, nullptr, kv0, h0->cross_precise, false), make_lane(h1, nullptr, kv1, h1->cross_precise, false)};
+  // (a raw-feature lane adds its token factors behind its other buffers: asked for whenever that form could run)
+  Lane lanes[2] = {make_lane(h0, nullptr, kv0, h0->cross_precise, false, true), make_lane(h1, nullptr, kv1, h1->cross_precise, false, true)};
   return layout_lanes(lanes, 2, nullptr, items, L);
 }
 
-// Pair forward: the layer chains of two Q-Formers of equal shape in ONE launch sequence (run_lanes with two lanes).
-int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
-                             const void* enc1, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0, float* out_cls0,
-                             float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream_) {
+// Pair forward: the layer chains of two Q-Formers of equal shape in ONE launch sequence (run_lanes with two lanes).  raw_mask bit l: lane l's
+// encoder features are raw (mra_qformer_forward_raw's form for that lane).
+static int forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
+                        const void* enc1, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0, float* out_cls0,
+                        float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream_, int raw_mask) {
   if (!h0 || !h1) return fail(MRA_EINVAL, "null handle");
   if (h0 == h1) return fail(MRA_EINVAL, "the two lanes need two handles");
   if (items < 0 || L < 0 || kv0 < 0 || kv1 < 0) return fail(MRA_EINVAL, "negative size");
@@ -1043,7 +1075,9 @@ int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* in
     if (hs[l]->cross_precise) return fail(MRA_ESTATE, "pair forward runs the operand-dtype score chain: use mra_qformer_forward for split precision");
     if (hs[l]->cross_auto && (hs[l]->auto_stale || hs[l]->auto_resolved != 0))
       return fail(MRA_ESTATE, "pair forward runs the operand-dtype score chain: auto precision must have resolved to op (use mra_qformer_forward)");
-    lanes[l] = make_lane(hs[l], encs[l], kvs[l], false, false);
+    const bool raw = raw_mask >> l & 1;
+    if (raw && !raw_ok(hs[l], kvs[l], hs[l]->cfg.op_dtype)) return fail(MRA_ESTATE, "raw features are not supported in this form: ask mra_qformer_raw_features_ok");
+    lanes[l] = make_lane(hs[l], encs[l], kvs[l], false, false, raw);
     if (lanes[l].plan.form == CrossPlan::FOLD_STREAM) return fail(MRA_ESTATE, "pair forward: the streaming fold kernels are not supported");
     if (int rc = check_loaded(hs[l])) return rc;
     lanes[l].out_query = outq[l];
@@ -1053,6 +1087,21 @@ int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* in
   if (!workspace || workspace_bytes < need) return fail(MRA_ENOMEM, "workspace too small: need " + std::to_string(need) + " bytes");
   if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(MRA_EINVAL, "workspace must be 256-byte aligned");
   return run_lanes(lanes, 2, input_ids, attention_mask, items, L, workspace, as_stream(stream_));
+}
+
+int mra_qformer_forward_pair(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
+                             const void* enc1, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0, float* out_cls0,
+                             float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream_) {
+  return forward_pair(h0, h1, input_ids, attention_mask, enc0, enc1, items, L, kv0, kv1, out_query0, out_cls0, out_query1, out_cls1, workspace,
+                      workspace_bytes, stream_, 0);
+}
+
+int mra_qformer_forward_pair_raw(mra_qformer* h0, mra_qformer* h1, const int64_t* input_ids, const int64_t* attention_mask, const void* enc0,
+                                 const void* enc1, int32_t raw_mask, int32_t items, int32_t L, int32_t kv0, int32_t kv1, float* out_query0,
+                                 float* out_cls0, float* out_query1, float* out_cls1, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (raw_mask < 0 || raw_mask > 3) return fail(MRA_EINVAL, "raw_mask has bits 0 and 1");
+  return forward_pair(h0, h1, input_ids, attention_mask, enc0, enc1, items, L, kv0, kv1, out_query0, out_cls0, out_query1, out_cls1, workspace,
+                      workspace_bytes, stream_, raw_mask);
 }
 
 namespace {
@@ -1195,6 +1244,18 @@ int mra_qformer_prepare(mra_qformer* h, void* stream) {
                                         64, (long long)64 * E, (long long)E * 64, c.heads, h->op(), as_stream(stream));
     if (rc) return chk(rc, "key weight regroup");
   }
+  if (h->params["ln.weight"].loaded && h->params["ln.bias"].loaded) {
+    // the raw-feature form's weights: the modality LayerNorm's gain and centring inside W_k and W_v, its bias inside the value bias; from the
+    // fp32 copies where the handle keeps them (the key weights), rounded to the operand dtype once
+    for (int ci = 0; ci < h->ncross; ++ci) {
+      const char* wk = (const char*)h->wkv + (size_t)(ci * 2) * H * E * esz;
+      const char* wv = (const char*)h->wkv + (size_t)(ci * 2 + 1) * H * E * esz;
+      int rc = h->wk32 ? launch_fold_ln_weight(h->wk32 + (size_t)ci * H * E, 1, (int)H, (int)E, h->encg, h->encb, nullptr, fold_raw_wk(h, ci), 1, nullptr, h->op(), as_stream(stream))
+                       : launch_fold_ln_weight(wk, 0, (int)H, (int)E, h->encg, h->encb, nullptr, fold_raw_wk(h, ci), 1, nullptr, h->op(), as_stream(stream));
+      if (!rc) rc = launch_fold_ln_weight(wv, 0, (int)H, (int)E, h->encg, h->encb, h->bkv + (size_t)(ci * 2 + 1) * H, fold_raw_wv(h, ci), 0, fold_raw_bv(h, ci), h->op(), as_stream(stream));
+      if (rc) return chk(rc, "raw-feature weight preparation");
+    }
+  }
   h->fold_stale = false;
   return MRA_OK;
 }
@@ -1260,6 +1321,11 @@ int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value) {
   if (key == "train_ring") {
     if (value < 0 || value > 7) return fail(MRA_EINVAL, "train_ring is a mask of bits 0-2");
     h->train_ring = value;
+    return MRA_OK;
+  }
+  if (key == "raw_features") {
+    if (value < 0 || value > 1) return fail(MRA_EINVAL, "raw_features is 0 or 1");
+    h->raw_features = value != 0;
     return MRA_OK;
   }
   if (key == "auto_split_pmax_milli") {
@@ -1736,6 +1802,13 @@ const char* dbg_gemm_prob(const mra_gemm_desc& d, int epi, GemmProb* out) {
     if (d.M > 384) return "pscale needs M <= 384 (one row tile)";
     p.pscale = d.pscale; p.ps_ntiles = d.ps_ntiles;
   }
+  if (d.col_scale || d.col_stats) {
+    if (epi != EPI_SOFTPART) return "col_scale belongs to EPI_SOFTPART";
+    if (!d.col_scale || !dbg_aligned(d.col_scale, 4)) return "col_scale must be given (4-byte aligned) with col_stats";
+    if (d.col_stats < 0 || d.col_stats > 1 || d.cs_bs < 0 || !(d.cs_eps >= 0.f)) return "col_stats is 0 or 1; cs_bs and cs_eps are not negative";
+    if (d.batch > 1 && d.cs_bs < d.N) return "cs_bs below N";
+    p.col_scale = d.col_scale; p.cs_bs = d.cs_bs; p.col_stats = d.col_stats; p.cs_eps = d.cs_eps;
+  }
   return nullptr;
 }
 
@@ -1787,6 +1860,7 @@ const char* dbg_gemm_footprint(const mra_gemm_desc& d, const GemmProb& p, const 
     if (!dbg_fits(n, 4, 0, d.stat_m_bytes) || !dbg_fits(n, 4, 0, d.stat_l_bytes)) return "stat_m / stat_l: batch * M * ntiles floats leave their sizes";
   }
   if (p.pscale && !dbg_fits((u128)nb * (u128)d.ps_ntiles * 512, 4, 0, d.pscale_bytes)) return "pscale: batch * ps_ntiles * 512 floats leave pscale_bytes";
+  if (p.col_scale && !dbg_fits((u128)d.N + (u128)(nb - 1) * (u128)d.cs_bs, 4, 0, d.col_scale_bytes)) return "col_scale: N floats and the batch stride leave col_scale_bytes";
   if (epi == EPI_RES_LN) {
     if (!dbg_fits((u128)d.N, 4, 0, d.ln_gain_bytes) || !dbg_fits((u128)d.N, 4, 0, d.ln_bias_bytes)) return "ln_gain / ln_bias: N floats leave their sizes";
     if (p.ln_y32 && (p.ln_y32v.ld < d.N || !dbg_fits(dbg_extent(p.ln_y32v, d.M, d.N), 4, 0, d.ln_y32_bytes))) return "ln_y32: row stride below N, or the view leaves ln_y32_bytes";

@@ -11,6 +11,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef short i16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T> struct Vec8;
 template <> struct Vec8<f16> { typedef _Float16 type __attribute__((ext_vector_type(8))); };

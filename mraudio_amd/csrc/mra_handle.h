@@ -145,8 +145,12 @@ struct mra_qformer {
   void* wllm = nullptr;
   float* bllm = nullptr;
   // folded cross-attention (mra_qformer_set_cross_mode): per cross layer the key weight regrouped as [heads][E][64]
+  // ... and, behind those, the weights of the raw-feature form (mra_qformer_forward_raw): per cross layer the key weight with the modality
+  // LayerNorm folded in, W_k diag(g) centred over E, in the same [heads][E][64] layout; the value weight likewise as [H][E]; and the
+  // value bias b_v + W_v b (mra_host::fold_raw_*).  Rebuilt with the regrouped key weights whenever a parameter is loaded (fold_stale).
   char* arena_f = nullptr;
   bool fold_stale = true;
+  bool raw_features = true;                       // mra_qformer_set_option "raw_features": 0 = mra_qformer_raw_features_ok answers no (A/B)
   bool inreg_rescale = true;                      // the P . enc GEMM applies the softmax row factors to its P~ fragments (false: a rescale pass over P; cross mode 5)
   int fold_tile = mra::GT_128;                    // GemmTile of the two batched GEMMs where the 176 x 384 tiles do not apply (GT_128 or GT_WS_128x384)
   bool fold_stream = false;                       // folded path on the streaming kernels of fold_stream.hip (mra_qformer_set_cross_mode 4)
@@ -209,6 +213,13 @@ struct mra_qformer {
 namespace mra_host {
 // padded score-row length: whole 128- and 176-row tiles of the scores GEMM, and a multiple of 128 (K of P . enc)
 inline int fold_kvp(int kv) { return (std::max((kv + 127) / 128 * 128, (kv + 175) / 176 * 176) + 127) / 128 * 128; }
+// raw-feature form: where cross layer ci's folded weights live in arena_f (W_k' | W_v' | value bias), and the arena's size
+inline size_t fold_raw_layer_bytes(const mra_qformer* h) { return align_up((size_t)2 * h->cfg.hidden * h->cfg.enc_width * 2 + (size_t)h->cfg.hidden * 4); }
+inline size_t fold_raw_off(const mra_qformer* h) { return align_up((size_t)h->ncross * h->cfg.hidden * h->cfg.enc_width * 2); }
+inline char* fold_raw_wk(const mra_qformer* h, int ci) { return h->arena_f + fold_raw_off(h) + (size_t)ci * fold_raw_layer_bytes(h); }
+inline char* fold_raw_wv(const mra_qformer* h, int ci) { return fold_raw_wk(h, ci) + (size_t)h->cfg.hidden * h->cfg.enc_width * 2; }
+inline float* fold_raw_bv(const mra_qformer* h, int ci) { return (float*)(fold_raw_wv(h, ci) + (size_t)h->cfg.hidden * h->cfg.enc_width * 2); }
+inline size_t fold_arena_bytes(const mra_qformer* h) { return fold_raw_off(h) + (size_t)h->ncross * fold_raw_layer_bytes(h); }
 // split-precision cross-attention: bytes of one cross layer's prepared weights, W_cq [H][3H] then W_k [heads][E][192] (operand dtype)
 inline size_t precise_wk_off(const mra_qformer* h) { return align_up((size_t)h->cfg.hidden * 3 * h->cfg.hidden * 2); }
 inline size_t precise_layer_bytes(const mra_qformer* h) {

@@ -447,8 +447,13 @@ class XInstructBLIP(nn.Module):
             # one's latency-bound chain phases, and one sequence hides nothing: 6.72-6.87 vs 6.57 ms per step, reference item shape 2.65 vs
             # 2.55 ms (r03p, same session).  Opt-in.  The heavier lane first (its cross-layer-0 block carries the roofline events).
             qfs = [getattr(self, f"{m}_Qformer") for m in live]
-            encs = [qf.modality_ln(embeds[m].to(self._device), item_index=None if index is None else index.get(m), items=n_local) for qf, m in zip(qfs, live)]
-            res = QFormer.forward_pair(qfs[0], qfs[1], ids, att, encs[0], encs[1], want_cls=True, kv_events=(self.roofline_events or {}).get(live[0]))
+            # (each lane as its own forward would run it: raw features where the library folds the LayerNorm into the cross-attention)
+            xs = [embeds[m].to(self._device) for m in live]
+            idxs = [None if index is None else index.get(m) for m in live]
+            raws = [x.dim() == 3 and x.shape[0] == n_local and qf.raw_features_ok(x, item_index=i) for qf, x, i in zip(qfs, xs, idxs)]
+            encs = [x if r else qf.modality_ln(x, item_index=i, items=n_local) for qf, x, i, r in zip(qfs, xs, idxs, raws)]
+            res = QFormer.forward_pair(qfs[0], qfs[1], ids, att, encs[0], encs[1], want_cls=True, kv_events=(self.roofline_events or {}).get(live[0]),
+                                       raw=raws)
             for m, (z, cls) in zip(live, res):
                 if sharded:
                     local[m] = (z, cls)
@@ -467,9 +472,12 @@ class XInstructBLIP(nn.Module):
                 if heavy_done is not None and pos > 0:
                     side.wait_event(heavy_done)
             with torch.cuda.stream(side):
-                enc = qf.modality_ln(embeds[m].to(self._device), item_index=idx, items=n_local)
+                # the folded cross-attention reads the encoder output itself where the library folds the LayerNorm into it (no normalised copy)
+                x = embeds[m].to(self._device)
+                raw = x.dim() == 3 and x.shape[0] == n_local and qf.raw_features_ok(x, item_index=idx)
+                enc = x if raw else qf.modality_ln(x, item_index=idx, items=n_local)
                 res = qf.forward_fused(ids, att, enc, want_query=True, want_full=want_full, want_cls=True,
-                                       kv_events=(self.roofline_events or {}).get(m))
+                                       kv_events=(self.roofline_events or {}).get(m), raw=raw)
                 z, cls = res["query"], res["cls"]
                 if sharded:      # scored after ONE packed all-gather of every modality's rows, below
                     local[m] = (z, cls)

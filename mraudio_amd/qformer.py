@@ -287,10 +287,22 @@ class QFormer(nn.Module):
                                         ptr(out), current_stream()), "mra_modality_ln")
         return out
 
+    def raw_features_ok(self, x: torch.Tensor, item_index: Optional[torch.Tensor] = None) -> bool:
+        """Can ``forward_fused(..., raw=True)`` read the encoder output ``x`` [N, Kv, E] itself, with no ``modality_ln`` pass
+        (``mra_qformer_raw_features_ok``)?  Contiguous features in the operand dtype on the handle's device, no item gather, and a form
+        the library folds the LayerNorm into."""
+        if item_index is not None or x.dim() != 3 or x.shape[-1] != self.cfg.enc_width or x.dtype != self.cfg.op_dtype or not x.is_contiguous():
+            return False
+        if x.shape[0] == 0 or x.device != self._device:
+            return False
+        self.sync_weights()
+        return bool(lib().mra_qformer_raw_features_ok(self._handle, int(x.shape[1]), _lib.mra_dtype(x.dtype)))
+
     def forward_fused(self, input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor], enc: torch.Tensor,
                       query_embeds: Optional[torch.Tensor] = None, want_query: bool = True, want_full: bool = False,
-                      want_cls: bool = False, kv_events=None) -> Dict[str, torch.Tensor]:
-        """A4 on the extension.  enc [N, Kv, E] in the operand dtype (``modality_ln`` output).
+                      want_cls: bool = False, kv_events=None, raw: bool = False) -> Dict[str, torch.Tensor]:
+        """A4 on the extension.  enc [N, Kv, E] in the operand dtype (``modality_ln`` output; with ``raw`` the encoder output itself,
+        where ``raw_features_ok`` allows it: ``mra_qformer_forward_raw``).
         Returns a dict with ``query`` [N,32,H], ``full`` [N,32+L,H], ``cls`` [N,H] (fp32) as requested.
         ``kv_events``: optional (start, stop) ``torch.cuda.Event`` pair for ``mra_qformer_set_kv_events`` (bench
         instrumentation of the dominant kernel, recorded by the library on the launch stream)."""
@@ -298,6 +310,8 @@ class QFormer(nn.Module):
         cfg = self.cfg
         if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
             raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
+        if raw and (enc.dtype != cfg.op_dtype or not enc.is_contiguous()):
+            raise MraError("raw features must be contiguous and in the operand dtype (ask raw_features_ok)")
         if enc.dtype != cfg.op_dtype:
             enc = enc.to(cfg.op_dtype)
         enc = enc.contiguous()
@@ -335,10 +349,11 @@ class QFormer(nn.Module):
                 e0, e1 = kv_events
                 check(lib().mra_qformer_set_kv_events(self._handle, e0.cuda_event, e1.cuda_event), "set_kv_events")
             try:
-                check(lib().mra_qformer_forward(
+                fwd = lib().mra_qformer_forward_raw if raw else lib().mra_qformer_forward
+                check(fwd(
                     self._handle, ptr(input_ids), ptr(attention_mask), ptr(query_embeds), q_items, ptr(enc), N, L, Kv,
                     ptr(out.get("query")), ptr(out.get("full")), ptr(out.get("cls")), ptr(ws), nbytes, current_stream()),
-                    "mra_qformer_forward")
+                    "mra_qformer_forward_raw" if raw else "mra_qformer_forward")
             finally:
                 if kv_events is not None:
                     check(lib().mra_qformer_set_kv_events(self._handle, None, None), "set_kv_events")
@@ -390,11 +405,12 @@ class QFormer(nn.Module):
 
     @staticmethod
     def forward_pair(qf0: "QFormer", qf1: "QFormer", input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor], enc0: torch.Tensor,
-                     enc1: torch.Tensor, want_cls: bool = True, kv_events=None):
+                     enc1: torch.Tensor, want_cls: bool = True, kv_events=None, raw=(False, False)):
         """Both modality Q-Formers of a step in ONE launch sequence (``mra_qformer_forward_pair``): the layer chains as grouped launches,
         each lane its own cross-attention.  enc0 / enc1 [N, Kv_l, E_l] in the operand dtype, the same prompt rows for both lanes.  Returns
         ``[(query0, cls0), (query1, cls1)]`` (fp32; cls ``None`` without ``want_cls``).  ``kv_events``: (start, stop) pair for lane 0's
-        cross-layer-0 block (bench instrumentation)."""
+        cross-layer-0 block (bench instrumentation).  ``raw[l]``: lane l's enc is the encoder output itself (``raw_features_ok``;
+        ``mra_qformer_forward_pair_raw``)."""
         qfs, encs = (qf0, qf1), []
         for qf, enc in zip(qfs, (enc0, enc1)):
             qf.sync_weights()
@@ -420,7 +436,8 @@ class QFormer(nn.Module):
             if kv_events is not None:
                 check(lib().mra_qformer_set_kv_events(qf0._handle, kv_events[0].cuda_event, kv_events[1].cuda_event), "set_kv_events")
             try:
-                check(lib().mra_qformer_forward_pair(qf0._handle, qf1._handle, ptr(input_ids), ptr(attention_mask), ptr(encs[0]), ptr(encs[1]), N, L,
+                check(lib().mra_qformer_forward_pair_raw(qf0._handle, qf1._handle, ptr(input_ids), ptr(attention_mask), ptr(encs[0]), ptr(encs[1]),
+                                                         int(bool(raw[0])) | int(bool(raw[1])) << 1, N, L,
                                                      int(encs[0].shape[1]), int(encs[1].shape[1]), ptr(outs[0][0]), ptr(outs[0][1]), ptr(outs[1][0]), ptr(outs[1][1]),
                                                      ptr(ws), nbytes, current_stream()), "mra_qformer_forward_pair")
             finally:
