@@ -324,7 +324,10 @@ int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, 
  *                                 buffer of mra_qformer_grad_bytes() in which parameter `name` (same names
  *                                 as mra_qformer_load) owns numel floats at mra_qformer_grad_offset().
  *                                 Gradients flow to every Q-Former parameter incl. query_tokens and the
- *                                 embeddings; not to enc / ln.* / llm_proj.* (encoder side frozen). */
+ *                                 embeddings.  The encoder side is a call of its own: mra_qformer_backward_enc gives
+ *                                 the gradient with respect to enc, mra_modality_ln_backward carries it through the
+ *                                 modality LayerNorm to ln.* and the raw features (below).  llm_proj.* still gets
+ *                                 none: it is not on the scorer's path. */
 size_t mra_qformer_grad_bytes(mra_qformer* h);
 /* Optimizer-side fast path: refreshes EVERY bert.* parameter in one launch from a flat f32 master buffer
  * laid out exactly like the gradient buffer (parameter `name` at mra_qformer_grad_offset(name)), converting
@@ -378,6 +381,35 @@ int mra_qformer_forward_multi_train(mra_qformer* h, const int64_t* input_ids, co
 int mra_qformer_backward_multi(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
                                int32_t enc_items, int32_t prompts, int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls,
                                float* grads, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Encoder side of the training step: gradients to the features the Q-Former was fed and to the modality LayerNorm in front of it.  Nothing
+ * here runs unless it is called: the two backward entries above are launch for launch what they were.
+ * mra_qformer_backward_enc: after the matching mra_qformer_backward (prompts = 1) or mra_qformer_backward_multi, on the untouched tape.  The
+ *   backward leaves dK / dV of every cross layer in the workspace (head-major [ncross][k | v][enc_items][heads][kv][64], operand dtype, for a
+ *   multi call already summed over the prompts of an item); this call contracts them with the stored K / V weights,
+ *     d_enc[item * kv + tok][e] = sum_k dKV[item * kv + tok][k] W_kv[k][e],   k = (cross layer * 2 + k | v) * hidden + head * 64 + d,
+ *   reading the cache in place (no token-major copy) and the weights as stored (no transposed copy): one launch, MFMA with fp32 accumulation,
+ *   the flops of one mra_kv_project.  d_enc [enc_items, kv, E] fp32 is WRITTEN: the gradient with respect to the operand-dtype enc given to
+ *   the forward (the rounding to the operand dtype is passed straight through, like every 16-bit tensor of the tape).  enc_width must be a
+ *   multiple of 128.  Checks as the training entries: prompts >= 1, negative size, NULL workspace / d_enc / handle (MRA_EINVAL); training not
+ *   enabled or the transposed copies stale (MRA_ESTATE); workspace_bytes below mra_qformer_multi_train_workspace_bytes(h, enc_items,
+ *   prompts, L, kv) (MRA_ENOMEM; with prompts = 1 that is mra_qformer_train_workspace_bytes).  enc_items == 0 is a no-op.  No allocation,
+ *   no synchronisation.
+ * mra_modality_ln_backward: backward of mra_modality_ln without an item index, with the handle's loaded ln.weight and enc_ln_eps (MRA_ESTATE
+ *   if ln.* is not loaded).  x [items, tokens, E] is the raw feature tensor the forward read (MRA_F32 / MRA_F16 / MRA_BF16), d_out [items,
+ *   tokens, E] fp32 the upstream gradient (mra_qformer_backward_enc's d_enc).  Statistics are recomputed two-pass from x:
+ *     d_x = r (g - mean(g) - xhat mean(g xhat)), g = d_out gain;   d_gain += sum_rows d_out xhat;   d_bias += sum_rows d_out.
+ *   d_x [items, tokens, E] fp32 is written and may be d_out itself (a row is read completely before it is written); d_gain / d_bias [E] fp32
+ *   are ADDED to (float atomics: the order over rows is not fixed).  Any of d_x, d_gain, d_bias may be NULL.  One launch, no allocation.
+ * mra_debug_kvgrad_gemm: the GEMM of mra_qformer_backward_enc alone on a caller-supplied cache dkv [ncross * 2][enc_items][heads][kv][64]
+ *   (operand dtype, 16-byte aligned) with the handle's K / V weights; needs neither a tape nor enabled training.  The read and the write
+ *   footprint are checked on the host against dkv_bytes and d_enc_bytes before the launch. */
+int mra_qformer_backward_enc(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv, const void* workspace,
+                             size_t workspace_bytes, float* d_enc, void* stream);
+int mra_modality_ln_backward(mra_qformer* h, const void* x, int32_t x_dtype, int32_t items, int32_t tokens, const float* d_out, float* d_x,
+                             float* d_gain, float* d_bias, void* stream);
+int mra_debug_kvgrad_gemm(mra_qformer* h, const void* dkv, size_t dkv_bytes, int32_t enc_items, int32_t kv, float* d_enc, size_t d_enc_bytes,
+                          void* stream);
 
 /* ---- introspection for the bench ------------------------------------------------------------------
  * Algorithmic flop count of one mra_qformer_forward (2 flops per MAC; formula in DESIGN.md). */

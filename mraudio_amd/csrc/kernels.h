@@ -214,6 +214,13 @@ struct GemmTnGroup {
   int nb_begin[GEMM_TN_MAX_JOBS + 1];   // filled by the launcher: first 64-row block of dW (grid.x index) of every job
 };
 int launch_gemm_tn_group(const GemmTnArgs* jobs, int njobs, int op_dtype, hipStream_t stream);
+// Encoder-side data gradient of the cross K / V projections (enc_grad.hip): d_enc [Ne * kv][E] fp32 = dKV W, with dKV the head-major dK / dV
+// tape [nsel][Ne][heads][kv][64] (operand dtype, nsel = ncross * 2) read in place and W [nsel * heads * 64][E] as stored.  E % 128 == 0.
+int launch_kvgrad_gemm(const void* dkv, const void* W, float* d_enc, int Ne, int kv, int heads, int nsel, int E, int op_dtype, hipStream_t stream);
+// Backward of launch_modality_ln without an item index (enc_grad.hip): x [items][tokens][E] (x_dtype 0 / 1 / 2 = f32 / f16 / bf16), d_out fp32;
+// d_x (may be NULL, may be d_out) is written, d_gain / d_bias [E] (each may be NULL) are ADDED to.  E a multiple of 8, <= 4096.
+int launch_modality_ln_bwd(const void* x, int x_dtype, int items, int tokens, int E, const float* gain, float eps, const float* d_out, float* d_x,
+                           float* d_gain, float* d_bias, hipStream_t stream);
 // db[n] (+)= sum_m dY[m][n]
 int launch_colsum(const void* dY, long long block_stride, RowView yv, int M, int N, float* db, int accumulate, int op_dtype,
                   hipStream_t stream);

@@ -617,6 +617,19 @@ int mra_modality_ln(mra_qformer* h, const void* x, int32_t x_dtype, const int64_
              "modality_ln");
 }
 
+int mra_modality_ln_backward(mra_qformer* h, const void* x, int32_t x_dtype, int32_t items, int32_t tokens, const float* d_out, float* d_x,
+                             float* d_gain, float* d_bias, void* stream) {
+  if (items < 0 || tokens < 0) return fail(MRA_EINVAL, "negative size");
+  if (x_dtype != MRA_F32 && x_dtype != MRA_F16 && x_dtype != MRA_BF16) return fail(MRA_EINVAL, "x_dtype must be f32, f16 or bf16");
+  if (items > 0 && tokens > 0 && (!x || !d_out)) return fail(MRA_EINVAL, "null x or d_out");
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (items == 0 || tokens == 0) return MRA_OK;
+  if (!h->params["ln.weight"].loaded || !h->params["ln.bias"].loaded) return fail(MRA_ESTATE, "ln.weight / ln.bias not loaded");
+  return chk(launch_modality_ln_bwd(x, x_dtype, items, tokens, h->cfg.enc_width, h->encg, h->cfg.enc_ln_eps, d_out, d_x, d_gain, d_bias,
+                                    as_stream(stream)),
+             "modality_ln backward");
+}
+
 size_t mra_qformer_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
   if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
   // (a raw-feature forward adds its token factors behind the other buffers: asked for whenever that form could run)
@@ -1900,6 +1913,24 @@ int mra_debug_gemm(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, 
   int op;
   if (const int rc = dbg_gemm_prepare(probs, nprob, epilogue, dtype, 0, ps, &pl, &op)) return rc;
   return chk(launch_gemm(ps, nprob, epilogue, op, as_stream(stream)), "debug gemm");
+}
+
+int mra_debug_kvgrad_gemm(mra_qformer* h, const void* dkv, size_t dkv_bytes, int32_t enc_items, int32_t kv, float* d_enc, size_t d_enc_bytes,
+                          void* stream) {
+  if (enc_items < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
+  if (enc_items > 0 && kv > 0 && (!dkv || !d_enc)) return fail(MRA_EINVAL, "null dkv or d_enc");
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (enc_items == 0 || kv == 0) return MRA_OK;
+  if (h->ncross <= 0) return fail(MRA_ESTATE, "the handle has no cross-attention layer");
+  if ((long long)enc_items * kv > 0x7fffffffLL - 64) return fail(MRA_EINVAL, "enc_items * kv exceeds int32");
+  if (!dbg_aligned(dkv, 16) || !dbg_aligned(d_enc, 4)) return fail(MRA_EINVAL, "dkv must be 16-byte aligned (d_enc: 4)");
+  // footprints: the whole head-major cache [ncross * 2][enc_items][heads][kv][64] is read, [enc_items * kv][E] floats are written
+  const size_t rows = (size_t)enc_items * kv;
+  const size_t need_dkv = (size_t)h->ncross * 2 * rows * h->cfg.hidden * 2, need_out = rows * h->cfg.enc_width * 4;
+  if (dkv_bytes < need_dkv) return fail(MRA_EINVAL, "dkv_bytes below the cache's footprint of " + std::to_string(need_dkv) + " bytes");
+  if (d_enc_bytes < need_out) return fail(MRA_EINVAL, "d_enc_bytes below the output's footprint of " + std::to_string(need_out) + " bytes");
+  return chk(launch_kvgrad_gemm(dkv, h->wkv, d_enc, enc_items, kv, h->cfg.heads, h->ncross * 2, h->cfg.enc_width, h->op(), as_stream(stream)),
+             "kvgrad gemm");
 }
 
 int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, int32_t cus, int32_t* out) {

@@ -664,4 +664,22 @@ int mra_qformer_backward_multi(mra_qformer* h, const int64_t* input_ids, const i
   return backward_body(h, input_ids, attention_mask, enc, enc_items * prompts, prompts, L, kv, d_out_query, d_out_cls, grads, workspace, as_stream(stream_));
 }
 
+int mra_qformer_backward_enc(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv, const void* workspace, size_t workspace_bytes,
+                             float* d_enc, void* stream_) {
+  if (prompts < 1) return fail(MRA_EINVAL, "prompts must be >= 1");
+  if (enc_items < 0 || L < 0 || kv < 0) return fail(MRA_EINVAL, "negative size");
+  if (enc_items > 0 && (!workspace || !d_enc)) return fail(MRA_EINVAL, "null workspace or d_enc");
+  if (!h) return fail(MRA_EINVAL, "null handle");
+  if (enc_items == 0) return MRA_OK;
+  if ((long long)enc_items * prompts > 0x7fffffffLL) return fail(MRA_EINVAL, "enc_items * prompts exceeds int32");
+  if (kv == 0) return fail(MRA_EINVAL, "kv must be >= 1");
+  if (!h->arena_t || h->transposes_stale || !h->wg_stream) return fail(MRA_ESTATE, "call mra_qformer_enable_training after the last weight upload");
+  if (h->ncross <= 0) return fail(MRA_ESTATE, "the handle has no cross-attention layer: nothing reads enc");
+  const size_t need = mra_qformer_multi_train_workspace_bytes(h, enc_items, prompts, L, kv);
+  if (workspace_bytes < need) return fail(MRA_ENOMEM, "training workspace too small: need " + std::to_string(need) + " bytes");
+  const TrainBufs t = layout_train(h, (char*)const_cast<void*>(workspace), enc_items * prompts, L, kv, prompts);
+  return chk(launch_kvgrad_gemm(t.dkv16, h->wkv, d_enc, enc_items, kv, h->cfg.heads, h->ncross * 2, h->cfg.enc_width, h->op(), as_stream(stream_)),
+             "encoder-side data gradient");
+}
+
 }  // extern "C"

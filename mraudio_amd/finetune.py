@@ -65,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="train on one record per video with all its queries: the encoders, the modality LayerNorm and the K/V projection run once per "
                          "video, the Q-Former layer chain once per query (XInstructBLIP.forward_multi); validation is unchanged")
     ap.add_argument("--max-queries-per-call", type=int, default=8, help="with --group-by-video: most queries of one video in one Q-Former call (at most 14)")
+    ap.add_argument("--train-ln", action="store_true",
+                    help="train the modality LayerNorms ({m}_ln) in front of the Q-Formers too (XInstructBLIP.enable_qformer_training(train_ln=True)); "
+                         "the checkpoints then carry {m}_ln.*")
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--warmup-steps", type=int, default=1000)
     ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],

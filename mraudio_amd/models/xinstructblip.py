@@ -828,10 +828,23 @@ class XInstructBLIP(nn.Module):
                 target[r] = torch.maximum(target[r], ((t >= s0) & (t <= e0)).float())
         return target
 
-    def enable_qformer_training(self) -> None:
+    def enable_qformer_training(self, train_ln: bool = False) -> None:
         """Unfreeze the Q-Formers (the reference keeps them frozen, ``:196-204``; BASELINE config 5 trains
-        them): parameters get ``requires_grad`` and gradients from the HIP backward."""
+        them): parameters get ``requires_grad`` and gradients from the HIP backward.  ``train_ln``: the modality
+        LayerNorms ``{m}_ln`` in front of them are trained too (``QFormer.modality_ln_train``: the encoder-side data
+        gradient of the Q-Former and the LayerNorm backward run on the HIP extension); they stay ordinary torch
+        parameters, which ``flat_optimizer_params`` lists behind the flat ones.  The default leaves the step as it is."""
         self.train_qformers = True
+        self.train_ln = bool(train_ln)
+
+        def ln_dirty():
+            self._extras_dirty = True          # fused optimizers do not bump version counters (see QFormer._run_backward)
+
+        for m in self.modalities:
+            if self.train_ln:
+                for p in getattr(self, f"{m}_ln").parameters():
+                    p.requires_grad_(True)
+            getattr(self, f"{m}_Qformer")._ln_grad_hook = ln_dirty if self.train_ln else None
         for m in self.modalities:
             qf: QFormer = getattr(self, f"{m}_Qformer")
             qf.enable_training()
@@ -887,7 +900,10 @@ class XInstructBLIP(nn.Module):
             with torch.cuda.stream(side):
                 with torch.no_grad():
                     raw, idx, bs, num = self._encode(samples, m)
-                    enc = qf.modality_ln(raw, item_index=idx, items=bs * num)
+                    if not getattr(self, "train_ln", False):
+                        enc = qf.modality_ln(raw, item_index=idx, items=bs * num)
+                if getattr(self, "train_ln", False):
+                    enc = self._ln_train(m, raw)
                 n = bs * num
                 ids_n, tm_n = (ids.repeat(num, 1), tmask.repeat(num, 1)) if self.compat_repeat else \
                               (ids.repeat_interleave(num, 0), tmask.repeat_interleave(num, 0))
@@ -902,6 +918,11 @@ class XInstructBLIP(nn.Module):
         w = self.fuse_weights or [1.0 / len(per_mod)] * len(per_mod)
         fused = sum(x * wt for x, wt in zip(per_mod, w))
         return {"loss": nn.functional.binary_cross_entropy_with_logits(fused.view(bs, num) * 20.0, self._targets(samples, bs, num))}
+
+    def _ln_train(self, m: str, raw: torch.Tensor) -> torch.Tensor:
+        """``{m}_ln`` over the encoder output as an autograd node (``enable_qformer_training(train_ln=True)``)."""
+        ln = getattr(self, f"{m}_ln")
+        return getattr(self, f"{m}_Qformer").modality_ln_train(raw.to(self._device), ln.weight, ln.bias)
 
     max_queries_per_call = 8      # forward_multi: most queries of one video in one Q-Former call (the backward core's LDS holds 14)
 
@@ -950,11 +971,17 @@ class XInstructBLIP(nn.Module):
         self._sync()
         encs: Dict[str, torch.Tensor] = {}
         bs = num = None
+        raws: Dict[str, torch.Tensor] = {}
         with torch.no_grad():
             for m in self.modalities:
                 if self._present(samples, m):
                     raw, idx, bs, num = self._encode(samples, m)
-                    encs[m] = getattr(self, f"{m}_Qformer").modality_ln(raw, item_index=idx, items=bs * num)
+                    if getattr(self, "train_ln", False):
+                        raws[m] = raw
+                    else:
+                        encs[m] = getattr(self, f"{m}_Qformer").modality_ln(raw, item_index=idx, items=bs * num)
+        for m, raw in raws.items():          # train_ln: the LayerNorm is a node of the graph
+            encs[m] = self._ln_train(m, raw)
         if bs is None:
             return {"loss": torch.tensor(0.0)}
         if bs != len(queries):
@@ -1005,7 +1032,8 @@ class XInstructBLIP(nn.Module):
 
     def all_reduce_grads(self) -> None:
         """Data-parallel gradient averaging over the process group: one all-reduce of each Q-Former's flat f32
-        gradient buffer (what DDP does bucket by bucket in the reference's trainer, ``utils/trainer.py:69,133``)."""
+        gradient buffer (what DDP does bucket by bucket in the reference's trainer, ``utils/trainer.py:69,133``).  Parameters outside
+        the flat buffers (``{m}_ln.*`` under ``train_ln``) carry ordinary ``.grad`` tensors: ``Trainer._sync_grads`` averages those."""
         rank, ws = parallel.world(self.process_group)
         if ws == 1:
             return

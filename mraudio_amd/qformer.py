@@ -218,6 +218,8 @@ class QFormer(nn.Module):
     # ---- weights -> handle ---------------------------------------------------------------------
     def push(self, name: str, t: torch.Tensor) -> None:
         """Copy one tensor into the handle under its ABI name (``include/mra.h`` mra_qformer_load)."""
+        if name in ("ln.weight", "ln.bias"):      # modality_ln_train checks that it is handed the tensors the handle holds
+            self.__dict__.setdefault("_pushed_ln", {})[name] = (weakref.ref(t), t._version)
         t = t.detach()
         if t.device != self._device:
             t = t.to(self._device)
@@ -286,6 +288,32 @@ class QFormer(nn.Module):
             check(lib().mra_modality_ln(self._handle, ptr(x), _lib.mra_dtype(x.dtype), ptr(item_index), n, x.shape[1],
                                         ptr(out), current_stream()), "mra_modality_ln")
         return out
+
+    def modality_ln_train(self, x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+        """``modality_ln(x)`` (identity item order, the same bits) connected to autograd: ``weight`` / ``bias`` are the ``{m}_ln``
+        tensors last pushed as ``ln.weight`` / ``ln.bias`` -- ordinary torch parameters, not slots of the flat buffer -- and receive
+        real ``.grad`` tensors from ``mra_modality_ln_backward``; ``x`` [items, tokens, E] receives one only if it requires grad.
+        ``MraError`` if the handle holds other tensors (or an older version of these) than the ones given."""
+        pushed = getattr(self, "_pushed_ln", {})
+        for name, t in (("ln.weight", weight), ("ln.bias", bias)):
+            ref, ver = pushed.get(name, (None, None))
+            if ref is None or ref() is not t:
+                raise MraError(f"modality_ln_train: {name} is not the tensor last pushed to the handle (push it first)")
+            if ver != t._version:
+                raise MraError(f"modality_ln_train: {name} changed since it was pushed (version {ver} -> {t._version}): push it again")
+        return _ModalityLNTrainFn.apply(x, weight, bias, self)
+
+    def _ln_backward(self, x: torch.Tensor, d_out: torch.Tensor, want_x: bool, want_gain: bool, want_bias: bool):
+        """``mra_modality_ln_backward`` over raw features x [items, tokens, E] and the fp32 upstream gradient: (d_x or None -- written
+        over ``d_out`` in place --, d_gain or None, d_bias or None), fp32."""
+        E = self.cfg.enc_width
+        d_gain = torch.zeros(E, dtype=torch.float32, device=x.device) if want_gain else None
+        d_bias = torch.zeros(E, dtype=torch.float32, device=x.device) if want_bias else None
+        with torch.cuda.device(self._device):
+            check(lib().mra_modality_ln_backward(self._handle, ptr(x), _lib.mra_dtype(x.dtype), int(x.shape[0]), int(x.shape[1]), ptr(d_out),
+                                                 ptr(d_out) if want_x else None, ptr(d_gain), ptr(d_bias), current_stream()),
+                  "mra_modality_ln_backward")
+        return (d_out if want_x else None), d_gain, d_bias
 
     def raw_features_ok(self, x: torch.Tensor, item_index: Optional[torch.Tensor] = None) -> bool:
         """Can ``forward_fused(..., raw=True)`` read the encoder output ``x`` [N, Kv, E] itself, with no ``modality_ln`` pass
@@ -633,6 +661,14 @@ class QFormer(nn.Module):
         self._dirty = False
         self._grads_zeroed = bool(zero_grad)
 
+    def _enc_grad(self, enc, N, L, Kv, prompts: int, workspace) -> torch.Tensor:
+        """``mra_qformer_backward_enc`` on the tape the backward just walked: the gradient with respect to ``enc``, in its dtype."""
+        d_enc = torch.empty(N, Kv, self.cfg.enc_width, dtype=torch.float32, device=enc.device)
+        with torch.cuda.device(self._device):
+            check(lib().mra_qformer_backward_enc(self._handle, N, prompts, L, Kv, ptr(workspace), workspace.numel(), ptr(d_enc), current_stream()),
+                  "mra_qformer_backward_enc")
+        return d_enc.to(enc.dtype)
+
     def _run_backward(self, input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts: int = 0, workspace=None) -> None:
         # optimizer.zero_grad(set_to_none=True) drops the views: start from a clean buffer in that case
         probe = self.bert.embeddings.LayerNorm.weight
@@ -696,7 +732,8 @@ class _QFormerTrainFn(torch.autograd.Function):
         d_q = None if d_q is None else d_q.to(torch.float32).contiguous()
         d_c = d_c.to(torch.float32).contiguous() if (ctx.want_cls and d_c is not None) else None
         owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c)
-        return torch.zeros_like(owner._anchor), None, None, None, None, None
+        d_enc = owner._enc_grad(enc, N, L, Kv, 1, owner._train_ws) if ctx.needs_input_grad[4] else None
+        return torch.zeros_like(owner._anchor), None, None, None, d_enc, None
 
 
 class _QFormerMultiTrainFn(torch.autograd.Function):
@@ -734,8 +771,39 @@ class _QFormerMultiTrainFn(torch.autograd.Function):
         d_q = None if d_q is None else d_q.to(torch.float32).contiguous()
         d_c = d_c.to(torch.float32).contiguous() if (ctx.want_cls and d_c is not None) else None
         owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts=P, workspace=ctx.ws)
+        d_enc = owner._enc_grad(enc, N, L, Kv, P, ctx.ws) if ctx.needs_input_grad[4] else None
         kept = getattr(owner, "_multi_train_ws", None)
         if kept is None or kept.numel() < ctx.ws.numel():
             owner._multi_train_ws = ctx.ws
         ctx.ws = None
-        return torch.zeros_like(owner._anchor), None, None, None, None, None, None
+        return torch.zeros_like(owner._anchor), None, None, None, d_enc, None, None
+
+
+class _ModalityLNTrainFn(torch.autograd.Function):
+    """Autograd node around ``mra_modality_ln`` / ``mra_modality_ln_backward`` (``QFormer.modality_ln_train``).  The LayerNorm's
+    parameters are read from the handle (the caller pushed them); ``weight`` / ``bias`` are inputs so that autograd hands them their
+    gradients."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, owner):
+        x = x.contiguous()
+        ctx.owner = owner
+        ctx.save_for_backward(x)
+        return owner.modality_ln(x)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        owner = ctx.owner
+        (x,) = ctx.saved_tensors
+        need_x, need_g, need_b = ctx.needs_input_grad[:3]
+        if not (need_x or need_g or need_b):
+            return None, None, None, None
+        d32 = d_out.to(torch.float32).contiguous()
+        if d32.data_ptr() == d_out.data_ptr():
+            d32 = d32.clone()        # d_x is written in place: never over a tensor autograd still owns
+        d_x, d_g, d_b = owner._ln_backward(x, d32, need_x, need_g, need_b)
+        # fused optimizers update the LayerNorm without bumping its version counter: the holder of the parameters pushes them again
+        hook = getattr(owner, "_ln_grad_hook", None)
+        if hook is not None and (need_g or need_b):
+            hook()
+        return (d_x.to(x.dtype) if need_x else None), d_g, d_b, None

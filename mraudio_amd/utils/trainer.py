@@ -21,6 +21,9 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     (``VideoGroupedDataset`` + ``collate_grouped``): ``model(samples)`` then runs ``XInstructBLIP.forward_multi`` -- encoders, modality
     LayerNorm and K/V projection once per video, at most ``args.max_queries_per_call`` (8) queries per Q-Former call.  The reference
     trains one ``(video, query)`` annotation line per sample; the grouped loss is the mean over the same lines.
+  * ``train_ln`` (constructor keyword, or ``args.train_ln``; default off; ``finetune --train-ln``) trains the modality LayerNorms
+    ``{m}_ln`` with the Q-Formers (``model.enable_qformer_training(train_ln=True)``): they are among "any other trainable parameter"
+    above, and the trainable-only checkpoints then carry ``{m}_ln.*``.
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -67,7 +70,7 @@ def _world():
 
 
 class Trainer:
-    def __init__(self, args, model: Optional[torch.nn.Module] = None, train_dataset=None, val_dataset=None):
+    def __init__(self, args, model: Optional[torch.nn.Module] = None, train_dataset=None, val_dataset=None, train_ln: Optional[bool] = None):
         self.val_freq, self.save_freq, self.max_epoch = args.val_freq, args.save_freq, args.max_epoch
         self.output_dir = args.output_dir
         self.resume_ckpt_path = getattr(args, "resume_ckpt_path", None)
@@ -91,7 +94,12 @@ class Trainer:
         if hasattr(model, "clip_parallel"):
             model.clip_parallel = False            # ranks see different samples
         if getattr(args, "train_qformers", True) and hasattr(model, "enable_qformer_training"):
-            model.enable_qformer_training()
+            # train_ln (or args.train_ln): the modality LayerNorms train with the Q-Formers and reach the checkpoints
+            self.train_ln = bool(getattr(args, "train_ln", False) if train_ln is None else train_ln)
+            if self.train_ln:
+                model.enable_qformer_training(train_ln=True)
+            else:
+                model.enable_qformer_training()
         if hasattr(model, "flat_optimizer_params") and getattr(args, "flat_params", True) and getattr(model, "train_qformers", False):
             params = model.flat_optimizer_params()      # one flat parameter per Q-Former: one fused update launch
         else:
