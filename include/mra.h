@@ -324,10 +324,8 @@ int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, 
  *                                 buffer of mra_qformer_grad_bytes() in which parameter `name` (same names
  *                                 as mra_qformer_load) owns numel floats at mra_qformer_grad_offset().
  *                                 Gradients flow to every Q-Former parameter incl. query_tokens and the
- *                                 embeddings.  The encoder side is a call of its own: mra_qformer_backward_enc gives
- *                                 the gradient with respect to enc, mra_modality_ln_backward carries it through the
- *                                 modality LayerNorm to ln.* and the raw features (below).  llm_proj.* still gets
- *                                 none: it is not on the scorer's path. */
+ *                                 embeddings; enc and ln.* get theirs from mra_qformer_backward_enc and
+ *                                 mra_modality_ln_backward (below); llm_proj.* is not on the scorer's path. */
 size_t mra_qformer_grad_bytes(mra_qformer* h);
 /* Optimizer-side fast path: refreshes EVERY bert.* parameter in one launch from a flat f32 master buffer
  * laid out exactly like the gradient buffer (parameter `name` at mra_qformer_grad_offset(name)), converting
@@ -370,10 +368,12 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
  * writes the log-sum-exp the backward needs, whatever mra_qformer_set_option "multi_core" says: the shared-stream core writes none and is
  * not used here.  Long KV splits by the rule of mra_qformer_forward_train on chain items.  Precision as mra_qformer_forward_train.
  * Argument checks worded as mra_qformer_forward_multi (prompts >= 1, enc_items == 0 is a no-op); ownership, workspace lifetime and
- * ADD-into-grads as mra_qformer_forward_train / mra_qformer_backward.  prompts == 1 is that pair launch for launch.  The attention
- * backward keeps fp32 dQ / lse / delta of all prompts of an encoder item in LDS: prompts above 14 (at 32 query rows, 160 KB) -> MRA_EINVAL
- * naming the limit; split the group.  Workspace: mra_qformer_multi_train_workspace_bytes (0 for a NULL handle or a non-positive size),
- * 256-byte aligned. */
+ * ADD-into-grads as mra_qformer_forward_train / mra_qformer_backward, which ARE these entries at prompts = 1, launch for launch, behind what
+ * their older contract keeps: items <= 0 or kv <= 0 is MRA_EINVAL; the forward reports a misaligned workspace as MRA_ENOMEM and runs with
+ * neither output asked for.  mra_qformer_backward thereby refuses with MRA_EINVAL what it used to launch on: L above max_pos, NULL input_ids
+ * with L > 0, d_out_cls with L < 1.  The attention backward keeps fp32 dQ / lse / delta of all prompts of an encoder item in LDS: prompts
+ * above 14 (at 32 query rows, 160 KB) -> MRA_EINVAL naming the limit; split the group.  Workspace: mra_qformer_multi_train_workspace_bytes
+ * (0 for a NULL handle or a non-positive size), 256-byte aligned. */
 size_t mra_qformer_multi_train_workspace_bytes(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv);
 int mra_qformer_forward_multi_train(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
                                     int32_t enc_items, int32_t prompts, int32_t L, int32_t kv, float* out_query, float* out_cls,
@@ -383,8 +383,8 @@ int mra_qformer_backward_multi(mra_qformer* h, const int64_t* input_ids, const i
                                float* grads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Encoder side of the training step: gradients to the features the Q-Former was fed and to the modality LayerNorm in front of it.  Nothing
- * here runs unless it is called: the two backward entries above are launch for launch what they were.
- * mra_qformer_backward_enc: after the matching mra_qformer_backward (prompts = 1) or mra_qformer_backward_multi, on the untouched tape.  The
+ * here runs unless it is called.
+ * mra_qformer_backward_enc: after the matching backward (mra_qformer_backward: prompts = 1), on the untouched tape.  The
  *   backward leaves dK / dV of every cross layer in the workspace (head-major [ncross][k | v][enc_items][heads][kv][64], operand dtype, for a
  *   multi call already summed over the prompts of an item); this call contracts them with the stored K / V weights,
  *     d_enc[item * kv + tok][e] = sum_k dKV[item * kv + tok][k] W_kv[k][e],   k = (cross layer * 2 + k | v) * hidden + head * 64 + d,
@@ -393,7 +393,7 @@ int mra_qformer_backward_multi(mra_qformer* h, const int64_t* input_ids, const i
  *   the forward (the rounding to the operand dtype is passed straight through, like every 16-bit tensor of the tape).  enc_width must be a
  *   multiple of 128.  Checks as the training entries: prompts >= 1, negative size, NULL workspace / d_enc / handle (MRA_EINVAL); training not
  *   enabled or the transposed copies stale (MRA_ESTATE); workspace_bytes below mra_qformer_multi_train_workspace_bytes(h, enc_items,
- *   prompts, L, kv) (MRA_ENOMEM; with prompts = 1 that is mra_qformer_train_workspace_bytes).  enc_items == 0 is a no-op.  No allocation,
+ *   prompts, L, kv) (MRA_ENOMEM).  enc_items == 0 is a no-op.  No allocation,
  *   no synchronisation.
  * mra_modality_ln_backward: backward of mra_modality_ln without an item index, with the handle's loaded ln.weight and enc_ln_eps (MRA_ESTATE
  *   if ln.* is not loaded).  x [items, tokens, E] is the raw feature tensor the forward read (MRA_F32 / MRA_F16 / MRA_BF16), d_out [items,

@@ -326,8 +326,7 @@ int mra_qformer_enable_training(mra_qformer* h, void* stream) {
 }
 
 size_t mra_qformer_train_workspace_bytes(mra_qformer* h, int32_t items, int32_t L, int32_t kv) {
-  if (!h || items <= 0 || L < 0 || kv <= 0) return 0;
-  return layout_train(h, nullptr, items, L, kv, 1).bytes;
+  return mra_qformer_multi_train_workspace_bytes(h, items, 1, L, kv);
 }
 
 }  // extern "C"
@@ -584,7 +583,7 @@ int backward_body(mra_qformer* h, const int64_t* input_ids, const int64_t* atten
   return MRA_OK;
 }
 
-// argument checks the multi entries share (wording as mra_qformer_forward_multi); MRA_OK with *empty set when there is nothing to do
+// the argument checks of every training entry (wording as mra_qformer_forward_multi); MRA_OK with *empty set when there is nothing to do
 int check_multi(mra_qformer* h, const int64_t* input_ids, const void* enc, int enc_items, int prompts, int L, int kv, bool want_cls, bool* empty) {
   *empty = false;
   if (prompts < 1) return fail(MRA_EINVAL, "prompts must be >= 1");
@@ -607,13 +606,15 @@ int check_multi(mra_qformer* h, const int64_t* input_ids, const void* enc, int e
 
 extern "C" {
 
+// The single-prompt entries: the multi entries at prompts = 1, behind the few checks in which the older contract differs -- zero items or
+// kv are refused, not a no-op, and the forward reports a misaligned workspace as MRA_ENOMEM and runs with no output asked for (the tape alone).
 int mra_qformer_forward_train(mra_qformer* h, const int64_t* input_ids, const int64_t* attention_mask, const void* enc,
                               int32_t items, int32_t L, int32_t kv, float* out_query, float* out_cls, void* workspace,
                               size_t workspace_bytes, void* stream_) {
   if (!h) return fail(MRA_EINVAL, "null handle");
-  if (items <= 0 || L < 0 || kv <= 0) return fail(MRA_EINVAL, "bad sizes");
-  const mra_cfg& c = h->cfg;
-  if (L > c.max_pos || !enc || (L > 0 && !input_ids) || (out_cls && L < 1)) return fail(MRA_EINVAL, "bad arguments");
+  if (items <= 0 || kv <= 0) return fail(MRA_EINVAL, "bad sizes");
+  bool empty;
+  if (int rc = check_multi(h, input_ids, enc, items, 1, L, kv, out_cls != nullptr, &empty)) return rc;
   if (!workspace || workspace_bytes < mra_qformer_train_workspace_bytes(h, items, L, kv) || reinterpret_cast<uintptr_t>(workspace) % 256)
     return fail(MRA_ENOMEM, "training workspace too small or misaligned");
   return forward_train_body(h, input_ids, attention_mask, enc, items, 1, L, kv, out_query, out_cls, workspace, as_stream(stream_));
@@ -623,12 +624,9 @@ int mra_qformer_backward(mra_qformer* h, const int64_t* input_ids, const int64_t
                          int32_t L, int32_t kv, const float* d_out_query, const float* d_out_cls, float* grads, void* workspace,
                          size_t workspace_bytes, void* stream_) {
   if (!h) return fail(MRA_EINVAL, "null handle");
-  if (items <= 0 || L < 0 || kv <= 0 || !grads || !enc) return fail(MRA_EINVAL, "bad arguments");
-  if (!d_out_query && !d_out_cls) return fail(MRA_EINVAL, "no upstream gradient");
-  if (!h->arena_t || h->transposes_stale) return fail(MRA_ESTATE, "call mra_qformer_enable_training after the last weight upload");
-  if (!workspace || workspace_bytes < mra_qformer_train_workspace_bytes(h, items, L, kv)) return fail(MRA_ENOMEM, "training workspace too small");
-  if (!h->wg_stream) return fail(MRA_ESTATE, "call mra_qformer_enable_training first");
-  return backward_body(h, input_ids, attention_mask, enc, items, 1, L, kv, d_out_query, d_out_cls, grads, workspace, as_stream(stream_));
+  if (items <= 0 || kv <= 0) return fail(MRA_EINVAL, "bad sizes");
+  return mra_qformer_backward_multi(h, input_ids, attention_mask, enc, items, 1, L, kv, d_out_query, d_out_cls, grads, workspace, workspace_bytes,
+                                    stream_);
 }
 
 size_t mra_qformer_multi_train_workspace_bytes(mra_qformer* h, int32_t enc_items, int32_t prompts, int32_t L, int32_t kv) {

@@ -326,6 +326,28 @@ class QFormer(nn.Module):
         self.sync_weights()
         return bool(lib().mra_qformer_raw_features_ok(self._handle, int(x.shape[1]), _lib.mra_dtype(x.dtype)))
 
+    def _prepare(self, input_ids, attention_mask, enc, prompts: int = 1):
+        """What every forward checks and casts before it calls the library: enc [N, Kv, E] to the operand dtype, contiguous; input_ids
+        [N * prompts, L] and attention_mask [N * prompts, 32 + L] to int64 on enc's device.  ``MraError`` on any other shape (the kernels
+        index by these sizes).  Returns ``(input_ids, attention_mask, enc, N, L, Kv)``."""
+        cfg = self.cfg
+        if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
+            raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
+        enc = enc.to(cfg.op_dtype).contiguous()
+        N, Kv = int(enc.shape[0]), int(enc.shape[1])
+        rows = N * prompts
+        L = 0
+        if input_ids is not None:
+            if input_ids.shape[0] != rows:
+                raise MraError(f"input_ids has {input_ids.shape[0]} rows, encoder_hidden_states {N}" + (f" x prompts {prompts}" if prompts != 1 else ""))
+            L = int(input_ids.shape[1])
+            input_ids = input_ids.to(device=enc.device, dtype=torch.int64).contiguous()
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != (rows, cfg.n_query + L):
+                raise MraError(f"attention_mask must be [{rows}, {cfg.n_query + L}], got {tuple(attention_mask.shape)}")
+            attention_mask = attention_mask.to(device=enc.device, dtype=torch.int64).contiguous()
+        return input_ids, attention_mask, enc, N, L, Kv
+
     def forward_fused(self, input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor], enc: torch.Tensor,
                       query_embeds: Optional[torch.Tensor] = None, want_query: bool = True, want_full: bool = False,
                       want_cls: bool = False, kv_events=None, raw: bool = False) -> Dict[str, torch.Tensor]:
@@ -336,24 +358,10 @@ class QFormer(nn.Module):
         instrumentation of the dominant kernel, recorded by the library on the launch stream)."""
         self.sync_weights()
         cfg = self.cfg
-        if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
-            raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
         if raw and (enc.dtype != cfg.op_dtype or not enc.is_contiguous()):
             raise MraError("raw features must be contiguous and in the operand dtype (ask raw_features_ok)")
-        if enc.dtype != cfg.op_dtype:
-            enc = enc.to(cfg.op_dtype)
-        enc = enc.contiguous()
-        N, Kv = int(enc.shape[0]), int(enc.shape[1])
-        L = 0 if input_ids is None else int(input_ids.shape[1])
+        input_ids, attention_mask, enc, N, L, Kv = self._prepare(input_ids, attention_mask, enc)
         dev = enc.device
-        if input_ids is not None:
-            if input_ids.shape[0] != N:
-                raise MraError(f"input_ids has {input_ids.shape[0]} rows, encoder_hidden_states {N}")
-            input_ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if attention_mask is not None:
-            if tuple(attention_mask.shape) != (N, cfg.n_query + L):
-                raise MraError(f"attention_mask must be [{N}, {cfg.n_query + L}], got {tuple(attention_mask.shape)}")
-            attention_mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous()
         q_items = 0
         if query_embeds is not None:
             if query_embeds.dim() != 3 or tuple(query_embeds.shape[1:]) != (cfg.n_query, cfg.hidden) or query_embeds.shape[0] not in (1, N):
@@ -400,22 +408,8 @@ class QFormer(nn.Module):
         P = int(prompts)
         if P < 1:
             raise MraError(f"prompts must be >= 1, got {prompts}")
-        if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
-            raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
-        if enc.dtype != cfg.op_dtype:
-            enc = enc.to(cfg.op_dtype)
-        enc = enc.contiguous()
-        N, Kv = int(enc.shape[0]), int(enc.shape[1])
-        L = 0 if input_ids is None else int(input_ids.shape[1])
+        input_ids, attention_mask, enc, N, L, Kv = self._prepare(input_ids, attention_mask, enc, P)
         dev = enc.device
-        if input_ids is not None:
-            if input_ids.shape[0] != N * P:
-                raise MraError(f"input_ids has {input_ids.shape[0]} rows, encoder_hidden_states {N} x prompts {P}")
-            input_ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if attention_mask is not None:
-            if tuple(attention_mask.shape) != (N * P, cfg.n_query + L):
-                raise MraError(f"attention_mask must be [{N * P}, {cfg.n_query + L}], got {tuple(attention_mask.shape)}")
-            attention_mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous()
         if N == 0:
             return {"query": torch.empty(0, cfg.n_query, cfg.hidden, device=dev), "cls": torch.empty(0, cfg.hidden, device=dev)}
         out: Dict[str, torch.Tensor] = {}
@@ -439,21 +433,14 @@ class QFormer(nn.Module):
         ``[(query0, cls0), (query1, cls1)]`` (fp32; cls ``None`` without ``want_cls``).  ``kv_events``: (start, stop) pair for lane 0's
         cross-layer-0 block (bench instrumentation).  ``raw[l]``: lane l's enc is the encoder output itself (``raw_features_ok``;
         ``mra_qformer_forward_pair_raw``)."""
-        qfs, encs = (qf0, qf1), []
-        for qf, enc in zip(qfs, (enc0, enc1)):
+        qfs = (qf0, qf1)
+        for qf in qfs:
             qf.sync_weights()
-            if enc.dim() != 3 or enc.shape[-1] != qf.cfg.enc_width:
-                raise MraError(f"encoder_hidden_states must be [N, Kv, {qf.cfg.enc_width}], got {tuple(enc.shape)}")
-            encs.append(enc.to(qf.cfg.op_dtype).contiguous())
-        N = int(encs[0].shape[0])
+        input_ids, attention_mask, enc0, N, L, _ = qf0._prepare(input_ids, attention_mask, enc0)
+        encs = [enc0, qf1._prepare(None, None, enc1)[2]]
         if int(encs[1].shape[0]) != N:
             raise MraError("forward_pair: both lanes need the same number of items")
-        dev = encs[0].device
-        L = 0 if input_ids is None else int(input_ids.shape[1])
-        if input_ids is not None:
-            input_ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if attention_mask is not None:
-            attention_mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous()
+        dev = enc0.device
         H, Q = qf0.cfg.hidden, qf0.cfg.n_query
         outs = [(torch.empty(N, Q, H, dtype=torch.float32, device=dev), torch.empty(N, H, dtype=torch.float32, device=dev) if want_cls else None) for _ in qfs]
         if N == 0:
@@ -535,7 +522,7 @@ class QFormer(nn.Module):
             n = int(lib().mra_qformer_grad_bytes(self._handle)) // 4
             self._grad_flat = torch.zeros(n, dtype=torch.float32, device=self._device)
             self._anchor = torch.zeros((), dtype=torch.float32, device=self._device, requires_grad=True)
-            self._train_ws = None
+            self._train_ws = None       # the spare tape buffer: the one a training node took last, handed back after its backward
             self._slices = {}
             for k, p in self.bert.state_dict(prefix="bert.", keep_vars=True).items():
                 self._slices[k] = (*self._slice_of(k), p)
@@ -579,16 +566,11 @@ class QFormer(nn.Module):
 
     def forward_train(self, input_ids, attention_mask, enc, want_cls: bool = True):
         """Training forward: ``(out_query [N,32,H], out_cls [N,H])`` connected to autograd.  ``loss.backward()``
-        accumulates parameter gradients (``p.grad`` of every ``bert.*`` parameter, ``grad_of('query_tokens')``)."""
-        self.enable_training()
-        cfg = self.cfg
-        enc = enc.to(cfg.op_dtype).contiguous()
-        if input_ids is not None:
-            input_ids = input_ids.to(device=enc.device, dtype=torch.int64).contiguous()
-        if attention_mask is not None:
-            attention_mask = attention_mask.to(device=enc.device, dtype=torch.int64).contiguous()
-        q, c = _QFormerTrainFn.apply(self._anchor, self, input_ids, attention_mask, enc, want_cls)
-        return (q, c) if want_cls else (q, None)
+        accumulates parameter gradients (``p.grad`` of every ``bert.*`` parameter, ``grad_of('query_tokens')``).
+        ``forward_multi_train`` with one prompt per item; ``MraError`` on zero items."""
+        if enc.dim() == 3 and enc.shape[0] == 0:
+            raise MraError("forward_train: no items")
+        return self.forward_multi_train(input_ids, attention_mask, enc, 1, want_cls)
 
 
     def forward_multi_train(self, input_ids, attention_mask, enc, prompts: int, want_cls: bool = True):
@@ -596,28 +578,15 @@ class QFormer(nn.Module):
         ``(out_query [N * prompts, 32, H], out_cls [N * prompts, H])`` connected to autograd, row ``i * prompts + p`` = item ``i``,
         prompt slot ``p`` (the row order of ``forward_multi``).  enc [N, Kv, E] is given once per item.  Equal to ``forward_train`` on
         ``enc.repeat_interleave(prompts, 0)``; the K/V projection, the dK / dV tape and the K/V weight gradients run once per item.
-        ``loss.backward()`` accumulates gradients exactly as after ``forward_train``.  ``prompts`` is limited by the LDS of the
-        attention backward (14 at 32 query tokens; ``MraError`` beyond).  The tape lives in a workspace of its own, so a second call
-        before the first one's backward gets a fresh one."""
+        ``loss.backward()`` accumulates gradients into the flat buffer.  ``prompts`` is limited by the LDS of the attention backward
+        (14 at 32 query tokens; ``MraError`` beyond).  Every call's node holds its tape until its backward has run, so several
+        forwards may precede their backwards, in any order."""
         self.enable_training()
-        cfg = self.cfg
         P = int(prompts)
         if P < 1:
             raise MraError(f"prompts must be >= 1, got {prompts}")
-        if enc.dim() != 3 or enc.shape[-1] != cfg.enc_width:
-            raise MraError(f"encoder_hidden_states must be [N, Kv, {cfg.enc_width}], got {tuple(enc.shape)}")
-        enc = enc.to(cfg.op_dtype).contiguous()
-        N = int(enc.shape[0])
-        L = 0 if input_ids is None else int(input_ids.shape[1])
-        if input_ids is not None:
-            if input_ids.shape[0] != N * P:
-                raise MraError(f"input_ids has {input_ids.shape[0]} rows, encoder_hidden_states {N} x prompts {P}")
-            input_ids = input_ids.to(device=enc.device, dtype=torch.int64).contiguous()
-        if attention_mask is not None:
-            if tuple(attention_mask.shape) != (N * P, cfg.n_query + L):
-                raise MraError(f"attention_mask must be [{N * P}, {cfg.n_query + L}], got {tuple(attention_mask.shape)}")
-            attention_mask = attention_mask.to(device=enc.device, dtype=torch.int64).contiguous()
-        q, c = _QFormerMultiTrainFn.apply(self._anchor, self, input_ids, attention_mask, enc, P, want_cls)
+        input_ids, attention_mask, enc, _, _, _ = self._prepare(input_ids, attention_mask, enc, P)
+        q, c = _QFormerTrainFn.apply(self._anchor, self, input_ids, attention_mask, enc, P, want_cls)
         return (q, c) if want_cls else (q, None)
 
 
@@ -669,7 +638,7 @@ class QFormer(nn.Module):
                   "mra_qformer_backward_enc")
         return d_enc.to(enc.dtype)
 
-    def _run_backward(self, input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts: int = 0, workspace=None) -> None:
+    def _run_backward(self, input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts: int, workspace) -> None:
         # optimizer.zero_grad(set_to_none=True) drops the views: start from a clean buffer in that case
         probe = self.bert.embeddings.LayerNorm.weight
         fp = getattr(self, "_flat_param", None)
@@ -677,15 +646,10 @@ class QFormer(nn.Module):
             self._grad_flat.zero_()
         if fp is not None:
             fp.grad = self._grad_flat
-        with torch.cuda.device(self._device):
-            if prompts:      # N encoder items x `prompts` chain items over the tape of forward_multi_train
-                check(lib().mra_qformer_backward_multi(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, prompts, L, Kv, ptr(d_q),
-                                                       ptr(d_c), ptr(self._grad_flat), ptr(workspace), workspace.numel(), current_stream()),
-                      "mra_qformer_backward_multi")
-            else:
-                check(lib().mra_qformer_backward(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, L, Kv, ptr(d_q), ptr(d_c),
-                                                 ptr(self._grad_flat), ptr(self._train_ws), self._train_ws.numel(), current_stream()),
-                      "mra_qformer_backward")
+        with torch.cuda.device(self._device):      # N encoder items x `prompts` chain items over the node's tape
+            check(lib().mra_qformer_backward_multi(self._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, prompts, L, Kv, ptr(d_q),
+                                                   ptr(d_c), ptr(self._grad_flat), ptr(workspace), workspace.numel(), current_stream()),
+                  "mra_qformer_backward_multi")
         self._bind_grads()
         binder = getattr(self, "_extra_grad_binder", None)
         if binder is not None:
@@ -699,46 +663,11 @@ class QFormer(nn.Module):
 # training (BASELINE config 5): forward with an activation tape + HIP backward behind torch.autograd
 # --------------------------------------------------------------------------------------------------
 class _QFormerTrainFn(torch.autograd.Function):
-    """Autograd node around ``mra_qformer_forward_train`` / ``mra_qformer_backward``.  The parameters
-    live inside the handle, so the node takes an anchor tensor that requires grad; its backward runs the
-    HIP backward, which ADDS into the owner's flat f32 gradient buffer (``QFormer.grad_of``)."""
-
-    @staticmethod
-    def forward(ctx, anchor, owner, input_ids, attention_mask, enc, want_cls):
-        cfg = owner.cfg
-        N, Kv = int(enc.shape[0]), int(enc.shape[1])
-        L = 0 if input_ids is None else int(input_ids.shape[1])
-        dev = enc.device
-        out_q = torch.empty(N, cfg.n_query, cfg.hidden, dtype=torch.float32, device=dev)
-        out_c = torch.empty(N, cfg.hidden, dtype=torch.float32, device=dev) if want_cls else None
-        with torch.cuda.device(dev):
-            nbytes = int(lib().mra_qformer_train_workspace_bytes(owner._handle, N, L, Kv))
-            if owner._train_ws is None or owner._train_ws.numel() < nbytes:
-                owner._train_ws = None
-                owner._train_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            check(lib().mra_qformer_forward_train(owner._handle, ptr(input_ids), ptr(attention_mask), ptr(enc), N, L, Kv, ptr(out_q),
-                                                  ptr(out_c), ptr(owner._train_ws), owner._train_ws.numel(), current_stream()),
-                  "mra_qformer_forward_train")
-        ctx.owner, ctx.shape = owner, (N, L, Kv)
-        ctx.save_for_backward(input_ids, attention_mask, enc)
-        ctx.want_cls = want_cls
-        return (out_q, out_c) if want_cls else (out_q, torch.empty(0, device=dev))
-
-    @staticmethod
-    def backward(ctx, d_q, d_c):
-        owner = ctx.owner
-        input_ids, attention_mask, enc = ctx.saved_tensors
-        N, L, Kv = ctx.shape
-        d_q = None if d_q is None else d_q.to(torch.float32).contiguous()
-        d_c = d_c.to(torch.float32).contiguous() if (ctx.want_cls and d_c is not None) else None
-        owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c)
-        d_enc = owner._enc_grad(enc, N, L, Kv, 1, owner._train_ws) if ctx.needs_input_grad[4] else None
-        return torch.zeros_like(owner._anchor), None, None, None, d_enc, None
-
-
-class _QFormerMultiTrainFn(torch.autograd.Function):
-    """Autograd node around ``mra_qformer_forward_multi_train`` / ``mra_qformer_backward_multi``: as ``_QFormerTrainFn`` (same anchor,
-    same gradient buffer and bookkeeping), with the tape in a workspace the node holds until its backward has run."""
+    """Autograd node around ``mra_qformer_forward_multi_train`` / ``mra_qformer_backward_multi`` (``prompts == 1``: the single-prompt
+    step, launch for launch).  The parameters live inside the handle, so the node takes an anchor tensor that requires grad; its backward
+    runs the HIP backward, which ADDS into the owner's flat f32 gradient buffer (``QFormer.grad_of``).  The node owns its tape: it takes
+    the owner's spare buffer if that is large enough (a fresh one otherwise), holds it in ``ctx.ws`` until its backward and
+    ``_enc_grad`` have run, and hands it back -- a forward / backward loop reuses one buffer, overlapping nodes never share one."""
 
     @staticmethod
     def forward(ctx, anchor, owner, input_ids, attention_mask, enc, prompts, want_cls):
@@ -750,8 +679,7 @@ class _QFormerMultiTrainFn(torch.autograd.Function):
         out_c = torch.empty(N * prompts, cfg.hidden, dtype=torch.float32, device=dev) if want_cls else None
         with torch.cuda.device(dev):
             nbytes = int(lib().mra_qformer_multi_train_workspace_bytes(owner._handle, N, prompts, L, Kv))
-            ws = getattr(owner, "_multi_train_ws", None)      # free again once the node that used it last has run its backward
-            owner._multi_train_ws = None
+            ws, owner._train_ws = owner._train_ws, None
             if ws is None or ws.numel() < nbytes:
                 ws = None
                 ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
@@ -770,11 +698,10 @@ class _QFormerMultiTrainFn(torch.autograd.Function):
         N, P, L, Kv = ctx.shape
         d_q = None if d_q is None else d_q.to(torch.float32).contiguous()
         d_c = d_c.to(torch.float32).contiguous() if (ctx.want_cls and d_c is not None) else None
-        owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, prompts=P, workspace=ctx.ws)
-        d_enc = owner._enc_grad(enc, N, L, Kv, P, ctx.ws) if ctx.needs_input_grad[4] else None
-        kept = getattr(owner, "_multi_train_ws", None)
-        if kept is None or kept.numel() < ctx.ws.numel():
-            owner._multi_train_ws = ctx.ws
+        owner._run_backward(input_ids, attention_mask, enc, N, L, Kv, d_q, d_c, P, ctx.ws)
+        d_enc = owner._enc_grad(enc, N, L, Kv, P, ctx.ws) if ctx.needs_input_grad[4] else None      # reads the tape the backward just walked
+        if owner._train_ws is None or owner._train_ws.numel() < ctx.ws.numel():
+            owner._train_ws = ctx.ws
         ctx.ws = None
         return torch.zeros_like(owner._anchor), None, None, None, d_enc, None, None
 

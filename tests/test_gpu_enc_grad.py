@@ -362,9 +362,8 @@ def test_requesting_the_encoder_gradient_changes_nothing_else(P, dev):
     _assert_same_step(qf, g0, g1, "with against without the encoder gradient")
     # inside one backward: the tape of a step WITHOUT the request, then the new launch alone on it
     q2, c2, g2, _, node = step(False)
-    ws = node.ws if P else qf._train_ws
-    if ws is None:
-        ws = qf._multi_train_ws                         # the multi node hands its tape back to the owner after its backward
+    assert node.ws is None
+    ws = qf._train_ws                                   # the node hands its tape back to the owner after its backward
     tape = ws.clone()
     again = qf._enc_grad(enc0, n, L, kv, max(P, 1), ws)
     torch.cuda.synchronize(dev)

@@ -110,27 +110,147 @@ def _enc(w, enc_items, kv, E, seed, op_dtype):
 
 
 def test_one_prompt_is_the_existing_training_step(dev):
+    """``mra_qformer_forward_train`` + ``mra_qformer_backward`` called directly, on a workspace and a gradient buffer of the test's own,
+    against ``forward_train`` + ``backward()``, which go through the multi entries with one prompt per item."""
+    from mraudio_amd import _lib
+
     qf, cfg, ocfg, w = _setup(dev, 768, 1)
     n, L, kv = 3, 5, 40
     ids, att = make_rows(cfg, n, L, 3)
-    enc = _enc(w, n, kv, 768, 4, torch.float16).to(dev)
+    ids, att = ids.to(dev).contiguous(), att.to(dev).contiguous()
+    enc = _enc(w, n, kv, 768, 4, torch.float16).to(dev).contiguous()
     g = torch.Generator().manual_seed(5)
     rq, rc = torch.randn(n, 32, 768, generator=g).to(dev), torch.randn(n, 768, generator=g).to(dev)
     qf.enable_training()
-    outs, grads = [], []
-    for multi in (False, True):
-        qf._grad_flat.zero_()
-        q, c = qf.forward_multi_train(ids.to(dev), att.to(dev), enc, 1) if multi else qf.forward_train(ids.to(dev), att.to(dev), enc)
-        ((q * rq).sum() + (c * rc).sum()).backward()
-        torch.cuda.synchronize()
-        outs.append((q.detach().clone(), c.detach().clone()))
-        grads.append(qf._grad_flat.clone())
-    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    assert grads[0].abs().max().item() > 0
-    assert torch.allclose(grads[1], grads[0], rtol=1e-3, atol=1e-5)
-    from mraudio_amd import _lib
     L_ = _lib.lib()
-    assert L_.mra_qformer_multi_train_workspace_bytes(qf._handle, n, 1, L, kv) == L_.mra_qformer_train_workspace_bytes(qf._handle, n, L, kv)
+    nbytes = int(L_.mra_qformer_train_workspace_bytes(qf._handle, n, L, kv))
+    assert nbytes > 0 and nbytes == L_.mra_qformer_multi_train_workspace_bytes(qf._handle, n, 1, L, kv)
+    # the single entries, directly: d loss / d q = rq and d loss / d cls = rc for the loss below
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    grads = torch.zeros_like(qf._grad_flat)
+    q0, c0 = torch.empty(n, 32, 768, device=dev), torch.empty(n, 768, device=dev)
+    with torch.cuda.device(dev):
+        rc_ = L_.mra_qformer_forward_train(qf._handle, _lib.ptr(ids), _lib.ptr(att), _lib.ptr(enc), n, L, kv, _lib.ptr(q0), _lib.ptr(c0), _lib.ptr(ws),
+                                           nbytes, _lib.current_stream())
+        assert rc_ == 0, L_.mra_last_error()
+        rc_ = L_.mra_qformer_backward(qf._handle, _lib.ptr(ids), _lib.ptr(att), _lib.ptr(enc), n, L, kv, _lib.ptr(rq), _lib.ptr(rc), _lib.ptr(grads),
+                                      _lib.ptr(ws), nbytes, _lib.current_stream())
+        assert rc_ == 0, L_.mra_last_error()
+    torch.cuda.synchronize()
+    qf._grad_flat.zero_()
+    q, c = qf.forward_train(ids, att, enc)
+    ((q * rq).sum() + (c * rc).sum()).backward()
+    torch.cuda.synchronize()
+    assert torch.equal(q0, q.detach()) and torch.equal(c0, c.detach())
+    assert grads.abs().max().item() > 0
+    assert torch.allclose(qf._grad_flat, grads, rtol=1e-3, atol=1e-5)
+
+
+# ---- 2b. one node, one tape policy --------------------------------------------------------------------------------------------------------
+STEPS = {"A": (2, 5, 24, 3), "B": (3, 7, 40, 13)}       # enc items, L, kv, seed; B's tape is the larger one
+
+
+@functools.lru_cache(maxsize=None)
+def _tape_qf():
+    return _setup(torch.device("cuda:0"), 768, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _step_inputs(name, P):
+    """Inputs of step ``name`` with ``P`` prompts per item (0: ``forward_train``), on the device."""
+    qf, cfg, ocfg, w = _tape_qf()
+    dev = torch.device("cuda:0")
+    n, L, kv, seed = STEPS[name]
+    N = n * max(P, 1)
+    ids, att = make_rows(cfg, N, L, seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    rq, rc = torch.randn(N, 32, 768, generator=g).to(dev), torch.randn(N, 768, generator=g).to(dev)
+    return ids.to(dev), att.to(dev), _enc(w, n, kv, 768, seed + 2, torch.float16).to(dev), rq, rc
+
+
+def _forward(name, P):
+    """The forward of a step: (loss, q, cls, enc leaf)."""
+    qf = _tape_qf()[0]
+    ids, att, enc0, rq, rc = _step_inputs(name, P)
+    enc = enc0.clone().requires_grad_(True)
+    q, c = qf.forward_multi_train(ids, att, enc, P) if P else qf.forward_train(ids, att, enc)
+    return (q * rq).sum() + (c * rc).sum(), q, c, enc
+
+
+@functools.lru_cache(maxsize=None)
+def _step_alone(name, P):
+    """One step on its own from a zeroed gradient buffer: (q, cls, enc.grad, flat gradient buffer), computed once."""
+    qf = _tape_qf()[0]
+    qf.enable_training()
+    qf._grad_flat.zero_()
+    loss, q, c, enc = _forward(name, P)
+    loss.backward()
+    torch.cuda.synchronize()
+    return q.detach().clone(), c.detach().clone(), enc.grad.clone(), qf._grad_flat.clone()
+
+
+@pytest.mark.parametrize("PA,PB", [(0, 0), (0, 3), (3, 0)], ids=["single-single", "single-multi3", "multi3-single"])
+def test_overlapping_tapes_do_not_disturb_each_other(dev, PA, PB):
+    """Forward A, forward B (a larger tape), backward B, backward A on one ``QFormer`` give what A and B give alone.  Before the training
+    node owned its tape, the single-prompt forward wrote it into a buffer of the owner that B's forward overwrote or replaced: the single
+    cases then gave wrong gradients for A with no error (not measured: that code is not run for this)."""
+    qf = _tape_qf()[0]
+    alone = {"A": _step_alone("A", PA), "B": _step_alone("B", PB)}
+    qf._grad_flat.zero_()
+    fa = _forward("A", PA)
+    fb = _forward("B", PB)
+    assert fa[1].grad_fn.ws is not fb[1].grad_fn.ws
+    fb[0].backward()
+    fa[0].backward()
+    torch.cuda.synchronize()
+    for name, (_, q, c, enc) in (("A", fa), ("B", fb)):
+        q1, c1, d_enc1, _ = alone[name]
+        assert torch.equal(q.detach(), q1) and torch.equal(c.detach(), c1), name
+        assert d_enc1.abs().max().item() > 0 and torch.equal(enc.grad, d_enc1), (name, (enc.grad - d_enc1).abs().max().item())
+    want = alone["A"][3] + alone["B"][3]
+    assert want.abs().max().item() > 0
+    assert torch.allclose(qf._grad_flat, want, rtol=1e-3, atol=1e-5), (qf._grad_flat - want).abs().max().item()
+
+
+def test_a_training_loop_reuses_one_tape_buffer(dev):
+    qf = _tape_qf()[0]
+    ids, att, enc, rq, rc = _step_inputs("B", 0)
+    ptrs, allocated = [], []
+    for _ in range(3):
+        q, c = qf.forward_train(ids, att, enc)
+        ptrs.append(q.grad_fn.ws.data_ptr())
+        ((q * rq).sum() + (c * rc).sum()).backward()
+        del q, c
+        torch.cuda.synchronize()
+        allocated.append(torch.cuda.memory_allocated(dev))
+    assert ptrs[0] == ptrs[1] == ptrs[2], ptrs
+    assert allocated[2] == allocated[1], allocated
+
+
+def test_forward_train_validates_its_arguments_before_any_launch(dev):
+    from mraudio_amd import _lib
+    from mraudio_amd._lib import MraError
+
+    qf, cfg, ocfg, w = _tape_qf()
+    n, L, kv, _ = STEPS["A"]
+    ids, att, enc, _, _ = _step_inputs("A", 0)
+    qf.enable_training()
+    qf._grad_flat.fill_(1.0)
+    nbytes = int(_lib.lib().mra_qformer_train_workspace_bytes(qf._handle, n + 1, L, kv))
+    spare = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=dev).view(torch.uint8)
+    qf._train_ws = spare
+    before = spare.clone()
+    bad = {"attention_mask [N, L]": (ids, att[:, 32:], enc),
+           "input_ids with N + 1 rows": (torch.cat([ids, ids[:1]]), att, enc),
+           "enc of the wrong width": (ids, att, enc[..., :704]),
+           "no items": (ids[:0], att[:0], enc[:0])}
+    for what, (i, a, e) in bad.items():
+        with pytest.raises(MraError):
+            qf.forward_train(i, a, e)
+        torch.cuda.synchronize()
+        assert qf._train_ws is spare and torch.equal(spare, before), what
+        assert bool((qf._grad_flat == 1.0).all()), what
+    qf._grad_flat.zero_()
 
 
 # ---- 3. gradients against oracle autograd on replicated encoder rows -------------------------------------------------------------------

@@ -315,6 +315,10 @@ def test_new_entries_reject_bad_arguments_before_any_launch():
                  lambda p: L.mra_qformer_backward_multi(None, None, None, None, 2, p, 9, 257, None, None, None, None, 0, None)):
         assert call(3) == -1 and b"null handle" in L.mra_last_error()
         assert call(0) == -1 and b"prompts" in L.mra_last_error()      # refused on its own ground, ahead of everything else
+    # the single entries: the same checks behind a null-handle test of their own
+    assert L.mra_qformer_train_workspace_bytes(None, 2, 9, 257) == 0
+    assert L.mra_qformer_forward_train(None, None, None, None, 2, 9, 257, None, None, None, 0, None) == -1 and b"null handle" in L.mra_last_error()
+    assert L.mra_qformer_backward(None, None, None, None, 2, 9, 257, None, None, None, None, 0, None) == -1 and b"null handle" in L.mra_last_error()
     # the core's debug entry: host buffers stand in for device memory, every call below must return before it would launch
     f = C.create_string_buffer(1 << 12)
     args = lambda **kw: [kw.get(k, d) for k, d in (("q", f), ("k", f), ("v", f), ("o", f), ("d_o", f), ("lse", f), ("dtype", _lib.MRA_F16),   # noqa: E731
