@@ -676,7 +676,8 @@ int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_vi
  *   struct_bytes   sizeof(mra_gemm_desc) as the caller sees it; a mismatch is refused, not misread
  *   *_view         row views, HOST triples {item_stride, rows per item, row stride} in elements
  *   *_bytes        bytes addressable from the pointer of the same name (0 with a NULL pointer)
- * mra_debug_gemm: epilogue one of EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART, EPI_RES_LN (0 .. 5, 9); dtype MRA_F16 /
+ * mra_debug_gemm: epilogue one of EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART, EPI_RES_LN (0 .. 5, 9) or one of the ViT's
+ *   (below); dtype MRA_F16 /
  *   MRA_BF16.  gemm_plan runs first (it picks the tile every footprint below is computed with); then refused with MRA_EINVAL and a message:
  *   a NULL A / W / C; A, W, C, R, bias, the LayerNorm buffers or pscale not 16-byte aligned (stat_m, stat_l, ln_counter: 4); an A view whose
  *   strides are not multiples of 8 or a batch stride the vector accesses cannot take (a_bs, w_bs: 8 elements; c_bs_bytes: 16 bytes;
@@ -693,6 +694,17 @@ int mra_debug_gemm_gelu(int32_t nprob, const void* const* A, const int64_t* a_vi
  *     ln_*     N floats of gain and bias, the output rows of the views, ceil(M / 64) counters; the counter ranges of two EPI_RES_LN problems
  *              of one launch must not overlap
  *   What the entry cannot see is device DATA: with pscale the caller keeps A zero from column ps_ntiles * 176 on, and the counters zero.
+ *   The ViT encoder's launches (csrc/vit.hip; tests/test_gpu_gemm_vit.py): epilogues EPI_RES_OP, EPI_RES_F32_STAT, EPI_LNF_OP, EPI_LNF_GELU_OP,
+ *   EPI_RES_OP_STAT (8, 10 .. 13) and tile_cfg GT_P8_MIXED (N = 256 k + 128 >= 384, K % 128 == 0; GT_P8_TAIL has no shipped call site and stays
+ *   refused).  One plain problem each: nprob > 1, a batch or n_ragged is refused.  Under them the LayerNorm fields mean other things --
+ *     aux      (8, 13) required, 16-byte aligned, the C footprint in the operand dtype; aux == C (in place) or no overlap with C at all
+ *     ln_y32   (11, 12) READ: M x 2 floats of (mean, rstd) per row; (10) WRITTEN: M x (N / 128) x 2 floats of (mean, sum of squared
+ *              deviations) per row and 128-column group; (13) the same per 64-column block, M x (N / 64) x 2.  8-byte aligned; ln_y32_view
+ *              is ignored
+ *     ln_gain  (11, 12) N floats: the column sums of the folded weight; ln_bias is not read
+ *     ln_y16   (10) the rows once more in the operand dtype: rows of ln_y16_view (strides multiples of 8) x N elements, 16-byte aligned
+ *     bias     (10, 13) required, N floats;  R (10) as for EPI_RES_F32
+ *   and whatever epilogue_rules / tile_rules of csrc/gemm.hip refuse for them is MRA_EINVAL here, never a launch.
  * mra_debug_gemm_plan: host only, no GPU needed and no pointer followed: the same checks over the same descriptors -- every refusal above --
  *   and gemm_plan for a device of `cus` compute units, without the launch.  out[0 .. 6] = tile (GemmTile), family (GemmFamily), threads, LDS
  *   bytes, grid, persistent flag, total tiles. */
@@ -717,9 +729,30 @@ typedef struct mra_gemm_desc {
    * + cs_eps)) and written there for n < N.  C = T(exp2(alpha r acc - stat_m) r), stat_m over r acc, stat_l the fp32 sum of the exponentials. */
   float* col_scale; int64_t cs_bs; int32_t col_stats; float cs_eps;
   uint64_t col_scale_bytes;
+  /* EPI_RES_OP / EPI_RES_OP_STAT (appended; NULL otherwise): the residual in the operand dtype, addressed with c_view.  aux == C updates the
+   * stream in place; any other overlap with C is refused. */
+  void* aux; uint64_t aux_bytes;
 } mra_gemm_desc;
 int mra_debug_gemm(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, void* stream);
 int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, int32_t cus, int32_t* out);
+
+/* The companions of the ViT's folded LayerNorm (csrc/vit.hip), one launch each through the launch forms of mra_vit_forward
+ * (tests/test_gpu_gemm_vit.py).  No handle, no allocation; device pointers, every buffer with its size in bytes; `dtype` is the operand dtype
+ * (MRA_F16 / MRA_BF16).  Checked on the host before the launch, MRA_EINVAL with a message: a NULL or misaligned buffer, a size out of range,
+ * a footprint that leaves the given bytes.  Zero rows is a no-op.
+ * mra_debug_vit_fold_weight: W [N][K] operand dtype, gain / beta [K], bias [N] or NULL -> Wf [N][K] = T(w gain), cs [N] = the row sums of
+ *   the ROUNDED Wf, bf [N] = bias + sum_k beta w.  Wf may be W itself; any other overlap is refused.
+ * mra_debug_vit_group_stats: groups [M][G] float2 (mean, sum of squared deviations) of group_cols columns each -> stats [M] float2
+ *   (mean, 1 / sqrt(variance + eps)) of the whole row.  G and group_cols 1 .. 4096; groups and stats 8-byte aligned.
+ * mra_debug_vit_row_stats: x [M][D] -> stats [M] float2 (mean, rstd).  x_dtype MRA_F32: x fp32 (8-byte aligned) and x16 [M][D] receives the
+ *   rows in the operand dtype; x_dtype == dtype: x in the operand dtype, x16 must be NULL.  D a multiple of 128, at most 2048. */
+int mra_debug_vit_fold_weight(const void* W, size_t w_bytes, const float* gain, size_t gain_bytes, const float* beta, size_t beta_bytes, const float* bias,
+                              size_t bias_bytes, void* Wf, size_t wf_bytes, float* cs, size_t cs_bytes, float* bf, size_t bf_bytes, int32_t N, int32_t K,
+                              int32_t dtype, void* stream);
+int mra_debug_vit_group_stats(const float* groups, size_t groups_bytes, int64_t M, int32_t G, int32_t group_cols, float eps, float* stats,
+                              size_t stats_bytes, void* stream);
+int mra_debug_vit_row_stats(const void* x, size_t x_bytes, int32_t x_dtype, int64_t M, int32_t D, float eps, float* stats, size_t stats_bytes, void* x16,
+                            size_t x16_bytes, int32_t dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,7 @@ class mra_gemm_desc(C.Structure):
         ("ln_counter_bytes", C.c_uint64), ("stat_m_bytes", C.c_uint64), ("stat_l_bytes", C.c_uint64), ("pscale_bytes", C.c_uint64),
         ("col_scale", C.c_void_p), ("cs_bs", C.c_int64), ("col_stats", C.c_int32), ("cs_eps", C.c_float),
         ("col_scale_bytes", C.c_uint64),
+        ("aux", C.c_void_p), ("aux_bytes", C.c_uint64),
     ]
 
 
@@ -198,6 +199,11 @@ PROTOTYPES = {
                                       C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mra_debug_gemm": (C.c_int, [C.POINTER(mra_gemm_desc), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mra_debug_gemm_plan": (C.c_int, [C.POINTER(mra_gemm_desc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "mra_debug_vit_fold_weight": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mra_debug_vit_group_stats": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mra_debug_vit_row_stats": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_size_t, C.c_int32, C.c_void_p]),
 }
 
 # GemmFamily / GemmEpi codes of mra_debug_gemm_launches (csrc/kernels.h)

@@ -1772,11 +1772,13 @@ const char* dbg_gemm_prob(const mra_gemm_desc& d, int epi, GemmProb* out) {
   if (d.batch < 0 || d.batch > 65535 || d.a_bs < 0 || d.w_bs < 0 || d.c_bs_bytes < 0 || d.bias_bs < 0) return "negative batch count or batch stride (batch <= 65535)";
   if (d.n_ragged < 0 || d.n_ragged > 1 || d.persist < 0 || d.persist > 1 || d.w_ld < 0 || d.k_rows < 0 || d.w_kwrap < 0 || d.ps_ntiles < 0)
     return "n_ragged and persist are 0 or 1; w_ld, k_rows, w_kwrap and ps_ntiles are not negative";
-  if (d.tile_cfg < GT_AUTO || d.tile_cfg >= GEMM_TILES || d.tile_cfg == GT_P8_TAIL || d.tile_cfg == GT_P8_MIXED) return "tile_cfg outside the forward's tiles";
+  if (d.tile_cfg < GT_AUTO || d.tile_cfg >= GEMM_TILES || d.tile_cfg == GT_P8_TAIL) return "tile_cfg outside the forwards' tiles";   // GT_P8_TAIL: no shipped call site
   if (!dbg_view8(d.a_view, &p.a)) return "the A view needs rows per item > 0 and strides that are non-negative multiples of 8";
   if (epi == EPI_KV) p.c = RowView{0, 1, 1};
   else if (!dbg_view(d.c_view, &p.c)) return "the C view needs rows per item > 0 and strides that are non-negative multiples of 4";
-  const bool res = epi == EPI_RES_F32 || epi == EPI_RES_LN;
+  const bool res = epi == EPI_RES_F32 || epi == EPI_RES_LN || epi == EPI_RES_F32_STAT;
+  const bool resop = epi == EPI_RES_OP || epi == EPI_RES_OP_STAT, lnf = epi == EPI_LNF_OP || epi == EPI_LNF_GELU_OP;
+  if ((resop || lnf || epi == EPI_RES_F32_STAT) && (d.batch > 1 || d.n_ragged)) return "the ViT's epilogues (8, 10 .. 13) take one plain problem: no batch, no n_ragged";
   if (res && (!d.R || !dbg_view(d.r_view, &p.r))) return "the residual needs a pointer and a view with strides that are multiples of 4";
   if (!dbg_aligned(d.A, 16) || !dbg_aligned(d.W, 16) || !dbg_aligned(d.C, 16) || !dbg_aligned(d.bias, 16) || (res && !dbg_aligned(d.R, 16)))
     return "A, W, C, R and bias must be 16-byte aligned";
@@ -1805,6 +1807,25 @@ const char* dbg_gemm_prob(const mra_gemm_desc& d, int epi, GemmProb* out) {
     if (!(d.ln_eps >= 0.f)) return "ln_eps must not be negative";
     p.ln_gain = d.ln_gain; p.ln_bias = d.ln_bias; p.ln_eps = d.ln_eps; p.ln_y32 = d.ln_y32; p.ln_y16 = d.ln_y16; p.ln_counter = d.ln_counter;
   }
+  if (resop) {   // the residual in the operand dtype, addressed like C; in place (aux == C) or apart from it (dbg_gemm_footprint)
+    if (!d.aux || !dbg_aligned(d.aux, 16)) return "EPI_RES_OP / EPI_RES_OP_STAT need aux (16-byte aligned)";
+    p.aux = d.aux;
+  }
+  if (epi == EPI_RES_F32_STAT || epi == EPI_RES_OP_STAT) {   // ln_y32: the group statistics, written as float2
+    if (!d.ln_y32 || !dbg_aligned(d.ln_y32, 8)) return "the statistics epilogues need ln_y32 (8-byte aligned)";
+    if (!d.bias) return "the statistics epilogues need a bias";
+    p.ln_y32 = d.ln_y32;
+  }
+  if (epi == EPI_RES_F32_STAT) {
+    if (!d.ln_y16 || !dbg_aligned(d.ln_y16, 16) || !dbg_view8(d.ln_y16_view, &p.ln_y16v))
+      return "EPI_RES_F32_STAT needs ln_y16 (16-byte aligned) and a view of it with strides that are multiples of 8";
+    p.ln_y16 = d.ln_y16;
+  }
+  if (lnf) {   // ln_y32: (mean, rstd) per row, read as float2; ln_gain: the column sums of W'
+    if (!d.ln_y32 || !dbg_aligned(d.ln_y32, 8)) return "EPI_LNF_* need ln_y32 = (mean, rstd) per row (8-byte aligned)";
+    if (!d.ln_gain || !dbg_aligned(d.ln_gain, 16)) return "EPI_LNF_* need ln_gain = the column sums (16-byte aligned)";
+    p.ln_y32 = d.ln_y32; p.ln_gain = d.ln_gain;
+  }
   if (epi == EPI_SOFTPART) {
     if (!d.stat_m || !d.stat_l || !dbg_aligned(d.stat_m, 4) || !dbg_aligned(d.stat_l, 4)) return "EPI_SOFTPART needs stat_m and stat_l (4-byte aligned)";
     if (!(d.alpha > 0.f) || !(d.alpha < 3.0e38f)) return "EPI_SOFTPART needs a finite alpha > 0";
@@ -1828,8 +1849,9 @@ const char* dbg_gemm_prob(const mra_gemm_desc& d, int epi, GemmProb* out) {
 const char* dbg_gemm_epi_ok(int epi) {
   switch (epi) {
     case EPI_OP: case EPI_GELU_OP: case EPI_RES_F32: case EPI_F32: case EPI_KV: case EPI_SOFTPART: case EPI_RES_LN: return nullptr;
+    case EPI_RES_OP: case EPI_RES_F32_STAT: case EPI_LNF_OP: case EPI_LNF_GELU_OP: case EPI_RES_OP_STAT: return nullptr;   // the ViT encoder's
   }
-  return "epilogue must be EPI_OP, EPI_GELU_OP, EPI_RES_F32, EPI_F32, EPI_KV, EPI_SOFTPART or EPI_RES_LN";
+  return "epilogue must be one of 0 .. 5 and 8 .. 13 (csrc/kernels.h): the training step's EPI_GELU_BOTH / EPI_GELU_BWD have an entry of their own";
 }
 
 // weight rows (output columns) of a family's tile: what n_ragged and EPI_SOFTPART round the written columns up to (the kTiles table of gemm.hip)
@@ -1851,7 +1873,7 @@ const char* dbg_gemm_footprint(const mra_gemm_desc& d, const GemmProb& p, const 
   const long long nb = d.batch > 1 ? d.batch : 1;
   const long long ntiles = pl.args.p[g].ntiles;
   const long long cols = (d.n_ragged || epi == EPI_SOFTPART) ? ntiles * dbg_tile_cols(pl.family) : d.N;   // columns of C a tile row writes
-  const size_t csz = (epi == EPI_RES_F32 || epi == EPI_F32 || epi == EPI_RES_LN) ? 4 : 2;
+  const size_t csz = (epi == EPI_RES_F32 || epi == EPI_F32 || epi == EPI_RES_LN || epi == EPI_RES_F32_STAT) ? 4 : 2;
   if ((d.n_ragged || epi == EPI_SOFTPART) && (cols < d.N || ntiles != (d.N + dbg_tile_cols(pl.family) - 1) / dbg_tile_cols(pl.family))) return "unknown tile";
   if (!dbg_fits(dbg_extent(p.a, d.M, d.K) + (u128)(nb - 1) * (u128)d.a_bs, 2, 0, d.a_bytes)) return "A: the view, K and the batch stride leave a_bytes";
   u128 w = d.w_ld ? (u128)(d.k_rows - 1) * (u128)d.w_ld + (u128)d.N : (u128)d.N * (u128)(d.w_kwrap ? d.K / 2 : d.K);
@@ -1867,6 +1889,23 @@ const char* dbg_gemm_footprint(const mra_gemm_desc& d, const GemmProb& p, const 
   if (p.R) {
     if (p.r.ld < d.N) return "R row stride below N";
     if (!dbg_fits(dbg_extent(p.r, d.M, d.N), 4, 0, d.r_bytes)) return "R: the view leaves r_bytes";
+  }
+  if (p.aux) {   // addressed with C's view: the same footprint; the stream updated in place is the one overlap a tile's read-then-write order allows
+    if (!dbg_fits(dbg_extent(p.c, d.M, cols), 2, 0, d.aux_bytes)) return "aux: the C view and the columns written leave aux_bytes";
+    const uintptr_t c0 = (uintptr_t)d.C, a0 = (uintptr_t)d.aux;
+    const u128 span = dbg_extent(p.c, d.M, cols) * 2;
+    if (a0 != c0 && (u128)a0 < (u128)c0 + span && (u128)c0 < (u128)a0 + span) return "aux overlaps C without being C";
+  }
+  if (epi == EPI_RES_F32_STAT || epi == EPI_RES_OP_STAT) {
+    const int gw = epi == EPI_RES_F32_STAT ? 128 : 64;
+    if (d.N % gw) return "the statistics epilogues need N to be a multiple of the group width (128 in fp32, 64 in the operand dtype)";
+    if (!dbg_fits((u128)d.M * (u128)(d.N / gw) * 2, 4, 0, d.ln_y32_bytes)) return "ln_y32: M x (N / group width) x 2 floats leave ln_y32_bytes";
+  }
+  if (epi == EPI_RES_F32_STAT && (p.ln_y16v.ld < d.N || !dbg_fits(dbg_extent(p.ln_y16v, d.M, d.N), 2, 0, d.ln_y16_bytes)))
+    return "ln_y16: row stride below N, or the view leaves ln_y16_bytes";
+  if (epi == EPI_LNF_OP || epi == EPI_LNF_GELU_OP) {
+    if (!dbg_fits((u128)d.M * 2, 4, 0, d.ln_y32_bytes)) return "ln_y32: M x 2 floats of (mean, rstd) leave ln_y32_bytes";
+    if (!dbg_fits((u128)d.N, 4, 0, d.ln_gain_bytes)) return "ln_gain: N floats of column sums leave ln_gain_bytes";
   }
   if (epi == EPI_SOFTPART) {
     const u128 n = (u128)nb * (u128)d.M * (u128)ntiles;
@@ -1888,12 +1927,13 @@ int dbg_gemm_prepare(const mra_gemm_desc* probs, int32_t nprob, int32_t epi, int
   if (nprob < 1 || nprob > GEMM_MAX_GROUPS) return fail(MRA_EINVAL, "1 .. 4 problems");
   if (!dbg_op(dtype, op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
   if (const char* e = dbg_gemm_epi_ok(epi)) return fail(MRA_EINVAL, e);
+  if (nprob > 1 && (epi == EPI_RES_OP || epi >= EPI_RES_F32_STAT)) return fail(MRA_EINVAL, "the ViT's epilogues (8, 10 .. 13) take one problem");
   if (!probs) return fail(MRA_EINVAL, "null descriptor array");
   for (int i = 0; i < nprob; ++i)
     if (const char* e = dbg_gemm_prob(probs[i], epi, &ps[i])) return fail(MRA_EINVAL, "problem " + std::to_string(i) + ": " + e);
   pl->cus = cus;
   const int rc = gemm_plan(ps, nprob, epi, *op, pl);
-  if (rc) return fail(MRA_EINVAL, rc == -2 ? "the tile has no such epilogue" : "gemm_plan refuses the launch (K % 64, N % tile, what the tile or the epilogue allows)");
+  if (rc) return fail(MRA_EINVAL, rc == -2 ? "the tile has no such epilogue" : "gemm_plan refuses the launch (K % 64, K % 128 on the 128-deep and eight-phase tiles, N % tile, N % 256 == 128 and N >= 384 on the mixed tile, what the tile or the epilogue allows)");
   for (int i = 0; i < nprob; ++i)
     if (const char* e = dbg_gemm_footprint(probs[i], ps[i], *pl, i, epi)) return fail(MRA_EINVAL, "problem " + std::to_string(i) + ": " + e);
   if (epi == EPI_RES_LN)

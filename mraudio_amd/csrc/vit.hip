@@ -819,6 +819,82 @@ int mra_debug_vit_attention(mra_vit* h, const void* qkv, int32_t n, void* ctx, v
   return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "vit attention launch");
 }
 
+// ---- the folded LayerNorm's companion kernels, one launch each (include/mra.h; tests/test_gpu_gemm_vit.py) -------------------------------
+namespace {
+bool ln_fold_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+bool ln_fold_fits(unsigned long long elements, size_t esz, size_t have) { return elements <= have / esz; }   // elements <= 2^53 here: no overflow
+}  // namespace
+
+int mra_debug_vit_fold_weight(const void* W, size_t w_bytes, const float* gain, size_t gain_bytes, const float* beta, size_t beta_bytes, const float* bias,
+                              size_t bias_bytes, void* Wf, size_t wf_bytes, float* cs, size_t cs_bytes, float* bf, size_t bf_bytes, int32_t N, int32_t K,
+                              int32_t dtype, void* stream_) {
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (N < 0 || K <= 0) return fail(MRA_EINVAL, "N must not be negative, K must be positive");
+  if (N == 0) return MRA_OK;
+  if (!W || !gain || !beta || !Wf || !cs || !bf) return fail(MRA_EINVAL, "null W, gain, beta, Wf, cs or bf");
+  if (!ln_fold_aligned(W, 2) || !ln_fold_aligned(Wf, 2) || !ln_fold_aligned(gain, 4) || !ln_fold_aligned(beta, 4) || !ln_fold_aligned(bias, 4) ||
+      !ln_fold_aligned(cs, 4) || !ln_fold_aligned(bf, 4))
+    return fail(MRA_EINVAL, "W and Wf must be 2-byte aligned, the fp32 buffers 4-byte aligned");
+  const unsigned long long nk = (unsigned long long)N * K;
+  if (!ln_fold_fits(nk, 2, w_bytes) || !ln_fold_fits(nk, 2, wf_bytes)) return fail(MRA_EINVAL, "W / Wf: N x K elements leave w_bytes / wf_bytes");
+  if (!ln_fold_fits(K, 4, gain_bytes) || !ln_fold_fits(K, 4, beta_bytes)) return fail(MRA_EINVAL, "gain / beta: K floats leave gain_bytes / beta_bytes");
+  if ((bias && !ln_fold_fits(N, 4, bias_bytes)) || !ln_fold_fits(N, 4, cs_bytes) || !ln_fold_fits(N, 4, bf_bytes))
+    return fail(MRA_EINVAL, "bias / cs / bf: N floats leave bias_bytes / cs_bytes / bf_bytes");
+  {   // the kernel reads a weight row while it writes the folded one: the same buffer (in place) or two apart
+    const uintptr_t a = (uintptr_t)W, b = (uintptr_t)Wf;
+    if (a != b && a < b + nk * 2 && b < a + nk * 2) return fail(MRA_EINVAL, "Wf overlaps W without being W");
+  }
+  hipStream_t st = as_stream(stream_);
+  with_op(dtype == MRA_BF16 ? OP_BF16 : OP_F16, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(vit_fold_weight_kernel<T>, dim3((N + 3) / 4), dim3(256), 0, st, (const T*)W, gain, beta, bias, (T*)Wf, cs, bf, N, K);
+  });
+  return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "vit fold weight launch");
+}
+
+int mra_debug_vit_group_stats(const float* groups, size_t groups_bytes, int64_t M, int32_t G, int32_t group_cols, float eps, float* stats,
+                              size_t stats_bytes, void* stream_) {
+  if (M < 0 || M > 0x7fffffffLL / 64) return fail(MRA_EINVAL, "M must be 0 .. (2^31 - 1) / 64");
+  if (G < 1 || G > 4096) return fail(MRA_EINVAL, "G must be 1 .. 4096 groups per row");
+  if (group_cols < 1 || group_cols > 4096) return fail(MRA_EINVAL, "group_cols must be 1 .. 4096 columns per group");
+  if (!(eps >= 0.f)) return fail(MRA_EINVAL, "eps must not be negative");
+  if (M == 0) return MRA_OK;
+  if (!groups || !stats) return fail(MRA_EINVAL, "null groups or stats");
+  if (!ln_fold_aligned(groups, 8) || !ln_fold_aligned(stats, 8)) return fail(MRA_EINVAL, "groups and stats are read and written as float2: 8-byte aligned");
+  if (!ln_fold_fits((unsigned long long)M * G * 2, 4, groups_bytes)) return fail(MRA_EINVAL, "groups: M x G x 2 floats leave groups_bytes");
+  if (!ln_fold_fits((unsigned long long)M * 2, 4, stats_bytes)) return fail(MRA_EINVAL, "stats: M x 2 floats leave stats_bytes");
+  hipLaunchKernelGGL(vit_group_stats_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, as_stream(stream_), reinterpret_cast<const float2*>(groups),
+                     (long long)M, G, (float)group_cols, eps, reinterpret_cast<float2*>(stats));
+  return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "vit group stats launch");
+}
+
+int mra_debug_vit_row_stats(const void* x, size_t x_bytes, int32_t x_dtype, int64_t M, int32_t D, float eps, float* stats, size_t stats_bytes, void* x16,
+                            size_t x16_bytes, int32_t dtype, void* stream_) {
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (x_dtype != MRA_F32 && x_dtype != dtype) return fail(MRA_EINVAL, "x_dtype must be MRA_F32 or the operand dtype");
+  if (M < 0 || M > 0x7fffffffLL / 64) return fail(MRA_EINVAL, "M must be 0 .. (2^31 - 1) / 64");
+  if (D <= 0 || D % 128 || D > 2048) return fail(MRA_EINVAL, "D must be a multiple of 128, at most 2048 (a lane holds 16 pairs)");
+  if (!(eps >= 0.f)) return fail(MRA_EINVAL, "eps must not be negative");
+  const bool f32 = x_dtype == MRA_F32;
+  if (f32 ? !x16 : x16 != nullptr) return fail(MRA_EINVAL, "x16 is the operand-dtype copy of fp32 rows: required with them, NULL with rows in the operand dtype");
+  if (M == 0) return MRA_OK;
+  if (!x || !stats) return fail(MRA_EINVAL, "null x or stats");
+  if (!ln_fold_aligned(x, f32 ? 8 : 4) || !ln_fold_aligned(stats, 8) || !ln_fold_aligned(x16, 4))
+    return fail(MRA_EINVAL, "fp32 rows and stats are read and written as float2 (8-byte aligned), 16-bit rows as pairs (4)");
+  if (!ln_fold_fits((unsigned long long)M * D, f32 ? 4 : 2, x_bytes)) return fail(MRA_EINVAL, "x: M x D elements leave x_bytes");
+  if (!ln_fold_fits((unsigned long long)M * 2, 4, stats_bytes)) return fail(MRA_EINVAL, "stats: M x 2 floats leave stats_bytes");
+  if (f32 && !ln_fold_fits((unsigned long long)M * D, 2, x16_bytes)) return fail(MRA_EINVAL, "x16: M x D elements leave x16_bytes");
+  hipStream_t st = as_stream(stream_);
+  const dim3 grid((unsigned)((M + 3) / 4)), block(256);
+  float2* out = reinterpret_cast<float2*>(stats);
+  with_op(dtype == MRA_BF16 ? OP_BF16 : OP_F16, [&](auto t) {
+    using T = decltype(t);
+    if (f32) hipLaunchKernelGGL(vit_row_stats_kernel<T>, grid, block, 0, st, (const float*)x, (long long)M, D, eps, out, (T*)x16);
+    else hipLaunchKernelGGL(vit_row_stats16_kernel<T>, grid, block, 0, st, (const T*)x, (long long)M, D, eps, out);
+  });
+  return hipGetLastError() == hipSuccess ? MRA_OK : fail(MRA_EHIP, "vit row stats launch");
+}
+
 double mra_vit_flops(mra_vit* h, int32_t frames) {
   if (!h) return 0.0;
   const double n = h->S, d = h->cfg.dim, I = h->cfg.mlp;

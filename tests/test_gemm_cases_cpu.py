@@ -164,7 +164,7 @@ def test_launch_level_refusals():
     _refused(arr, 0, c["epi"], word="1 .. 4")
     _refused(arr, 5, c["epi"], word="1 .. 4")
     _refused(None, 1, c["epi"], word="null")
-    for epi in (6, 7, 8, 10, 11, 12, 13, -1, 16):
+    for epi in (6, 7, 14, 15, -1, 16):      # (8 and 10 .. 13 are the ViT's: tests/test_vit_gemm_cases_cpu.py)
         _refused(arr, 1, epi, word="epilogue")
     before = _launched()
     assert L.lib().mra_debug_gemm(arr, 1, c["epi"], L.MRA_F32, None) == -1 and _launched() == before
