@@ -253,7 +253,15 @@ int mra_qformer_cross_precision_report(mra_qformer* h, int32_t* resolved, int32_
  *   "multi_core"  the cross core of mra_qformer_forward_multi with prompts > 1: 0 the core of mra_qformer_forward, each chain item taking the
  *                 K/V of its encoder item; 1 the shared-stream core (one workgroup per encoder item, head and 4 prompt slots, the K/V tiles
  *                 staged once into a workgroup-shared LDS ring).  Default 1 (faster at P >= 4 on both shapes of tools/bench_multi_query.py, by 0.2 - 2.3 %;
- *                 0 is 6 % ahead at P = 2, Kv 8224).  mra_qformer_multi_workspace_bytes follows it. */
+ *                 0 is 6 % ahead at P = 2, Kv 8224).  mra_qformer_multi_workspace_bytes follows it.
+ *   "cross_fuse"  mask over the launches around the two big GEMMs of the folded cross-attention; only the default folded plan follows it (the
+ *                 176 x 384 tiles with in-register row factors, operand precision, no probe; raw features or the normalised copy), every
+ *                 other form keeps its launches.  1: cross query projection and per-head Q' in ONE launch (mra_debug_fold_query), Q is not
+ *                 written; 4: the per-head context GEMM on the 64 x 64 tile with 128-deep K steps (enc_width % 128 == 0, >= 512 query
+ *                 rows); 2: the row factors of the split softmax computed inside the P . enc launch from the scores launch's tile
+ *                 statistics (no fold_rowfactor launch).  All bit-identical to mask 0, which issues the launches as before.  Default 1: the
+ *                 only bit that measured a gain in the step.  Bit 4 measured no difference and bit 2 measured a loss (+0.30 ms per
+ *                 step: the P . enc launch grows by more than the launch it absorbs); both stay as tested opt-ins. */
 int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value);
 /* Derives what the folded path needs from the loaded weights (W_k of every cross layer regrouped per head) on
  * `stream`, if a load made it stale.  mra_qformer_forward does this itself; a caller that runs SEVERAL forwards of one
@@ -613,6 +621,18 @@ int mra_debug_modality_ln(const void* x, int32_t x_dtype, const int64_t* item_in
                           const float* bias, float eps, void* out, int32_t dtype, void* stream);
 int mra_debug_softmax_rows(const float* S, int64_t ld_s, void* P, int64_t ld_p, int32_t rows, int32_t kv, int32_t kvp, float scale, int32_t dtype,
                            void* stream);
+/* mra_debug_fold_query: steps 5 + 6a of a folded cross-attention layer in ONE launch (mra_qformer_set_option "cross_fuse" bit 1; the default
+ * folded plan takes it): per head Q_h = x W_q,h^T + b_q,h over the `rows` compact query rows behind x_view (item stride, rows per item, row
+ * stride; K = H), rounded to the operand dtype, then q_prime[item][head * Q + q][0 .. E) = Q_h W_k,h with w_k the per-head [E][64] blocks
+ * (heads of 64 dims; H, E multiples of 64; rows a multiple of Q).  Bit-identical to the two GEMM launches it replaces.  b_q may be NULL.  Each
+ * *_bytes is the size of its buffer: a view or a size that leaves it is refused, like every null or misaligned (16 bytes) buffer, before the
+ * launch.  mra_debug_fold_query_launches: such launches since the library was loaded (the forward's included). */
+int mra_debug_fold_query(const void* x, const int64_t* x_view, size_t x_bytes, const void* w_q, size_t w_q_bytes, const float* b_q, size_t b_q_bytes,
+                         const void* w_k, size_t w_k_bytes, void* q_prime, size_t q_prime_bytes, int32_t rows, int32_t H, int32_t E, int32_t Q,
+                         int32_t heads, int32_t dtype, void* stream);
+int64_t mra_debug_fold_query_launches(void);
+/* launches of the row-factor kernel (mra_debug_fold_rowfactor and the forwards' step 6c, plain and probe) since the library was loaded */
+int64_t mra_debug_fold_rowfactor_launches(void);
 int mra_debug_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int32_t rows, int32_t R, int32_t ntiles, void* P, int64_t ld_p,
                              int32_t tile_cols, int32_t kvp, int32_t* hist, void* stream);
 int mra_debug_softmax_rescale(void* P, int64_t ld_p, const float* stat_m, const float* stat_l, int32_t rows, int32_t ntiles, int32_t tile_cols,
@@ -732,6 +752,13 @@ typedef struct mra_gemm_desc {
   /* EPI_RES_OP / EPI_RES_OP_STAT (appended; NULL otherwise): the residual in the operand dtype, addressed with c_view.  aux == C updates the
    * stream in place; any other overlap with C is refused. */
   void* aux; uint64_t aux_bytes;
+  /* tile_cfg GT_64 only (appended; 0 = off): k128 = 1 takes the 64 x 64 tile with 128-deep K steps (family 10) whenever K % 128 == 0, not only
+   * from K = 2048 on -- the folded context GEMM under mra_qformer_set_option "cross_fuse" bit 4. */
+  /* EPI_OP over K-major weights on the 176 x 384 tile (appended; 0 = off): ps_stats = 1 feeds the launch the tile statistics of the scores
+   * launch -- stat_m / stat_l, batch x M x ps_ntiles floats, M <= 384 -- instead of pscale (which must be NULL): it computes the row factors
+   * exp2(m_tile - m_row) / L_row itself, bit for bit those of mra_debug_fold_rowfactor, and A need not be zero from column ps_ntiles * 176
+   * on (mra_qformer_set_option "cross_fuse" bit 2). */
+  int32_t k128, ps_stats;
 } mra_gemm_desc;
 int mra_debug_gemm(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, void* stream);
 int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilogue, int32_t dtype, int32_t cus, int32_t* out);

@@ -66,6 +66,7 @@ class mra_gemm_desc(C.Structure):
         ("col_scale", C.c_void_p), ("cs_bs", C.c_int64), ("col_stats", C.c_int32), ("cs_eps", C.c_float),
         ("col_scale_bytes", C.c_uint64),
         ("aux", C.c_void_p), ("aux_bytes", C.c_uint64),
+        ("k128", C.c_int32), ("ps_stats", C.c_int32),
     ]
 
 
@@ -176,6 +177,10 @@ PROTOTYPES = {
                                         C.c_void_p, C.c_int32, C.c_void_p]),
     "mra_debug_softmax_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p]),
+    "mra_debug_fold_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mra_debug_fold_query_launches": (C.c_int64, []),
+    "mra_debug_fold_rowfactor_launches": (C.c_int64, []),
     "mra_debug_fold_rowfactor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p]),
     "mra_debug_softmax_rescale": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -6,7 +6,10 @@
 //   softmax_rows_kernel   fp32 score rows [rows][ld_s] -> P rows [rows][ld_p] in the operand dtype, padding zeroed
 //   transpose_pad_kernel  batched [R][C] -> [C][ld_d] transpose with zeroed padding columns: enc -> enc^T per item
 //                         (the K-contiguous B operand of P . enc) and W_k -> per-head [E][64] blocks
+//   fold_query_kernel     cross query projection + per-head Q' = Q_h W_k,h in one launch (the default folded plan)
 // Reference arithmetic: HF modeling_instructblip.py:464-515 (the same softmax(QK^T/8)V, re-associated).
+#include <atomic>
+
 #include "kernels.h"
 #include "mra_common.h"
 
@@ -215,7 +218,256 @@ __global__ void __launch_bounds__(256) transpose_pad64_kernel(const T* src, T* d
   }
 }
 
+// Cross query projection and Q' of the folded cross-attention in ONE launch (steps 5 + 6a; mra_qformer_set_option "cross_fuse" bit 1).
+// One workgroup per (128-row tile of the compact query rows, head, slice of E); 4 waves.
+//   phase 1  Q_h = X W_cq,h^T + b_cq,h for the tile: gemm_kernel's two-buffer loop on a 64 (weight rows of the head) x 128 tile, K = hidden in
+//            64-deep steps, fp32 accumulators, + bias, rounded to the operand dtype -- into LDS, laid out as the K = 64 activation tile of
+//            phase 2 (128-byte rows, chunk index XOR (row >> 1) & 7).  Q never reaches HBM.
+//   phase 2  Q'_h = Q_h W_k,h for the slice's 128-column blocks of E, ONE 64-deep step each.  Up to three blocks of W_k,h [128][64] are brought
+//            into LDS at once (LDS-DMA, one wait); then every wave works alone on its 32 rows: Q_h fragments in registers, per 64-column half
+//            block 16 MFMAs, its 32 x 64 result through its own 4 KB of LDS and out as whole 16-byte pieces of 128-byte lines into
+//            Q' [N][head * 32 + q][E].  No wait on a store and no workgroup barrier inside a group: the stores only queue.  (A first form that
+//            exchanged one block per barrier pair and waited for the previous block's stores ran 23.6 us at the headline shape.)
+// Both phases issue the MFMAs of the two launches they replace on the same operands in the same ascending K order (an output element is one
+// accumulator chain from zero, 32 k per instruction; the bias is one fp32 add), so Q' is theirs bit for bit.  A phase-1 tile is recomputed by
+// every slice of E (4 of 3 blocks at E = 1408: 384 workgroups, two of them fit a CU): 294 KB from L2 against the 96 KB a workgroup stores.
+// E % 64 == 0: the last block may be half (64 columns), its weight rows clamped and its second column block not stored.
+// Rows past M are computed on the clamped last row and never stored.
+struct FoldQueryArgs {
+  const void* X; RowView xv;   // query-side hidden state, row view over the M compact rows (K = H contiguous)
+  const void* Wq;              // W_cq [heads * 64][H]
+  const float* bq;             // [heads * 64] or nullptr
+  const void* Wk;              // per head [E][64]
+  void* QP;                    // Q' [M / Q][heads * Q][E]
+  int M, H, E, Q, heads, mtiles, blocks_per_slice;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) fold_query_kernel(const FoldQueryArgs a) {
+  constexpr int ROWB = 128, TM = 128, NT = 256;
+  constexpr int QH_BYTES = TM * ROWB;                 // Q_h tile
+  constexpr int BUF1 = (64 + TM) * ROWB;              // phase 1: one K step of W_cq,h (64 rows) and X (128 rows)
+  constexpr int WK_BYTES = 128 * ROWB, WK_GROUP = 3;  // phase 2: one block of W_k,h; blocks resident at a time
+  constexpr int P1 = QH_BYTES, WK0 = QH_BYTES, OUT = QH_BYTES + WK_GROUP * WK_BYTES;   // phase 1's buffers lie where phase 2 keeps W_k,h (behind a barrier)
+  static_assert(2 * BUF1 <= WK_GROUP * WK_BYTES, "phase 1 fits in what phase 2 uses");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using V8 = typename Vec8<T>::type;
+  using V4 = typename Vec4<T>::type;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int mt = blockIdx.x % a.mtiles, rest = blockIdx.x / a.mtiles;
+  const int head = rest % a.heads, slice = rest / a.heads;
+  const int m0 = mt * TM, M = a.M, H = a.H, E = a.E;
+  const int lm = lane & 15, ln = (lane >> 4) * 4;
+
+  // ---- phase 1 ----
+  const char* srcW[2];
+  const char* srcX[4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int q = tid + i * NT;
+    const int row = q >> 3, c = (q & 7) ^ ((row >> 1) & 7);
+    srcW[i] = (const char*)a.Wq + ((long long)(head * 64 + row) * H + c * 8) * 2;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = tid + i * NT;
+    const int row = q >> 3, c = (q & 7) ^ ((row >> 1) & 7);
+    const int m = min(m0 + row, M - 1);
+    const int item = m / a.xv.rpi, r = m - item * a.xv.rpi;
+    srcX[i] = (const char*)a.X + ((long long)item * a.xv.item_stride + (long long)r * a.xv.ld + c * 8) * 2;
+  }
+  const int wave_q0 = wave * 64;
+  auto stage1 = [&](int buf, int kt) {
+    char* base = smem + P1 + buf * BUF1;
+    const long long koff = (long long)kt * ROWB;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) glds16(srcW[i] + koff, base + (wave_q0 + i * NT) * 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16(srcX[i] + koff, base + 64 * ROWB + (wave_q0 + i * NT) * 16);
+  };
+  int foff[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) foff[ks] = lm * ROWB + (((4 * ks + (lane >> 4)) ^ ((lm >> 1) & 7)) << 4);
+  {
+    const int wn0 = (wave >> 1) * 32, wm0 = (wave & 1) * 64;   // 2 x 2 waves, 32 weight rows x 64 activation rows each
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 bv[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      bv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (a.bq) bv[i] = *reinterpret_cast<const f32x4*>(a.bq + head * 64 + wn0 + i * 16 + ln);
+    }
+    const int nk = H / 64;
+    stage1(0, 0);
+    for (int kt = 0; kt < nk; ++kt) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (kt + 1 < nk) stage1((kt + 1) & 1, kt + 1);
+      const char* wb = smem + P1 + (kt & 1) * BUF1 + wn0 * ROWB;
+      const char* xb = smem + P1 + (kt & 1) * BUF1 + 64 * ROWB + wm0 * ROWB;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        V8 wa[2], xa[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) wa[i] = lds_read8<T>(wb + i * 16 * ROWB + foff[ks]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xa[j] = lds_read8<T>(xb + j * 16 * ROWB + foff[ks]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<T>(wa[i], xa[j], acc[i][j]);
+      }
+    }
+    // Q_h[m][d .. d + 3] -> the activation tile of phase 2 (its own 16 KB: no barrier needed against phase 1's reads)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int d = wn0 + i * 16 + ln;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int ml = wm0 + j * 16 + lm;
+        const f32x4 v = acc[i][j] + bv[i];
+        V4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(v[e]);
+        *reinterpret_cast<V4*>(smem + ml * ROWB + (((d >> 3) ^ ((ml >> 1) & 7)) << 4) + (d & 4) * 2) = o;
+      }
+    }
+  }
+  __syncthreads();   // phase 1's buffers are dead, Q_h is complete
+
+  // ---- phase 2 ----
+  // wave w owns rows 32 w .. 32 w + 31 of the tile against every column: its Q_h fragments stay in registers, its 32 x 64 staging area is its
+  // own, so from here on the waves meet only where a group of W_k,h blocks is exchanged
+  const int nblk = (E + 127) / 128;
+  const int b0 = slice * a.blocks_per_slice, b1 = min(b0 + a.blocks_per_slice, nblk);
+  if (b0 >= b1) return;   // (workgroup-uniform)
+  const char* wk = (const char*)a.Wk + (long long)head * E * 64 * 2;
+  int wrow[4], wchunk[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = tid + i * NT;
+    wrow[i] = q >> 3;
+    wchunk[i] = ((q & 7) ^ ((wrow[i] >> 1) & 7)) * 16;
+  }
+  const int wm0 = wave * 32;
+  V8 xa[2][2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) xa[ks][j] = lds_read8<T>(smem + (wm0 + j * 16) * ROWB + foff[ks]);
+  // copy-out: lane l moves chunk l & 7 of rows (l >> 3) + 8 u of the wave's 32
+  long long rowoff[4];
+  bool live[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int row = (lane >> 3) + u * 8;
+    const int m = m0 + wm0 + row;
+    live[u] = m < M;
+    const int mc = live[u] ? m : M - 1;
+    const int item = mc / a.Q, qq = mc - item * a.Q;
+    rowoff[u] = (((long long)item * a.heads + head) * a.Q + qq) * E + ((lane & 7) ^ (row & 7)) * 8;
+  }
+  char* st = smem + OUT + wave * (32 * 128);
+  for (int g0 = b0; g0 < b1; g0 += WK_GROUP) {
+    const int g1 = min(g0 + WK_GROUP, b1);
+    if (g0 > b0) __syncthreads();   // every wave is done with the previous group's blocks
+    for (int blk = g0; blk < g1; ++blk) {
+      char* base = smem + WK0 + (blk - g0) * WK_BYTES;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) glds16(wk + (long long)min(blk * 128 + wrow[i], E - 1) * ROWB + wchunk[i], base + (wave_q0 + i * NT) * 16);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (also drains the previous group's stores: once per group, not per block)
+    __syncthreads();
+    for (int hb = 2 * g0; hb < 2 * g1; ++hb) {   // 64-column half blocks
+      const int nb = hb * 64;
+      if (nb >= E) break;
+      f32x4 acc[4][2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const char* wb = smem + WK0 + (hb - 2 * g0) * (64 * ROWB);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        V8 wa[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wa[i] = lds_read8<T>(wb + i * 16 * ROWB + foff[ks]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<T>(wa[i], xa[ks][j], acc[i][j]);
+      }
+      // the wave's [32 rows][64 columns] as 128-byte lines (chunk index XOR row & 7), then out in 16-byte pieces: 8 whole lines per instruction
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int d = i * 16 + ln;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int ml = j * 16 + lm;
+          V4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(acc[i][j][e]);
+          *reinterpret_cast<V4*>(st + ml * 128 + (((d >> 3) ^ (ml & 7)) << 4) + ((d >> 2) & 1) * 8) = o;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own writes have landed (its LDS operations run in order)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const V8 val = *reinterpret_cast<const V8*>(st + (lane + u * 64) * 16);
+        if (live[u]) *reinterpret_cast<V8*>((T*)a.QP + nb + rowoff[u]) = val;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its reads are over before the next half block overwrites the area
+    }
+  }
+}
+
+std::atomic<long long> g_fold_query_launches, g_fold_rowfactor_launches;
+
+// CU count of the current device, asked once per device (256, the MI355X's, where the runtime does not say)
+int device_cus() {
+  static std::atomic<int> memo[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  int cus = memo[dev].load(std::memory_order_relaxed);
+  if (!cus) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    memo[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
+}
+
 }  // namespace
+
+long long fold_rowfactor_launch_count() { return g_fold_rowfactor_launches.load(std::memory_order_relaxed); }
+long long fold_query_launch_count() { return g_fold_query_launches.load(std::memory_order_relaxed); }
+
+int launch_fold_query(const void* X, RowView xv, const void* Wq, const float* bq, const void* Wk, void* QP, int M, int H, int E, int Q, int heads,
+                      int op_dtype, hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (!X || !Wq || !Wk || !QP || H < 64 || H % 64 || E < 64 || E % 64 || Q <= 0 || M % Q || heads <= 0 || xv.rpi <= 0 || (xv.ld & 7) || (xv.item_stride & 7)) return -1;
+  FoldQueryArgs a{X, xv, Wq, bq, Wk, QP, M, H, E, Q, heads, (M + 127) / 128, 0};
+  // slices of E: enough workgroups for every CU of the device, not more (each repeats phase 1)
+  const int nblk = (E + 127) / 128, pairs = a.mtiles * heads, cus = device_cus();
+  int slices = (cus + pairs - 1) / pairs;
+  if (slices > nblk) slices = nblk;
+  a.blocks_per_slice = (nblk + slices - 1) / slices;
+  if (a.blocks_per_slice > 3) a.blocks_per_slice = a.blocks_per_slice / 3 * 3;   // whole groups of three resident blocks
+  slices = (nblk + a.blocks_per_slice - 1) / a.blocks_per_slice;
+  constexpr size_t lds = 128 * 128 + 3 * 128 * 128 + 4 * 32 * 128;   // Q_h, three W_k,h blocks, a 32 x 64 staging area per wave: 80 KB
+  const void* fn = op_dtype == OP_F16 ? (const void*)fold_query_kernel<f16> : (const void*)fold_query_kernel<bf16>;
+  if (!ensure_lds(fn, lds)) return -3;
+  const dim3 grid(pairs * slices);
+  if (op_dtype == OP_F16) hipLaunchKernelGGL(fold_query_kernel<f16>, grid, dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL(fold_query_kernel<bf16>, grid, dim3(256), lds, stream, a);
+  if (hipGetLastError() != hipSuccess) return -4;
+  g_fold_query_launches.fetch_add(1, std::memory_order_relaxed);
+  return 0;
+}
 
 int launch_softmax_rows(const float* S, long long ld_s, void* P, long long ld_p, int rows, int kv, int kvp, float scale, int op_dtype,
                         hipStream_t stream) {
@@ -245,7 +497,9 @@ int launch_fold_rowfactor(const float* stat_m, const float* stat_l, float* facto
   else
     hipLaunchKernelGGL(fold_rowfactor_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, stream, stat_m, stat_l, factors, rows, R, ntiles,
                        (unsigned short*)P, ld_p, tile_cols, kvp, (int*)nullptr);
-  return hipGetLastError() == hipSuccess ? 0 : -4;
+  if (hipGetLastError() != hipSuccess) return -4;
+  g_fold_rowfactor_launches.fetch_add(1, std::memory_order_relaxed);
+  return 0;
 }
 
 int launch_softmax_rescale(void* P, long long ld_p, const float* stat_m, const float* stat_l, int rows, int ntiles, int tile_cols, int kvp,

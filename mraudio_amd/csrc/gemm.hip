@@ -687,13 +687,15 @@ __global__ void __launch_bounds__(WGN* WGM * 64) gemm_kernel(const GemmArgs args
 // no E[x^2] - mean^2 anywhere); after the loop the eight lanes of a row merge by lane swaps, r = 1 / sqrt(M2 / K + eps) goes to LDS -- into
 // the K buffer the last step did not use -- and, behind the one workgroup barrier both wave groups reach, wave 8 stores the tile's factors to
 // GemmProb::col_scale for the later layers.  A column tile belongs to one workgroup: no atomics, no waiting across workgroups.
-template <typename T, int EPI, bool NODMA = false, int TN = 256, int TM = 256, int WGM = 4, bool NTW = false, bool WKM = false, bool PSC = false, int CS = 0>  // NODMA: diagnostic only (wrong results); NTW: non-temporal loads of the weight-side slab; WKM: K-major W (GemmProb::w_ld); PSC: GemmProb::pscale
+template <typename T, int EPI, bool NODMA = false, int TN = 256, int TM = 256, int WGM = 4, bool NTW = false, bool WKM = false, bool PSC = false, int CS = 0, bool PST = false>  // NODMA: diagnostic only (wrong results); NTW: non-temporal loads of the weight-side slab; WKM: K-major W (GemmProb::w_ld); PSC: GemmProb::pscale; PST (with PSC): GemmProb::ps_stats
 __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
   constexpr int BK = 64, ROWB = BK * 2;
   constexpr int WGN = 8 / WGM, WTN = TN / WGN, WTM = TM / WGM, FN = WTN / 16, FM = WTM / 16;
   constexpr int BUF = (TN + TM) * ROWB;
   constexpr int PS_TILE = 176, GT_OFF = 2 * BUF, GT_SLICE = 2048;   // PSC: ring of four factor slices (one per 176-column tile of P~) behind the K buffers
   static_assert(!PSC || (TM <= 512 && PS_TILE % 8 == 0), "factor slices hold 512 rows; an 8-k fragment piece never straddles a tile");
+  static_assert(!PST || (PSC && TM % 64 == 0), "statistics-fed factors: a mode of PSC; whole waves of rows");
+  constexpr int ST_OFF = GT_OFF + 4 * GT_SLICE;   // PST: m_row [512] and 1 / L_row [512] behind the factor ring
   constexpr int NCHUNK = (TN + TM) * 8, NLD = (NCHUNK + 255) / 256;  // 16-byte chunks of a K tile (W rows, then A rows) / loader lanes
   constexpr bool STAGED = (EPI == EPI_OP || EPI == EPI_GELU_OP || EPI == EPI_KV || EPI == EPI_RES_OP) && TN % 64 == 0;   // LDS-staged 16-bit epilogue
   static_assert(WTN % 16 == 0 && WTM % 16 == 0 && TN % 16 == 0 && NCHUNK % 64 == 0, "tile must split over the waves; whole waves per DMA piece");
@@ -707,6 +709,36 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
   const GemmProb& P = pick_tile<TN, TM>(args, n0, m0);
   const int K = P.K, M = P.M;
   const int nk = K / BK;
+  // PST (GemmProb::ps_stats): the row factors of the split softmax are computed HERE from the tile statistics the scores launch wrote
+  // (stat_m / stat_l [batch row][ps_ntiles]) -- no fold_rowfactor launch, no factor array.  Before the K loop all 12 waves find m_row and
+  // 1 / L_row of the tile's rows (row r by wave r % 12: fold_rowfactor_kernel's arithmetic and its 64-lane strided reduction order, so the
+  // factors are that kernel's bit for bit) and leave them in LDS; the loaders have issued K tile 0 first, so this runs under that load.  One
+  // barrier of all 12 waves closes it.  In the loop wave 8 fills the four-slot ring itself: exp2(m_tile - m_row) / L_row from one stat_m
+  // load per row and tile, where stage_factors copies a slice.  The P~ columns from ps_ntiles * 176 to K, which nobody has zeroed now, are
+  // zeroed in LDS by the loader lane that staged them (the last one or two K steps only), before the barrier that publishes the tile.
+  auto row_stats = [&]() {
+    if constexpr (PST) {
+      float* mrow = reinterpret_cast<float*>(smem + ST_OFF);
+      float* rinv = mrow + 512;
+      const int nt = P.ps_ntiles;
+      for (int r = wave; r < TM; r += 12) {
+        const long long row = (long long)P.batch_row0 + min(m0 + r, M - 1);
+        const float* sm = P.stat_m + row * nt;
+        const float* sl = P.stat_l + row * nt;
+        float m = -3.0e38f;
+        for (int t = lane; t < nt; t += 64) m = fmaxf(m, sm[t]);
+        m = wave_max(m);
+        float l = 0.f;
+        for (int t = lane; t < nt; t += 64) l += __builtin_amdgcn_exp2f(sm[t] - m) * sl[t];
+        l = wave_sum(l);
+        const float inv = 1.0f / l;
+        if (lane == 0) { mrow[r] = m; rinv[r] = inv; }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    }
+  };
 
   if (wave >= 8) {
     // ------------------------------- loader waves -------------------------------
@@ -759,6 +791,21 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
       if constexpr (PSC) {
         if (wave != 8) return;
         const int t_hi = (kt * BK + BK - 1) / PS_TILE;
+        if constexpr (PST) {
+          const float* mrow = reinterpret_cast<const float*>(smem + ST_OFF);
+          const float* rinv = mrow + 512;
+          for (; gt_next <= t_hi; ++gt_next) {   // same slots, same "past the last tile" rule
+            const int tt = min(gt_next, P.ps_ntiles - 1);
+            float* dg = reinterpret_cast<float*>(smem + GT_OFF + (gt_next & 3) * GT_SLICE);
+#pragma unroll
+            for (int k = 0; k < TM / 64; ++k) {
+              const int r = lane + 64 * k;
+              const float smt = P.stat_m[((long long)P.batch_row0 + min(m0 + r, M - 1)) * P.ps_ntiles + tt];
+              dg[r] = __builtin_amdgcn_exp2f(smt - mrow[r]) * rinv[r];
+            }
+          }
+          return;
+        }
         for (; gt_next <= t_hi; ++gt_next) {   // past the last tile: its factors again (finite; the P~ columns there are zero)
           const char* sg = (const char*)(P.pscale + (long long)min(gt_next, P.ps_ntiles - 1) * 512) + lane * 16;
           char* dg = smem + GT_OFF + (gt_next & 3) * GT_SLICE;
@@ -780,9 +827,22 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
 #pragma unroll
     for (int i = 0; i < NWS; ++i) cmean[i] = cm2[i] = 0.f;
     stage(0, 0);
+    row_stats();
     stage_factors(0);
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (PST) {
+        const int pad0 = P.ps_ntiles * PS_TILE;   // first P~ column the scores launch did not write
+        if (kt * BK + BK > pad0) {
+#pragma unroll
+          for (int i = 0; i < NLD; ++i) {
+            const int q = lt + i * 256;   // this lane's own chunk: row q >> 3, logical chunk (q & 7) ^ ((row >> 1) & 7)
+            if (q >= TN * 8 && q < NCHUNK && kt * BK + (((q & 7) ^ ((q >> 4) & 7)) << 3) >= pad0)
+              *reinterpret_cast<i32x4*>(smem + (kt & 1) * BUF + q * 16) = i32x4{0, 0, 0, 0};
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zeros, and wave 8's factor slices
+      }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if (kt + 1 < nk && !(NODMA && kt >= 1)) { stage((kt + 1) & 1, kt + 1); stage_factors(kt + 1); }
@@ -876,6 +936,7 @@ __global__ void __launch_bounds__(768) gemm_ws_kernel(const GemmArgs args) {
       for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
+  row_stats();
   for (int kt = 0; kt < nk; ++kt) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1767,6 +1828,7 @@ int launch_family(const GemmPlan& pl, int epi, hipStream_t stream) {
     case GF_WS_128x384: return with_epi(EpiWs128{}, epi, [&](auto e) { return go(gemm_ws_kernel<T, e(), false, 128, 384>); });
     case GF_WS_176x384:
       if (a.p[0].w_ld > 0) {   // K-major weights (P . enc straight from the encoder tokens); EPI_OP (tile_rules)
+        if (a.p[0].ps_stats) return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true, true, 0, true>);
         if (a.p[0].pscale) return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true, true>);
         return go(gemm_ws_kernel<T, EPI_OP, false, 176, 384, 8, true, true>);
       }
@@ -1831,7 +1893,7 @@ int pick_family(int tile, const GemmProb* probs, int ngroups, int epi) {
   bool even = true, deep = true;
   for (int g = 0; g < ngroups; ++g) {
     even = even && probs[g].K % 128 == 0;
-    deep = deep && probs[g].K % 128 == 0 && probs[g].K >= 2048;
+    deep = deep && probs[g].K % 128 == 0 && (probs[g].K >= 2048 || probs[g].k128);
   }
   if (tile == GT_256) {
     if (g_variant == 1) return GF_V1_256;
@@ -1891,6 +1953,7 @@ bool tile_rules(const TileDesc& d, int family, const GemmProb& p, int ngroups, i
   if (p.w_ld && (!(d.allow & T_WLD) || epi != EPI_OP || (p.w_ld & 7) || p.k_rows <= 0 || p.N % d.tn)) return false;
   if (p.w_kwrap && (!(d.allow & T_KWRAP) || p.w_kwrap < 0 || p.w_ld || 2 * p.w_kwrap * 64 != p.K)) return false;   // K = 2 passes over the weights
   if (p.col_scale && (epi != EPI_SOFTPART || family != GF_WS_176x384 || p.w_ld || ngroups != 1)) return false;
+  if (p.ps_stats && (p.pscale || !p.stat_m || !p.stat_l || !p.w_ld || p.M > d.tm || p.ps_ntiles <= 0 || p.K > p.ps_ntiles * d.tn + 4 * d.tn || ngroups != 1)) return false;
   if (p.pscale && (!p.w_ld || p.M > d.tm || p.ps_ntiles <= 0 || p.K > p.ps_ntiles * d.tn + 4 * d.tn)) return false;   // one row tile: the factor slice (512 rows) is indexed by the row inside the tile
   return true;
 }
@@ -1951,7 +2014,7 @@ int gemm_plan(const GemmProb* probs, int ngroups, int epi, int op_dtype, GemmPla
   a.dbg = g_dbg;
   a.order = g_order ? g_order : probs[0].order;
   pl.threads = d.threads;
-  pl.lds = d.lds + (a.p[0].pscale ? 4 * 2048 : 0);
+  pl.lds = d.lds + (a.p[0].pscale || a.p[0].ps_stats ? 4 * 2048 : 0) + (a.p[0].ps_stats ? 2 * 2048 : 0);   // factor ring; row statistics
   // one workgroup per CU that walks over the tiles (the grid must be a multiple of the 8 XCDs for the remap to hold)
   pl.persistent = pl.family == GF_P8_256 && a.p[0].persist && ngroups == 1 && a.p[0].batch <= 1 && has_epi(epi_mask(EpiP8Persist{}), epi) && pl.cus >= 8 && tiles > pl.cus;
   pl.grid = pl.persistent ? pl.cus & ~7 : tiles;

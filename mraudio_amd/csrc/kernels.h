@@ -134,6 +134,11 @@ struct GemmProb {
   int tile_begin;  // filled by the launcher
   int mtiles, ntiles;
   int batch_row0;  // filled per workgroup: first row of its batch entry in the EPI_SOFTPART statistics
+  int k128;        // GT_64 only: 128-deep K steps (gemm_k128_kernel's 64 x 64 tile) whenever K % 128 == 0, not only from K = 2048 on -- the folded
+                   // context GEMM at K = enc_width (mra_qformer_set_option "cross_fuse" bit 4); same ascending K order, same bits
+  int ps_stats;    // 1 (176 x 384 loader-wave tile with K-major W, instead of pscale): the row factors are computed in the launch from the tile
+                   // statistics stat_m / stat_l [batch * M][ps_ntiles] of the scores launch (fold_rowfactor_kernel's arithmetic and reduction
+                   // order: the same bits), and A need NOT be zero from column ps_ntiles * 176 on -- those columns are zeroed in LDS
 };
 
 constexpr int GEMM_MAX_GROUPS = 4;   // problems per launch (round 3: the pair forward groups the query / text problems of two Q-Formers)
@@ -299,6 +304,13 @@ int launch_softmax_rows(const float* S, long long ld_s, void* P, long long ld_p,
 // (automatic cross-attention precision); the factors and P~ are the same bits.
 int launch_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int rows, int R, int ntiles, void* P, long long ld_p, int tile_cols,
                           int kvp, hipStream_t stream, int* hist = nullptr);
+// Steps 5 + 6a of a folded cross-attention layer in one launch (fold.hip: fold_query_kernel): Q_h = X W_cq,h^T + b_cq,h per head (X: M compact
+// query rows behind the row view xv, K = H), rounded to the operand dtype, then Q'[item][head * Q + q][:] = Q_h W_k,h with Wk the per-head
+// [E][64] blocks.  H and E multiples of 64, M a multiple of Q, head width 64; bit-identical to the two GEMM launches it replaces.
+int launch_fold_query(const void* X, RowView xv, const void* Wq, const float* bq, const void* Wk, void* QP, int M, int H, int E, int Q, int heads,
+                      int op_dtype, hipStream_t stream);
+long long fold_rowfactor_launch_count();   // launch_fold_rowfactor launches (plain and probe) since the library was loaded
+long long fold_query_launch_count();   // launches since the library was loaded (read-only diagnostics, as gemm_launch_count)
 // hist != nullptr: the probe variant (as launch_fold_rowfactor's)
 int launch_softmax_rescale(void* P, long long ld_p, const float* stat_m, const float* stat_l, int rows, int ntiles, int tile_cols, int kvp,
                            int op_dtype, hipStream_t stream, int* hist = nullptr);

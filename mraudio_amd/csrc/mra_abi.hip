@@ -155,6 +155,9 @@ struct CrossPlan {
   bool inreg;      // with softpart: P . enc applies the row factors to its P~ fragments (otherwise a rescale pass over P)
   bool raw;        // the encoder features are RAW (no modality LayerNorm pass): its gain and centring live in the folded weights, the token
                    // factors 1 / sqrt(var + eps) come out of cross layer 0's scores launch (FOLD with softpart && kmajor && inreg only)
+  bool fuse_query; // steps 5 + 6a in one launch (launch_fold_query): the default folded plan with "cross_fuse" bit 1, 64-wide heads
+  bool stat_factors; // step 6c inside the P . enc launch (GemmProb::ps_stats): no fold_rowfactor launch, no factor array ("cross_fuse" bit 2)
+  bool ctx_64;     // step 6e on the 64 x 64 tile with 128-deep K steps ("cross_fuse" bit 4): twice the workgroups, each pulls 2/3 of the bytes
   int scores_tile, penc_tile;   // GemmTile of the scores and the P . enc GEMMs
 };
 
@@ -174,7 +177,12 @@ CrossPlan cross_plan(const mra_qformer* h, int kv, bool precise, bool probe, boo
   x.inreg = (h->inreg_rescale || probe) && x.softpart && x.kmajor;
   x.scores_tile = R == 384 ? GT_WS_176x384 : GT_128;
   x.penc_tile = x.kmajor ? GT_WS_176x384 : (R == 384 ? h->fold_tile : GT_128);
-  x.raw = raw && x.form == CrossPlan::FOLD && x.softpart && x.kmajor && x.inreg && !precise && !probe;
+  // the default folded plan: the 176 x 384 tiles with in-register row factors, operand precision, no probe
+  const bool default_fold = x.form == CrossPlan::FOLD && x.softpart && x.kmajor && x.inreg && !precise && !probe;
+  x.raw = raw && default_fold;
+  x.fuse_query = (h->cross_fuse & 1) && default_fold && c.hidden == c.heads * 64 && c.enc_width % 64 == 0;
+  x.stat_factors = (h->cross_fuse & 2) && default_fold;
+  x.ctx_64 = (h->cross_fuse & 4) && default_fold && c.enc_width % 128 == 0;
   return x;
 }
 
@@ -308,7 +316,7 @@ size_t work_bytes(Lane x, int N, int L) { return layout_lanes(&x, 1, nullptr, N,
 
 // Steps 6 / 6a-6e of one cross-attention layer of one lane: from the query projection Q (w.qc16, or w.qc32 in split precision) to the
 // attention context (w.ctx16 [N*Q][H]) -- the folded form (per-head Q' GEMM, scores + split softmax, P . enc, per-head context GEMM) or the
-// core over the head-major K/V cache.
+// core over the head-major K/V cache.  With CrossPlan::fuse_query step 6a has already run, fused into the query projection (run_lanes).
 int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
   const mra_qformer* h = lane.h;
   const CrossPlan& x = lane.plan;
@@ -331,7 +339,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
     return rc ? chk(rc, "cross attention") : MRA_OK;
   }
   const bool timed = ci == 0 && h->kv_ev0 && h->kv_ev1;
-  if (timed) (void)hipEventRecord(h->kv_ev0, stream);
+  if (timed && !x.fuse_query) (void)hipEventRecord(h->kv_ev0, stream);   // (fused: run_lanes recorded it in front of step 6a)
   int* hist = x.probe ? h->auto_hist + (size_t)ci * 256 : nullptr;
   // 6a. Q' = Q_h W_k,h per head: [N*32, 64] x [E, 64]^T -> Q' [N][head*32 + q][E]
   GemmProb d{};
@@ -347,7 +355,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
     if (rc) return chk(rc, "fold q' gemm (split precision)");
     rc = launch_split_rows(w.qp32, plain(N * R, E), N * R, E, E, 2, w.qp16, op, stream);
     if (rc) return chk(rc, "split q'");
-  } else {
+  } else if (!x.fuse_query) {   // (fused: run_lanes wrote Q' together with the query projection)
     d.A = w.qc16; d.a = qc_rows; d.a_bs = 64;
     d.W = x.raw ? fold_raw_wk(h, ci) : h->arena_f + (size_t)ci * H * E * esz; d.w_bs = (long long)E * 64;
     d.C = w.qp16; d.c = items_view((long long)R * E, Q, E); d.c_bs_bytes = (long long)Q * E * esz;
@@ -387,7 +395,9 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
       }
       rc = launch_gemm(&sc, 1, EPI_SOFTPART, op, stream);
       if (rc) return chk(rc, "fold scores gemm (softmax partials)");
-      if (x.inreg) {
+      if (x.stat_factors) {
+        // the P . enc launch computes the row factors itself from these statistics (and zeroes the unwritten P~ columns in its LDS)
+      } else if (x.inreg) {
         // second half of the softmax without a pass over P: only the row factors are computed here, the P . enc GEMM applies them
         // to its P~ fragments in registers (same arithmetic, same rounding as the rescale pass)
         rc = launch_fold_rowfactor(sc.stat_m, sc.stat_l, w.gfac, N * R, R, ntiles, w.p16, kvp, 176, kvp, stream, hist);
@@ -415,7 +425,8 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
     pv.C = w.u16; pv.c = plain(R, E); pv.c_bs_bytes = (long long)R * E * esz;
     pv.M = R; pv.N = E; pv.K = kvp; pv.batch = N;
     pv.tile_cfg = x.penc_tile;
-    if (x.inreg) { pv.pscale = w.gfac; pv.ps_ntiles = ntiles; }
+    if (x.stat_factors) { pv.stat_m = sc.stat_m; pv.stat_l = sc.stat_l; pv.ps_stats = 1; pv.ps_ntiles = ntiles; }
+    else if (x.inreg) { pv.pscale = w.gfac; pv.ps_ntiles = ntiles; }
     rc = launch_gemm(&pv, 1, EPI_OP, op, stream);
     if (rc) return chk(rc, "fold p.enc gemm");
   }
@@ -427,6 +438,7 @@ int cross_core(const Lane& lane, const LayerW& Lw, int N, hipStream_t stream) {
   if (x.raw) { cx.W = fold_raw_wv(h, ci); cx.bias = fold_raw_bv(h, ci); }   // U is over raw tokens: W_v' and b_v + W_v b
   cx.C = w.ctx16; cx.c = qc_rows; cx.c_bs_bytes = 64 * esz;
   cx.M = N * Q; cx.N = 64; cx.K = E; cx.batch = c.heads; cx.tile_cfg = E % 128 == 0 && N * Q >= 512 ? GT_K128_64x128 : GT_64;
+  if (x.ctx_64 && cx.tile_cfg == GT_K128_64x128) { cx.tile_cfg = GT_64; cx.k128 = 1; }
   rc = launch_gemm(&cx, 1, EPI_OP, op, stream);
   if (rc) return chk(rc, "fold context gemm");
   if (timed) (void)hipEventRecord(h->kv_ev1, stream);
@@ -796,14 +808,27 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
         p.M = N * Q; p.N = H; p.K = 3 * H;
         rc = launch_gemm(&p, 1, EPI_F32, op, stream);
       } else {
+        // lanes whose plan fuses steps 5 + 6a write Q' here (Q itself has no other reader in that plan); the others share one grouped GEMM
         GemmProb p[2] = {};
-        for (int l = 0; l < nl; ++l) {
-          p[l].A = lanes[l].w.hB16; p[l].a = q_view;
-          p[l].W = Lw[l]->wcq; p[l].bias = Lw[l]->bcq;
-          p[l].C = lanes[l].w.qc16; p[l].c = qc_rows;
-          p[l].M = N * Q; p[l].N = H; p[l].K = H;
+        int ng = 0;
+        rc = 0;
+        for (int l = 0; l < nl && !rc; ++l) {
+          const Lane& x = lanes[l];
+          if (x.plan.fuse_query) {
+            const int ci = Lw[l]->cross_index, E = x.h->cfg.enc_width;
+            const void* wk = x.plan.raw ? fold_raw_wk(x.h, ci) : x.h->arena_f + (size_t)ci * H * E * esz;
+            // the timed block of cross layer 0 keeps meaning steps 6a-6e: here it opens in front of the launch that holds 6a (and step 5)
+            if (ci == 0 && x.h->kv_ev0 && x.h->kv_ev1) (void)hipEventRecord(x.h->kv_ev0, stream);
+            rc = launch_fold_query(x.w.hB16, q_view, Lw[l]->wcq, Lw[l]->bcq, wk, x.w.qp16, N * Q, H, E, Q, c.heads, op, stream);
+            continue;
+          }
+          p[ng].A = x.w.hB16; p[ng].a = q_view;
+          p[ng].W = Lw[l]->wcq; p[ng].bias = Lw[l]->bcq;
+          p[ng].C = x.w.qc16; p[ng].c = qc_rows;
+          p[ng].M = N * Q; p[ng].N = H; p[ng].K = H;
+          ++ng;
         }
-        rc = launch_gemm(p, nl, EPI_OP, op, stream);
+        if (!rc && ng) rc = launch_gemm(p, ng, EPI_OP, op, stream);
       }
       if (rc) return chk(rc, "cross q gemm");
       // 6. each lane's own cross-attention
@@ -1351,6 +1376,12 @@ int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value) {
     h->chain_ring = value;
     return MRA_OK;
   }
+  if (key == "cross_fuse") {
+    if (value < 0 || (value & ~7))
+      return fail(MRA_EINVAL, "cross_fuse is a mask of 1 (query projection and Q' in one launch), 2 (row factors inside the P.enc launch) and 4 (context GEMM on the 64 x 64 tile)");
+    h->cross_fuse = value;
+    return MRA_OK;
+  }
   if (key == "multi_core") {
     if (value < 0 || value > 1) return fail(MRA_EINVAL, "multi_core is 0 (attn_kernel with kv_share) or 1 (shared-stream core)");
     h->multi_core = value;   // the workspace size of the multi forward follows it (grid-split partials)
@@ -1793,6 +1824,15 @@ const char* dbg_gemm_prob(const mra_gemm_desc& d, int epi, GemmProb* out) {
   p.batch = d.batch; p.a_bs = d.a_bs; p.w_bs = d.w_bs; p.c_bs_bytes = d.c_bs_bytes; p.bias_bs = d.bias_bs;
   p.n_ragged = d.n_ragged; p.w_ld = d.w_ld; p.k_rows = d.k_rows; p.w_kwrap = d.w_kwrap;
   p.tile_cfg = d.tile_cfg; p.persist = d.persist;
+  if (d.k128 < 0 || d.k128 > 1 || d.ps_stats < 0 || d.ps_stats > 1) return "k128 and ps_stats are 0 or 1";
+  if (d.ps_stats) {   // P . enc fed by the scores launch's tile statistics: stat_m / stat_l in, no pscale
+    if (epi != EPI_OP || d.pscale || !d.w_ld) return "ps_stats goes with EPI_OP over K-major weights (w_ld) and without pscale";
+    if (!d.stat_m || !d.stat_l || !dbg_aligned(d.stat_m, 4) || !dbg_aligned(d.stat_l, 4)) return "ps_stats needs stat_m and stat_l (4-byte aligned)";
+    if (d.M > 384 || d.ps_ntiles <= 0) return "ps_stats needs M <= 384 (one row tile) and ps_ntiles > 0";
+    p.stat_m = d.stat_m; p.stat_l = d.stat_l; p.ps_stats = 1; p.ps_ntiles = d.ps_ntiles;
+  }
+  if (d.k128 && (d.tile_cfg != GT_64 || d.K % 128)) return "k128 goes with tile_cfg GT_64 and K % 128 == 0";
+  p.k128 = d.k128;
   if (epi == EPI_KV) {
     if (d.kv_tokens <= 0 || d.kv_items <= 0 || d.kv_heads <= 0 || d.kv_heads > 1024) return "EPI_KV needs kv_tokens, kv_items and kv_heads > 0";
     if (d.N % (d.kv_heads * 64)) return "EPI_KV: N must be a multiple of kv_heads * 64";
@@ -1911,6 +1951,10 @@ const char* dbg_gemm_footprint(const mra_gemm_desc& d, const GemmProb& p, const 
     const u128 n = (u128)nb * (u128)d.M * (u128)ntiles;
     if (!dbg_fits(n, 4, 0, d.stat_m_bytes) || !dbg_fits(n, 4, 0, d.stat_l_bytes)) return "stat_m / stat_l: batch * M * ntiles floats leave their sizes";
   }
+  if (p.ps_stats) {
+    const u128 n = (u128)nb * (u128)d.M * (u128)d.ps_ntiles;
+    if (!dbg_fits(n, 4, 0, d.stat_m_bytes) || !dbg_fits(n, 4, 0, d.stat_l_bytes)) return "ps_stats: batch * M * ps_ntiles floats of stat_m / stat_l leave their sizes";
+  }
   if (p.pscale && !dbg_fits((u128)nb * (u128)d.ps_ntiles * 512, 4, 0, d.pscale_bytes)) return "pscale: batch * ps_ntiles * 512 floats leave pscale_bytes";
   if (p.col_scale && !dbg_fits((u128)d.N + (u128)(nb - 1) * (u128)d.cs_bs, 4, 0, d.col_scale_bytes)) return "col_scale: N floats and the batch stride leave col_scale_bytes";
   if (epi == EPI_RES_LN) {
@@ -1984,5 +2028,32 @@ int mra_debug_gemm_plan(const mra_gemm_desc* probs, int32_t nprob, int32_t epilo
   for (int i = 0; i < 7; ++i) out[i] = r[i];
   return MRA_OK;
 }
+
+// The fused query launch of the folded cross-attention (fold.hip: fold_query_kernel; "cross_fuse" bit 1) on its own, through the launch function
+// the forward calls.  Every null, misaligned or short buffer is refused before anything is launched; nothing is allocated.
+int mra_debug_fold_query(const void* x, const int64_t* x_view, size_t x_bytes, const void* w_q, size_t w_q_bytes, const float* b_q, size_t b_q_bytes,
+                         const void* w_k, size_t w_k_bytes, void* q_prime, size_t q_prime_bytes, int32_t rows, int32_t H, int32_t E, int32_t Q,
+                         int32_t heads, int32_t dtype, void* stream) {
+  int op;
+  if (rows < 0) return fail(MRA_EINVAL, "negative rows");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (H < 64 || H % 64 || E < 64 || E % 64 || Q <= 0 || heads <= 0 || heads > 1024 || rows % Q)
+    return fail(MRA_EINVAL, "need H and E positive multiples of 64, Q > 0, 0 < heads <= 1024, rows % Q == 0");
+  RowView xv;
+  if (!dbg_view8(x_view, &xv) || xv.ld < H) return fail(MRA_EINVAL, "bad row view of x: strides multiples of 8, row stride >= H");
+  if (rows == 0) return MRA_OK;
+  if (!x || !w_q || !w_k || !q_prime) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(x, 16) || !dbg_aligned(w_q, 16) || !dbg_aligned(w_k, 16) || !dbg_aligned(q_prime, 16) || !dbg_aligned(b_q, 16))
+    return fail(MRA_EINVAL, "misaligned buffer");
+  if (!dbg_fits(dbg_extent(xv, rows, H), 2, 0, x_bytes)) return fail(MRA_EINVAL, "x: the view and H leave x_bytes");
+  if (!dbg_fits((u128)heads * 64 * (u128)H, 2, 0, w_q_bytes)) return fail(MRA_EINVAL, "w_q: heads * 64 rows of H leave w_q_bytes");
+  if (b_q && !dbg_fits((u128)heads * 64, 4, 0, b_q_bytes)) return fail(MRA_EINVAL, "b_q: heads * 64 floats leave b_q_bytes");
+  if (!dbg_fits((u128)heads * (u128)E * 64, 2, 0, w_k_bytes)) return fail(MRA_EINVAL, "w_k: heads blocks of [E][64] leave w_k_bytes");
+  if (!dbg_fits((u128)rows * (u128)heads * (u128)E, 2, 0, q_prime_bytes)) return fail(MRA_EINVAL, "q_prime: rows * heads * E elements leave q_prime_bytes");
+  return chk(launch_fold_query(x, xv, w_q, b_q, w_k, q_prime, rows, H, E, Q, heads, op, as_stream(stream)), "fold_query");
+}
+
+int64_t mra_debug_fold_query_launches(void) { return fold_query_launch_count(); }
+int64_t mra_debug_fold_rowfactor_launches(void) { return fold_rowfactor_launch_count(); }
 
 }  // extern "C"

@@ -166,6 +166,12 @@ struct mra_qformer {
   int train_ring = 4;   // the same mask for the training forward / backward GEMMs (mra_qformer_set_option "train_ring"): bit 0 QKV, bit 2 every N = hidden
                         // GEMM whose epilogue the ring kernel has (projections with a residual, the data gradients).  Measured at B = 1 x T = 20 (r03x,
                         // one session): 14.6-15.2 ms per step with 0, 14.0-14.3 with 4, 14.2 with 5
+  // folded cross-attention, default plan only (mra_qformer_set_option "cross_fuse"): bit 1 = cross query projection and Q' in one launch
+  // (fold.hip: fold_query_kernel, bit-identical to the two GEMM launches); bit 4 = the per-head context GEMM on the 64 x 64 tile with 128-deep
+  // K steps (192 workgroups that pull 360 KB each instead of 96 that pull 540 KB; bit-identical too); bit 2 = the row factors computed inside
+  // the P . enc launch from the scores launch's tile statistics (GemmProb::ps_stats: no fold_rowfactor launch, no factor array; bit-identical,
+  // but that launch grows by 61 us to save 11: measured slower, opt-in only); 0 = the launches as they were
+  int cross_fuse = 1;   // measured in the step, one process, masks in turn: 0 / 1 / 2 / 3 / 4 / 7 = 6.463 / 6.380 / 6.760 / 6.675 / 6.460 / 6.668 ms
   // mra_qformer_forward_multi: the cross core that lets several prompts read one K/V stream (mra_qformer_set_option "multi_core"):
   // 0 attn_kernel with AttnArgs::kv_share, 1 the shared-stream core (attn_shared_kernel).  The rule for the default: whichever the line of
   // tools/bench_multi_query.py shows faster at P >= 4 on both of its shapes.  Measured (profiles/multi_query_line.json, one session): 1 at
