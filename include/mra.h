@@ -60,7 +60,7 @@ typedef struct mra_cfg {
   int32_t max_pos;     /* 512 */
   float ln_eps;        /* 1e-12 (BERT LayerNorm) */
   float enc_ln_eps;    /* 1e-5  (modality LayerNorm, torch default) */
-  int32_t llm_hidden;  /* 4096, or 0 when no llm_proj is loaded */
+  int32_t llm_hidden;  /* 4096 (a multiple of 64), or 0 when no llm_proj is loaded */
   int32_t op_dtype;    /* MRA_F16 (default, the reference's autocast dtype) or MRA_BF16: MFMA operand type */
 } mra_cfg;
 
@@ -280,6 +280,24 @@ int mra_qformer_set_kv_done_event(mra_qformer* h, void* ev);
  * workspace: rows * hidden operand elements. */
 int mra_llm_proj(mra_qformer* h, const float* z, int32_t rows, void* out, int32_t out_dtype, void* workspace,
                  size_t workspace_bytes, void* stream);
+/* Backward of mra_llm_proj: the link that lets the language model's loss on the answer tokens reach the Q-Former.  Beyond the reference on
+ * this path ({modality}_llm_proj at models/xinstructblip.py:303 is trained there only by torch autograd).  With y = op(z) W^T + b, op the
+ * rounding to the operand dtype and dY = op(d_out):
+ *   d_z [rows, hidden] f32       = dY W            WRITTEN.  One MFMA launch that reads W [llm_hidden, hidden] as stored through the LDS
+ *                                                  transpose read (the kernel of mra_qformer_backward_enc on a row-major dY): no transposed
+ *                                                  copy of the weight exists, so none can go stale; no atomics.
+ *   d_weight [llm_hidden, hidden] f32 += dY^T op(z),   d_bias [llm_hidden] f32 += colsum(dY)     ADDED to, one launch for both (float atomics
+ *                                                  where the contraction over rows is split: the order over rows is then not fixed).
+ * z [rows, hidden] f32 is what the forward was given; d_out [rows, llm_hidden] is MRA_F32 (rounded to the operand dtype into the workspace
+ * first; the rounding of z and d_out is passed straight through) or the handle's operand dtype (16-byte aligned).  Each of d_z, d_weight,
+ * d_bias may be NULL and skips its work.  Nothing is written into the flat gradient buffer of mra_qformer_backward: its llm_proj.* slots stay
+ * zero.  Checks, all before any launch: NULL handle, negative rows (rows == 0 is a no-op), llm_proj.* not loaded (MRA_ESTATE), llm_hidden not
+ * a multiple of 64 or hidden not a multiple of 128, d_out_dtype, NULL z / d_out, rows * llm_hidden above int32 (MRA_EINVAL), workspace below
+ * mra_llm_proj_backward_workspace_bytes (MRA_ENOMEM, naming the need; 0 for a NULL handle or non-positive rows, 256-byte aligned).
+ * No allocation, no synchronisation. */
+size_t mra_llm_proj_backward_workspace_bytes(mra_qformer* h, int32_t rows, int32_t d_out_dtype);
+int mra_llm_proj_backward(mra_qformer* h, const float* z, int32_t rows, const void* d_out, int32_t d_out_dtype, float* d_z, float* d_weight,
+                          float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- A6: scorer (build-defined; the reference has no scorer) ----------------------------------
  * sim[n][q] = cos(z[n][q][:], t[n or 0][:]); logit[n] = max_q sim[n][q].  sim may be NULL. */
@@ -333,7 +351,8 @@ int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, 
  *                                 as mra_qformer_load) owns numel floats at mra_qformer_grad_offset().
  *                                 Gradients flow to every Q-Former parameter incl. query_tokens and the
  *                                 embeddings; enc and ln.* get theirs from mra_qformer_backward_enc and
- *                                 mra_modality_ln_backward (below); llm_proj.* is not on the scorer's path. */
+ *                                 mra_modality_ln_backward (below); llm_proj.* is not on the scorer's path
+ *                                 (its gradients come from mra_llm_proj_backward, never into `grads`). */
 size_t mra_qformer_grad_bytes(mra_qformer* h);
 /* Optimizer-side fast path: refreshes EVERY bert.* parameter in one launch from a flat f32 master buffer
  * laid out exactly like the gradient buffer (parameter `name` at mra_qformer_grad_offset(name)), converting

@@ -12,6 +12,9 @@
 //     ds_read_b64_tr_b16 exactly like the X operand of gemm_tn.hip.  No transposed copy of the weights exists, so none can go stale.
 //     One workgroup = 128 rows x 128 columns (4 waves, 64 x 64 each: four v_mfma_f32_32x32x16 accumulators), two LDS stages of 32 KB: the
 //     next K step is in flight while this one is multiplied, one barrier per step.  fp32 out, rows past M are loaded clamped and not stored.
+//     ROWS = true is the second A-side addressing mode (launch_rowgrad_gemm: the data gradient of the LLM projection, proj_grad.hip): A is a
+//     plain row-major [M][K] matrix, i.e. the tape above with kv = 1 and K / 64 heads of one selector, so the per-row division and the
+//     per-step selector split drop out at compile time; staging, fragment order and arithmetic are the ones above.
 //   modality_ln_bwd_kernel   d_x = r (g - mean(g) - xhat mean(g xhat)), g = d_out gain; d_gain += sum_rows d_out xhat; d_bias += sum_rows d_out.
 //     One wave per row, the row in registers (8 elements per lane and step, the buckets of modality_ln_kernel), statistics two-pass from
 //     x.  A row is read completely before it is written, so d_x may be d_out.  Column sums meet in LDS (one fp32 LDS atomic per element
@@ -30,7 +33,7 @@ constexpr int KG_A_BYTES = KG_BM * 128;            // [128 rows][64 k]
 constexpr int KG_W_TILE = 32 * 128;                // [32 k][64 e]
 constexpr int KG_STAGE = KG_A_BYTES + 4 * KG_W_TILE;
 
-template <typename T>
+template <typename T, bool ROWS>
 __global__ void __launch_bounds__(256) kvgrad_gemm_kernel(const T* __restrict__ dkv, const T* __restrict__ W, float* __restrict__ out, int M, int kv,
                                                            int Ne, int heads, int nseg, int E) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -45,7 +48,7 @@ __global__ void __launch_bounds__(256) kvgrad_gemm_kernel(const T* __restrict__ 
   for (int i = 0; i < 4; ++i) {
     const int idx = tid + 256 * i, r = idx >> 3;
     const int m = min(m0 + r, M - 1);              // rows past M: a valid row again, never stored
-    const int item = m / kv, tok = m - item * kv;
+    const int item = ROWS ? m : m / kv, tok = ROWS ? 0 : m - item * kv;
     arow[i] = dkv + ((long long)item * heads * kv + tok) * 64 + (((idx & 7) ^ (r & 7)) << 3);
   }
   const long long head_stride = (long long)kv * 64, sel_stride = (long long)Ne * heads * kv * 64;
@@ -54,7 +57,7 @@ __global__ void __launch_bounds__(256) kvgrad_gemm_kernel(const T* __restrict__ 
   const T* wsrc = W + (long long)srow * E + e0 + ((sc ^ (((srow >> 1) & 1) << 2)) << 3);
   auto issue = [&](int buf, int s) {
     char* st = smem + buf * KG_STAGE;
-    const int g = s / heads;
+    const int g = ROWS ? 0 : s / heads;
     const long long seg = (long long)g * sel_stride + (long long)(s - g * heads) * head_stride;
 #pragma unroll
     for (int i = 0; i < 4; ++i) glds16(arow[i] + seg, st + i * 4096 + wave * 1024);
@@ -286,9 +289,22 @@ int launch_kvgrad_gemm(const void* dkv, const void* W, float* d_enc, int Ne, int
   const dim3 grid((unsigned)((M + KG_BM - 1) / KG_BM), E / KG_BN), block(256);
   const size_t lds = 2 * KG_STAGE;
   if (op_dtype == OP_F16)
-    hipLaunchKernelGGL(kvgrad_gemm_kernel<f16>, grid, block, lds, stream, (const f16*)dkv, (const f16*)W, d_enc, (int)M, kv, Ne, heads, nsel * heads, E);
+    hipLaunchKernelGGL((kvgrad_gemm_kernel<f16, false>), grid, block, lds, stream, (const f16*)dkv, (const f16*)W, d_enc, (int)M, kv, Ne, heads, nsel * heads, E);
   else
-    hipLaunchKernelGGL(kvgrad_gemm_kernel<bf16>, grid, block, lds, stream, (const bf16*)dkv, (const bf16*)W, d_enc, (int)M, kv, Ne, heads, nsel * heads, E);
+    hipLaunchKernelGGL((kvgrad_gemm_kernel<bf16, false>), grid, block, lds, stream, (const bf16*)dkv, (const bf16*)W, d_enc, (int)M, kv, Ne, heads, nsel * heads, E);
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_rowgrad_gemm(const void* dY, const void* W, float* dX, int M, int K, int E, int op_dtype, hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (K <= 0 || K % 64 || E <= 0 || E % KG_BN || M > 0x7fffffff - KG_BM) return -1;
+  const dim3 grid((unsigned)((M + KG_BM - 1) / KG_BM), E / KG_BN), block(256);
+  const size_t lds = 2 * KG_STAGE;
+  // row m is "item" m of one token with K / 64 heads: the head-major address of K step s is then m * K + s * 64
+  if (op_dtype == OP_F16)
+    hipLaunchKernelGGL((kvgrad_gemm_kernel<f16, true>), grid, block, lds, stream, (const f16*)dY, (const f16*)W, dX, M, 1, M, K / 64, K / 64, E);
+  else
+    hipLaunchKernelGGL((kvgrad_gemm_kernel<bf16, true>), grid, block, lds, stream, (const bf16*)dY, (const bf16*)W, dX, M, 1, M, K / 64, K / 64, E);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -222,6 +222,16 @@ int launch_gemm_tn_group(const GemmTnArgs* jobs, int njobs, int op_dtype, hipStr
 // Encoder-side data gradient of the cross K / V projections (enc_grad.hip): d_enc [Ne * kv][E] fp32 = dKV W, with dKV the head-major dK / dV
 // tape [nsel][Ne][heads][kv][64] (operand dtype, nsel = ncross * 2) read in place and W [nsel * heads * 64][E] as stored.  E % 128 == 0.
 int launch_kvgrad_gemm(const void* dkv, const void* W, float* d_enc, int Ne, int kv, int heads, int nsel, int E, int op_dtype, hipStream_t stream);
+// The same kernel on a plain row-major A (its second A-side addressing mode): dX [M][E] fp32 = dY W, dY [M][K] operand dtype with contiguous
+// K (16-byte aligned rows), W [K][E] as stored -- the data gradient of a linear layer y = x W^T without a transposed copy of W.  K % 64 == 0,
+// E % 128 == 0; dX is written, rows past M are loaded clamped and not stored; no atomics.
+int launch_rowgrad_gemm(const void* dY, const void* W, float* dX, int M, int K, int E, int op_dtype, hipStream_t stream);
+// Backward of the LLM projection y = op(z) W^T + b (proj_grad.hip), W [Lh][H] operand dtype: d_z [R][H] = dY W (written, one
+// launch_rowgrad_gemm), d_W [Lh][H] += dY^T op(z) and d_b [Lh] += colsum(dY) (one launch_gemm_tn with its db output; d_b alone: the same
+// launch on the first 64 columns of op(z) into `scratch` [Lh][64], so its bits are those of the joint call).  dY [R][Lh] operand dtype, z16 =
+// op(z) [R][H]; every output may be NULL.  Lh % 64 == 0, H % 128 == 0.
+int launch_llm_proj_bwd(const void* dY, const void* z16, const void* W, int R, int Lh, int H, float* d_z, float* d_W, float* d_b, float* scratch,
+                        int op_dtype, hipStream_t stream);
 // Backward of launch_modality_ln without an item index (enc_grad.hip): x [items][tokens][E] (x_dtype 0 / 1 / 2 = f32 / f16 / bf16), d_out fp32;
 // d_x (may be NULL, may be d_out) is written, d_gain / d_bias [E] (each may be NULL) are ADDED to.  E a multiple of 8, <= 4096.
 int launch_modality_ln_bwd(const void* x, int x_dtype, int items, int tokens, int E, const float* gain, float eps, const float* d_out, float* d_x,

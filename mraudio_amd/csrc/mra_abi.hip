@@ -501,7 +501,7 @@ int mra_qformer_create(const mra_cfg* cfg, mra_qformer** out) {
   if (c.inter <= 0 || c.inter % 256) return fail(MRA_EINVAL, "inter must be a multiple of 256");
   if (c.enc_width <= 0 || c.enc_width % 64) return fail(MRA_EINVAL, "enc_width must be a multiple of 64");
   if (c.layers <= 0 || c.cross_freq <= 0 || c.vocab <= 0 || c.max_pos <= 0) return fail(MRA_EINVAL, "bad layer/vocab config");
-  if (c.llm_hidden < 0 || c.llm_hidden % 256) return fail(MRA_EINVAL, "llm_hidden must be 0 or a multiple of 256");
+  if (c.llm_hidden < 0 || c.llm_hidden % 64) return fail(MRA_EINVAL, "llm_hidden must be 0 or a multiple of 64");
   if (c.op_dtype != MRA_F16 && c.op_dtype != MRA_BF16) return fail(MRA_EINVAL, "op_dtype must be MRA_F16 or MRA_BF16");
   mra_qformer* h = new mra_qformer();
   h->cfg = c;

@@ -32,13 +32,32 @@ def init_distributed_mode(args) -> None:
 
 def run_train(args):
     init_distributed_mode(args)
-    trainer = Trainer(args)
+    trainer = Trainer(args, model=build_llm_model(args) if args.llm_path else None)
     out = trainer.train()
     if args.rank == 0:
         print({"history": trainer.history, **out})
     if dist.is_initialized():
         dist.destroy_process_group()
     return out
+
+
+def build_llm_model(args):
+    """The model as ``Trainer`` would build it, with the causal LM of ``--llm-path`` attached: a LOCAL directory (``local_files_only``,
+    never a hub name), loaded in the trainer's operand dtype (bf16), every LM parameter frozen."""
+    from transformers import AutoModelForCausalLM, AutoTokenizer
+
+    from .models.xinstructblip import XInstructBLIP
+    if not os.path.isdir(args.llm_path):
+        raise SystemExit(f"--llm-path {args.llm_path!r} is not a local directory (hub names are not fetched)")
+    dev = torch.device("cuda", args.gpu)
+    llm = AutoModelForCausalLM.from_pretrained(args.llm_path, local_files_only=True, torch_dtype=torch.bfloat16).to(dev)
+    tok = AutoTokenizer.from_pretrained(args.llm_path, local_files_only=True, use_fast=False)
+    llm.requires_grad_(False)
+    model = XInstructBLIP(args.model_path, args.audio_encoder, device=dev, op_dtype=torch.bfloat16, checkpoint=args.checkpoint,
+                          checkpoint_strict=not args.partial_checkpoint, cross_precision=args.cross_precision,
+                          llm_hidden_size=llm.get_input_embeddings().weight.shape[1])
+    model.attach_llm(llm, tok)
+    return model
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -68,6 +87,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--train-ln", action="store_true",
                     help="train the modality LayerNorms ({m}_ln) in front of the Q-Formers too (XInstructBLIP.enable_qformer_training(train_ln=True)); "
                          "the checkpoints then carry {m}_ln.*")
+    ap.add_argument("--objective", default="score", choices=["score", "llm", "both"],
+                    help="training loss: score (the build-defined scorer BCE), llm (the LM's cross-entropy on the answer tokens, the reference's "
+                         "objective, through {m}_llm_proj into the Q-Formers) or both (bce + lm-weight * lm); validation stays on the scorer")
+    ap.add_argument("--lm-weight", type=float, default=1.0, help="with --objective both: weight of the LM term")
+    ap.add_argument("--train-proj", action="store_true",
+                    help="train the projections into the LM ({m}_llm_proj) too (XInstructBLIP.enable_qformer_training(train_proj=True)); "
+                         "the checkpoints then carry {m}_llm_proj.*")
+    ap.add_argument("--llm-path", default=None, help="local directory of the causal LM (loaded with local_files_only, frozen, bf16); "
+                                                     "required by --objective llm / both")
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--warmup-steps", type=int, default=1000)
     ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],
@@ -77,7 +105,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.objective != "score" and not args.llm_path:
+        parser.error(f"--objective {args.objective} needs --llm-path DIR")
     logging.basicConfig(level=logging.INFO)
     return run_train(args)
 

@@ -110,10 +110,28 @@ class _Proj(nn.Module):
         return self._qformer_ref().llm_proj(z)
 
 
+class _ScaleGrad(torch.autograd.Function):
+    """Identity whose gradient is multiplied by ``scale`` (``XInstructBLIP.loss_scale``: the value of the LM loss stays the loss)."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale = scale
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.scale, None
+
+
 ENC_WIDTH = {"video": 1408, "audio": 768}  # EVA ViT-g / BEATs num_features (reference :123)
 
 
 class XInstructBLIP(nn.Module):
+    # what forward() trains on: "score" (the build-defined scorer loss), "llm" (the attached LM's cross-entropy on the answer tokens,
+    # reference :399-606) or "both" (bce + lm_weight * lm over ONE Q-Former forward per modality).  loss_scale: the LM term's
+    # gradient is multiplied by it on its way into the LM and divided out again in the projection's backward (see forward_llm)
+    objective, lm_weight, loss_scale = "score", 1.0, 1.0
+
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
                  audio_encoder=None, tokenizer=None, seed: Optional[int] = 0,
@@ -797,9 +815,33 @@ class XInstructBLIP(nn.Module):
         outputs[outputs == 0] = 2                                      # :392
         return [o.strip() for o in self.llm_tokenizer.batch_decode(outputs, skip_special_tokens=True)]
 
-    def forward_llm(self, samples):
-        """Reference ``forward`` end to end (``:399-606``): the LM's cross-entropy on the answer tokens.  The Q-Former
-        side is computed without grad (frozen, as in the reference); the loss trains whatever the LM leaves trainable."""
+    def _check_lm_training(self) -> None:
+        if self.prompt_assembler is None:
+            raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
+        if not getattr(self, "train_qformers", False):
+            raise MraError("the LM objective trains the Q-Formers: call enable_qformer_training() first")
+
+    def forward_llm(self, samples, train: Optional[bool] = None):
+        """Reference ``forward`` end to end (``:399-606``): the LM's cross-entropy on the answer tokens.  ``train=False``: the
+        Q-Former side is computed without grad (frozen, as in the reference); the loss trains whatever the LM leaves trainable.
+        ``train=True`` (default: ``objective != "score"`` after ``enable_qformer_training()``): the loss is differentiable with
+        respect to the Q-Formers, the query tokens, ``{m}_ln`` under ``train_ln`` and ``{m}_llm_proj`` under ``train_proj`` -- the
+        BLIP-2 stage-2 / InstructBLIP recipe with a frozen LM.  Encoders run under ``no_grad``; the Q-Former text rows follow
+        ``forward`` (``compat_repeat``).  The LM is never modified: whatever it leaves trainable still receives gradients.
+        A 16-bit LM's activation gradients are 16-bit too and the LM loss is a mean over the answer tokens, so with an f16 LM the small
+        ones flush to zero before they reach the projection: use bf16, or set ``loss_scale`` (e.g. 1024): the LM term's gradient is
+        multiplied by it going into the LM and divided out in fp32 inside the projection's backward, so the loss value and the
+        gradients of the projections, Q-Formers and LayerNorms are unscaled.  Gradients of parameters INSIDE the LM are then
+        ``loss_scale`` times too large (divide them yourself): a frozen LM is the intended use."""
+        if train is None:
+            train = self.objective != "score" and getattr(self, "train_qformers", False)
+        if train:
+            self._check_lm_training()
+            ti = samples.get("text_input")
+            if ti is not None and len(ti) > 0 and isinstance(ti[0], (list, tuple)):
+                raise MraError("the LM objective has no multi-query form: one text_input string per sample")
+            _, inputs_llm, _, _ = self._train_pass(samples, want_score=False, want_llm=True)
+            return {"loss": self._lm_loss(samples, inputs_llm)}
         inputs_llm, atts_llm = self._llm_inputs(samples)
         embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, inputs_llm, atts_llm)
         return {"loss": self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss}
@@ -828,14 +870,17 @@ class XInstructBLIP(nn.Module):
                 target[r] = torch.maximum(target[r], ((t >= s0) & (t <= e0)).float())
         return target
 
-    def enable_qformer_training(self, train_ln: bool = False) -> None:
+    def enable_qformer_training(self, train_ln: bool = False, train_proj: bool = False) -> None:
         """Unfreeze the Q-Formers (the reference keeps them frozen, ``:196-204``; BASELINE config 5 trains
         them): parameters get ``requires_grad`` and gradients from the HIP backward.  ``train_ln``: the modality
         LayerNorms ``{m}_ln`` in front of them are trained too (``QFormer.modality_ln_train``: the encoder-side data
         gradient of the Q-Former and the LayerNorm backward run on the HIP extension); they stay ordinary torch
-        parameters, which ``flat_optimizer_params`` lists behind the flat ones.  The default leaves the step as it is."""
+        parameters, which ``flat_optimizer_params`` lists behind the flat ones.  ``train_proj``: likewise the projections
+        ``{m}_llm_proj`` into the LM (``QFormer.llm_proj_train``, ``mra_llm_proj_backward``), which only the LM objectives
+        (``objective`` "llm" / "both") reach.  The default leaves the step as it is."""
         self.train_qformers = True
         self.train_ln = bool(train_ln)
+        self.train_proj = bool(train_proj)
 
         def ln_dirty():
             self._extras_dirty = True          # fused optimizers do not bump version counters (see QFormer._run_backward)
@@ -844,7 +889,11 @@ class XInstructBLIP(nn.Module):
             if self.train_ln:
                 for p in getattr(self, f"{m}_ln").parameters():
                     p.requires_grad_(True)
+            if self.train_proj:
+                for p in getattr(self, f"{m}_llm_proj").parameters():
+                    p.requires_grad_(True)
             getattr(self, f"{m}_Qformer")._ln_grad_hook = ln_dirty if self.train_ln else None
+            getattr(self, f"{m}_Qformer")._proj_grad_hook = ln_dirty if self.train_proj else None
         for m in self.modalities:
             qf: QFormer = getattr(self, f"{m}_Qformer")
             qf.enable_training()
@@ -874,17 +923,42 @@ class XInstructBLIP(nn.Module):
         if samples is None or samples == {} or not any(self._present(samples, m) for m in self.modalities):
             return {"loss": torch.tensor(0.0)}
         ti = samples.get("text_input")
-        if ti is not None and len(ti) > 0 and isinstance(ti[0], (list, tuple)):   # one record per video with the list of its queries
+        grouped = ti is not None and len(ti) > 0 and isinstance(ti[0], (list, tuple))
+        if self.objective != "score":
+            if self.objective not in ("llm", "both"):
+                raise MraError(f"objective must be 'score', 'llm' or 'both', got {self.objective!r}")
+            if grouped:
+                raise MraError(f"objective {self.objective!r} has no multi-query form: train grouped batches with objective 'score'")
+            if self.objective == "llm":
+                return self.forward_llm(samples, train=True)
+            self._check_lm_training()
+            per_mod, inputs_llm, bs, num = self._train_pass(samples, want_score=True, want_llm=True)
+            bce, lm = self._score_loss(samples, per_mod, bs, num), self._lm_loss(samples, inputs_llm)
+            return {"loss": bce + self.lm_weight * lm, "loss_score": bce.detach(), "loss_lm": lm.detach()}
+        if grouped:   # one record per video with the list of its queries
             return self.forward_multi(samples)
         if not getattr(self, "train_qformers", False):
             out = self.encode_fuse(samples)
             bs, num = out["bs"], out["num"]
             logits = out["fused"].view(bs, num) * 20.0
             return {"loss": nn.functional.binary_cross_entropy_with_logits(logits, self._targets(samples, bs, num))}
+        per_mod, _, bs, num = self._train_pass(samples, want_score=True, want_llm=False)
+        return {"loss": self._score_loss(samples, per_mod, bs, num)}
+
+    def _score_loss(self, samples, per_mod, bs, num):
+        w = self.fuse_weights or [1.0 / len(per_mod)] * len(per_mod)
+        fused = sum(x * wt for x, wt in zip(per_mod, w))
+        return nn.functional.binary_cross_entropy_with_logits(fused.view(bs, num) * 20.0, self._targets(samples, bs, num))
+
+    def _train_pass(self, samples, want_score: bool, want_llm: bool):
+        """ONE training forward per modality Q-Former (``forward_train``), connected to autograd, feeding what the objective asks for:
+        ``want_score`` the per-position scorer logits ``max_q cos(z, cls)``, ``want_llm`` the projections into the LM
+        ``inputs_llm[m]`` [B, T * 32, D] (fp32; ``llm_proj_train``, always a node: the Q-Former gets its gradient whether or not the
+        projection is trained).  Returns ``(per_mod, inputs_llm, bs, num)``."""
         self._sync()
         text = self.tokenizer(samples["text_input"], padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
         ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)
-        per_mod, bs, num = [], None, None
+        per_mod, inputs_llm, bs, num = [], {}, None, None
         # ``train_streams``: each modality's forward (and, since autograd runs a node's backward on its forward's stream, its backward)
         # on its own stream.  Round 2 measured nothing from it (17.4 vs 17.0 ms: the step was bound by the GPU time of its ~1300 launches);
         # measured again after the launch merges of round 3 -- see DESIGN.md section 8.
@@ -908,16 +982,28 @@ class XInstructBLIP(nn.Module):
                 ids_n, tm_n = (ids.repeat(num, 1), tmask.repeat(num, 1)) if self.compat_repeat else \
                               (ids.repeat_interleave(num, 0), tmask.repeat_interleave(num, 0))
                 att = torch.cat([torch.ones(n, self.num_query_token, dtype=torch.long, device=self._device), tm_n], dim=1)
-                z, cls = qf.forward_train(ids_n, att, enc)
-                sim = nn.functional.cosine_similarity(z, cls[:, None, :], dim=-1, eps=1e-8)
-                per_mod.append(sim.max(dim=1).values)
+                z, cls = qf.forward_train(ids_n, att, enc, want_cls=want_score)
+                if want_score:
+                    sim = nn.functional.cosine_similarity(z, cls[:, None, :], dim=-1, eps=1e-8)
+                    per_mod.append(sim.max(dim=1).values)
+                if want_llm:  # reference :303-306
+                    proj = getattr(self, f"{m}_llm_proj")
+                    y = qf.llm_proj_train(z, proj.weight, proj.bias, grad_scale=self.loss_scale)
+                    inputs_llm[m] = y.reshape(bs, num * self.num_query_token, -1)
         if use_streams:
             for m in self.modalities:
                 if (m, False) in self._streams:
                     cur.wait_stream(self._streams[(m, False)])
-        w = self.fuse_weights or [1.0 / len(per_mod)] * len(per_mod)
-        fused = sum(x * wt for x, wt in zip(per_mod, w))
-        return {"loss": nn.functional.binary_cross_entropy_with_logits(fused.view(bs, num) * 20.0, self._targets(samples, bs, num))}
+        return per_mod, inputs_llm, bs, num
+
+    def _lm_loss(self, samples, inputs_llm):
+        """The attached LM's cross-entropy on the answer tokens over differentiable ``inputs_llm`` (``PromptAssembler.assemble_forward`` is
+        plain ``torch.cat``).  The value is the loss itself; only its gradient carries ``loss_scale`` into the LM."""
+        dt = self.llm_model.get_input_embeddings().weight.dtype
+        atts = {m: torch.ones(v.shape[0], v.shape[1], dtype=torch.long, device=self._device) for m, v in inputs_llm.items()}
+        embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in inputs_llm.items()}, atts)
+        loss = self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
+        return _ScaleGrad.apply(loss, float(self.loss_scale)) if self.loss_scale != 1.0 else loss
 
     def _ln_train(self, m: str, raw: torch.Tensor) -> torch.Tensor:
         """``{m}_ln`` over the encoder output as an autograd node (``enable_qformer_training(train_ln=True)``)."""
@@ -1033,7 +1119,7 @@ class XInstructBLIP(nn.Module):
     def all_reduce_grads(self) -> None:
         """Data-parallel gradient averaging over the process group: one all-reduce of each Q-Former's flat f32
         gradient buffer (what DDP does bucket by bucket in the reference's trainer, ``utils/trainer.py:69,133``).  Parameters outside
-        the flat buffers (``{m}_ln.*`` under ``train_ln``) carry ordinary ``.grad`` tensors: ``Trainer._sync_grads`` averages those."""
+        the flat buffers (``{m}_ln.*`` under ``train_ln``, ``{m}_llm_proj.*`` under ``train_proj``) carry ordinary ``.grad`` tensors: ``Trainer._sync_grads`` averages those."""
         rank, ws = parallel.world(self.process_group)
         if ws == 1:
             return

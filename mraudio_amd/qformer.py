@@ -220,6 +220,8 @@ class QFormer(nn.Module):
         """Copy one tensor into the handle under its ABI name (``include/mra.h`` mra_qformer_load)."""
         if name in ("ln.weight", "ln.bias"):      # modality_ln_train checks that it is handed the tensors the handle holds
             self.__dict__.setdefault("_pushed_ln", {})[name] = (weakref.ref(t), t._version)
+        if name in ("llm_proj.weight", "llm_proj.bias"):      # likewise llm_proj_train
+            self.__dict__.setdefault("_pushed_proj", {})[name] = (weakref.ref(t), t._version)
         t = t.detach()
         if t.device != self._device:
             t = t.to(self._device)
@@ -471,6 +473,39 @@ class QFormer(nn.Module):
             check(lib().mra_llm_proj(self._handle, ptr(zz), rows, ptr(out), _lib.mra_dtype(out_dtype), ptr(ws), ws.numel(),
                                      current_stream()), "mra_llm_proj")
         return out.reshape(*z.shape[:-1], cfg.llm_hidden)
+
+    def llm_proj_train(self, z: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, out_dtype: torch.dtype = torch.float32,
+                       grad_scale: float = 1.0) -> torch.Tensor:
+        """``llm_proj(z, out_dtype)`` (the same bits) connected to autograd: ``weight`` / ``bias`` are the ``{m}_llm_proj`` tensors last
+        pushed as ``llm_proj.weight`` / ``llm_proj.bias`` -- ordinary torch parameters, not slots of the flat buffer -- and receive real
+        ``.grad`` tensors from ``mra_llm_proj_backward`` if they require one; ``z`` receives its gradient if it requires one (the output of
+        ``forward_train`` does).  ``MraError`` if the handle holds other tensors (or an older version of these) than the ones given.
+        ``grad_scale``: the upstream gradient arrives multiplied by it (a loss scale that keeps a 16-bit LM's gradients out of the
+        underflow range) and is divided by it in fp32 before the backward runs, so every gradient this node hands on is unscaled."""
+        pushed = getattr(self, "_pushed_proj", {})
+        for name, t in (("llm_proj.weight", weight), ("llm_proj.bias", bias)):
+            ref, ver = pushed.get(name, (None, None))
+            if ref is None or ref() is not t:
+                raise MraError(f"llm_proj_train: {name} is not the tensor last pushed to the handle (push it first)")
+            if ver != t._version:
+                raise MraError(f"llm_proj_train: {name} changed since it was pushed (version {ver} -> {t._version}): push it again")
+        return _LlmProjTrainFn.apply(z, weight, bias, self, out_dtype, float(grad_scale))
+
+    def _proj_backward(self, z: torch.Tensor, d_out: torch.Tensor, want_z: bool, want_w: bool, want_b: bool):
+        """One ``mra_llm_proj_backward`` over z [rows, H] fp32 and d_out [rows, llm_hidden] (fp32 or the operand dtype): (d_z or None,
+        d_weight or None, d_bias or None), fp32, the parameter gradients fresh zeroed buffers the entry added to."""
+        cfg = self.cfg
+        rows, dev = int(z.shape[0]), z.device
+        d_z = torch.empty(rows, cfg.hidden, dtype=torch.float32, device=dev) if want_z else None
+        d_w = torch.zeros(cfg.llm_hidden, cfg.hidden, dtype=torch.float32, device=dev) if want_w else None
+        d_b = torch.zeros(cfg.llm_hidden, dtype=torch.float32, device=dev) if want_b else None
+        with torch.cuda.device(self._device):
+            dt = _lib.mra_dtype(d_out.dtype)
+            nbytes = int(lib().mra_llm_proj_backward_workspace_bytes(self._handle, rows, dt))
+            ws = self._workspace(max(256, nbytes))
+            check(lib().mra_llm_proj_backward(self._handle, ptr(z), rows, ptr(d_out), dt, ptr(d_z), ptr(d_w), ptr(d_b), ptr(ws), ws.numel(),
+                                              current_stream()), "mra_llm_proj_backward")
+        return d_z, d_w, d_b
 
     def set_cross_mode(self, mode) -> None:
         """How the cross-attention layers run: ``"auto"`` (folded from Kv >= 2048), ``"kv_cache"``, ``"fold"``, or the
@@ -734,3 +769,34 @@ class _ModalityLNTrainFn(torch.autograd.Function):
         if hook is not None and (need_g or need_b):
             hook()
         return (d_x.to(x.dtype) if need_x else None), d_g, d_b, None
+
+
+class _LlmProjTrainFn(torch.autograd.Function):
+    """Autograd node around ``mra_llm_proj`` / ``mra_llm_proj_backward`` (``QFormer.llm_proj_train``).  The projection's parameters are
+    read from the handle (the caller pushed them); ``weight`` / ``bias`` are inputs so that autograd hands them their gradients."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, owner, out_dtype, grad_scale):
+        z2 = z.reshape(-1, owner.cfg.hidden).to(torch.float32).contiguous()
+        ctx.owner, ctx.z_shape, ctx.z_dtype, ctx.grad_scale = owner, z.shape, z.dtype, grad_scale
+        ctx.save_for_backward(z2)
+        return owner.llm_proj(z, out_dtype)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        owner = ctx.owner
+        (z2,) = ctx.saved_tensors
+        need_z, need_w, need_b = ctx.needs_input_grad[:3]
+        if not (need_z or need_w or need_b):
+            return None, None, None, None, None, None
+        d2 = d_out.reshape(-1, owner.cfg.llm_hidden)
+        if ctx.grad_scale != 1.0:
+            d2 = d2.to(torch.float32) / ctx.grad_scale
+        elif d2.dtype != owner.cfg.op_dtype:
+            d2 = d2.to(torch.float32)
+        d_z, d_w, d_b = owner._proj_backward(z2, d2.contiguous(), need_z, need_w, need_b)
+        # fused optimizers update the projection without bumping its version counter: the holder of the parameters pushes them again
+        hook = getattr(owner, "_proj_grad_hook", None)
+        if hook is not None and (need_w or need_b):
+            hook()
+        return (d_z.reshape(ctx.z_shape).to(ctx.z_dtype) if need_z else None), d_w, d_b, None, None, None

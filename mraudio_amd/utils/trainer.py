@@ -24,6 +24,11 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
   * ``train_ln`` (constructor keyword, or ``args.train_ln``; default off; ``finetune --train-ln``) trains the modality LayerNorms
     ``{m}_ln`` with the Q-Formers (``model.enable_qformer_training(train_ln=True)``): they are among "any other trainable parameter"
     above, and the trainable-only checkpoints then carry ``{m}_ln.*``.
+  * ``args.objective`` (``"score"`` default, ``"llm"``, ``"both"``; ``finetune --objective``), ``args.lm_weight`` and ``args.train_proj``
+    (``finetune --train-proj``): the reference's own loss, the LM's cross-entropy on the answer tokens, alone or added to the scorer
+    loss, carried through ``{m}_llm_proj`` into the Q-Formers (``XInstructBLIP.forward_llm``).  The model is handed over with its (frozen)
+    LM attached; the LM is neither optimized nor saved.  Validation stays on the scorer: ``"both"`` is the objective under which
+    ``MR-full-R1-avg`` says something about what was trained.
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -93,13 +98,22 @@ class Trainer:
         self.model = model
         if hasattr(model, "clip_parallel"):
             model.clip_parallel = False            # ranks see different samples
+        # objective "llm" / "both": the attached LM's cross-entropy on the answer tokens (alone, or added to the scorer loss with weight
+        # lm_weight) -- the model is handed over with its LM attached (Trainer(args, model=model)); validation stays on the scorer
+        self.objective = getattr(args, "objective", None) or "score"
+        if self.objective not in ("score", "llm", "both"):
+            raise ValueError(f"objective must be 'score', 'llm' or 'both', got {self.objective!r}")
+        self.train_proj = bool(getattr(args, "train_proj", False))
+        if self.objective != "score":
+            if getattr(model, "llm_model", None) is None:
+                raise RuntimeError(f"objective {self.objective!r} needs a model with an LM attached (attach_llm; finetune --llm-path)")
+            model.objective, model.lm_weight = self.objective, float(getattr(args, "lm_weight", 1.0))
         if getattr(args, "train_qformers", True) and hasattr(model, "enable_qformer_training"):
-            # train_ln (or args.train_ln): the modality LayerNorms train with the Q-Formers and reach the checkpoints
+            # train_ln (or args.train_ln): the modality LayerNorms train with the Q-Formers and reach the checkpoints; train_proj likewise
+            # the projections into the LM
             self.train_ln = bool(getattr(args, "train_ln", False) if train_ln is None else train_ln)
-            if self.train_ln:
-                model.enable_qformer_training(train_ln=True)
-            else:
-                model.enable_qformer_training()
+            kw = {**({"train_ln": True} if self.train_ln else {}), **({"train_proj": True} if self.train_proj else {})}
+            model.enable_qformer_training(**kw)
         if hasattr(model, "flat_optimizer_params") and getattr(args, "flat_params", True) and getattr(model, "train_qformers", False):
             params = model.flat_optimizer_params()      # one flat parameter per Q-Former: one fused update launch
         else:
