@@ -553,6 +553,36 @@ int mra_fbank_forward(mra_fbank* h, const float* wave, int64_t total_samples, co
 /* executed flops of one forward (2 per MAC: the dense 400 x 512 transform, the power spectrum, the sparse mel sums) */
 double mra_fbank_flops(mra_fbank* h, int32_t n_seg, int32_t frame_length);
 
+/* ---- audio front end: band-limited resampling to the model's rate (row A1, in front of mra_fbank_forward) ------------
+ * replaces: the resampling inside LAVIS BeatsAudioProcessor.__call__ (torchaudio's windowed-sinc `resample`: Hann window,
+ * lowpass_filter_width 6, rolloff 0.99), with the channel downmix.  The arithmetic is that of
+ * mraudio_amd/processors/audio_processors.py (resample_sinc, the definition; resample_table, the sparse per-phase form the kernel
+ * uses); those arguments are constants.  fp32 throughout.  With g = gcd(rate_in, rate_out), orig = rate_in / g, new = rate_out / g.
+ * mra_resample_create builds the per-phase tap table on the host in float64, rounds it to fp32 once and uploads it: the only
+ * allocation.  Arguments are checked before anything touches the GPU; MRA_EINVAL with a message naming the limit for a rate <= 0, a
+ * NULL out, and a rate pair beyond the kernel's limits: new <= 1024 phases, <= 256 taps per phase (2 * 6 * orig / (0.99 min(orig,
+ * new)) + 1), a table new * (taps | 1) <= 16384 coefficients, and ceil(1023 * orig / new) + taps + 1 <= 16384 staged input samples
+ * per workgroup.  Every pair of {8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000} -> 16000 is admitted;
+ * equal rates give the identity (the channel mean). */
+typedef struct mra_resample mra_resample;
+int mra_resample_create(int32_t rate_in, int32_t rate_out, mra_resample** out);
+void mra_resample_destroy(mra_resample* h);
+/* ceil(new * n_in / orig): the output length of a clip of n_in samples per channel.  No handle, no GPU; 0 for a rate <= 0 or n_in < 0. */
+int64_t mra_resample_out_samples(int32_t rate_in, int32_t rate_out, int64_t n_in);
+/* wave fp32 [total_in] (device): the clips of a step that share rate_in, concatenated; clips int64 [n_clip][6] (device), per clip
+ *   {first input sample, samples per channel n_in, channels C (planes consecutive: channel c at first + c * n_in; 1 .. 32),
+ *    first output sample, output samples n_out, first workgroup}
+ * with first workgroup = the sum of ceil(n_out / 1024) over the rows before (ascending); out fp32 [total_out] (device): output m of
+ * a clip, the filter over the channel MEAN of its samples with zeros outside [0, n_in), goes to first output sample + m.  A clip's
+ * output does not depend on its neighbours in the buffer.  One launch of total_out / 1024 + n_clip workgroups (the outputs of the
+ * clips are disjoint parts of out, so this covers every row); the host side does not read the table, allocates nothing and does
+ * not synchronise.  Inside the kernel every row is clipped: no read outside [0, total_in), no write outside [0, total_out).
+ * n_clip == 0 (or total_out == 0) is a no-op. */
+int mra_resample_forward(mra_resample* h, const float* wave, int64_t total_in, const int64_t* clips, int32_t n_clip, float* out,
+                         int64_t total_out, void* stream);
+/* executed flops of total_out output samples (2 per MAC over the non-zero taps, averaged over the phases) */
+double mra_resample_flops(mra_resample* h, int64_t total_out);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------
  * Number of GEMM launches of one main loop ("family") with one epilogue since the library was loaded; read-only, the only
  * process-wide state of the library.  `family` is a GemmFamily and `epilogue` a GemmEpi of csrc/kernels.h (the numbers mraudio_amd/_lib.py

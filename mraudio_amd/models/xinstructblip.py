@@ -17,6 +17,9 @@ encoders (row A1) are pluggable modules (``audio_encoder="beats"`` builds the HI
 as ``samples["video_embeds"] [B,T,Kv,1408]`` / ``samples["audio_embeds"] [B,T,Kv,768]``.  With ``audio_processor=`` a device
 ``BeatsAudioProcessor``, audio may also enter as raw 16 kHz waveforms, ``samples["audio_wave"]`` (a list of B tensors or ``[B, samples]``,
 ``samples["audio"]`` absent): the filterbank is computed on the GPU (``csrc/fbank.hip``) and T is the processor's ``n_frames``.
+``samples["audio_wave_rate"]`` (an int, or a list of B ints; the processor built with ``resample="sinc"``) gives the waveforms' own
+sample rates: each clip goes up as decoded, ``[samples]`` or ``[channels, samples]``, and is band-limited to 16 kHz mono on the GPU
+(``csrc/resample.hip``) in front of the filterbank.  Without the key nothing changes.
 
 All arithmetic between the encoder output and the span runs in ``libmra_hip.so``: modality
 LayerNorm + reorder (``:265,281-285``), Q-Former (``:286-293``), slice + llm_proj (``:303-306``),
@@ -397,7 +400,8 @@ class XInstructBLIP(nn.Module):
             waves = samples["audio_wave"]
             waves = list(waves.unbind(0)) if isinstance(waves, torch.Tensor) else list(waves)
             bs, num = len(waves), int(proc.n_frames)
-            frames = proc.flat(waves, lo, hi, out_dtype=torch.float16)
+            rates = samples.get("audio_wave_rate")      # the waveforms' own sample rates: resampled on the device (csrc/resample.hip)
+            frames = proc.flat(waves, lo, hi, out_dtype=torch.float16, **({} if rates is None else {"rates": rates}))
             outs = []
             with torch.no_grad():
                 for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
