@@ -583,6 +583,46 @@ int mra_resample_forward(mra_resample* h, const float* wave, int64_t total_in, c
 /* executed flops of total_out output samples (2 per MAC over the non-zero taps, averaged over the phases) */
 double mra_resample_flops(mra_resample* h, int64_t total_out);
 
+/* ---- video front end: decoded uint8 frames -> the encoder's normalised pixels (row A1, in front of mra_vit_forward) ------------
+ * replaces: LAVIS AlproVideoTrainProcessor.transform / AlproVideoEvalProcessor.transform on the host (random resized crop of the whole
+ * clip, bicubic; horizontal flip; ToUint8; / 255; Normalize) and the host permutes to [B*T, 3, H, W].  The arithmetic is that of
+ * mraudio_amd/processors/alpro_processors.py (crop_resize_table and preprocess_frames_ref, the float64 definition, pinned there to
+ * torch's bicubic interpolate with align_corners = False): separable 4-tap tables with cubic coefficient A = -0.75, source coordinate
+ * (crop / out)(o + 0.5) - 0.5, taps clamped to the CROP.  fp32 throughout; no handle, no allocation.
+ *
+ * mra_video_crop_table: host only, no GPU.  One axis of a crop box: idx int16 [n_out][4] (absolute in the source frame, inside
+ * [offset, offset + n_src_crop)) and w fp32 [n_out][4], built in float64 and rounded to fp32 once.  MRA_EINVAL with a message for a
+ * NULL pointer, a non-positive size, a negative offset, or a crop that ends beyond index 32767 (int16). */
+int mra_video_crop_table(int32_t n_src_crop, int32_t offset, int32_t n_out, int16_t* idx, float* w);
+#define MRA_VIDEO_QUANT_NONE 0   /* the resized value goes to the normalisation as it is */
+#define MRA_VIDEO_QUANT_FLOOR 1  /* the reference's ToUint8 first: floor(min(max(v, 0), 255)) (the clamp is this build's: the bare cast is undefined there) */
+/* src uint8 (device), src_bytes: the step's decoded frames, interleaved RGB, [H][W][3] each, concatenated at any byte offsets;
+ * frames int64 [n_out][5] (device), per OUTPUT frame
+ *   {byte offset of its source frame in src, source height H, source width W, table row, flip (0 / non-zero)};
+ * tap_idx int16 / tap_w fp32 [n_tab][2][size][4] (device): per table row the y table then the x table of mra_video_crop_table for one
+ * crop box (a clip: its frames share the row; source frames may repeat, as the last-frame padding does; clips of different H x W go in
+ * one call); mean[3] / std[3]: HOST arrays; out [n_out][3][size][size], MRA_F32 or MRA_F16 (device), sample-major, what
+ * mra_vit_forward reads:
+ *   out = ((q(h) / 255) - mean_c) / std_c,  h = the horizontal 4-tap sum over the vertical 4-tap sums, x reversed when flip is set,
+ * q = identity or the MRA_VIDEO_QUANT_FLOOR step; two divisions, as the host processor.  With the whole frame as the box and
+ * size == H == W the weights are exactly 0 / 1 and the result is the host processor's normalisation of the bytes.
+ * One launch of n_out * size / 8 workgroups; the host side does not read the descriptors, allocates nothing and does not synchronise.
+ * Inside the kernel every descriptor is clipped: no read outside [0, src_bytes) (such a byte counts as 0), no write outside out.
+ * Checked before any launch, MRA_EINVAL with a message: a negative count, an out_dtype or quantize value not listed, size not a
+ * positive multiple of 8 or above 768 (what one workgroup's LDS holds: 8 output rows x 3 channels x size columns of fp32, the 12
+ * source rows under them and the x table), NULL mean / std, std <= 0, non-finite mean / std; and, with n_out > 0, a NULL pointer, n_tab < 1, frames /
+ * tap_idx not 8-byte or tap_w / out not 16-byte aligned.  n_out == 0 is a no-op. */
+int mra_video_frames_forward(const void* src, int64_t src_bytes, const int64_t* frames, int32_t n_out, const int16_t* tap_idx,
+                             const float* tap_w, int32_t n_tab, int32_t size, const float* mean, const float* std, int32_t quantize,
+                             void* out, int32_t out_dtype, void* stream);
+/* algorithmic bytes of such a call with every source frame read once: n_out * (3 src_h src_w + 3 size^2 sizeof(out element)) */
+double mra_video_frames_bytes(int64_t n_out, int32_t src_h, int32_t src_w, int32_t size, int32_t out_dtype);
+/* mra_video_frames_forward with the kernel's form chosen: 0 = as the product entry (source rows and vertical sums staged in LDS where the
+ * crop does not downscale, otherwise the gather), 1 = every workgroup gathers its 16 taps per output from global memory.  Same bits. */
+int mra_debug_video_frames_forward(const void* src, int64_t src_bytes, const int64_t* frames, int32_t n_out, const int16_t* tap_idx,
+                                   const float* tap_w, int32_t n_tab, int32_t size, const float* mean, const float* std, int32_t quantize,
+                                   void* out, int32_t out_dtype, int32_t form, void* stream);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------
  * Number of GEMM launches of one main loop ("family") with one epilogue since the library was loaded; read-only, the only
  * process-wide state of the library.  `family` is a GemmFamily and `epilogue` a GemmEpi of csrc/kernels.h (the numbers mraudio_amd/_lib.py

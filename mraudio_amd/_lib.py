@@ -167,6 +167,13 @@ PROTOTYPES = {
     "mra_resample_out_samples": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "mra_resample_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "mra_resample_flops": (C.c_double, [C.c_void_p, C.c_int64]),
+    "mra_video_crop_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mra_video_frames_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mra_video_frames_bytes": (C.c_double, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mra_debug_video_frames_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_void_p]),
     "mra_debug_gemm_launches": (C.c_int64, [C.c_int32, C.c_int32]),
     "mra_debug_vit_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mra_debug_shared_kv_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

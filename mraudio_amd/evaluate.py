@@ -126,6 +126,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--group-by-video", action="store_true",
                     help="encode every video once and score its queries together over one shared K/V cache (same records, annotation order)")
     ap.add_argument("--max-queries-per-call", type=int, default=16, help="with --group-by-video: most queries of one video scored in one call")
+    ap.add_argument("--video-on-device", action="store_true",
+                    help="decoded video goes to the GPU as uint8 frames and is normalised there (mra_video_frames_forward) instead of as float32 "
+                         "pixels made on the host")
     return ap
 
 
@@ -137,13 +140,18 @@ def main(argv=None) -> None:
 
     args = build_parser().parse_args(argv)
     n_frms = 60 if args.dataset == "QVH" else 20
+    vproc = None
+    if args.video_on_device:
+        from .processors.alpro_processors import AlproVideoEvalProcessor_Stamps
+        vproc = AlproVideoEvalProcessor_Stamps(n_frms=n_frms, image_size=224, device=args.device)
     model = XInstructBLIP(args.model_path, args.audio_encoder, device=args.device, checkpoint=args.checkpoint, checkpoint_strict=not args.partial_checkpoint,
-                          cross_precision=args.cross_precision, top_k=args.top_k, nms_thd=args.nms_thd, max_window=args.max_window)
+                          cross_precision=args.cross_precision, top_k=args.top_k, nms_thd=args.nms_thd, max_window=args.max_window,
+                          **({} if vproc is None else {"video_processor": vproc}))
     print(f"weights: {model.weights_source}")
     if args.synthetic:
         ds = SyntheticMRDataset(args.synthetic, T=n_frms)
     else:
-        ds = MRDataset(args.video_folder, args.annotation_file, None, None, model=args.model, embeds_root=args.embeds_folder)
+        ds = MRDataset(args.video_folder, args.annotation_file, vproc, None, model=args.model, embeds_root=args.embeds_folder)
     if args.group_by_video:
         dl = DataLoader(VideoGroupedDataset(ds, args.max_queries_per_call), shuffle=False, batch_size=args.batch_size, num_workers=args.num_workers,
                         collate_fn=collate_grouped)

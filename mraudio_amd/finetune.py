@@ -96,6 +96,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "the checkpoints then carry {m}_llm_proj.*")
     ap.add_argument("--llm-path", default=None, help="local directory of the causal LM (loaded with local_files_only, frozen, bf16); "
                                                      "required by --objective llm / both")
+    ap.add_argument("--video-on-device", dest="video_device", action="store_true",
+                    help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
+                         "(mra_video_frames_forward) instead of as float32 pixels made on the host")
+    ap.add_argument("--video-augment", action="store_true",
+                    help="train on the reference's video augmentation: one random resized crop (bicubic, area share 0.9 .. 1.0) and one random "
+                         "horizontal flip per clip, then the cast to uint8 (on the host, or on the GPU with --video-on-device)")
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--warmup-steps", type=int, default=1000)
     ap.add_argument("--cross-precision", default="op", choices=["op", "split", "auto"],

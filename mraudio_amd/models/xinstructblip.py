@@ -19,7 +19,10 @@ as ``samples["video_embeds"] [B,T,Kv,1408]`` / ``samples["audio_embeds"] [B,T,Kv
 ``samples["audio"]`` absent): the filterbank is computed on the GPU (``csrc/fbank.hip``) and T is the processor's ``n_frames``.
 ``samples["audio_wave_rate"]`` (an int, or a list of B ints; the processor built with ``resample="sinc"``) gives the waveforms' own
 sample rates: each clip goes up as decoded, ``[samples]`` or ``[channels, samples]``, and is band-limited to 16 kHz mono on the GPU
-(``csrc/resample.hip``) in front of the filterbank.  Without the key nothing changes.
+(``csrc/resample.hip``) in front of the filterbank.  Without the key nothing changes.  Likewise with ``video_processor=`` a device Alpro
+video processor: ``samples["video_raw"]`` (decoded uint8 frames ``[B, T, H, W, 3]`` or a list of B clips, ``samples["video"]`` absent) with
+the optional clip-wide ``samples["video_box"]`` / ``samples["video_flip"]`` is cropped, resized, flipped and normalised on the GPU
+(``csrc/video_pre.hip``) into the f16 pixels the video encoder reads; T is the processor's ``n_frms``.
 
 All arithmetic between the encoder output and the span runs in ``libmra_hip.so``: modality
 LayerNorm + reorder (``:265,281-285``), Q-Former (``:286-293``), slice + llm_proj (``:303-306``),
@@ -142,7 +145,8 @@ class XInstructBLIP(nn.Module):
                  compat_repeat: bool = True, score_alpha: float = 0.5, fuse_weights: Optional[Sequence[float]] = None,
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
-                 cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0):
+                 cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0,
+                 video_processor=None):
         super().__init__()
         self.model_path, self.audio_path = model_path, audio_path
         self.modalities = list(modalities) if modalities is not None else ["audio", "video"]  # reference :71
@@ -179,6 +183,9 @@ class XInstructBLIP(nn.Module):
         # a device BeatsAudioProcessor (processors/audio_processors.py): samples["audio_wave"] becomes the step's filterbank on the GPU
         # (mra_fbank_forward) and goes to audio_encoder without leaving it; its n_frames is T
         self.audio_processor = audio_processor
+        # a device Alpro video processor (processors/alpro_processors.py): samples["video_raw"], the decoded uint8 frames, become the
+        # encoder's normalised f16 pixels on the GPU (mra_video_frames_forward: crop, resize, flip, normalise); its n_frms is T
+        self.video_processor = video_processor
         self.llm_hidden_size = llm_hidden_size   # Vicuna-7B: 4096 (reference :167)
         self.llm_model = None                    # stock causal LM, attached by attach_llm (row N2)
         self.llm_tokenizer = None
@@ -328,7 +335,7 @@ class XInstructBLIP(nn.Module):
 
     def _present(self, samples, m: str) -> bool:
         """Whether ``samples`` carries modality ``m``: its encoder input, pre-computed encoder outputs, or (audio) raw waveforms."""
-        return m in samples or f"{m}_embeds" in samples or (m == "audio" and "audio_wave" in samples)
+        return m in samples or f"{m}_embeds" in samples or (m == "audio" and "audio_wave" in samples) or (m == "video" and "video_raw" in samples)
 
     def _clip_world(self):
         return parallel.world(self.process_group) if self.clip_parallel else (0, 1)
@@ -402,6 +409,20 @@ class XInstructBLIP(nn.Module):
             bs, num = len(waves), int(proc.n_frames)
             rates = samples.get("audio_wave_rate")      # the waveforms' own sample rates: resampled on the device (csrc/resample.hip)
             frames = proc.flat(waves, lo, hi, out_dtype=torch.float16, **({} if rates is None else {"rates": rates}))
+            outs = []
+            with torch.no_grad():
+                for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
+                    outs.append(encoder(frames[c0: c0 + self.encode_chunk]))
+            return (outs[0] if len(outs) == 1 else torch.cat(outs)), None, bs, num
+        if modality == "video" and modality not in samples and "video_raw" in samples:
+            # decoded uint8 frames ([B, T, H, W, 3] or a list of B clips): this rank's frames only go up, as bytes, and one launch
+            # crops, resizes, flips and normalises them into the f16 pixels the encoder reads
+            proc = self.video_processor
+            if proc is None or getattr(proc, "device", None) is None:
+                raise MraError("samples['video_raw'] needs XInstructBLIP(video_processor=<an Alpro video processor built with device=<cuda device>>)")
+            clips = samples["video_raw"]
+            bs, num = len(clips), int(proc.n_frms)
+            frames = proc.flat(clips, samples.get("video_box"), samples.get("video_flip"), lo, hi, out_dtype=torch.float16)
             outs = []
             with torch.no_grad():
                 for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
@@ -582,7 +603,9 @@ class XInstructBLIP(nn.Module):
             if not self._present(samples, m):
                 continue
             src = samples.get(f"{m}_embeds", samples.get(m))
-            if src is None:      # audio as raw waveforms: B clips x the processor's temporal positions
+            if src is None and m == "video":   # video as decoded bytes: B clips x the processor's frames
+                n_items = len(samples["video_raw"]) * int(getattr(self.video_processor, "n_frms", 0))
+            elif src is None:    # audio as raw waveforms: B clips x the processor's temporal positions
                 n_items = len(samples["audio_wave"]) * int(getattr(self.audio_processor, "n_frames", 0))
             else:
                 n_items = int(src.shape[0]) * int(src.shape[2] if (m == "video" and f"{m}_embeds" not in samples) else src.shape[1])

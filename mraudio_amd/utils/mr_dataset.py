@@ -1,7 +1,8 @@
 """Moment-retrieval dataset with the reference's record layout (``utils/mr_dataset.py:7-119``).
 
 A record is what ``XInstructBLIP.generate`` / ``forward`` read: ``text_input`` (the two-line prompt of
-``:96-98``), ``text_output`` (``str(relevant_windows)``), ``video`` [C, T, H, W], ``audio`` [T, F, 128],
+``:96-98``), ``text_output`` (``str(relevant_windows)``), ``video`` [C, T, H, W] (with a device video processor instead ``video_raw`` uint8 [T, H, W, 3], ``video_box`` int64 [4] and
+``video_flip``: the decoded bytes and the clip's crop box and flip), ``audio`` [T, F, 128],
 ``timestamps`` (``round(index / fps)`` per sampled frame, ``:44``), ``duration``, ``qid``, ``query``, ``vid``.
 
 Decoding is not part of the hot path and neither ffmpeg nor decord exists in this image, so the decoders
@@ -60,8 +61,18 @@ class MRDataset(Dataset):
         path = os.path.join(self.vis_root, ann["vid"] + ".mp4")
         if self.audio_processor is not None:
             rec["audio"] = self._call(self.audio_processor, path, ann)
-        video, indices, fps = self._call(self.video_processor, path, ann)
-        rec["video"] = video
+        if getattr(self.video_processor, "device", None) is not None and hasattr(self.video_processor, "raw"):
+            # a device processor: the record carries the decoded bytes and the clip's augmentation, the pixels are made on the GPU
+            # inside the model (XInstructBLIP(video_processor=...)); no "video" key
+            fn = self.video_processor.raw
+            if "start" in ann and "clip" in inspect.signature(fn).parameters:
+                frames, box, flip, indices, fps = fn(path, clip=(float(ann["start"]), float(ann["end"])))
+            else:
+                frames, box, flip, indices, fps = fn(path)
+            rec["video_raw"], rec["video_box"], rec["video_flip"] = frames, box, torch.tensor(int(flip), dtype=torch.int64)
+        else:
+            video, indices, fps = self._call(self.video_processor, path, ann)
+            rec["video"] = video
         rec["timestamps"] = [round(idx / fps) for idx in indices]
         return rec
 

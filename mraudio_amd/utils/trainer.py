@@ -133,8 +133,14 @@ class Trainer:
             else:
                 from ..processors.alpro_processors import AlproVideoEvalProcessor_Stamps, AlproVideoTrainProcessor_Stamps
                 emb = getattr(args, "embeds_folder", None)
-                tp = None if emb else AlproVideoTrainProcessor_Stamps(n_frms=n_frms, image_size=224)
-                vp = None if emb else AlproVideoEvalProcessor_Stamps(n_frms=n_frms, image_size=224)
+                # video_device (finetune --video-on-device): the processors hand over decoded bytes and csrc/video_pre.hip makes the
+                # encoder's pixels on that device; video_augment (--video-augment): the reference's random resized crop and flip per clip
+                vdev = self.device if getattr(args, "video_device", False) is True else (getattr(args, "video_device", None) or None)
+                vkw = {} if vdev is None else {"device": vdev}
+                tp = None if emb else AlproVideoTrainProcessor_Stamps(n_frms=n_frms, image_size=224, augment=bool(getattr(args, "video_augment", False)), **vkw)
+                vp = None if emb else AlproVideoEvalProcessor_Stamps(n_frms=n_frms, image_size=224, **vkw)
+                if vdev is not None and not emb:
+                    self._video_processors = (tp, vp)
                 from ..processors.audio_processors import BeatsAudioProcessor
                 ap_ = None if emb else BeatsAudioProcessor(model_name="iter3", sampling_rate=16000, n_frames=n_frms, is_eval=False, frame_length=512)
                 train_dataset = MRDataset(args.video_folder, args.train_annotation_file, tp, ap_, model="X-InstructBLIP", embeds_root=emb)
@@ -206,6 +212,8 @@ class Trainer:
 
     def train_epoch(self, cur_epoch: int) -> Dict[str, str]:
         self.model.train()
+        if getattr(self, "_video_processors", None):
+            self.model.video_processor = self._video_processors[0]
         self.train_sampler.set_epoch(cur_epoch)
         log.info("Start training epoch %d, %d iters per inner epoch.", cur_epoch, len(self.train_dataloader))
         loss_sum, n_it = 0.0, 0
@@ -232,6 +240,8 @@ class Trainer:
     @torch.no_grad()
     def eval_epoch(self):
         self.model.eval()
+        if getattr(self, "_video_processors", None):
+            self.model.video_processor = self._video_processors[1]
         results = []
         for samples in self.val_dataloader:
             samples = prepare_sample(samples, self.device if self.device.type == "cuda" else None)
