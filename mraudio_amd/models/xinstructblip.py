@@ -30,6 +30,7 @@ scorer.  No CPU fallback exists.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import re
 import zlib
@@ -132,6 +133,83 @@ class _ScaleGrad(torch.autograd.Function):
 ENC_WIDTH = {"video": 1408, "audio": 768}  # EVA ViT-g / BEATs num_features (reference :123)
 
 
+# ---- host steps that read no model state: every path through XInstructBLIP shares them ------------------------
+def _encode_chunked(encoder, frames: torch.Tensor, chunk: int) -> torch.Tensor:
+    """``encoder`` over ``frames`` [n, ...] in pieces of ``chunk`` frames under ``no_grad``: the concatenation of its outputs."""
+    outs = []
+    with torch.no_grad():
+        for c0 in range(0, int(frames.shape[0]), max(1, int(chunk))):
+            outs.append(encoder(frames[c0: c0 + chunk]))
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+def _timestamps(samples, bs: int, num: int) -> List[list]:
+    """Per video the timestamps of its ``num`` positions as a list: ``samples["timestamps"]`` (tensors converted), else ``range(num)``."""
+    ts = samples.get("timestamps")
+    if ts is None or len(ts) == 0:      # (the training targets have always taken an empty list as absent)
+        ts = [list(range(num))] * bs
+    return [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
+
+
+def _membership_targets(parse, windows: Sequence[str], stamps: Sequence[float], rows: torch.Tensor) -> torch.Tensor:
+    """Clip-membership targets, written into the zeroed ``rows`` [len(windows), len(stamps)] and returned: row ``p`` becomes 1 where a timestamp
+    lies inside ANY of the windows that ``parse`` (``XInstructBLIP.parse_windows``) reads from ``windows[p]`` (union over windows, float
+    seconds honoured)."""
+    t = torch.as_tensor(stamps, dtype=torch.float32, device=rows.device)
+    for p, txt in enumerate(windows):
+        for s0, e0 in parse(txt):
+            rows[p] = torch.maximum(rows[p], ((t >= s0) & (t <= e0)).float())
+    return rows
+
+
+def _prompt_rows(ids: torch.Tensor, tmask: torch.Tensor, n_query: int, num: Optional[int] = None, prompts: int = 1, tile: bool = False):
+    """The Q-Former chain's ``(input_ids, attention_mask)`` from tokenised prompts ``ids`` / ``tmask`` [B * prompts, L] (row ``b * prompts + p``):
+    one row per (video, position, prompt), the mask with the ``n_query`` query-token ones in front.  ``tile`` is the reference's
+    ``ids.repeat(num, 1)`` (``:287-288``): row k carries prompt ``k % B``.  Otherwise row ``(b * num + t) * prompts + p`` carries prompt ``p`` of
+    video ``b`` -- with one prompt per video, row k carries the prompt of its own sample ``k // num``.  ``num=None``: the rows as given."""
+    if num is not None:
+        ids, tmask = _expand_rows(ids, num, prompts, tile), _expand_rows(tmask, num, prompts, tile)
+    ones = torch.ones(tmask.shape[0], n_query, dtype=torch.long, device=tmask.device)
+    return ids, torch.cat([ones, tmask], dim=1)
+
+
+def _expand_rows(x: torch.Tensor, num: int, prompts: int = 1, tile: bool = False) -> torch.Tensor:
+    """One of ``ids`` / ``tmask`` in ``_prompt_rows``' row order, ``[B * num * prompts, L]``."""
+    if tile:
+        return x.repeat(num, 1)
+    bs, L = int(x.shape[0]) // prompts, int(x.shape[1])
+    return x.view(bs, 1, prompts, L).expand(bs, num, prompts, L).reshape(bs * num * prompts, L)
+
+
+def _train_logit(z: torch.Tensor, cls: torch.Tensor) -> torch.Tensor:
+    """The scorer logit of the training paths as torch ops: per row ``max_q cos(z[q], cls)``."""
+    return nn.functional.cosine_similarity(z, cls[:, None, :], dim=-1, eps=1e-8).max(dim=1).values
+
+
+def _weighted_fuse(per_mod: Sequence[torch.Tensor], weights: Optional[Sequence[float]]) -> torch.Tensor:
+    """The weighted sum of the per-modality training logits (default: their mean)."""
+    w = weights or [1.0 / len(per_mod)] * len(per_mod)
+    return sum(x * wt for x, wt in zip(per_mod, w))
+
+
+def _store_scores(out: Dict[str, object], m: str, z: torch.Tensor, cls: torch.Tensor):
+    """``cosine_scores`` of one modality's rows into ``out["z" / "cls" / "sim" / "logit"][m]``; returns ``(sim, logit)``."""
+    sim, logit = scorer.cosine_scores(z, cls)
+    out["z"][m], out["cls"][m], out["sim"][m], out["logit"][m] = z, cls, sim, logit
+    return sim, logit
+
+
+def _span_texts(spans: torch.Tensor, ts: Sequence[list]) -> List[str]:
+    """One ``"[[start, end]]"`` string (seconds) per row of ``spans`` [n, 2]; ``ts[i]`` the timestamps row ``i`` indexes."""
+    return [o.strip() for o in scorer.spans_to_text(spans.cpu().tolist(), ts)]
+
+
+def _window_texts(win: torch.Tensor, sc: torch.Tensor, cnt: torch.Tensor, ts: Sequence[list]):
+    """``(texts, records)`` of ranked windows ``win`` [n, k, 2] / ``sc`` [n, k] / ``cnt`` [n]; ``ts[i]`` the timestamps row ``i`` indexes."""
+    win, sc, cnt = win.cpu(), sc.cpu(), cnt.cpu()
+    return scorer.windows_to_text(win, cnt, ts), scorer.windows_to_records(win, sc, cnt, ts)
+
+
 class XInstructBLIP(nn.Module):
     # what forward() trains on: "score" (the build-defined scorer loss), "llm" (the attached LM's cross-entropy on the answer tokens,
     # reference :399-606) or "both" (bce + lm_weight * lm over ONE Q-Former forward per modality).  loss_scale: the LM term's
@@ -155,7 +233,7 @@ class XInstructBLIP(nn.Module):
         self.num_query_token = 32        # reference :120
         self.compat_repeat = compat_repeat
         self.score_alpha = score_alpha
-        # ranked proposals (scorer.windows_from_logits): with top_k > 1 fuse_score also returns the top_k windows under temporal NMS
+        # ranked proposals (the scorer's windows kernel, _score_tail): with top_k > 1 fuse_score also returns the top_k windows under temporal NMS
         # (threshold nms_thd, window length capped at max_window clips, 0 = none); 1 = the single span only, no extra launch
         self.top_k, self.nms_thd, self.max_window = int(top_k), float(nms_thd), int(max_window)
         self.fuse_weights = fuse_weights
@@ -362,6 +440,75 @@ class XInstructBLIP(nn.Module):
             self._streams[key] = torch.cuda.Stream(device=self._device, priority=-1 if high_priority else 0)
         return self._streams[key]
 
+    @contextlib.contextmanager
+    def _modality_streams(self, fork: bool):
+        """The fork / join of the per-modality side streams.  Yields ``lane``; ``with lane(m, high_priority, after) as hand:`` runs its body
+        on modality ``m``'s side stream, which first waits for the caller's stream and, if given, for the event ``after``.  The tensors
+        the body passes to ``hand(...)`` (``None`` entries skipped) are consumed on the caller's stream and recorded on it.  Leaving the
+        outer block joins exactly the streams that were forked.  Without ``fork`` the bodies run where they are and nothing under
+        ``torch.cuda`` is touched."""
+        cur = torch.cuda.current_stream(self._device) if fork else None
+        forked = []
+
+        @contextlib.contextmanager
+        def lane(m: str, high_priority: bool = False, after: Optional[torch.cuda.Event] = None):
+            handed = []
+            if not fork:
+                yield handed.extend
+                return
+            side = self._side_stream(m, high_priority)
+            forked.append(side)
+            side.wait_stream(cur)
+            if after is not None:
+                side.wait_event(after)
+            with torch.cuda.stream(side):
+                yield handed.extend
+            for t in handed:
+                if t is not None:
+                    t.record_stream(cur)
+
+        yield lane
+        for side in forked:
+            cur.wait_stream(side)
+
+    def _tokenize(self, prompts):
+        """``(input_ids, attention_mask)`` of ``prompts`` on the device, one row per prompt, padded to the longest."""
+        text = self.tokenizer(prompts, padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
+        return text.input_ids.to(self._device), text.attention_mask.to(self._device)
+
+    def _qformer_input(self, qf: QFormer, x: torch.Tensor, idx: Optional[torch.Tensor], items: int):
+        """What ``qf`` reads at inference, as ``(enc, raw)``: the folded cross-attention reads the encoder output itself where the library
+        folds the LayerNorm into it (no normalised copy, ``raw`` True), else the ``modality_ln`` output."""
+        x = x.to(self._device)
+        raw = x.dim() == 3 and x.shape[0] == items and qf.raw_features_ok(x, item_index=idx)
+        return (x if raw else qf.modality_ln(x, item_index=idx, items=items)), raw
+
+    def _train_norm(self, m: str, raw: torch.Tensor, idx: Optional[torch.Tensor], items: int) -> torch.Tensor:
+        """What ``{m}_Qformer`` reads in training: under ``train_ln`` the LayerNorm is a node of the graph, else it runs under ``no_grad``."""
+        if getattr(self, "train_ln", False):
+            return self._ln_train(m, raw)
+        with torch.no_grad():
+            return getattr(self, f"{m}_Qformer").modality_ln(raw, item_index=idx, items=items)
+
+    def _pack_llm(self, out: Dict[str, object], m: str, z: torch.Tensor, bs: int, num: int):
+        """Reference ``:303-306``: ``{m}_llm_proj`` of the query embeddings into ``out["inputs_llm"][m]`` [B, T * 32, D] with its
+        ``out["atts_llm"][m]``; returns the two tensors."""
+        y = getattr(self, f"{m}_Qformer").llm_proj(z)
+        y = y.reshape(bs, num, self.num_query_token, -1).view(bs, num * self.num_query_token, -1)
+        atts = torch.ones(bs, num * self.num_query_token, dtype=torch.long, device=self._device)
+        out.setdefault("inputs_llm", {})[m], out.setdefault("atts_llm", {})[m] = y, atts
+        return y, atts
+
+    def _score_tail(self, logits: Sequence[torch.Tensor], videos: int, num: int) -> Dict[str, object]:
+        """From per-modality logits over ``videos x num`` positions to ``fused``, ``spans`` and, with ``top_k > 1``, ``windows`` /
+        ``window_scores`` / ``window_counts``."""
+        out: Dict[str, object] = {"fused": scorer.fuse_logits(list(logits), self.fuse_weights)}
+        out["spans"] = scorer.spans_from_logits(out["fused"], videos, num, self.score_alpha)
+        if self.top_k > 1:
+            out["windows"], out["window_scores"], out["window_counts"] = scorer.windows_from_logits(
+                out["fused"], videos, num, self.score_alpha, self.top_k, self.nms_thd, self.max_window)
+        return out
+
     def _sync(self):
         ver = sum(getattr(self, f"{m}_{n}")._version if n == "query_tokens" else sum(p._version for p in getattr(self, f"{m}_{n}").parameters())
                   for m in self.modalities for n in ("query_tokens", "ln", "llm_proj"))
@@ -409,11 +556,7 @@ class XInstructBLIP(nn.Module):
             bs, num = len(waves), int(proc.n_frames)
             rates = samples.get("audio_wave_rate")      # the waveforms' own sample rates: resampled on the device (csrc/resample.hip)
             frames = proc.flat(waves, lo, hi, out_dtype=torch.float16, **({} if rates is None else {"rates": rates}))
-            outs = []
-            with torch.no_grad():
-                for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
-                    outs.append(encoder(frames[c0: c0 + self.encode_chunk]))
-            return (outs[0] if len(outs) == 1 else torch.cat(outs)), None, bs, num
+            return _encode_chunked(encoder, frames, self.encode_chunk), None, bs, num
         if modality == "video" and modality not in samples and "video_raw" in samples:
             # decoded uint8 frames ([B, T, H, W, 3] or a list of B clips): this rank's frames only go up, as bytes, and one launch
             # crops, resizes, flips and normalises them into the f16 pixels the encoder reads
@@ -423,11 +566,7 @@ class XInstructBLIP(nn.Module):
             clips = samples["video_raw"]
             bs, num = len(clips), int(proc.n_frms)
             frames = proc.flat(clips, samples.get("video_box"), samples.get("video_flip"), lo, hi, out_dtype=torch.float16)
-            outs = []
-            with torch.no_grad():
-                for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
-                    outs.append(encoder(frames[c0: c0 + self.encode_chunk]))
-            return (outs[0] if len(outs) == 1 else torch.cat(outs)), None, bs, num
+            return _encode_chunked(encoder, frames, self.encode_chunk), None, bs, num
         data = samples[modality]
         if modality == "video":      # [B, 3, T, H, W] -> sample-major frames [B*T, 3, H, W]
             bs, num = int(data.shape[0]), int(data.shape[2])
@@ -437,12 +576,7 @@ class XInstructBLIP(nn.Module):
             frames = data.reshape(bs * num, data.shape[2], data.shape[3])
         if lo is not None:
             frames = frames[lo:hi]
-        outs = []
-        with torch.no_grad():
-            for c0 in range(0, int(frames.shape[0]), max(1, int(self.encode_chunk))):
-                outs.append(encoder(frames[c0: c0 + self.encode_chunk].to(self._device)))
-        raw = outs[0] if len(outs) == 1 else torch.cat(outs)
-        return raw, None, bs, num
+        return _encode_chunked(lambda chunk: encoder(chunk.to(self._device)), frames, self.encode_chunk), None, bs, num
 
     @torch.no_grad()
     def fuse_score(self, embeds: Dict[str, torch.Tensor], input_ids: torch.Tensor, text_mask: torch.Tensor, bs: int, num: int,
@@ -460,12 +594,9 @@ class XInstructBLIP(nn.Module):
         lo, hi = parallel.shard_range(n, rank, ws)
         n_local = hi - lo
         out: Dict[str, object] = {"z": {}, "cls": {}, "sim": {}, "logit": {}, "full": {}}
-        ids = input_ids.to(self._device)
-        tmask = text_mask.to(self._device)
-        att = torch.cat([torch.ones(n_local, self.num_query_token, dtype=torch.long, device=self._device), tmask], dim=1)
+        ids, att = _prompt_rows(input_ids.to(self._device), text_mask.to(self._device), self.num_query_token)
         # The modality Q-Formers are independent until the fusion: each runs on its own HIP stream so
         # the short launches of one chain fill the gaps of the other (and of its K/V projection).
-        cur = torch.cuda.current_stream(self._device)
         live = [m for m in self.modalities if m in embeds]
         use_streams = self.overlap_modalities and len(live) > 1
         heavy_done = None
@@ -475,12 +606,10 @@ class XInstructBLIP(nn.Module):
             # The modality with the largest K/V projection goes first and the others start when that GEMM has
             # finished: a chip-filling GEMM gains nothing from sharing CUs with a latency-bound layer chain (it
             # ran 20 % longer beside one), whereas two layer chains overlap each other almost for free.
-            live.sort(key=lambda m: int(embeds[m].shape[-2]) * int(embeds[m].shape[-1]), reverse=True)
             heavy = live[0]
             kv_flops = 2.0 * n_local * embeds[heavy].shape[-2] * embeds[heavy].shape[-1] * 9216
             if kv_flops >= 1e12:                  # ~1 ms of GEMM; below that the wait costs more than the contention
                 heavy_done = self._kv_done_event(heavy)
-        used_streams = []
         sharded = ws > 1
         local: Dict[str, tuple] = {}
         if self.pair_forward and len(live) == 2 and not want_full and not want_llm and self._pair_ok(live):
@@ -491,80 +620,50 @@ class XInstructBLIP(nn.Module):
             # 2.55 ms (r03p, same session).  Opt-in.  The heavier lane first (its cross-layer-0 block carries the roofline events).
             qfs = [getattr(self, f"{m}_Qformer") for m in live]
             # (each lane as its own forward would run it: raw features where the library folds the LayerNorm into the cross-attention)
-            xs = [embeds[m].to(self._device) for m in live]
-            idxs = [None if index is None else index.get(m) for m in live]
-            raws = [x.dim() == 3 and x.shape[0] == n_local and qf.raw_features_ok(x, item_index=i) for qf, x, i in zip(qfs, xs, idxs)]
-            encs = [x if r else qf.modality_ln(x, item_index=i, items=n_local) for qf, x, i, r in zip(qfs, xs, idxs, raws)]
-            res = QFormer.forward_pair(qfs[0], qfs[1], ids, att, encs[0], encs[1], want_cls=True, kv_events=(self.roofline_events or {}).get(live[0]),
-                                       raw=raws)
+            lanes = [self._qformer_input(qf, embeds[m], None if index is None else index.get(m), n_local) for qf, m in zip(qfs, live)]
+            res = QFormer.forward_pair(qfs[0], qfs[1], ids, att, lanes[0][0], lanes[1][0], want_cls=True,
+                                       kv_events=(self.roofline_events or {}).get(live[0]), raw=[raw for _, raw in lanes])
             for m, (z, cls) in zip(live, res):
                 if sharded:
                     local[m] = (z, cls)
                 else:
-                    sim, logit = scorer.cosine_scores(z, cls)
-                    out["z"][m], out["cls"][m], out["sim"][m], out["logit"][m] = z, cls, sim, logit
+                    _store_scores(out, m, z, cls)
             live = []
-        for pos, m in enumerate(live):
-            qf: QFormer = getattr(self, f"{m}_Qformer")
-            idx = None if index is None else index.get(m)
-            # the modality with the most work is the step's critical path: its launches go first when both streams are ready
-            side = self._side_stream(m, high_priority=self.prioritize_heavy and pos == 0) if use_streams else cur
-            if use_streams:
-                used_streams.append(side)
-                side.wait_stream(cur)
-                if heavy_done is not None and pos > 0:
-                    side.wait_event(heavy_done)
-            with torch.cuda.stream(side):
-                # the folded cross-attention reads the encoder output itself where the library folds the LayerNorm into it (no normalised copy)
-                x = embeds[m].to(self._device)
-                raw = x.dim() == 3 and x.shape[0] == n_local and qf.raw_features_ok(x, item_index=idx)
-                enc = x if raw else qf.modality_ln(x, item_index=idx, items=n_local)
-                res = qf.forward_fused(ids, att, enc, want_query=True, want_full=want_full, want_cls=True,
-                                       kv_events=(self.roofline_events or {}).get(m), raw=raw)
-                z, cls = res["query"], res["cls"]
-                if sharded:      # scored after ONE packed all-gather of every modality's rows, below
-                    local[m] = (z, cls)
+        with self._modality_streams(use_streams) as lane:
+            for pos, m in enumerate(live):
+                qf: QFormer = getattr(self, f"{m}_Qformer")
+                # the modality with the most work is the step's critical path: its launches go first when both streams are ready
+                with lane(m, high_priority=self.prioritize_heavy and pos == 0, after=heavy_done if pos > 0 else None) as hand:
+                    enc, raw = self._qformer_input(qf, embeds[m], None if index is None else index.get(m), n_local)
+                    res = qf.forward_fused(ids, att, enc, want_query=True, want_full=want_full, want_cls=True,
+                                           kv_events=(self.roofline_events or {}).get(m), raw=raw)
+                    z, cls = res["query"], res["cls"]
+                    hand((enc, z, cls))
+                    if sharded:      # scored after ONE packed all-gather of every modality's rows, below
+                        local[m] = (z, cls)
+                        if want_full:
+                            out["full"][m] = self._gather(res["full"], n)
+                            hand((out["full"][m],))
+                        continue
+                    hand(_store_scores(out, m, z, cls))
                     if want_full:
-                        out["full"][m] = self._gather(res["full"], n)
-                    if use_streams:
-                        for t in (enc, z, cls, out["full"].get(m)):
-                            if t is not None:
-                                t.record_stream(cur)
-                    continue
-                sim, logit = scorer.cosine_scores(z, cls)
-                out["z"][m], out["cls"][m], out["sim"][m], out["logit"][m] = z, cls, sim, logit
-                if want_full:
-                    out["full"][m] = res["full"]
-                if want_llm:  # reference :303-306
-                    y = qf.llm_proj(z)
-                    out.setdefault("inputs_llm", {})[m] = y.reshape(bs, num, self.num_query_token, -1).view(bs, num * self.num_query_token, -1)
-                    out.setdefault("atts_llm", {})[m] = torch.ones(bs, num * self.num_query_token, dtype=torch.long, device=self._device)
-                if use_streams:  # the results are consumed on the caller's stream
-                    for t in (enc, z, cls, sim, logit, out["full"].get(m), out.get("inputs_llm", {}).get(m), out.get("atts_llm", {}).get(m)):
-                        if t is not None:
-                            t.record_stream(cur)
-        for side in used_streams:          # join exactly the streams that were forked
-            cur.wait_stream(side)
+                        out["full"][m] = res["full"]
+                        hand((res["full"],))
+                    if want_llm:
+                        hand(self._pack_llm(out, m, z, bs, num))
         if sharded and local:
             # the only exchange of the path: query embeddings and [CLS] vectors of all modalities in one RCCL all-gather
             mods_l = list(local)
             gathered = parallel.all_gather_packed([t for m in mods_l for t in local[m]], n, self.process_group)
             for k, m in enumerate(mods_l):
-                z, cls = gathered[2 * k], gathered[2 * k + 1]
-                sim, logit = scorer.cosine_scores(z, cls)
-                out["z"][m], out["cls"][m], out["sim"][m], out["logit"][m] = z, cls, sim, logit
+                _store_scores(out, m, gathered[2 * k], gathered[2 * k + 1])
                 if want_llm:
-                    y = getattr(self, f"{m}_Qformer").llm_proj(z)
-                    out.setdefault("inputs_llm", {})[m] = y.reshape(bs, num, self.num_query_token, -1).view(bs, num * self.num_query_token, -1)
-                    out.setdefault("atts_llm", {})[m] = torch.ones(bs, num * self.num_query_token, dtype=torch.long, device=self._device)
+                    self._pack_llm(out, m, out["z"][m], bs, num)
         mods = [m for m in self.modalities if m in out["logit"]]
         if not mods:
             raise MraError("no features for any of the model's modalities")
-        out["fused"] = scorer.fuse_logits([out["logit"][m] for m in mods], self.fuse_weights)
-        out["spans"] = scorer.spans_from_logits(out["fused"], bs, num, self.score_alpha)
-        if self.top_k > 1:   # on the gathered logits: every rank of a sharded run ranks the same windows
-            out["windows"], out["window_scores"], out["window_counts"] = scorer.windows_from_logits(
-                out["fused"], bs, num, self.score_alpha, self.top_k, self.nms_thd, self.max_window)
+        # (sharded: on the gathered logits, so every rank ranks the same windows)
+        out.update(self._score_tail([out["logit"][m] for m in mods], bs, num))
         out["bs"], out["num"] = bs, num
         return out
 
@@ -593,9 +692,7 @@ class XInstructBLIP(nn.Module):
         [N,32], ``logit[m]`` [N], ``fused`` [N], ``spans`` int32 [B,2]; with ``want_llm`` also
         ``inputs_llm[m]`` [B, T*32, 4096] and ``atts_llm[m]`` (``:303-306``).  With a process group the
         items are sharded in contiguous blocks over the ranks (every rank is given the same samples)."""
-        prompt = samples["text_input"]
-        text = self.tokenizer(prompt, padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
-        ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)
+        ids, tmask = self._tokenize(samples["text_input"])
         rank, ws = self._clip_world()
         embeds, index = {}, {}
         bs = num = None
@@ -613,10 +710,8 @@ class XInstructBLIP(nn.Module):
             embeds[m], _, bs, num = self._encode(samples, m, lo, hi)     # this rank's block only: the encoder is sharded too
         if bs is None:
             raise MraError("samples holds none of the model's modalities")
-        if self.compat_repeat:   # reference :287-288  ids.repeat(num, 1): row k carries prompt k % bs
-            ids_n, tm_n = ids.repeat(num, 1), tmask.repeat(num, 1)
-        else:                    # aligned: row k carries the prompt of its own sample k // num
-            ids_n, tm_n = ids.repeat_interleave(num, 0), tmask.repeat_interleave(num, 0)
+        # (fuse_score puts the query-token ones in front of this rank's rows of the mask)
+        ids_n, tm_n = _expand_rows(ids, num, tile=self.compat_repeat), _expand_rows(tmask, num, tile=self.compat_repeat)
         lo, hi = parallel.shard_range(bs * num, rank, ws)
         return self.fuse_score(embeds, ids_n[lo:hi], tm_n[lo:hi], bs, num, index=index or None, want_llm=want_llm, want_full=want_full)
 
@@ -625,25 +720,15 @@ class XInstructBLIP(nn.Module):
         """Reference ``:221-397`` with the LLM decode replaced by the scorer: one ``"[[start, end]]"``
         string (seconds) per sample."""
         out = self.encode_fuse(samples)
-        spans = out["spans"].cpu().tolist()
-        ts = samples.get("timestamps")
-        if ts is None:
-            ts = [list(range(out["num"]))] * out["bs"]
-        ts = [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
-        return [o.strip() for o in scorer.spans_to_text(spans, ts)]
+        return _span_texts(out["spans"], _timestamps(samples, out["bs"], out["num"]))
 
     @torch.no_grad()
     def generate_with_scores(self, samples):
         """``generate`` plus the fused per-position logits ``[B][T]`` the spans were cut from (the
         ``pred_saliency_scores`` of the highlight metrics, ``eval/mr_eval.py:291-325``)."""
         out = self.encode_fuse(samples)
-        spans = out["spans"].cpu().tolist()
-        ts = samples.get("timestamps")
-        if ts is None:
-            ts = [list(range(out["num"]))] * out["bs"]
-        ts = [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
         scores = out["fused"].view(out["bs"], out["num"]).float().cpu().tolist()
-        return [o.strip() for o in scorer.spans_to_text(spans, ts)], scores
+        return _span_texts(out["spans"], _timestamps(samples, out["bs"], out["num"])), scores
 
     @torch.no_grad()
     def generate_windows(self, samples):
@@ -653,13 +738,9 @@ class XInstructBLIP(nn.Module):
         if self.top_k <= 1:
             raise MraError("generate_windows needs a model built with top_k > 1")
         out = self.encode_fuse(samples)
-        ts = samples.get("timestamps")
-        if ts is None:
-            ts = [list(range(out["num"]))] * out["bs"]
-        ts = [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
-        win, sc, cnt = out["windows"].cpu(), out["window_scores"].cpu(), out["window_counts"].cpu()
+        texts, records = _window_texts(out["windows"], out["window_scores"], out["window_counts"], _timestamps(samples, out["bs"], out["num"]))
         saliency = out["fused"].view(out["bs"], out["num"]).float().cpu().tolist()
-        return scorer.windows_to_text(win, cnt, ts), scorer.windows_to_records(win, sc, cnt, ts), saliency
+        return texts, records, saliency
 
     # ---- several queries per video over one shared K/V cache ---------------------------------------------------
     def _multi_pack(self, flat: Dict[str, object], logit: Dict[str, torch.Tensor], bs: int, num: int, P: int, counts: Sequence[int]) -> Dict[str, object]:
@@ -717,8 +798,7 @@ class XInstructBLIP(nn.Module):
             if res["bs"] != len(queries):
                 raise MraError(f"encode_fuse_multi: {len(queries)} query lists for {res['bs']} videos")
             return self._multi_pack(res, res["logit"], res["bs"], res["num"], 1, counts)
-        text = self.tokenizer([t for q in padded for t in q], padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
-        ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)      # [B * P, L], row b * P + p
+        ids, tmask = self._tokenize([t for q in padded for t in q])      # [B * P, L], row b * P + p
         embeds = {}
         bs = num = None
         for m in self.modalities:
@@ -729,69 +809,46 @@ class XInstructBLIP(nn.Module):
         if bs != len(queries):
             raise MraError(f"encode_fuse_multi: {len(queries)} query lists for {bs} videos")
         self._sync()
-        L = int(ids.shape[1])
         # chain row (b * T + t) * P + p carries prompt p of video b
-        ids_n = ids.view(bs, 1, P, L).expand(bs, num, P, L).reshape(bs * num * P, L)
-        tm_n = tmask.view(bs, 1, P, L).expand(bs, num, P, L).reshape(bs * num * P, L)
-        att = torch.cat([torch.ones(bs * num * P, self.num_query_token, dtype=torch.long, device=self._device), tm_n], dim=1)
-        cur = torch.cuda.current_stream(self._device)
+        ids_n, att = _prompt_rows(ids, tmask, self.num_query_token, num, P)
         live = [m for m in self.modalities if m in embeds]
-        use_streams = self.overlap_modalities and len(live) > 1
         logit: Dict[str, torch.Tensor] = {}
-        used = []
-        for m in live:
-            qf: QFormer = getattr(self, f"{m}_Qformer")
-            side = self._side_stream(m) if use_streams else cur
-            if use_streams:
-                used.append(side)
-                side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                enc = qf.modality_ln(embeds[m].to(self._device))
-                if self._multi_op_chain(qf, ids_n[0:num * P:P], att[0:num * P:P], enc[:num]):
-                    res = qf.forward_multi(ids_n, att, enc, P, want_query=True, want_cls=True)
-                    z, cls = res["query"], res["cls"]
-                else:
-                    if not getattr(self, "_multi_split_warned", False):
-                        logging.warning("encode_fuse_multi: split precision is in force for %s -- one ordinary forward per prompt slot, "
-                                        "no shared K/V cache", m)
-                        self._multi_split_warned = True
-                    per = [qf.forward_fused(ids_n[p::P], att[p::P], enc, want_query=True, want_cls=True) for p in range(P)]
-                    z = torch.stack([r["query"] for r in per], dim=1).reshape(bs * num * P, self.num_query_token, -1)
-                    cls = torch.stack([r["cls"] for r in per], dim=1).reshape(bs * num * P, -1)
-                _, lg = scorer.cosine_scores(z, cls, want_sim=False)
-                # (b, t, p) -> (b, p, t): the scorer's heads then see bs * P "videos" of num positions
-                logit[m] = lg.index_select(0, bpt_index(bs, num, P).to(lg.device))
-                if use_streams:
-                    for t in (enc, z, cls, lg, logit[m]):
-                        t.record_stream(cur)
-        for side in used:
-            cur.wait_stream(side)
-        flat: Dict[str, object] = {"fused": scorer.fuse_logits([logit[m] for m in live], self.fuse_weights)}
-        flat["spans"] = scorer.spans_from_logits(flat["fused"], bs * P, num, self.score_alpha)
-        if self.top_k > 1:
-            flat["windows"], flat["window_scores"], flat["window_counts"] = scorer.windows_from_logits(
-                flat["fused"], bs * P, num, self.score_alpha, self.top_k, self.nms_thd, self.max_window)
+        with self._modality_streams(self.overlap_modalities and len(live) > 1) as lane:
+            for m in live:
+                qf: QFormer = getattr(self, f"{m}_Qformer")
+                with lane(m) as hand:
+                    enc = qf.modality_ln(embeds[m].to(self._device))
+                    if self._multi_op_chain(qf, ids_n[0:num * P:P], att[0:num * P:P], enc[:num]):
+                        res = qf.forward_multi(ids_n, att, enc, P, want_query=True, want_cls=True)
+                        z, cls = res["query"], res["cls"]
+                    else:
+                        if not getattr(self, "_multi_split_warned", False):
+                            logging.warning("encode_fuse_multi: split precision is in force for %s -- one ordinary forward per prompt slot, "
+                                            "no shared K/V cache", m)
+                            self._multi_split_warned = True
+                        per = [qf.forward_fused(ids_n[p::P], att[p::P], enc, want_query=True, want_cls=True) for p in range(P)]
+                        z = torch.stack([r["query"] for r in per], dim=1).reshape(bs * num * P, self.num_query_token, -1)
+                        cls = torch.stack([r["cls"] for r in per], dim=1).reshape(bs * num * P, -1)
+                    _, lg = scorer.cosine_scores(z, cls, want_sim=False)
+                    # (b, t, p) -> (b, p, t): the scorer's heads then see bs * P "videos" of num positions
+                    logit[m] = lg.index_select(0, bpt_index(bs, num, P).to(lg.device))
+                    hand((enc, z, cls, lg, logit[m]))
+        flat = self._score_tail([logit[m] for m in live], bs * P, num)
         return self._multi_pack(flat, logit, bs, num, P, counts)
-
-    def _multi_timestamps(self, samples, out) -> list:
-        ts = samples.get("timestamps")
-        if ts is None:
-            ts = [list(range(out["num"]))] * out["bs"]
-        return [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
 
     @torch.no_grad()
     def generate_multi(self, samples, queries: Sequence[Sequence[str]]) -> List[List[str]]:
         """``generate`` for several queries per video (``encode_fuse_multi``): per video one ``"[[start, end]]"`` string per query."""
         out = self.encode_fuse_multi(samples, queries)
-        ts = self._multi_timestamps(samples, out)
-        return [[o.strip() for o in scorer.spans_to_text(sp.cpu().tolist(), [t] * int(sp.shape[0]))] for sp, t in zip(out["spans"], ts)]
+        ts = _timestamps(samples, out["bs"], out["num"])
+        return [_span_texts(sp, [t] * int(sp.shape[0])) for sp, t in zip(out["spans"], ts)]
 
     @torch.no_grad()
     def generate_multi_with_scores(self, samples, queries: Sequence[Sequence[str]]):
         """``generate_multi`` plus the fused per-position logits ``[B][P_b][T]`` the spans were cut from."""
         out = self.encode_fuse_multi(samples, queries)
-        ts = self._multi_timestamps(samples, out)
-        texts = [[o.strip() for o in scorer.spans_to_text(sp.cpu().tolist(), [t] * int(sp.shape[0]))] for sp, t in zip(out["spans"], ts)]
+        ts = _timestamps(samples, out["bs"], out["num"])
+        texts = [_span_texts(sp, [t] * int(sp.shape[0])) for sp, t in zip(out["spans"], ts)]
         return texts, [f.float().cpu().tolist() for f in out["fused"]]
 
     @torch.no_grad()
@@ -800,14 +857,10 @@ class XInstructBLIP(nn.Module):
         if self.top_k <= 1:
             raise MraError("generate_multi_windows needs a model built with top_k > 1")
         out = self.encode_fuse_multi(samples, queries)
-        ts = self._multi_timestamps(samples, out)
-        texts, records = [], []
-        for win, sc, cnt, t in zip(out["windows"], out["window_scores"], out["window_counts"], ts):
-            tt = [t] * int(win.shape[0])
-            win, sc, cnt = win.cpu(), sc.cpu(), cnt.cpu()
-            texts.append(scorer.windows_to_text(win, cnt, tt))
-            records.append(scorer.windows_to_records(win, sc, cnt, tt))
-        return texts, records, [f.float().cpu().tolist() for f in out["fused"]]
+        ts = _timestamps(samples, out["bs"], out["num"])
+        per_video = [_window_texts(win, sc, cnt, [t] * int(win.shape[0]))
+                     for win, sc, cnt, t in zip(out["windows"], out["window_scores"], out["window_counts"], ts)]
+        return [texts for texts, _ in per_video], [records for _, records in per_video], [f.float().cpu().tolist() for f in out["fused"]]
 
     # ---- row N2: the reference's own decode, for callers that attach a stock LLM ----------------------------
     def attach_llm(self, llm_model: nn.Module, llm_tokenizer, enumerate_inputs: bool = False, interleave_seconds: bool = True) -> None:
@@ -890,11 +943,9 @@ class XInstructBLIP(nn.Module):
         """Clip-membership targets: position ``i`` of sample ``r`` is positive when its timestamp lies inside ANY of
         the windows of ``samples["text_output"][r]`` (union over windows, float seconds honoured)."""
         target = torch.zeros(bs, num, dtype=torch.float32, device=self._device)
-        ts = samples.get("timestamps") or [list(range(num))] * bs
+        ts = _timestamps(samples, bs, num)
         for r, txt in enumerate(samples.get("text_output", ["[[-1, -1]]"] * bs)):
-            t = torch.as_tensor(ts[r], dtype=torch.float32, device=self._device)
-            for s0, e0 in self.parse_windows(txt):
-                target[r] = torch.maximum(target[r], ((t >= s0) & (t <= e0)).float())
+            _membership_targets(self.parse_windows, [txt], ts[r], target[r: r + 1])
         return target
 
     def enable_qformer_training(self, train_ln: bool = False, train_proj: bool = False) -> None:
@@ -973,8 +1024,7 @@ class XInstructBLIP(nn.Module):
         return {"loss": self._score_loss(samples, per_mod, bs, num)}
 
     def _score_loss(self, samples, per_mod, bs, num):
-        w = self.fuse_weights or [1.0 / len(per_mod)] * len(per_mod)
-        fused = sum(x * wt for x, wt in zip(per_mod, w))
+        fused = _weighted_fuse(per_mod, self.fuse_weights)
         return nn.functional.binary_cross_entropy_with_logits(fused.view(bs, num) * 20.0, self._targets(samples, bs, num))
 
     def _train_pass(self, samples, want_score: bool, want_llm: bool):
@@ -983,44 +1033,31 @@ class XInstructBLIP(nn.Module):
         ``inputs_llm[m]`` [B, T * 32, D] (fp32; ``llm_proj_train``, always a node: the Q-Former gets its gradient whether or not the
         projection is trained).  Returns ``(per_mod, inputs_llm, bs, num)``."""
         self._sync()
-        text = self.tokenizer(samples["text_input"], padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
-        ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)
+        ids, tmask = self._tokenize(samples["text_input"])
         per_mod, inputs_llm, bs, num = [], {}, None, None
         # ``train_streams``: each modality's forward (and, since autograd runs a node's backward on its forward's stream, its backward)
         # on its own stream.  Round 2 measured nothing from it (17.4 vs 17.0 ms: the step was bound by the GPU time of its ~1300 launches);
         # measured again after the launch merges of round 3 -- see DESIGN.md section 8.
-        cur = torch.cuda.current_stream(self._device)
-        use_streams = bool(getattr(self, "train_streams", False))
-        for m in self.modalities:
-            if not self._present(samples, m):
-                continue
-            qf: QFormer = getattr(self, f"{m}_Qformer")
-            side = self._side_stream(m) if use_streams else cur
-            if use_streams:
-                side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                with torch.no_grad():
-                    raw, idx, bs, num = self._encode(samples, m)
-                    if not getattr(self, "train_ln", False):
-                        enc = qf.modality_ln(raw, item_index=idx, items=bs * num)
-                if getattr(self, "train_ln", False):
-                    enc = self._ln_train(m, raw)
-                n = bs * num
-                ids_n, tm_n = (ids.repeat(num, 1), tmask.repeat(num, 1)) if self.compat_repeat else \
-                              (ids.repeat_interleave(num, 0), tmask.repeat_interleave(num, 0))
-                att = torch.cat([torch.ones(n, self.num_query_token, dtype=torch.long, device=self._device), tm_n], dim=1)
-                z, cls = qf.forward_train(ids_n, att, enc, want_cls=want_score)
-                if want_score:
-                    sim = nn.functional.cosine_similarity(z, cls[:, None, :], dim=-1, eps=1e-8)
-                    per_mod.append(sim.max(dim=1).values)
-                if want_llm:  # reference :303-306
-                    proj = getattr(self, f"{m}_llm_proj")
-                    y = qf.llm_proj_train(z, proj.weight, proj.bias, grad_scale=self.loss_scale)
-                    inputs_llm[m] = y.reshape(bs, num * self.num_query_token, -1)
-        if use_streams:
+        with self._modality_streams(bool(getattr(self, "train_streams", False))) as lane:
             for m in self.modalities:
-                if (m, False) in self._streams:
-                    cur.wait_stream(self._streams[(m, False)])
+                if not self._present(samples, m):
+                    continue
+                qf: QFormer = getattr(self, f"{m}_Qformer")
+                with lane(m) as hand:
+                    with torch.no_grad():
+                        raw, idx, bs, num = self._encode(samples, m)
+                    enc = self._train_norm(m, raw, idx, bs * num)
+                    ids_n, att = _prompt_rows(ids, tmask, self.num_query_token, num, tile=self.compat_repeat)
+                    z, cls = qf.forward_train(ids_n, att, enc, want_cls=want_score)
+                    hand((enc, z, cls))
+                    if want_score:
+                        per_mod.append(_train_logit(z, cls))
+                        hand(per_mod[-1:])
+                    if want_llm:  # reference :303-306
+                        proj = getattr(self, f"{m}_llm_proj")
+                        y = qf.llm_proj_train(z, proj.weight, proj.bias, grad_scale=self.loss_scale)
+                        inputs_llm[m] = y.reshape(bs, num * self.num_query_token, -1)
+                        hand((inputs_llm[m],))
         return per_mod, inputs_llm, bs, num
 
     def _lm_loss(self, samples, inputs_llm):
@@ -1041,16 +1078,9 @@ class XInstructBLIP(nn.Module):
 
     def _multi_targets(self, samples, windows: Sequence[Sequence[str]], num: int) -> List[torch.Tensor]:
         """Per video ``[P_b, T]`` clip-membership targets: row ``p`` from the windows of the video's query ``p`` (as ``_targets``)."""
-        ts = samples.get("timestamps") or [list(range(num))] * len(windows)
-        out = []
-        for b, txts in enumerate(windows):
-            t = torch.as_tensor(ts[b], dtype=torch.float32, device=self._device)
-            rows = torch.zeros(len(txts), num, dtype=torch.float32, device=self._device)
-            for p, txt in enumerate(txts):
-                for s0, e0 in self.parse_windows(txt):
-                    rows[p] = torch.maximum(rows[p], ((t >= s0) & (t <= e0)).float())
-            out.append(rows)
-        return out
+        ts = _timestamps(samples, len(windows), num)
+        return [_membership_targets(self.parse_windows, txts, ts[b], torch.zeros(len(txts), num, dtype=torch.float32, device=self._device))
+                for b, txts in enumerate(windows)]
 
     def forward_multi(self, samples, queries: Optional[Sequence[Sequence[str]]] = None, targets: Optional[Sequence[Sequence[str]]] = None):
         """``forward`` for one record per video with several queries: ``queries[b]`` / ``targets[b]`` are the prompts and the
@@ -1084,44 +1114,33 @@ class XInstructBLIP(nn.Module):
         self._sync()
         encs: Dict[str, torch.Tensor] = {}
         bs = num = None
-        raws: Dict[str, torch.Tensor] = {}
-        with torch.no_grad():
-            for m in self.modalities:
-                if self._present(samples, m):
+        for m in self.modalities:
+            if self._present(samples, m):
+                with torch.no_grad():
                     raw, idx, bs, num = self._encode(samples, m)
-                    if getattr(self, "train_ln", False):
-                        raws[m] = raw
-                    else:
-                        encs[m] = getattr(self, f"{m}_Qformer").modality_ln(raw, item_index=idx, items=bs * num)
-        for m, raw in raws.items():          # train_ln: the LayerNorm is a node of the graph
-            encs[m] = self._ln_train(m, raw)
+                encs[m] = self._train_norm(m, raw, idx, bs * num)
         if bs is None:
             return {"loss": torch.tensor(0.0)}
         if bs != len(queries):
             raise MraError(f"forward_multi: {len(queries)} query lists for {bs} videos")
         tg = self._multi_targets(samples, targets, num)
-        w = self.fuse_weights or [1.0 / len(encs)] * len(encs)
         triples = float(sum(counts) * num)
         loss = None
         for lo in range(0, max(counts), step):
             vids = [b for b, c in enumerate(counts) if c > lo]            # the videos that still have queries in this round
             padded, cnt = pad_queries([queries[b][lo: lo + step] for b in vids])
             nb, P = len(vids), max(cnt)
-            text = self.tokenizer([t for q in padded for t in q], padding="longest", truncation=True, max_length=self.max_txt_len, return_tensors="pt")
-            ids, tmask = text.input_ids.to(self._device), text.attention_mask.to(self._device)      # [nb * P, L], row b * P + p
-            L = int(ids.shape[1])
+            ids, tmask = self._tokenize([t for q in padded for t in q])      # [nb * P, L], row b * P + p
             # chain row (b * T + t) * P + p carries prompt p of video b
-            ids_n = ids.view(nb, 1, P, L).expand(nb, num, P, L).reshape(nb * num * P, L)
-            tm_n = tmask.view(nb, 1, P, L).expand(nb, num, P, L).reshape(nb * num * P, L)
-            att = torch.cat([torch.ones(nb * num * P, self.num_query_token, dtype=torch.long, device=self._device), tm_n], dim=1)
+            ids_n, att = _prompt_rows(ids, tmask, self.num_query_token, num, P)
             sel = None if nb == bs else torch.as_tensor(vids, device=self._device)
             per_mod = []
             for m, enc in encs.items():
                 if sel is not None:
                     enc = enc.view(bs, num, *enc.shape[1:]).index_select(0, sel).reshape(nb * num, *enc.shape[1:])
                 z, cls = getattr(self, f"{m}_Qformer").forward_multi_train(ids_n, att, enc, P)
-                per_mod.append(nn.functional.cosine_similarity(z, cls[:, None, :], dim=-1, eps=1e-8).max(dim=1).values)
-            fused = sum(x * wt for x, wt in zip(per_mod, w)).view(nb, num, P).permute(0, 2, 1)      # (b, t, p) -> [nb, P, T]
+                per_mod.append(_train_logit(z, cls))
+            fused = _weighted_fuse(per_mod, self.fuse_weights).view(nb, num, P).permute(0, 2, 1)      # (b, t, p) -> [nb, P, T]
             target = torch.zeros(nb, P, num, dtype=torch.float32, device=self._device)
             real = torch.zeros(nb, P, 1, dtype=torch.float32, device=self._device)                  # 0 on padded slots: no loss, no gradient
             for k, b in enumerate(vids):

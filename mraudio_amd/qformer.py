@@ -16,6 +16,7 @@ memory and the stream.  There is no CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import weakref
 from dataclasses import dataclass
@@ -50,6 +51,34 @@ class QFormerConfig:
         return mra_cfg(self.hidden, self.heads, self.inter, self.layers, self.cross_freq, self.enc_width, self.n_query,
                        self.vocab, self.max_pos, self.ln_eps, self.enc_ln_eps, self.llm_hidden,
                        MRA_BF16 if self.op_dtype == torch.bfloat16 else MRA_F16)
+
+
+CROSS_MODES = {"auto": 0, "kv_cache": 1, "fold": 2, "fold384": 3, "fold_stream": 4, "fold_rescale_pass": 5}   # mra_qformer_set_cross_mode
+
+
+def _check_pushed(what: str, pairs, pushed: dict) -> None:
+    """``MraError`` unless every ``(name, tensor)`` of ``pairs`` is the tensor last pushed to the handle under ``name``, at the version it
+    was pushed at (``pushed[name]`` = (weak reference, version)).  ``what``: the calling method, for the message."""
+    for name, t in pairs:
+        ref, ver = pushed.get(name, (None, None))
+        if ref is None or ref() is not t:
+            raise MraError(f"{what}: {name} is not the tensor last pushed to the handle (push it first)")
+        if ver != t._version:
+            raise MraError(f"{what}: {name} changed since it was pushed (version {ver} -> {t._version}): push it again")
+
+
+@contextlib.contextmanager
+def _kv_events(handle, events):
+    """While the block runs, the library records the (start, stop) ``torch.cuda.Event`` pair ``events`` around the handle's dominant
+    kernel on the launch stream (``mra_qformer_set_kv_events``); cleared again on the way out, also after an error.  ``None``: nothing."""
+    if events is None:
+        yield
+        return
+    check(lib().mra_qformer_set_kv_events(handle, events[0].cuda_event, events[1].cuda_event), "set_kv_events")
+    try:
+        yield
+    finally:
+        check(lib().mra_qformer_set_kv_events(handle, None, None), "set_kv_events")
 
 
 class _Lin(nn.Module):
@@ -296,13 +325,7 @@ class QFormer(nn.Module):
         tensors last pushed as ``ln.weight`` / ``ln.bias`` -- ordinary torch parameters, not slots of the flat buffer -- and receive
         real ``.grad`` tensors from ``mra_modality_ln_backward``; ``x`` [items, tokens, E] receives one only if it requires grad.
         ``MraError`` if the handle holds other tensors (or an older version of these) than the ones given."""
-        pushed = getattr(self, "_pushed_ln", {})
-        for name, t in (("ln.weight", weight), ("ln.bias", bias)):
-            ref, ver = pushed.get(name, (None, None))
-            if ref is None or ref() is not t:
-                raise MraError(f"modality_ln_train: {name} is not the tensor last pushed to the handle (push it first)")
-            if ver != t._version:
-                raise MraError(f"modality_ln_train: {name} changed since it was pushed (version {ver} -> {t._version}): push it again")
+        _check_pushed("modality_ln_train", (("ln.weight", weight), ("ln.bias", bias)), getattr(self, "_pushed_ln", {}))
         return _ModalityLNTrainFn.apply(x, weight, bias, self)
 
     def _ln_backward(self, x: torch.Tensor, d_out: torch.Tensor, want_x: bool, want_gain: bool, want_bias: bool):
@@ -356,7 +379,7 @@ class QFormer(nn.Module):
         """A4 on the extension.  enc [N, Kv, E] in the operand dtype (``modality_ln`` output; with ``raw`` the encoder output itself,
         where ``raw_features_ok`` allows it: ``mra_qformer_forward_raw``).
         Returns a dict with ``query`` [N,32,H], ``full`` [N,32+L,H], ``cls`` [N,H] (fp32) as requested.
-        ``kv_events``: optional (start, stop) ``torch.cuda.Event`` pair for ``mra_qformer_set_kv_events`` (bench
+        ``kv_events``: optional (start, stop) ``torch.cuda.Event`` pair for ``_kv_events`` (bench
         instrumentation of the dominant kernel, recorded by the library on the launch stream)."""
         self.sync_weights()
         cfg = self.cfg
@@ -383,18 +406,12 @@ class QFormer(nn.Module):
         with torch.cuda.device(self._device):
             nbytes = (int(lib().mra_qformer_workspace_bytes(self._handle, N, L, Kv)) + 255) // 256 * 256
             ws = self._workspace(nbytes)
-            if kv_events is not None:
-                e0, e1 = kv_events
-                check(lib().mra_qformer_set_kv_events(self._handle, e0.cuda_event, e1.cuda_event), "set_kv_events")
-            try:
+            with _kv_events(self._handle, kv_events):
                 fwd = lib().mra_qformer_forward_raw if raw else lib().mra_qformer_forward
                 check(fwd(
                     self._handle, ptr(input_ids), ptr(attention_mask), ptr(query_embeds), q_items, ptr(enc), N, L, Kv,
                     ptr(out.get("query")), ptr(out.get("full")), ptr(out.get("cls")), ptr(ws), nbytes, current_stream()),
                     "mra_qformer_forward_raw" if raw else "mra_qformer_forward")
-            finally:
-                if kv_events is not None:
-                    check(lib().mra_qformer_set_kv_events(self._handle, None, None), "set_kv_events")
         return out
 
     def forward_multi(self, input_ids: Optional[torch.Tensor], attention_mask: Optional[torch.Tensor], enc: torch.Tensor, prompts: int,
@@ -450,16 +467,11 @@ class QFormer(nn.Module):
         with torch.cuda.device(qf0._device):
             nbytes = (int(lib().mra_qformer_pair_workspace_bytes(qf0._handle, qf1._handle, N, L, int(encs[0].shape[1]), int(encs[1].shape[1]))) + 255) // 256 * 256
             ws = qf0._workspace(nbytes)
-            if kv_events is not None:
-                check(lib().mra_qformer_set_kv_events(qf0._handle, kv_events[0].cuda_event, kv_events[1].cuda_event), "set_kv_events")
-            try:
+            with _kv_events(qf0._handle, kv_events):
                 check(lib().mra_qformer_forward_pair_raw(qf0._handle, qf1._handle, ptr(input_ids), ptr(attention_mask), ptr(encs[0]), ptr(encs[1]),
                                                          int(bool(raw[0])) | int(bool(raw[1])) << 1, N, L,
-                                                     int(encs[0].shape[1]), int(encs[1].shape[1]), ptr(outs[0][0]), ptr(outs[0][1]), ptr(outs[1][0]), ptr(outs[1][1]),
-                                                     ptr(ws), nbytes, current_stream()), "mra_qformer_forward_pair")
-            finally:
-                if kv_events is not None:
-                    check(lib().mra_qformer_set_kv_events(qf0._handle, None, None), "set_kv_events")
+                                                         int(encs[0].shape[1]), int(encs[1].shape[1]), ptr(outs[0][0]), ptr(outs[0][1]), ptr(outs[1][0]), ptr(outs[1][1]),
+                                                         ptr(ws), nbytes, current_stream()), "mra_qformer_forward_pair")
         return outs
 
     def llm_proj(self, z: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -482,13 +494,7 @@ class QFormer(nn.Module):
         ``forward_train`` does).  ``MraError`` if the handle holds other tensors (or an older version of these) than the ones given.
         ``grad_scale``: the upstream gradient arrives multiplied by it (a loss scale that keeps a 16-bit LM's gradients out of the
         underflow range) and is divided by it in fp32 before the backward runs, so every gradient this node hands on is unscaled."""
-        pushed = getattr(self, "_pushed_proj", {})
-        for name, t in (("llm_proj.weight", weight), ("llm_proj.bias", bias)):
-            ref, ver = pushed.get(name, (None, None))
-            if ref is None or ref() is not t:
-                raise MraError(f"llm_proj_train: {name} is not the tensor last pushed to the handle (push it first)")
-            if ver != t._version:
-                raise MraError(f"llm_proj_train: {name} changed since it was pushed (version {ver} -> {t._version}): push it again")
+        _check_pushed("llm_proj_train", (("llm_proj.weight", weight), ("llm_proj.bias", bias)), getattr(self, "_pushed_proj", {}))
         return _LlmProjTrainFn.apply(z, weight, bias, self, out_dtype, float(grad_scale))
 
     def _proj_backward(self, z: torch.Tensor, d_out: torch.Tensor, want_z: bool, want_w: bool, want_b: bool):
@@ -511,9 +517,9 @@ class QFormer(nn.Module):
         """How the cross-attention layers run: ``"auto"`` (folded from Kv >= 2048), ``"kv_cache"``, ``"fold"``, or the
         A/B formulations ``"fold384"`` (128 x 384 tiles) / ``"fold_stream"`` (streaming kernels, f16 only)
         (``mra_qformer_set_cross_mode``).  Same arithmetic, re-associated; the workspace size follows the mode."""
-        code = {"auto": 0, "kv_cache": 1, "fold": 2, "fold384": 3, "fold_stream": 4, "fold_rescale_pass": 5}.get(mode, mode)
+        code = CROSS_MODES.get(mode, mode)
         check(lib().mra_qformer_set_cross_mode(self._handle, int(code)), "mra_qformer_set_cross_mode")
-        self._cross_mode = mode if isinstance(mode, str) else {v: k for k, v in {"auto": 0, "kv_cache": 1, "fold": 2, "fold384": 3, "fold_stream": 4, "fold_rescale_pass": 5}.items()}.get(int(mode), "auto")
+        self._cross_mode = mode if isinstance(mode, str) else {v: k for k, v in CROSS_MODES.items()}.get(int(mode), "auto")
 
     def set_option(self, name: str, value: int) -> None:
         """Per-handle tuning option (``mra_qformer_set_option``), e.g. ``("chain_ring", mask)``."""

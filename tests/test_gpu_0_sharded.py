@@ -111,6 +111,14 @@ def _worker(rank, ws, port, out_path):
             torch.cuda.synchronize()
             res[name] = {"fused": out["fused"].cpu(), "spans": out["spans"].cpu(), "strings": strings,
                          "z_video": out["z"]["video"].cpu(), "logit_audio": out["logit"]["audio"].cpu()}
+        # the projections into the LM (one rank: inside the modality's lane; sharded: from the gathered query embeddings).  Beside them what
+        # the file's 1e-6 on z can do to them: it may flip the f16 rounding of an operand (one ulp, 2^-10 relative) under |W|
+        out = model.encode_fuse(_samples(7, False), want_llm=True)
+        torch.cuda.synchronize()
+        for m in model.modalities:
+            w = getattr(model, f"{m}_llm_proj").weight.float().abs()
+            room = (out["z"][m].abs() * 2.0 ** -10 + 1e-6).reshape(1, 7 * 32, -1) @ w.t()
+            res["ragged7"][f"llm_{m}"] = {"inputs": out["inputs_llm"][m].cpu(), "atts": out["atts_llm"][m].cpu(), "room": room.cpu()}
         torch.save(res, out_path)
     finally:
         if ws > 1:
@@ -167,6 +175,14 @@ def test_sharded_scores_and_spans_equal_the_single_process_run(tmp_path):
             assert (got["fused"] - ref["fused"]).abs().max().item() <= 1e-6, (name, r)
             assert (got["logit_audio"] - ref["logit_audio"]).abs().max().item() <= 1e-6, (name, r)
         assert torch.equal(ranks[0][name]["fused"], ranks[1][name]["fused"])   # the ranks agree bit for bit
+    for m in ("video", "audio"):          # encode_fuse(want_llm=True): the gather branch packs what the single process packs
+        ref = single["ragged7"][f"llm_{m}"]
+        assert ref["inputs"].shape == (1, 7 * 32, 4096) and ref["atts"].shape == (1, 7 * 32) and bool((ref["atts"] == 1).all())
+        for r, rk in enumerate(ranks):
+            got = rk["ragged7"][f"llm_{m}"]
+            assert got["inputs"].shape == ref["inputs"].shape and torch.equal(got["atts"], ref["atts"]), (m, r)
+            assert bool(((got["inputs"] - ref["inputs"]).abs() <= ref["room"]).all()), (m, r, (got["inputs"] - ref["inputs"]).abs().max().item())
+        assert torch.equal(ranks[0]["ragged7"][f"llm_{m}"]["inputs"], ranks[1]["ragged7"][f"llm_{m}"]["inputs"])
 
 
 def test_config4_per_rank_shape_two_ranks_equal_one_process(tmp_path):

@@ -237,6 +237,15 @@ def test_model_multi_query_against_one_call_per_video_and_query(dev):
         for m in model.modalities:
             getattr(model, f"{m}_Qformer").set_option("multi_core", core)
         check_model_against_single_calls(model, samples, model.encode_fuse_multi(samples, PROMPTS))
+    # one stream or one per modality: the same launches, so the same bits
+    assert model.overlap_modalities
+    forked = model.encode_fuse_multi(samples, PROMPTS)
+    model.overlap_modalities = False
+    plain = model.encode_fuse_multi(samples, PROMPTS)
+    model.overlap_modalities = True
+    for key in ("fused", "spans", "windows", "window_scores", "window_counts"):
+        assert all(torch.equal(a, b) for a, b in zip(forked[key], plain[key])), key
+    assert all(torch.equal(a, b) for m in model.modalities for a, b in zip(forked["logit"][m], plain["logit"][m]))
     strings = model.generate_multi(samples, PROMPTS)
     assert [len(s) for s in strings] == [3, 1]
     for row in strings:

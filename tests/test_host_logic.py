@@ -138,6 +138,59 @@ def test_text_output_windows_float_and_multi_window():
     assert tgt.tolist() == [[0.0, 1.0, 1.0, 0.0, 0.0, 1.0, 1.0]]
 
 
+def test_prompt_rows_in_the_three_orders_against_explicit_loops():
+    """The chain's text rows: ``compat_repeat`` (row k carries prompt k % bs), aligned (k // num) and multi-query (row (b * T + t) * P + p
+    carries prompt p of video b), the attention mask with the query-token ones in front of each row's own text mask."""
+    from mraudio_amd.models.xinstructblip import _prompt_rows
+
+    bs, num, P, L, Q = 2, 3, 2, 4, 32
+    g = torch.Generator().manual_seed(3)
+    ids = torch.randint(1000, 30000, (bs, L), generator=g)
+    tmask = torch.tensor([[1, 1, 1, 0], [1, 1, 0, 0]])
+
+    def check(got, want_ids, want_tm):
+        got_ids, att = got
+        assert got_ids.tolist() == want_ids and att.dtype == torch.long and att.shape == (len(want_ids), Q + L)
+        assert att.tolist() == [[1] * Q + row for row in want_tm]
+
+    n = bs * num
+    check(_prompt_rows(ids, tmask, Q, num, tile=True), [ids[k % bs].tolist() for k in range(n)], [tmask[k % bs].tolist() for k in range(n)])
+    check(_prompt_rows(ids, tmask, Q, num), [ids[k // num].tolist() for k in range(n)], [tmask[k // num].tolist() for k in range(n)])
+    assert _prompt_rows(ids, tmask, Q, num, tile=True)[0][1].tolist() == ids[1].tolist() != ids[0].tolist() == _prompt_rows(ids, tmask, Q, num)[0][1].tolist()
+    ids_p = torch.randint(1000, 30000, (bs * P, L), generator=g)                     # row b * P + p
+    tm_p = torch.tensor([[1, 1, 1, 1], [1, 0, 0, 0], [1, 1, 0, 0], [1, 1, 1, 0]])
+    order = [b * P + p for b in range(bs) for t in range(num) for p in range(P)]
+    check(_prompt_rows(ids_p, tm_p, Q, num, P), [ids_p[r].tolist() for r in order], [tm_p[r].tolist() for r in order])
+    check(_prompt_rows(ids, tmask, Q), ids.tolist(), tmask.tolist())                # no position count: the rows as given
+
+
+def test_timestamps_default_and_tensor_valued():
+    from mraudio_amd.models.xinstructblip import _timestamps
+
+    assert _timestamps({}, 2, 3) == [[0, 1, 2], [0, 1, 2]]
+    assert _timestamps({"timestamps": None}, 1, 2) == [[0, 1]]
+    assert _timestamps({"timestamps": [torch.tensor([0, 2, 4]), (1, 3, 5)]}, 2, 3) == [[0, 2, 4], [1, 3, 5]]
+    assert _timestamps({"timestamps": torch.tensor([[0.5, 2.5], [1.0, 3.0]])}, 2, 2) == [[0.5, 2.5], [1.0, 3.0]]
+
+
+def test_single_query_targets_are_row_0_of_the_multi_query_targets():
+    from mraudio_amd.models.xinstructblip import XInstructBLIP as X
+
+    stub = type("S", (), {"_device": torch.device("cpu"), "parse_windows": X.parse_windows})()
+    stamps = [[0, 5, 10, 15, 20, 25, 30], torch.tensor([0.0, 2.5, 5.0, 7.5, 10.0, 12.5, 15.0])]
+    texts = ["[[4.5, 10.2], [24.9, 30]]", "[[-1, -1]]", "[[2.5, 7.5]]", "[[12, 5]]"]
+    for ts in stamps:
+        want = [[float(any(min(a, b) <= float(t) <= max(a, b) for a, b in X.parse_windows(txt))) for t in ts] for txt in texts]
+        multi = X._multi_targets(stub, {"timestamps": [ts]}, [texts], 7)
+        assert len(multi) == 1 and multi[0].tolist() == want and any(map(any, want))
+        for p, txt in enumerate(texts):
+            single = X._targets(stub, {"timestamps": [ts], "text_output": [txt]}, 1, 7)
+            assert torch.equal(single[0], X._multi_targets(stub, {"timestamps": [ts]}, [[txt] + texts], 7)[0][0]) and single.tolist() == [want[p]]
+    # no timestamps: positions 0 .. num - 1; no text_output: no window
+    assert X._targets(stub, {"text_output": ["[[1, 2]]", "[[0, 0]]"]}, 2, 4).tolist() == [[0.0, 1.0, 1.0, 0.0], [1.0, 0.0, 0.0, 0.0]]
+    assert X._targets(stub, {}, 2, 3).tolist() == [[0.0] * 3] * 2
+
+
 def test_batched_encode_is_sample_major_and_sharded():
     """Row A1: the reference's T sequential encoder calls at batch B (models/xinstructblip.py:262-275) followed by
     ``cat(embeds)[indices]`` (:281-285) equal ONE sample-major [B*T] batch; a rank's [lo, hi) block touches only
