@@ -299,6 +299,34 @@ size_t mra_llm_proj_backward_workspace_bytes(mra_qformer* h, int32_t rows, int32
 int mra_llm_proj_backward(mra_qformer* h, const float* z, int32_t rows, const void* d_out, int32_t d_out_dtype, float* d_z, float* d_weight,
                           float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LoRA: the low-rank branch of one adapted linear of the attached LM ---------------------------------------
+ * replaces: the peft LoraLayer branch the reference configures in models/model_utils.py:4-14 (r = 8, lora_alpha = 8, lora_dropout = 0.05,
+ * bias "none") and applies at models/xinstructblip.py:163 -- restated from the published algorithm, unpinned to peft.  Stateless like
+ * mra_cosine_score: caller-owned buffers, a stream, no allocation, no synchronisation.  With x [rows][K], y [rows][N] in `dtype` (MRA_F16 /
+ * MRA_BF16; op = rounding to it), fp32 adapters A [R][K], B [N][R], s = alpha / R, q = 1 - p:
+ *   forward   u = mra_lora_down(x, A as RN, scale 1/q, p, seed);   mra_lora_up_add(y = x W^T, u, B as NR, scale s, p 0)
+ *   backward  du = mra_lora_down(dY, B as NR, scale s, p 0);        mra_lora_wgrad(dY, u -> dB as NR, scale s, p 0);
+ *             mra_lora_wgrad(x, du -> dA as RN, scale 1/q, p, seed);   mra_lora_up_add(dx = dY W, du, A as RN, scale 1/q, p, seed)
+ * A small fp32 matrix over (width index n, rank index j) is MRA_LORA_NR = [width][R] or MRA_LORA_RN = [R][width].  Dropout is counter based
+ * and never stored: element (m, n) of a [rows][width] tensor is kept when lowbias32(lo32(i) ^ lo32(seed) ^ hi32(i) * 0x9E3779B9 ^ hi32(seed))
+ * >= floor(p 2^32 + 0.5), i = m * width + n (the width, not the pitch); p == 0 hashes nothing.  The scale is applied as given (the caller
+ * passes 1/q).  Checked before any launch (MRA_EINVAL): NULL pointers, R outside 1..16, a width that is not a positive multiple of 8, pointers or
+ * pitches that are not 16-byte aligned, ld < width, p outside [0, 1), unknown dtype or layout, negative rows; rows == 0 is a no-op.
+ *
+ * out [rows][R] f32 (dense) = scale * drop(x)[rows][K] op(w)^T: matrix cores, fp32 accumulation, w rounded to `dtype` on its way in. */
+#define MRA_LORA_NR 0
+#define MRA_LORA_RN 1
+int mra_lora_down(const void* x, int64_t ldx, int32_t rows, int32_t K, int32_t dtype, const float* w, int32_t R, int32_t w_layout, float scale,
+                  double p, uint64_t seed, float* out, void* stream);
+/* y [rows][N] (`dtype`, pitch ldy) = op(float(y) + scale * keep * sum_j u[m][j] w(n, j)) IN PLACE: an fp32 fma chain from 0 with j ascending, then
+ * one fma onto float(y); a dropped element keeps its bits. */
+int mra_lora_up_add(void* y, int64_t ldy, int32_t rows, int32_t N, int32_t dtype, const float* u, int32_t R, const float* w, int32_t w_layout,
+                    float scale, double p, uint64_t seed, void* stream);
+/* dw (f32, dw_layout) += scale * drop(x)[rows][N]^T op(u)[rows][R]: the contraction over rows on the matrix cores, u rounded to `dtype` on load;
+ * a workgroup owns a column block and walks all rows in a fixed order (no atomics: two runs give the same bits). */
+int mra_lora_wgrad(const void* x, int64_t ldx, int32_t rows, int32_t N, int32_t dtype, const float* u, int32_t R, float* dw, int32_t dw_layout,
+                   float scale, double p, uint64_t seed, void* stream);
+
 /* ---- A6: scorer (build-defined; the reference has no scorer) ----------------------------------
  * sim[n][q] = cos(z[n][q][:], t[n or 0][:]); logit[n] = max_q sim[n][q].  sim may be NULL. */
 int mra_cosine_score(const float* z, const float* t, int32_t t_rows, int32_t items, int32_t n_query, int32_t hidden,

@@ -34,6 +34,7 @@ class mra_vit_cfg(C.Structure):
 
 
 MRA_BEATS_GATE_Q, MRA_BEATS_GATE_INPUT = 0, 1
+MRA_LORA_NR, MRA_LORA_RN = 0, 1                  # a small fp32 matrix stored [width][R] (lora_B) or [R][width] (lora_A)
 
 
 class mra_beats_cfg(C.Structure):
@@ -114,6 +115,12 @@ PROTOTYPES = {
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     "mra_cosine_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "mra_lora_down": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_double,
+                                C.c_uint64, C.c_void_p, C.c_void_p]),
+    "mra_lora_up_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+                                  C.c_double, C.c_uint64, C.c_void_p]),
+    "mra_lora_wgrad": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+                                 C.c_double, C.c_uint64, C.c_void_p]),
     "mra_fuse_logits": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p]),
     "mra_span_from_logits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),

@@ -232,6 +232,19 @@ int launch_rowgrad_gemm(const void* dY, const void* W, float* dX, int M, int K, 
 // op(z) [R][H]; every output may be NULL.  Lh % 64 == 0, H % 128 == 0.
 int launch_llm_proj_bwd(const void* dY, const void* z16, const void* W, int R, int Lh, int H, float* d_z, float* d_W, float* d_b, float* scratch,
                         int op_dtype, hipStream_t stream);
+// The low-rank branch of an adapted linear (lora.hip; R <= 16, widths and pitches multiples of 8 elements, 16-byte aligned rows).  A small fp32
+// matrix over (width index n, rank index j) is stored [width][R] (LORA_NR, as lora_B) or [R][width] (LORA_RN, as lora_A).  thr = round(p 2^32) is
+// the dropout threshold of keep(seed, m * width + n) (0: no mask, no hashing); the scale is the caller's (1/q, alpha / R, a loss scale divided out).
+enum LoraLayout { LORA_NR = 0, LORA_RN = 1 };
+// out [M][R] fp32 = scale * drop(X)[M][K] op(W)^T, X in the operand dtype with pitch ldx, W fp32 rounded on its way in.
+int launch_lora_down(const void* X, long long ldx, int M, int K, const float* W, int R, int w_layout, float scale, unsigned thr,
+                     unsigned long long seed, float* out, int op_dtype, hipStream_t stream);
+// Y [M][N] (operand dtype, pitch ld) = op(float(Y) + scale * keep * U [M][R] W), in place; fp32 fma chain over j ascending.
+int launch_lora_up_add(void* Y, long long ld, int M, int N, const float* U, int R, const float* W, int w_layout, float scale, unsigned thr,
+                       unsigned long long seed, int op_dtype, hipStream_t stream);
+// dW (fp32, either layout) += scale * drop(X)[M][N]^T op(U)[M][R]; a workgroup owns 32 columns and walks all rows, no atomics.
+int launch_lora_wgrad(const void* X, long long ld, int M, int N, const float* U, int R, float* dW, int dw_layout, float scale, unsigned thr,
+                      unsigned long long seed, int op_dtype, hipStream_t stream);
 // Backward of launch_modality_ln without an item index (enc_grad.hip): x [items][tokens][E] (x_dtype 0 / 1 / 2 = f32 / f16 / bf16), d_out fp32;
 // d_x (may be NULL, may be d_out) is written, d_gain / d_bias [E] (each may be NULL) are ADDED to.  E a multiple of 8, <= 4096.
 int launch_modality_ln_bwd(const void* x, int x_dtype, int items, int tokens, int E, const float* gain, float eps, const float* d_out, float* d_x,

@@ -11,6 +11,7 @@
 //     through row views (no slicing copies); the two feed-forwards run as one grouped launch;
 //   * residual stream, LayerNorm statistics and softmax are fp32; only MFMA operands are f16/bf16.
 // No allocation and no synchronisation after create/load; everything is enqueued on `stream`.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -1468,6 +1469,61 @@ int mra_windows_from_logits(const float* logits, int32_t videos, int32_t clips, 
   if (max_len < 0) return fail(MRA_EINVAL, "negative max_len (0 = no length cap)");
   return chk(launch_windows(logits, videos, clips, alpha, top_k, nms_thd, max_len, windows, scores, counts, as_stream(stream)),
              "windows_from_logits");
+}
+
+// ---- LoRA: the low-rank branch of an adapted linear of the attached LM (lora.hip) -------------------------------------------------------
+// replaces: the peft LoraLayer branch of models/model_utils.py:4-14, applied at models/xinstructblip.py:163.  Every check comes before a launch.
+namespace {
+
+bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// the checks the three entries share; *thr = floor(p 2^32 + 0.5), the threshold the Python side computes the same way
+int lora_check(const char* what, const void* t16, int64_t ld, int32_t rows, int32_t width, int32_t dtype, const void* a, const void* b, int32_t R,
+               int32_t layout, double p, unsigned* thr) {
+  const std::string w(what);
+  if (rows < 0) return fail(MRA_EINVAL, w + ": negative rows");
+  if (rows == 0) return MRA_OK;   // a no-op whatever else is passed (an empty tensor has no address)
+  if (!t16 || !a || !b) return fail(MRA_EINVAL, w + ": null argument");
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": dtype must be MRA_F16 or MRA_BF16");
+  if (layout != MRA_LORA_NR && layout != MRA_LORA_RN) return fail(MRA_EINVAL, w + ": layout must be MRA_LORA_NR or MRA_LORA_RN");
+  if (R < 1 || R > 16) return fail(MRA_EINVAL, w + ": R must be in 1..16");
+  if (width <= 0 || width % 8) return fail(MRA_EINVAL, w + ": the width (K / N) must be a positive multiple of 8");
+  if (ld < width) return fail(MRA_EINVAL, w + ": ld < width");
+  if (ld % 8) return fail(MRA_EINVAL, w + ": the pitch must be a multiple of 8 elements (16 bytes)");
+  if (!aligned16(t16) || !aligned16(a) || !aligned16(b)) return fail(MRA_EINVAL, w + ": pointers must be 16-byte aligned");
+  if (!(p >= 0.0 && p < 1.0)) return fail(MRA_EINVAL, w + ": p must be in [0, 1)");
+  const double t = std::floor(p * 4294967296.0 + 0.5);
+  *thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+  return MRA_OK;
+}
+
+}  // namespace
+
+int mra_lora_down(const void* x, int64_t ldx, int32_t rows, int32_t K, int32_t dtype, const float* w, int32_t R, int32_t w_layout, float scale,
+                  double p, uint64_t seed, float* out, void* stream) {
+  unsigned thr = 0;
+  if (int rc = lora_check("lora_down", x, ldx, rows, K, dtype, w, out, R, w_layout, p, &thr)) return rc;
+  if (rows == 0) return MRA_OK;
+  return chk(launch_lora_down(x, ldx, rows, K, w, R, w_layout, scale, thr, seed, out, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)),
+             "lora_down");
+}
+
+int mra_lora_up_add(void* y, int64_t ldy, int32_t rows, int32_t N, int32_t dtype, const float* u, int32_t R, const float* w, int32_t w_layout,
+                    float scale, double p, uint64_t seed, void* stream) {
+  unsigned thr = 0;
+  if (int rc = lora_check("lora_up_add", y, ldy, rows, N, dtype, u, w, R, w_layout, p, &thr)) return rc;
+  if (rows == 0) return MRA_OK;
+  return chk(launch_lora_up_add(y, ldy, rows, N, u, R, w, w_layout, scale, thr, seed, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)),
+             "lora_up_add");
+}
+
+int mra_lora_wgrad(const void* x, int64_t ldx, int32_t rows, int32_t N, int32_t dtype, const float* u, int32_t R, float* dw, int32_t dw_layout,
+                   float scale, double p, uint64_t seed, void* stream) {
+  unsigned thr = 0;
+  if (int rc = lora_check("lora_wgrad", x, ldx, rows, N, dtype, u, dw, R, dw_layout, p, &thr)) return rc;
+  if (rows == 0) return MRA_OK;
+  return chk(launch_lora_wgrad(x, ldx, rows, N, u, R, dw, dw_layout, scale, thr, seed, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)),
+             "lora_wgrad");
 }
 
 // ---- the Q-Former forward's own kernels, one launch each (include/mra.h; tests/test_gpu_qformer_kernels.py) ----------------------------

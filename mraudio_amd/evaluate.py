@@ -21,7 +21,7 @@ from .utils.spans import moment_str_to_list, post_process
 
 @torch.no_grad()
 def run_inference(model, dataloader: Iterable[dict], output_file: Optional[str] = None, with_saliency: bool = True,
-                  device=None, top_k: int = 1) -> List[dict]:
+                  device=None, top_k: int = 1, use_llm: bool = False) -> List[dict]:
     records: List[dict] = []
     fh = None
     if output_file:
@@ -30,7 +30,9 @@ def run_inference(model, dataloader: Iterable[dict], output_file: Optional[str] 
     for samples in dataloader:
         samples = prepare_sample(samples, device)
         scores = windows = None
-        if top_k > 1:   # ranked proposals: [start_s, end_s, score] triples in rank order, raw_out the multi-window string
+        if use_llm:     # the reference's own decode: the attached LM (with its LoRA adapters, in eval mode) writes the answer
+            outputs = model.generate_llm(samples)
+        elif top_k > 1:   # ranked proposals: [start_s, end_s, score] triples in rank order, raw_out the multi-window string
             outputs, windows, scores = model.generate_windows(samples)
             if not with_saliency:
                 scores = None
@@ -126,6 +128,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--group-by-video", action="store_true",
                     help="encode every video once and score its queries together over one shared K/V cache (same records, annotation order)")
     ap.add_argument("--max-queries-per-call", type=int, default=16, help="with --group-by-video: most queries of one video scored in one call")
+    ap.add_argument("--llm-path", default=None, help="local directory of the causal LM (local_files_only, bf16): predictions then come from "
+                                                     "generate_llm, the reference's decode")
+    ap.add_argument("--lora", action="store_true", help="with --llm-path: put LoRA adapters on the LM and load their weights (llm_model.* keys) from --checkpoint")
+    ap.add_argument("--lora-r", type=int, default=8)
+    ap.add_argument("--lora-alpha", type=float, default=8.0)
+    ap.add_argument("--lora-dropout", type=float, default=0.05)
     ap.add_argument("--video-on-device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is normalised there (mra_video_frames_forward) instead of as float32 "
                          "pixels made on the host")
@@ -138,15 +146,37 @@ def main(argv=None) -> None:
     from .models.xinstructblip import XInstructBLIP
     from .utils.mr_dataset import MRDataset, SyntheticMRDataset, VideoGroupedDataset, collate_fn, collate_grouped
 
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.lora and not args.llm_path:
+        parser.error("--lora needs --llm-path DIR")
+    if args.llm_path and (args.group_by_video or args.top_k > 1):
+        parser.error("--llm-path decodes one answer per query: not with --group-by-video or --top-k")
     n_frms = 60 if args.dataset == "QVH" else 20
     vproc = None
     if args.video_on_device:
         from .processors.alpro_processors import AlproVideoEvalProcessor_Stamps
         vproc = AlproVideoEvalProcessor_Stamps(n_frms=n_frms, image_size=224, device=args.device)
-    model = XInstructBLIP(args.model_path, args.audio_encoder, device=args.device, checkpoint=args.checkpoint, checkpoint_strict=not args.partial_checkpoint,
+    llm = tok = None
+    if args.llm_path:
+        from transformers import AutoModelForCausalLM, AutoTokenizer
+        if not os.path.isdir(args.llm_path):
+            raise SystemExit(f"--llm-path {args.llm_path!r} is not a local directory (hub names are not fetched)")
+        llm = AutoModelForCausalLM.from_pretrained(args.llm_path, local_files_only=True, torch_dtype=torch.bfloat16).to(args.device).eval()
+        tok = AutoTokenizer.from_pretrained(args.llm_path, local_files_only=True, use_fast=False)
+        llm.requires_grad_(False)
+    model = XInstructBLIP(args.model_path, args.audio_encoder, device=args.device, checkpoint=None if args.lora else args.checkpoint,
+                          checkpoint_strict=not args.partial_checkpoint,
                           cross_precision=args.cross_precision, top_k=args.top_k, nms_thd=args.nms_thd, max_window=args.max_window,
-                          **({} if vproc is None else {"video_processor": vproc}))
+                          **({} if vproc is None else {"video_processor": vproc}),
+                          **({} if llm is None else {"op_dtype": torch.bfloat16, "llm_hidden_size": llm.get_input_embeddings().weight.shape[1]}))
+    if llm is not None:
+        model.attach_llm(llm, tok)
+        if args.lora:       # the adapters must exist before the file's llm_model.* keys can be routed into them
+            model.enable_lora(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout)
+            if args.checkpoint:
+                model.load_checkpoint(args.checkpoint, strict=not args.partial_checkpoint)
+        model.eval()
     print(f"weights: {model.weights_source}")
     if args.synthetic:
         ds = SyntheticMRDataset(args.synthetic, T=n_frms)
@@ -158,7 +188,7 @@ def main(argv=None) -> None:
         recs = run_inference_grouped(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k)
     else:
         dl = DataLoader(ds, shuffle=False, batch_size=args.batch_size, num_workers=args.num_workers, collate_fn=collate_fn)
-        recs = run_inference(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k)
+        recs = run_inference(model, dl, args.output_file, device=torch.device(args.device), top_k=args.top_k, use_llm=llm is not None)
     print(f"wrote {len(recs)} predictions to {args.output_file}")
 
 

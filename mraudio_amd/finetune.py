@@ -57,7 +57,7 @@ def build_llm_model(args):
                           checkpoint_strict=not args.partial_checkpoint, cross_precision=args.cross_precision,
                           llm_hidden_size=llm.get_input_embeddings().weight.shape[1])
     model.attach_llm(llm, tok)
-    return model
+    return model       # --lora: Trainer calls model.enable_lora (after the bf16 cast above, so the adapters stay fp32 masters)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -96,6 +96,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "the checkpoints then carry {m}_llm_proj.*")
     ap.add_argument("--llm-path", default=None, help="local directory of the causal LM (loaded with local_files_only, frozen, bf16); "
                                                      "required by --objective llm / both")
+    ap.add_argument("--lora", action="store_true",
+                    help="train LoRA adapters on every linear of the LM except lm_head (the reference's trainable set; HIP low-rank forward and "
+                         "backward); needs --llm-path and --objective llm / both; the checkpoints then carry llm_model.*lora_{A,B}*")
+    ap.add_argument("--lora-r", type=int, default=8, help="with --lora: the rank (at most 16)")
+    ap.add_argument("--lora-alpha", type=float, default=8.0, help="with --lora: the scale is lora-alpha / lora-r")
+    ap.add_argument("--lora-dropout", type=float, default=0.05, help="with --lora: dropout on the adapter branch's input, in [0, 1)")
+    ap.add_argument("--freeze-qformers", dest="train_qformers", action="store_false",
+                    help="keep the Q-Formers frozen (with --lora: the reference's step, only the adapters train)")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
                          "(mra_video_frames_forward) instead of as float32 pixels made on the host")
@@ -115,6 +123,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.objective != "score" and not args.llm_path:
         parser.error(f"--objective {args.objective} needs --llm-path DIR")
+    if args.lora and (args.objective == "score" or not args.llm_path):
+        parser.error("--lora needs --llm-path DIR and --objective llm or both")
     logging.basicConfig(level=logging.INFO)
     return run_train(args)
 

@@ -215,6 +215,7 @@ class XInstructBLIP(nn.Module):
     # reference :399-606) or "both" (bce + lm_weight * lm over ONE Q-Former forward per modality).  loss_scale: the LM term's
     # gradient is multiplied by it on its way into the LM and divided out again in the projection's backward (see forward_llm)
     objective, lm_weight, loss_scale = "score", 1.0, 1.0
+    lora = False                                 # LoRA adapters inside the attached LM (enable_lora): the reference's own trainable set
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
@@ -345,8 +346,11 @@ class XInstructBLIP(nn.Module):
     # ---- checkpoints (reference :737-816) --------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, assign=False):
         """Routes ``{m}_Qformer.*``, ``{m}_query_tokens``, ``{m}_ln.*``, ``{m}_llm_proj.*`` as the
-        reference does (``:769-816``); ``llm_model.*`` and encoder keys are ignored here (no LLM on
-        this path)."""
+        reference does (``:769-816``); encoder keys are ignored.  ``llm_model.*`` keys are ignored too (no LLM on this path) unless
+        ``enable_lora()`` was called: then, as in the reference (``:807-813``), they go into the LM's adapters (``load_lora_state_dict``);
+        adapter keys the file lacks are listed as missing ``llm_model.*`` keys but, as there (``:815``), never make ``strict`` raise.
+        A file whose keys are ALL ``llm_model.*`` -- what the reference's trainer writes, and this one's with frozen Q-Formers -- is an
+        adapter file: with LoRA on it says nothing about the Q-Former side, which keeps its weights and is neither reported nor raised on."""
         missing, unexpected = [], []
         for m in self.modalities:
             sub = {".".join(k.split(".")[1:]): v for k, v in state_dict.items() if k.split(".")[0] == f"{m}_Qformer"}
@@ -366,17 +370,29 @@ class XInstructBLIP(nn.Module):
         unexpected += [k for k in state_dict if not k.startswith(known) and k.split(".")[0] != "llm_model"
                        and "encoder" not in k.split(".")[0]]
         self._extras_dirty = True
+        lora_missing = []
+        lora_sd = {k[len("llm_model."):]: v for k, v in state_dict.items() if k.startswith("llm_model.")} if self.lora else {}
+        if lora_sd:
+            from .lora import load_lora_state_dict
+            miss, unexp = load_lora_state_dict(self.llm_model, lora_sd)
+            lora_missing = [f"llm_model.{k}" for k in miss]
+            unexpected += [f"llm_model.{k}" for k in unexp]
+            if all(k.startswith("llm_model.") for k in state_dict):
+                missing = []
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict for XInstructBLIP: missing {missing}, unexpected {unexpected}")
-        return _IncompatibleKeys(missing, unexpected)
+        return _IncompatibleKeys(missing + lora_missing, unexpected)
 
     def _load_file(self, filename, strict: bool):
         ckpt = torch.load(filename, map_location="cpu", weights_only=True)
         sd = ckpt["model"] if "model" in ckpt else ckpt
         mine = [k for k in sd if k.startswith(tuple(f"{m}_" for m in self.modalities))]
-        if not mine:
+        if not mine and not (self.lora and any(k.startswith("llm_model.") for k in sd)):
             raise RuntimeError(f"{filename}: no key of this model's modalities {self.modalities} found")
         msg = self.load_state_dict(sd, strict=strict)
+        if not mine:            # an adapter file: the Q-Former side is what it was
+            self.weights_source = f"{getattr(self, 'weights_source', 'seeded init')} + LoRA adapters of {filename}"
+            return msg
         self.weights_source = f"checkpoint {filename}"
         if msg.missing_keys:
             self.weights_source += f" ({len(msg.missing_keys)} parameters NOT in the file keep their previous values)"
@@ -878,6 +894,49 @@ class XInstructBLIP(nn.Module):
                                                 enumerate_inputs=enumerate_inputs, interleave_seconds=interleave_seconds,
                                                 max_txt_len=self.max_txt_len, max_output_txt_len=self.max_output_txt_len, device=self._device)
 
+    def enable_lora(self, r: int = 8, alpha: float = 8, dropout: float = 0.05) -> None:
+        """LoRA adapters on every linear of the attached LM except ``lm_head`` -- the reference's own trainable set (``:147-165``,
+        ``models/model_utils.py``; ``models/lora.py`` here).  Needs ``attach_llm`` first; a second call changes nothing.  The adapters are
+        the LM's parameters: outside ``state_dict()``, listed by ``lora_parameters()``, saved by the trainer under ``llm_model.*``.  With
+        ``objective`` "llm" / "both" the Q-Formers may then stay frozen (the reference's regime): the Q-Former side runs without grad and the
+        loss is differentiable with respect to the adapters; with ``enable_qformer_training()`` as well everything trains together."""
+        from .lora import apply_lora, lora_modules
+
+        if self.llm_model is None:
+            raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
+        if self.lora:
+            return
+        apply_lora(self.llm_model, r=r, alpha=alpha, dropout=dropout)
+        self._lora_mods = list(lora_modules(self.llm_model).values())
+        if not self._lora_mods:
+            raise MraError("the attached LM has no nn.Linear to adapt")
+        self.lora = True
+        for mod in self._lora_mods:
+            mod.train(self.training)
+
+    def lora_parameters(self) -> List[nn.Parameter]:
+        from .lora import lora_parameters
+
+        return lora_parameters(self.llm_model) if self.lora else []
+
+    def train(self, mode: bool = True):
+        """The attached LM is not a submodule and keeps its own mode; its adapters follow this model's (their dropout is a training-mode op)."""
+        nn.Module.train(self, mode)
+        if self.lora:
+            for mod in self._lora_mods:
+                mod.train(mode)
+        return self
+
+    def _lora_loss(self, loss: torch.Tensor) -> torch.Tensor:
+        """With the Q-Formers frozen the LM loss reaches only the adapters: its gradient carries ``loss_scale`` into the LM here (with the
+        Q-Formers training ``_lm_loss`` does it) and every ``LoraLinear`` divides it out of its adapter gradients in fp32."""
+        return _ScaleGrad.apply(loss, float(self.loss_scale)) if self.loss_scale != 1.0 and loss.requires_grad else loss
+
+    def _lora_unscale(self) -> None:
+        if self.lora:
+            for mod in self._lora_mods:
+                mod.grad_unscale = 1.0 / float(self.loss_scale)
+
     def _llm_inputs(self, samples):
         if self.prompt_assembler is None:
             raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
@@ -912,7 +971,9 @@ class XInstructBLIP(nn.Module):
         ones flush to zero before they reach the projection: use bf16, or set ``loss_scale`` (e.g. 1024): the LM term's gradient is
         multiplied by it going into the LM and divided out in fp32 inside the projection's backward, so the loss value and the
         gradients of the projections, Q-Formers and LayerNorms are unscaled.  Gradients of parameters INSIDE the LM are then
-        ``loss_scale`` times too large (divide them yourself): a frozen LM is the intended use."""
+        ``loss_scale`` times too large (divide them yourself): a frozen LM is the intended use.  The LoRA adapters of ``enable_lora()`` are
+        the exception: each ``LoraLinear`` divides the scale out of its own gradients in fp32, so adapter ``.grad``s are unscaled.  With
+        LoRA on and the Q-Formers frozen, ``train=False`` is the training route (the reference's regime)."""
         if train is None:
             train = self.objective != "score" and getattr(self, "train_qformers", False)
         if train:
@@ -924,7 +985,9 @@ class XInstructBLIP(nn.Module):
             return {"loss": self._lm_loss(samples, inputs_llm)}
         inputs_llm, atts_llm = self._llm_inputs(samples)
         embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, inputs_llm, atts_llm)
-        return {"loss": self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss}
+        self._lora_unscale()
+        loss = self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
+        return {"loss": self._lora_loss(loss) if self.lora else loss}
 
     _WINDOW = re.compile(r"\[\s*(-?\d+(?:\.\d+)?)\s*,\s*(-?\d+(?:\.\d+)?)\s*\]")
 
@@ -1007,8 +1070,20 @@ class XInstructBLIP(nn.Module):
                 raise MraError(f"objective must be 'score', 'llm' or 'both', got {self.objective!r}")
             if grouped:
                 raise MraError(f"objective {self.objective!r} has no multi-query form: train grouped batches with objective 'score'")
+            frozen = self.lora and not getattr(self, "train_qformers", False)     # the reference's regime: only the adapters train
             if self.objective == "llm":
-                return self.forward_llm(samples, train=True)
+                return self.forward_llm(samples, train=not frozen)
+            if frozen:
+                with torch.no_grad():
+                    out = self.encode_fuse(samples, want_llm=True)
+                    bce = nn.functional.binary_cross_entropy_with_logits(out["fused"].view(out["bs"], out["num"]) * 20.0,
+                                                                         self._targets(samples, out["bs"], out["num"]))
+                dt = self.llm_model.get_input_embeddings().weight.dtype
+                embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in out["inputs_llm"].items()},
+                                                                               out["atts_llm"])
+                self._lora_unscale()
+                lm = self._lora_loss(self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss)
+                return {"loss": bce + self.lm_weight * lm, "loss_score": bce.detach(), "loss_lm": lm.detach()}
             self._check_lm_training()
             per_mod, inputs_llm, bs, num = self._train_pass(samples, want_score=True, want_llm=True)
             bce, lm = self._score_loss(samples, per_mod, bs, num), self._lm_loss(samples, inputs_llm)
@@ -1066,6 +1141,7 @@ class XInstructBLIP(nn.Module):
         dt = self.llm_model.get_input_embeddings().weight.dtype
         atts = {m: torch.ones(v.shape[0], v.shape[1], dtype=torch.long, device=self._device) for m, v in inputs_llm.items()}
         embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in inputs_llm.items()}, atts)
+        self._lora_unscale()
         loss = self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
         return _ScaleGrad.apply(loss, float(self.loss_scale)) if self.loss_scale != 1.0 else loss
 

@@ -29,6 +29,11 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     loss, carried through ``{m}_llm_proj`` into the Q-Formers (``XInstructBLIP.forward_llm``).  The model is handed over with its (frozen)
     LM attached; the LM is neither optimized nor saved.  Validation stays on the scorer: ``"both"`` is the objective under which
     ``MR-full-R1-avg`` says something about what was trained.
+  * ``args.lora`` with ``args.lora_r`` / ``lora_alpha`` / ``lora_dropout`` (``finetune --lora``; needs an LM objective): LoRA adapters inside
+    the attached LM (``XInstructBLIP.enable_lora``), the reference's own trainable set.  They join the optimizer behind the flat parameters,
+    are averaged with the other non-flat gradients, and the checkpoints carry them as ``llm_model.base_model.model.<path>.lora_{A,B}.default.weight``
+    (the reference's keys); resume and ``_reload_best_model`` restore them.  ``args.train_qformers = False`` (``--freeze-qformers``) with
+    ``lora`` is the reference's step: frozen Q-Formers, only the adapters train and reach the checkpoint.
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -108,6 +113,12 @@ class Trainer:
             if getattr(model, "llm_model", None) is None:
                 raise RuntimeError(f"objective {self.objective!r} needs a model with an LM attached (attach_llm; finetune --llm-path)")
             model.objective, model.lm_weight = self.objective, float(getattr(args, "lm_weight", 1.0))
+        self.lora = bool(getattr(args, "lora", False))
+        if self.lora:
+            if self.objective == "score":
+                raise ValueError("lora trains the LM's adapters: it needs objective 'llm' or 'both'")
+            model.enable_lora(r=int(getattr(args, "lora_r", 8)), alpha=float(getattr(args, "lora_alpha", 8)),
+                              dropout=float(getattr(args, "lora_dropout", 0.05)))
         if getattr(args, "train_qformers", True) and hasattr(model, "enable_qformer_training"):
             # train_ln (or args.train_ln): the modality LayerNorms train with the Q-Formers and reach the checkpoints; train_proj likewise
             # the projections into the LM
@@ -118,6 +129,8 @@ class Trainer:
             params = model.flat_optimizer_params()      # one flat parameter per Q-Former: one fused update launch
         else:
             params = [p for p in model.parameters() if p.requires_grad]
+        if self.lora:
+            params = params + model.lora_parameters()       # the adapters live in the LM, which is not a submodule
         if not params:
             raise RuntimeError("the model has no trainable parameter")
         lr = float(getattr(args, "lr", 3e-4))
@@ -201,6 +214,8 @@ class Trainer:
                     covered.update(id(p) for p in qf.parameters())
                     covered.add(id(getattr(self.model, f"{m}_query_tokens")))
         rest = [p.grad for p in self.model.parameters() if p.requires_grad and p.grad is not None and id(p) not in covered]
+        if self.lora:
+            rest += [p.grad for p in self.model.lora_parameters() if p.grad is not None]
         if rest:
             flat = torch.cat([g.reshape(-1).float() for g in rest])
             dist.all_reduce(flat)
@@ -269,6 +284,9 @@ class Trainer:
         trainable = {k for k, v in self.model.named_parameters() if v.requires_grad}
         named = {k for k, _ in self.model.named_parameters()}
         state = {k: v.detach().cpu() for k, v in self.model.state_dict().items() if k in trainable or k not in named}
+        if self.lora:
+            from ..models.lora import lora_state_dict
+            state.update({f"llm_model.{k}": v.cpu() for k, v in lora_state_dict(self.model.llm_model).items()})
         os.makedirs(self.output_dir, exist_ok=True)
         save_to = os.path.join(self.output_dir, "checkpoint_{}.pth".format("best" if is_best else cur_epoch))
         log.info("Saving checkpoint at epoch %d to %s.", cur_epoch, save_to)
