@@ -327,6 +327,36 @@ int mra_lora_up_add(void* y, int64_t ldy, int32_t rows, int32_t N, int32_t dtype
 int mra_lora_wgrad(const void* x, int64_t ldx, int32_t rows, int32_t N, int32_t dtype, const float* u, int32_t R, float* dw, int32_t dw_layout,
                    float scale, double p, uint64_t seed, void* stream);
 
+/* ---- LM objective: the vocabulary head and its cross-entropy on the labelled rows only -------------------------
+ * replaces: lm_head over every position + ForCausalLMLoss inside the reference's self.llm_model(inputs_embeds=..., attention_mask=...,
+ * return_dict=True, labels=targets) (models/xinstructblip.py:599-604), of which only the labelled rows matter.  Stateless like mra_lora_*:
+ * caller-owned buffers, a stream, no allocation, no synchronisation.  h [R][K] (`dtype` MRA_F16 / MRA_BF16, pitch ldh: the gathered hidden
+ * rows after the LM's final norm), W [V][K] (same dtype, pitch ldw: lm_head.weight as stored; never copied, transposed or converted),
+ * labels int32 [R].  z = h W^T in fp32, never rounded to 16 bits;  lse_r = log sum_v exp z_rv;  nll_r = lse_r - z_r,y_r;
+ * dh_r = g_r (softmax(z_r) - e_y_r) W.  A label outside [0, V) reads nothing out of bounds: that row's nll is NaN (its lse is right) and its
+ * dh row is the softmax term g_r softmax(z_r) W alone.
+ * Checked before any launch (MRA_EINVAL, named in mra_last_error): negative R, V < 1, K not a positive multiple of 8, unknown dtype, NULL
+ * pointers, h / dh / W / workspace not 16-byte aligned, labels / nll / lse / g not 4-byte aligned, a pitch < K or not a multiple of 8, a short
+ * workspace.  R == 0 launches nothing, touches nothing and returns MRA_OK whatever else is passed.
+ *
+ * Workspace bytes, with T = ceil(V / 64) vocabulary tiles, up(x) = x rounded up to 256, and
+ * S = ceil(T / ceil(T / min(16, max(1, 512 / (ceil(K / 128) * ceil(R / 128))))))  (integer divisions) splits of the backward's sum over V:
+ *     2 up(4 R T) + up(4 R)                       tile maxima, tile sums [R][T] f32, target logits [R] f32
+ *   + want_grad ? up(2 R 64 T) + up(4 S R K) : 0  P~ = op(exp(z - tile maximum)) [R][64 T] in `dtype`, partial sums [S][R][K] f32
+ * Host only; 0 (and a message) for arguments the entries would refuse. */
+size_t mra_lm_head_ce_workspace_bytes(int32_t R, int32_t V, int32_t K, int32_t dtype, int32_t want_grad);
+/* One streaming pass over W (a workgroup owns a 64-column vocabulary tile; the ragged tail past V is excluded from maximum and sum) and a merge
+ * launch with a fixed order: nll, lse f32 [R].  want_grad != 0 also leaves P~ and the tile maxima in the workspace for the backward; the nll
+ * bits do not depend on it. */
+int mra_lm_head_ce_forward(const void* h, int64_t ldh, int32_t R, int32_t K, const void* W, int64_t ldw, int32_t V, int32_t dtype,
+                           const int32_t* labels, float* nll, float* lse, void* workspace, size_t workspace_bytes, int32_t want_grad, void* stream);
+/* dh [R][K] (`dtype`, pitch lddh) = sum_v f_rv P~_rv W_v - g_r W_y_r from the workspace a want_grad forward of the same (R, V, K, W, labels)
+ * left; g f32 [R] on the device; the fp32 row factors f = g_r exp(tile maximum - lse_r) are applied inside the product (per tile, to the fp32
+ * tile product).  The sum over V is split over S workgroup rows whose fp32 partial sums are added in ascending order, then the one-hot term is
+ * subtracted in fp32 and the result rounded once.  No atomics: two runs give the same bits. */
+int mra_lm_head_ce_backward(const float* g, const void* W, int64_t ldw, int32_t V, int32_t K, int32_t dtype, const int32_t* labels, const float* lse,
+                            void* workspace, size_t workspace_bytes, void* dh, int64_t lddh, int32_t R, void* stream);
+
 /* ---- A6: scorer (build-defined; the reference has no scorer) ----------------------------------
  * sim[n][q] = cos(z[n][q][:], t[n or 0][:]); logit[n] = max_q sim[n][q].  sim may be NULL. */
 int mra_cosine_score(const float* z, const float* t, int32_t t_rows, int32_t items, int32_t n_query, int32_t hidden,

@@ -245,6 +245,25 @@ int launch_lora_up_add(void* Y, long long ld, int M, int N, const float* U, int 
 // dW (fp32, either layout) += scale * drop(X)[M][N]^T op(U)[M][R]; a workgroup owns 32 columns and walks all rows, no atomics.
 int launch_lora_wgrad(const void* X, long long ld, int M, int N, const float* U, int R, float* dW, int dw_layout, float scale, unsigned thr,
                       unsigned long long seed, int op_dtype, hipStream_t stream);
+// The LM head + cross-entropy on gathered rows (lm_head.hip).  Geometry the workspace layout depends on: 64-column vocabulary tiles, 128-row
+// groups, 128-column hidden blocks in the backward, whose contraction over V is split into at most 16 ranges of whole tiles (about 512
+// workgroups on a large shape); lm_head_splits is the number of fp32 partial-sum planes [R][K] the backward writes and reduces in order.
+constexpr int LM_HEAD_TILE = 64, LM_HEAD_ROWS = 128, LM_HEAD_KBLOCK = 128, LM_HEAD_MAX_SPLITS = 16;
+inline int lm_head_tiles(int V) { return (V + LM_HEAD_TILE - 1) / LM_HEAD_TILE; }
+inline int lm_head_splits(int R, int V, int K) {
+  const long long wgs = (long long)((K + LM_HEAD_KBLOCK - 1) / LM_HEAD_KBLOCK) * ((R + LM_HEAD_ROWS - 1) / LM_HEAD_ROWS);
+  long long smax = wgs > 0 ? 512 / wgs : 1;
+  smax = smax < 1 ? 1 : (smax > LM_HEAD_MAX_SPLITS ? LM_HEAD_MAX_SPLITS : smax);
+  const int nt = lm_head_tiles(V), tps = (int)((nt + smax - 1) / smax);
+  return (nt + tps - 1) / tps;
+}
+// H [R][K], W [V][K] (operand dtype, pitches ldh / ldw), labels int32 [R] -> nll, lse f32 [R]; tmax, tsum f32 [R][tiles], zy f32 [R] and
+// P (operand dtype [R][64 tiles], NULL: not written) are workspace.  One W pass + a merge launch.
+int launch_lm_head_fwd(const void* H, long long ldh, int R, int K, const void* W, long long ldw, int V, const int* labels, float* nll, float* lse,
+                       float* tmax, float* tsum, float* zy, void* P, int op_dtype, hipStream_t stream);
+// dh [R][K] (operand dtype, pitch lddh) = sum_v g_r exp(tmax - lse) P~ W - g_r W[y_r]; part f32 [lm_head_splits][R][K] is workspace.
+int launch_lm_head_bwd(const float* g, const void* W, long long ldw, int V, int K, const int* labels, const float* lse, const float* tmax,
+                       const void* P, float* part, void* dh, long long lddh, int R, int op_dtype, hipStream_t stream);
 // Backward of launch_modality_ln without an item index (enc_grad.hip): x [items][tokens][E] (x_dtype 0 / 1 / 2 = f32 / f16 / bf16), d_out fp32;
 // d_x (may be NULL, may be d_out) is written, d_gain / d_bias [E] (each may be NULL) are ADDED to.  E a multiple of 8, <= 4096.
 int launch_modality_ln_bwd(const void* x, int x_dtype, int items, int tokens, int E, const float* gain, float eps, const float* d_out, float* d_x,

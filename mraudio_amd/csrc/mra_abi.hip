@@ -1526,6 +1526,85 @@ int mra_lora_wgrad(const void* x, int64_t ldx, int32_t rows, int32_t N, int32_t 
              "lora_wgrad");
 }
 
+// ---- the LM head + cross-entropy on the labelled rows (lm_head.hip) ----------------------------------------------------------------------
+// replaces: lm_head + ForCausalLMLoss behind self.llm_model(..., labels=targets), models/xinstructblip.py:599-604.  Every check comes before a launch.
+namespace {
+
+size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+
+// the workspace, in this order: tmax, tsum [R][tiles] f32 | zy [R] f32 | (want_grad) P~ [R][64 tiles] 16-bit | part [splits][R][K] f32
+struct LmHeadWs {
+  size_t stat, zy, p, part, total;
+};
+LmHeadWs lm_head_ws(int32_t R, int32_t V, int32_t K, int32_t want_grad) {
+  LmHeadWs w{};
+  const size_t nt = (size_t)lm_head_tiles(V);
+  w.stat = up256(4 * (size_t)R * nt);
+  w.zy = up256(4 * (size_t)R);
+  w.p = want_grad ? up256(2 * (size_t)R * nt * LM_HEAD_TILE) : 0;
+  w.part = want_grad ? up256(4 * (size_t)lm_head_splits(R, V, K) * (size_t)R * (size_t)K) : 0;
+  w.total = 2 * w.stat + w.zy + w.p + w.part;
+  return w;
+}
+
+int lm_head_check(const std::string& w, int32_t R, int32_t K, int32_t V, int32_t dtype, const void* x16, int64_t ldx, const char* xname,
+                  const void* W, int64_t ldw, const void* labels, const void* a, const void* b, const void* workspace, size_t workspace_bytes, int32_t want_grad) {
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": dtype must be MRA_F16 or MRA_BF16");
+  if (V < 1) return fail(MRA_EINVAL, w + ": V must be at least 1");
+  if (K <= 0 || K % 8) return fail(MRA_EINVAL, w + ": K must be a positive multiple of 8");
+  if (!x16 || !W || !labels || !a || !b || !workspace) return fail(MRA_EINVAL, w + ": null argument");
+  if (ldx < K) return fail(MRA_EINVAL, w + ": " + xname + " < K");
+  if (ldw < K) return fail(MRA_EINVAL, w + ": ldw < K");
+  if (ldx % 8 || ldw % 8) return fail(MRA_EINVAL, w + ": the pitches must be multiples of 8 elements (16 bytes)");
+  if (!aligned16(x16) || !aligned16(W) || !aligned16(workspace)) return fail(MRA_EINVAL, w + ": h / dh, W and the workspace must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(labels) % 4 || reinterpret_cast<uintptr_t>(a) % 4 || reinterpret_cast<uintptr_t>(b) % 4)
+    return fail(MRA_EINVAL, w + ": labels and the fp32 vectors must be 4-byte aligned");
+  if (workspace_bytes < lm_head_ws(R, V, K, want_grad).total)
+    return fail(MRA_EINVAL, w + ": workspace too small (mra_lm_head_ce_workspace_bytes)");
+  return MRA_OK;
+}
+
+}  // namespace
+
+size_t mra_lm_head_ce_workspace_bytes(int32_t R, int32_t V, int32_t K, int32_t dtype, int32_t want_grad) {
+  if (R < 0 || V < 1 || K <= 0 || K % 8 || (dtype != MRA_F16 && dtype != MRA_BF16)) {
+    fail(MRA_EINVAL, "lm_head_ce_workspace_bytes: R >= 0, V >= 1, K a positive multiple of 8, dtype MRA_F16 or MRA_BF16");
+    return 0;
+  }
+  return lm_head_ws(R, V, K, want_grad != 0).total;
+}
+
+int mra_lm_head_ce_forward(const void* h, int64_t ldh, int32_t R, int32_t K, const void* W, int64_t ldw, int32_t V, int32_t dtype,
+                           const int32_t* labels, float* nll, float* lse, void* workspace, size_t workspace_bytes, int32_t want_grad, void* stream) {
+  const std::string w("lm_head_ce_forward");
+  if (R < 0) return fail(MRA_EINVAL, w + ": negative R");
+  if (R == 0) return MRA_OK;   // launches nothing, touches nothing
+  if (int rc = lm_head_check(w, R, K, V, dtype, h, ldh, "ldh", W, ldw, labels, nll, lse, workspace, workspace_bytes, want_grad != 0)) return rc;
+  const LmHeadWs ws = lm_head_ws(R, V, K, want_grad != 0);
+  char* base = static_cast<char*>(workspace);
+  float* tmax = reinterpret_cast<float*>(base);
+  float* tsum = reinterpret_cast<float*>(base + ws.stat);
+  float* zy = reinterpret_cast<float*>(base + 2 * ws.stat);
+  void* P = want_grad ? base + 2 * ws.stat + ws.zy : nullptr;
+  return chk(launch_lm_head_fwd(h, ldh, R, K, W, ldw, V, labels, nll, lse, tmax, tsum, zy, P, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)),
+             "lm_head_ce_forward");
+}
+
+int mra_lm_head_ce_backward(const float* g, const void* W, int64_t ldw, int32_t V, int32_t K, int32_t dtype, const int32_t* labels, const float* lse,
+                            void* workspace, size_t workspace_bytes, void* dh, int64_t lddh, int32_t R, void* stream) {
+  const std::string w("lm_head_ce_backward");
+  if (R < 0) return fail(MRA_EINVAL, w + ": negative R");
+  if (R == 0) return MRA_OK;
+  if (int rc = lm_head_check(w, R, K, V, dtype, dh, lddh, "lddh", W, ldw, labels, g, lse, workspace, workspace_bytes, 1)) return rc;
+  const LmHeadWs ws = lm_head_ws(R, V, K, 1);
+  char* base = static_cast<char*>(workspace);
+  const float* tmax = reinterpret_cast<const float*>(base);
+  const void* P = base + 2 * ws.stat + ws.zy;
+  float* part = reinterpret_cast<float*>(base + 2 * ws.stat + ws.zy + ws.p);
+  return chk(launch_lm_head_bwd(g, W, ldw, V, K, labels, lse, tmax, P, part, dh, lddh, R, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)),
+             "lm_head_ce_backward");
+}
+
 // ---- the Q-Former forward's own kernels, one launch each (include/mra.h; tests/test_gpu_qformer_kernels.py) ----------------------------
 // Every entry checks its arguments before any launch, allocates nothing and calls the launch function the forward calls.
 namespace {

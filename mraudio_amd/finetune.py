@@ -104,6 +104,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lora-dropout", type=float, default=0.05, help="with --lora: dropout on the adapter branch's input, in [0, 1)")
     ap.add_argument("--freeze-qformers", dest="train_qformers", action="store_false",
                     help="keep the Q-Formers frozen (with --lora: the reference's step, only the adapters train)")
+    ap.add_argument("--lm-loss", choices=("stock", "rows", "fused"), default="stock",
+                    help="how the LM loss is computed: stock = the LM's own forward with labels (lm_head over every position); rows = the LM's "
+                         "decoder, then lm_head + cross-entropy on the labelled rows only (torch ops); fused = the same on the HIP entries "
+                         "mra_lm_head_ce_* (no [B, S, V] tensor in either direction); rows / fused need --objective llm or both")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
                          "(mra_video_frames_forward) instead of as float32 pixels made on the host")
@@ -125,6 +129,8 @@ def main(argv=None):
         parser.error(f"--objective {args.objective} needs --llm-path DIR")
     if args.lora and (args.objective == "score" or not args.llm_path):
         parser.error("--lora needs --llm-path DIR and --objective llm or both")
+    if args.lm_loss != "stock" and args.objective == "score":
+        parser.error("--lm-loss rows / fused needs --objective llm or both")
     logging.basicConfig(level=logging.INFO)
     return run_train(args)
 

@@ -216,6 +216,9 @@ class XInstructBLIP(nn.Module):
     # gradient is multiplied by it on its way into the LM and divided out again in the projection's backward (see forward_llm)
     objective, lm_weight, loss_scale = "score", 1.0, 1.0
     lora = False                                 # LoRA adapters inside the attached LM (enable_lora): the reference's own trainable set
+    # how the LM loss is computed (_lm_ce): "stock" = the LM's own forward with labels (lm_head over every position), "rows" = the LM's decoder,
+    # then lm_head + cross-entropy on the labelled rows only as torch ops, "fused" = the same on the HIP entries (models/lm_head.py)
+    lm_loss = "stock"
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
@@ -225,8 +228,11 @@ class XInstructBLIP(nn.Module):
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
                  cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0,
-                 video_processor=None):
+                 video_processor=None, lm_loss: str = "stock"):
         super().__init__()
+        if lm_loss not in ("stock", "rows", "fused"):
+            raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
+        self.lm_loss = lm_loss
         self.model_path, self.audio_path = model_path, audio_path
         self.modalities = list(modalities) if modalities is not None else ["audio", "video"]  # reference :71
         self.max_txt_len = 128           # reference :75
@@ -937,6 +943,30 @@ class XInstructBLIP(nn.Module):
             for mod in self._lora_mods:
                 mod.grad_unscale = 1.0 / float(self.loss_scale)
 
+    def _lm_ce(self, embeds, mask, targets):
+        """The LM's cross-entropy on the answer tokens.  ``lm_loss = "stock"``: the LM's own forward with ``labels`` (the reference's call,
+        ``:599-604``; ``lm_head`` runs over every position).  ``"rows"`` / ``"fused"``: the LM's decoder alone, then ``lm_head_ce`` on the
+        final hidden states -- the head and the loss on the labelled rows only, as torch ops or on the HIP entries; ``lm_head`` itself is
+        never called, so its weight gets no gradient under ``"fused"`` (the reference never trains it)."""
+        if self.lm_loss == "stock":
+            return self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
+        if self.lm_loss not in ("rows", "fused"):
+            raise MraError(f"lm_loss must be 'stock', 'rows' or 'fused', got {self.lm_loss!r}")
+        from .lm_head import lm_head_ce
+
+        llm = self.llm_model
+        prefix = getattr(llm, "base_model_prefix", "")
+        dec = llm.get_decoder() if hasattr(llm, "get_decoder") else (getattr(llm, prefix, None) if prefix else None)
+        if dec is None or dec is llm:
+            raise MraError(f"lm_loss {self.lm_loss!r} needs an LM that exposes its decoder (get_decoder() or its base_model_prefix attribute)")
+        head = llm.get_output_embeddings() if hasattr(llm, "get_output_embeddings") else None
+        if head is None or getattr(head, "weight", None) is None:
+            raise MraError(f"lm_loss {self.lm_loss!r} needs an LM with an output embedding (get_output_embeddings())")
+        if getattr(head, "bias", None) is not None:
+            raise MraError(f"lm_loss {self.lm_loss!r}: the LM's output embedding has a bias, which the row-wise head does not take")
+        hidden = dec(inputs_embeds=embeds, attention_mask=mask, return_dict=True).last_hidden_state
+        return lm_head_ce(hidden, head.weight, targets, hip=False if self.lm_loss == "rows" else None)
+
     def _llm_inputs(self, samples):
         if self.prompt_assembler is None:
             raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
@@ -986,7 +1016,7 @@ class XInstructBLIP(nn.Module):
         inputs_llm, atts_llm = self._llm_inputs(samples)
         embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, inputs_llm, atts_llm)
         self._lora_unscale()
-        loss = self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
+        loss = self._lm_ce(embeds, mask, targets)
         return {"loss": self._lora_loss(loss) if self.lora else loss}
 
     _WINDOW = re.compile(r"\[\s*(-?\d+(?:\.\d+)?)\s*,\s*(-?\d+(?:\.\d+)?)\s*\]")
@@ -1082,7 +1112,7 @@ class XInstructBLIP(nn.Module):
                 embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in out["inputs_llm"].items()},
                                                                                out["atts_llm"])
                 self._lora_unscale()
-                lm = self._lora_loss(self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss)
+                lm = self._lora_loss(self._lm_ce(embeds, mask, targets))
                 return {"loss": bce + self.lm_weight * lm, "loss_score": bce.detach(), "loss_lm": lm.detach()}
             self._check_lm_training()
             per_mod, inputs_llm, bs, num = self._train_pass(samples, want_score=True, want_llm=True)
@@ -1142,7 +1172,7 @@ class XInstructBLIP(nn.Module):
         atts = {m: torch.ones(v.shape[0], v.shape[1], dtype=torch.long, device=self._device) for m, v in inputs_llm.items()}
         embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in inputs_llm.items()}, atts)
         self._lora_unscale()
-        loss = self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
+        loss = self._lm_ce(embeds, mask, targets)
         return _ScaleGrad.apply(loss, float(self.loss_scale)) if self.loss_scale != 1.0 else loss
 
     def _ln_train(self, m: str, raw: torch.Tensor) -> torch.Tensor:

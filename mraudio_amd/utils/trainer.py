@@ -34,6 +34,9 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     are averaged with the other non-flat gradients, and the checkpoints carry them as ``llm_model.base_model.model.<path>.lora_{A,B}.default.weight``
     (the reference's keys); resume and ``_reload_best_model`` restore them.  ``args.train_qformers = False`` (``--freeze-qformers``) with
     ``lora`` is the reference's step: frozen Q-Formers, only the adapters train and reach the checkpoint.
+  * ``args.lm_loss`` ("stock" | "rows" | "fused", ``finetune --lm-loss``; needs an LM objective unless "stock"): how the LM loss is computed
+    (``XInstructBLIP._lm_ce``).  "stock" is the LM's own forward with labels; "rows" and "fused" run the LM's decoder and then the head and
+    the cross-entropy on the labelled rows only, as torch ops or on the HIP entries ``mra_lm_head_ce_*`` (``models/lm_head.py``).
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -113,6 +116,13 @@ class Trainer:
             if getattr(model, "llm_model", None) is None:
                 raise RuntimeError(f"objective {self.objective!r} needs a model with an LM attached (attach_llm; finetune --llm-path)")
             model.objective, model.lm_weight = self.objective, float(getattr(args, "lm_weight", 1.0))
+        lm_loss = getattr(args, "lm_loss", None) or "stock"
+        if lm_loss not in ("stock", "rows", "fused"):
+            raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
+        if lm_loss != "stock":
+            if self.objective == "score":
+                raise ValueError("lm_loss changes how the LM loss is computed: it needs objective 'llm' or 'both'")
+            model.lm_loss = lm_loss
         self.lora = bool(getattr(args, "lora", False))
         if self.lora:
             if self.objective == "score":
