@@ -357,6 +357,27 @@ int mra_lm_head_ce_forward(const void* h, int64_t ldh, int32_t R, int32_t K, con
 int mra_lm_head_ce_backward(const float* g, const void* W, int64_t ldw, int32_t V, int32_t K, int32_t dtype, const int32_t* labels, const float* lse,
                             void* workspace, size_t workspace_bytes, void* dh, int64_t lddh, int32_t R, void* stream);
 
+/* ---- LM objective: prompt assembly as one row gather -------------------------------------------------------------
+ * replaces: the torch.cat of cue, media, timestamp, duration and prompt pieces in front of the LM (models/xinstructblip.py:341-381, :541-595)
+ * and, through the inverse plan, its backward.  Stateless like mra_lora_* and mra_lm_head_ce_*: caller-owned buffers, a stream, no allocation,
+ * no synchronisation.  out [n_rows][width] (out_dtype, pitch ldo);  plan int32 [n_rows][2] = (source, row) on the DEVICE;  srcs a HOST array.
+ *   out[i][0:width] = cast(srcs[s].ptr[r * srcs[s].ld + 0:width])   for plan[i] = (s, r), 0 <= s < n_src, 0 <= r < srcs[s].rows
+ *   s == -1 writes a row of +0;  every other entry out of range reads nothing and writes a row of NaN (as a bad label does in mra_lm_head_ce_*).
+ * Casts: f32 -> f16 / bf16 rounds to nearest even (overflow to infinity, NaN stays NaN); f16 / bf16 -> f32 is exact; equal types are a bit
+ * copy; f16 <-> bf16 is refused.  The backward of a gather whose rows are used at most once is the same entry with d_out as the one source and
+ * the inverse plan.  A wave owns an output row: no atomics, two runs give the same bits.
+ * Checked before any launch (MRA_EINVAL, named in mra_last_error): negative n_rows, NULL out / srcs / plan / a source's ptr, n_src outside 1..4,
+ * width not a positive multiple of 8, an unknown dtype or a refused pair, negative source rows, a pitch below width or not a multiple of 16
+ * bytes, out or a source not 16-byte aligned, plan not 8-byte aligned.  n_rows == 0 launches nothing and returns MRA_OK whatever else is passed. */
+typedef struct mra_rows_src {
+  const void* ptr; /* device, [rows][ld] of dtype */
+  int64_t ld;      /* pitch in elements */
+  int32_t rows;
+  int32_t dtype;   /* MRA_F32 / MRA_F16 / MRA_BF16 */
+} mra_rows_src;
+int mra_gather_rows(void* out, int64_t ldo, int32_t out_dtype, int32_t n_rows, int32_t width, const mra_rows_src* srcs, int32_t n_src,
+                    const int32_t* plan, void* stream);
+
 /* ---- A6: scorer (build-defined; the reference has no scorer) ----------------------------------
  * sim[n][q] = cos(z[n][q][:], t[n or 0][:]); logit[n] = max_q sim[n][q].  sim may be NULL. */
 int mra_cosine_score(const float* z, const float* t, int32_t t_rows, int32_t items, int32_t n_query, int32_t hidden,

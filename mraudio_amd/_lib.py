@@ -44,6 +44,11 @@ class mra_beats_cfg(C.Structure):
                 ("gate_from", C.c_int32), ("op_dtype", C.c_int32)]
 
 
+class mra_rows_src(C.Structure):
+    """include/mra.h mra_rows_src: one source of mra_gather_rows, ``[rows][ld]`` of ``dtype`` on the device."""
+    _fields_ = [("ptr", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("dtype", C.c_int32)]
+
+
 class mra_gemm_desc(C.Structure):
     """include/mra.h mra_gemm_desc: one problem of mra_debug_gemm / mra_debug_gemm_plan (the GemmProb fields of csrc/kernels.h the forwards
     set, plus the byte size of every buffer).  ``struct_bytes`` must be ``ctypes.sizeof(mra_gemm_desc)``."""
@@ -126,6 +131,8 @@ PROTOTYPES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     "mra_lm_head_ce_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "mra_gather_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(mra_rows_src), C.c_int32, C.c_void_p,
+                                  C.c_void_p]),
     "mra_fuse_logits": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p]),
     "mra_span_from_logits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),

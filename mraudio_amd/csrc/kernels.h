@@ -264,6 +264,12 @@ int launch_lm_head_fwd(const void* H, long long ldh, int R, int K, const void* W
 // dh [R][K] (operand dtype, pitch lddh) = sum_v g_r exp(tmax - lse) P~ W - g_r W[y_r]; part f32 [lm_head_splits][R][K] is workspace.
 int launch_lm_head_bwd(const float* g, const void* W, long long ldw, int V, int K, const int* labels, const float* lse, const float* tmax,
                        const void* P, float* part, void* dh, long long lddh, int R, int op_dtype, hipStream_t stream);
+// Row gather with a cast (prompt.hip): out [n_rows][width] (out_dtype 0 / 1 / 2 = f32 / f16 / bf16, pitch ldo) row i = source plan[i][0], row
+// plan[i][1]; source -1 -> +0, any other entry out of range -> NaN, nothing read.  The per-source arguments are host arrays of n_src <=
+// GATHER_MAX_SRC entries; plan int32 [n_rows][2] on the device.  width % 8 == 0, 16-byte aligned rows everywhere; a wave owns a row, no atomics.
+constexpr int GATHER_MAX_SRC = 4;
+int launch_gather_rows(void* out, long long ldo, int out_dtype, int n_rows, int width, const void* const* src_ptr, const long long* src_ld,
+                       const int* src_rows, const int* src_dtype, int n_src, const int* plan, hipStream_t stream);
 // Backward of launch_modality_ln without an item index (enc_grad.hip): x [items][tokens][E] (x_dtype 0 / 1 / 2 = f32 / f16 / bf16), d_out fp32;
 // d_x (may be NULL, may be d_out) is written, d_gain / d_bias [E] (each may be NULL) are ADDED to.  E a multiple of 8, <= 4096.
 int launch_modality_ln_bwd(const void* x, int x_dtype, int items, int tokens, int E, const float* gain, float eps, const float* d_out, float* d_x,

@@ -1605,6 +1605,43 @@ int mra_lm_head_ce_backward(const float* g, const void* W, int64_t ldw, int32_t 
              "lm_head_ce_backward");
 }
 
+// ---- prompt assembly: one row gather with a cast (prompt.hip) -----------------------------------------------------------------------------
+// replaces: the torch.cat in front of the LM, models/xinstructblip.py:341-381, :541-595.  Every check comes before a launch.
+int mra_gather_rows(void* out, int64_t ldo, int32_t out_dtype, int32_t n_rows, int32_t width, const mra_rows_src* srcs, int32_t n_src,
+                    const int32_t* plan, void* stream) {
+  const std::string w("gather_rows");
+  if (n_rows < 0) return fail(MRA_EINVAL, w + ": negative n_rows");
+  if (n_rows == 0) return MRA_OK;   // launches nothing, touches nothing
+  if (!out || !srcs || !plan) return fail(MRA_EINVAL, w + ": null argument");
+  if (n_src < 1 || n_src > GATHER_MAX_SRC) return fail(MRA_EINVAL, w + ": n_src must be in 1..4");
+  if (width <= 0 || width % 8) return fail(MRA_EINVAL, w + ": width must be a positive multiple of 8");
+  if (out_dtype != MRA_F32 && out_dtype != MRA_F16 && out_dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": unknown out_dtype");
+  if (ldo < width) return fail(MRA_EINVAL, w + ": ldo < width");
+  if (ldo % (out_dtype == MRA_F32 ? 4 : 8)) return fail(MRA_EINVAL, w + ": the output pitch must be a multiple of 16 bytes");
+  if (!aligned16(out)) return fail(MRA_EINVAL, w + ": out must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(plan) % 8) return fail(MRA_EINVAL, w + ": plan must be 8-byte aligned");
+  const void* ptrs[GATHER_MAX_SRC];
+  long long lds[GATHER_MAX_SRC];
+  int rows[GATHER_MAX_SRC], dts[GATHER_MAX_SRC];
+  for (int k = 0; k < n_src; ++k) {
+    const mra_rows_src& s = srcs[k];
+    const std::string sk = w + ": source " + std::to_string(k);
+    if (!s.ptr) return fail(MRA_EINVAL, sk + ": null ptr");
+    if (s.dtype != MRA_F32 && s.dtype != MRA_F16 && s.dtype != MRA_BF16) return fail(MRA_EINVAL, sk + ": unknown dtype");
+    if (s.dtype != MRA_F32 && out_dtype != MRA_F32 && s.dtype != out_dtype)
+      return fail(MRA_EINVAL, sk + ": f16 <-> bf16 is refused (equal 16-bit types, or f32 on one side)");
+    if (s.rows < 0) return fail(MRA_EINVAL, sk + ": negative rows");
+    if (s.ld < width) return fail(MRA_EINVAL, sk + ": ld < width");
+    if (s.ld % (s.dtype == MRA_F32 ? 4 : 8)) return fail(MRA_EINVAL, sk + ": the pitch must be a multiple of 16 bytes");
+    if (!aligned16(s.ptr)) return fail(MRA_EINVAL, sk + ": ptr must be 16-byte aligned");
+    ptrs[k] = s.ptr;
+    lds[k] = s.ld;
+    rows[k] = s.rows;
+    dts[k] = s.dtype;   // MRA_F32 / MRA_F16 / MRA_BF16 = 0 / 1 / 2, the kernel's own codes
+  }
+  return chk(launch_gather_rows(out, ldo, out_dtype, n_rows, width, ptrs, lds, rows, dts, n_src, plan, as_stream(stream)), "gather_rows");
+}
+
 // ---- the Q-Former forward's own kernels, one launch each (include/mra.h; tests/test_gpu_qformer_kernels.py) ----------------------------
 // Every entry checks its arguments before any launch, allocates nothing and calls the launch function the forward calls.
 namespace {

@@ -108,6 +108,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="how the LM loss is computed: stock = the LM's own forward with labels (lm_head over every position); rows = the LM's "
                          "decoder, then lm_head + cross-entropy on the labelled rows only (torch ops); fused = the same on the HIP entries "
                          "mra_lm_head_ce_* (no [B, S, V] tensor in either direction); rows / fused need --objective llm or both")
+    ap.add_argument("--prompt-assembly", choices=("cat", "plan"), default="cat",
+                    help="how the prompt in front of the LM is put together: cat = torch.cat of its pieces; plan = a table of (source, row) "
+                         "executed as one row gather forward and one per modality backward (mra_gather_rows); plan needs --objective llm or "
+                         "both; --group-by-video with an LM objective always takes the plan")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
                          "(mra_video_frames_forward) instead of as float32 pixels made on the host")
@@ -131,6 +135,8 @@ def main(argv=None):
         parser.error("--lora needs --llm-path DIR and --objective llm or both")
     if args.lm_loss != "stock" and args.objective == "score":
         parser.error("--lm-loss rows / fused needs --objective llm or both")
+    if args.prompt_assembly != "cat" and args.objective == "score":
+        parser.error("--prompt-assembly plan needs --objective llm or both")
     logging.basicConfig(level=logging.INFO)
     return run_train(args)
 

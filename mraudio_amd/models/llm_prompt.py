@@ -21,12 +21,22 @@ Neither Vicuna weights nor the Llama sentencepiece model exist offline, so ``Sim
 stand-in vocabulary for tests and smoke runs; with real checkpoints pass ``LlamaTokenizer`` instead.
 Parity: the reference's class cannot be imported here (LAVIS / peft / Vicuna absent) and holds no fixtures for
 this step -> **unpinned**; the tests re-derive the layout index by index from the lines cited above.
+
+Every row of the embedded sequence is a row of the LM's embedding table or a row of a modality's projection, so the same two layouts
+also exist as tables of integers: ``PromptAssembler.plan_forward`` / ``plan_generate`` make the same tokenizer calls in the same order and
+return a ``PromptPlan`` (``plan [B, S, 2]`` = (source, row), ``mask``, ``targets``, one inverse plan per modality), and ``assemble_plan``
+executes it as ONE autograd node: one ``mra_gather_rows`` launch forward and one per projection backward (``csrc/prompt.hip``), or
+``index_select`` / ``index_copy_`` on the torch route, which is the oracle of the tests.  ``media_rows(seq, pos)`` names the first
+projection row of a sequence at a position, so the ``(video, position, prompt)`` row order of ``forward_multi_train`` needs no permuted copy.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
+
+from .._lib import MraError, check, current_stream, lib, mra_dtype, mra_rows_src, ptr
 
 MODALITY_TO_CUE = {"video": " video: ", "audio": " audio: "}       # reference :206-209
 
@@ -191,3 +201,261 @@ class PromptAssembler:
         inp.append(self.embed(llm["input_ids"]))
         embeds, mask = self._cat(inp, att)
         return embeds, mask, torch.cat([empty, targets], dim=1)
+
+    # ---- the same two layouts as tables of integers (``PromptPlan``, ``assemble_plan``) ---------------------------------
+    def _plan_prefix(self, samples, B: int, T: int, first_rows: torch.Tensor, Q: int, mods: Sequence[str]):
+        """``_prefix`` on token ids: the same tokenizer calls in the same order, every piece a ``[B, L]`` triple (source, row, mask).
+        Source 0 is the embedding table (row = token id, pad tokens included), source ``1 + i`` the projection of ``mods[i]``."""
+        src: List[torch.Tensor] = []
+        row: List[torch.Tensor] = []
+        att: List[torch.Tensor] = []
+
+        def tokens(ids, mask):
+            src.append(torch.zeros_like(ids))
+            row.append(ids)
+            att.append(mask)
+
+        ts_ids = ts_att = None
+        if self.interleave_seconds:
+            flat = [f" {t} " for r in samples["timestamps"] for t in (r.tolist() if torch.is_tensor(r) else r)]
+            tt = self.tok(flat, padding="longest", truncation=True, return_tensors="pt", add_special_tokens=False)
+            n_rows, per_row = len(samples["timestamps"]), len(samples["timestamps"][0])
+            if n_rows != B or per_row < T:
+                raise MraError(f"timestamps must hold one row of {T} stamps per sequence: got {n_rows} rows of {per_row} for {B} sequences")
+            ts_ids = tt.input_ids.view(n_rows, per_row, -1)
+            ts_att = tt.attention_mask.view(n_rows, per_row, -1)
+        q = torch.arange(Q, dtype=torch.long)
+        for pos in range(T):
+            if self.enumerate_inputs:
+                en = self.tok([f"{'' if pos == 0 else ' '}({chr(97 + pos)}) " for _ in range(B)], return_tensors="pt", add_special_tokens=pos == 0)
+                tokens(en.input_ids, en.attention_mask)
+            for i, m in enumerate(mods):
+                cue = self.tokenized_cue[m]
+                tokens(cue.input_ids.repeat(B, 1), cue.attention_mask.repeat(B, 1))
+                src.append(torch.full((B, Q), 1 + i, dtype=torch.long))
+                row.append(first_rows[:, pos, None] + q)
+                att.append(torch.ones(B, Q, dtype=torch.long))
+            if self.interleave_seconds:
+                tokens(ts_ids[:, pos], ts_att[:, pos])
+        dur = self.tok([f"{d} " for d in samples["duration"]], padding="longest", truncation=True, return_tensors="pt", add_special_tokens=False)
+        tokens(dur.input_ids, dur.attention_mask)
+        return src, row, att
+
+    def _plan(self, samples, text_ids, text_att, targets, media_rows, n_query, num, rows, modalities) -> "PromptPlan":
+        B = int(text_ids.shape[0])
+        Q = int(n_query) if n_query is not None else self.num_query_token
+        mods = [m for m in self.modalities if modalities is None or m in modalities]
+        if not mods:
+            raise MraError("a prompt plan needs at least one modality")
+        T = int(num) if num is not None else len(samples["timestamps"][0])
+        if media_rows is None:            # the ordinary layout: one contiguous [T * Q, D] block per sequence
+            first = (torch.arange(B)[:, None] * T + torch.arange(T)[None, :]) * Q
+        elif callable(media_rows):
+            first = torch.tensor([[int(media_rows(b, pos)) for pos in range(T)] for b in range(B)], dtype=torch.long).view(B, T)
+        else:
+            first = torch.as_tensor(media_rows, dtype=torch.long).view(B, T)
+        src, row, att = self._plan_prefix(samples, B, T, first, Q, mods)
+        n_prefix = sum(int(a.shape[1]) for a in att)
+        src.append(torch.zeros_like(text_ids))
+        row.append(text_ids)
+        att.append(text_att)
+        src, row, mask = torch.cat(src, dim=1), torch.cat(row, dim=1), torch.cat(att, dim=1)
+        if targets is not None:
+            targets = torch.cat([torch.full((B, n_prefix), -100, dtype=torch.long), targets], dim=1)
+        n_rows = {m: int(rows[m] if isinstance(rows, dict) else rows) if rows is not None else B * T * Q for m in mods}
+        return PromptPlan(torch.stack([src, row], dim=2).to(torch.int32), mask, targets, mods, n_rows)
+
+    def plan_generate(self, samples, media_rows=None, n_query: Optional[int] = None, *, num: Optional[int] = None, rows=None,
+                      modalities: Optional[Sequence[str]] = None) -> "PromptPlan":
+        """``assemble_generate`` as a ``PromptPlan``.  ``media_rows(seq, pos)`` (a callable or a ``[B, T]`` table; default the ordinary
+        layout ``(seq * T + pos) * n_query``) is the first of the ``n_query`` projection rows of sequence ``seq`` at position ``pos``;
+        ``num`` is T (default: the length of a ``timestamps`` row) and ``rows`` the row count of each projection (default ``B * T *
+        n_query``; rows no sequence uses get -1 in the inverse plan)."""
+        self.tok.padding_side = "left"
+        prompt = [p.strip() for p in samples["text_input"]]
+        llm = self.tok(prompt, padding="longest", return_tensors="pt", add_special_tokens=False)
+        return self._plan(samples, llm.input_ids, llm.attention_mask, None, media_rows, n_query, num, rows, modalities)
+
+    def plan_forward(self, samples, media_rows=None, n_query: Optional[int] = None, *, num: Optional[int] = None, rows=None,
+                     modalities: Optional[Sequence[str]] = None) -> "PromptPlan":
+        """``assemble_forward`` as a ``PromptPlan`` (arguments as ``plan_generate``); ``targets`` carries the labels."""
+        tok = self.tok
+        tok.padding_side, tok.truncation_side = "right", "left"
+        tin = tok(samples["text_input"], return_tensors="pt", padding="longest", truncation=True, max_length=self.max_txt_len, add_special_tokens=True)
+        tok.truncation_side = "right"
+        tout = tok([t + tok.eos_token for t in samples["text_output"]], return_tensors="pt", padding="longest", truncation=True,
+                   max_length=self.max_output_txt_len)
+        llm, in_len = concat_text_input_output(tin.input_ids, tin.attention_mask, tout.input_ids, tout.attention_mask)
+        targets = llm["input_ids"].masked_fill(llm["input_ids"] == tok.pad_token_id, -100)
+        for i, n in enumerate(in_len):
+            targets[i][:n] = -100
+        return self._plan(samples, llm["input_ids"], llm["attention_mask"], targets, media_rows, n_query, num, rows, modalities)
+
+
+class PromptPlan:
+    """An assembled prompt as host integer tables: ``plan`` int32 [B, S, 2] = (source, row) per position (source 0 the LM's embedding table,
+    ``1 + i`` the projection of ``modalities[i]``), ``mask`` [B, S], ``targets`` [B, S] (``plan_forward`` only) and per modality the inverse
+    plan ``inverse[m]`` [rows_m]: the flat output row ``b * S + s`` that projection row lands on, or -1 for a row no sequence uses."""
+
+    def __init__(self, plan: torch.Tensor, mask: torch.Tensor, targets: Optional[torch.Tensor], modalities: Sequence[str], rows: Dict[str, int]):
+        self.plan, self.mask, self.targets = plan, mask, targets
+        self.modalities, self.rows = list(modalities), dict(rows)
+        flat = plan.view(-1, 2).to(torch.long)
+        self.inverse: Dict[str, torch.Tensor] = {}
+        self._used: Dict[str, torch.Tensor] = {}
+        for i, m in enumerate(self.modalities):
+            pos = torch.nonzero(flat[:, 0] == 1 + i).squeeze(1)
+            self._used[m] = pos
+            inv = torch.full((self.rows[m],), -1, dtype=torch.long)
+            r = flat[pos, 1]
+            ok = (r >= 0) & (r < self.rows[m])
+            inv[r[ok]] = pos[ok]          # validate() refuses what this line cannot express: a row out of range or used twice
+            self.inverse[m] = inv
+        self._dev: Dict[torch.device, dict] = {}
+
+    def validate(self, table_rows: Optional[int] = None) -> "PromptPlan":
+        """Host check before upload: every source and row in range, every media row used at most once."""
+        flat = self.plan.view(-1, 2).to(torch.long)
+        s, r = flat[:, 0], flat[:, 1]
+        if ((s < 0) | (s > len(self.modalities))).any():
+            raise MraError(f"prompt plan: a source outside [0, {len(self.modalities)}]")
+        tok = r[s == 0]
+        if (tok < 0).any() or (table_rows is not None and (tok >= table_rows).any()):
+            raise MraError(f"prompt plan: a token id outside the embedding table's {table_rows} rows")
+        for i, m in enumerate(self.modalities):
+            mr = r[s == 1 + i]
+            if ((mr < 0) | (mr >= self.rows[m])).any():
+                raise MraError(f"prompt plan: a {m} row outside [0, {self.rows[m]})")
+            if torch.unique(mr).numel() != mr.numel():
+                raise MraError(f"prompt plan: a {m} row is used twice (its gradient would need a sum)")
+        if self.mask.shape != self.plan.shape[:2] or (self.targets is not None and self.targets.shape != self.mask.shape):
+            raise MraError("prompt plan: plan, mask and targets disagree on [B, S]")
+        return self
+
+    def on(self, device) -> dict:
+        """The device copies, uploaded once per device: ``plan`` int32 [B * S, 2], ``mask``, ``targets``, per modality ``inv`` int32
+        [rows_m, 2] (the backward's plan over d_embeds; (-1, 0) = a zero row) and the index vectors of the torch route."""
+        device = torch.device(device)
+        d = self._dev.get(device)
+        if d is None:
+            flat = self.plan.view(-1, 2)
+            is_tok = flat[:, 0] == 0
+            d = {"plan": flat.contiguous().to(device), "mask": self.mask.to(device), "targets": None if self.targets is None else self.targets.to(device),
+                 "tok_pos": torch.nonzero(is_tok).squeeze(1).to(device), "tok": flat[:, 1].to(torch.long).masked_fill(~is_tok, 0).to(device),
+                 "inv": {}, "pos": {}, "row": {}}
+            for m in self.modalities:
+                inv = self.inverse[m]
+                d["inv"][m] = torch.stack([torch.where(inv < 0, -1, 0), inv.clamp(min=0)], dim=1).to(torch.int32).contiguous().to(device)
+                d["pos"][m] = self._used[m].to(device)
+                d["row"][m] = flat[self._used[m], 1].to(torch.long).to(device)
+            self._dev[device] = d
+        return d
+
+
+def gather_rows(srcs: Sequence[torch.Tensor], plan: torch.Tensor, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None
+                ) -> torch.Tensor:
+    """``mra_gather_rows``: ``out[i] = cast(srcs[s][r])`` for ``plan[i] = (s, r)`` (int32 [n, 2] on the device); ``srcs`` are 2-D with unit
+    column stride, pitched rows allowed.  ``out`` (pitched allowed) is allocated ``[n, width]`` of ``out_dtype`` when not given."""
+    n, width = int(plan.shape[0]), int(srcs[0].shape[1])
+    if out is None:
+        out = torch.empty(n, width, dtype=out_dtype or srcs[0].dtype, device=plan.device)
+    arr = (mra_rows_src * len(srcs))()
+    for k, t in enumerate(srcs):
+        if t.dim() != 2 or t.shape[1] != width or t.stride(1) != 1:
+            raise MraError(f"gather_rows: source {k} must be [rows, {width}] with unit column stride, got {tuple(t.shape)} / {t.stride()}")
+        arr[k] = mra_rows_src(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else max(t.stride(0), width), t.shape[0], mra_dtype(t.dtype))
+    if out.dim() != 2 or out.shape[0] != n or out.shape[1] != width or out.stride(1) != 1 or plan.dtype != torch.int32 or not plan.is_contiguous():
+        raise MraError("gather_rows: out must be [n, width] with unit column stride and plan a contiguous int32 [n, 2]")
+    check(lib().mra_gather_rows(ptr(out), out.stride(0) if n > 1 else max(out.stride(0), width), mra_dtype(out.dtype), n, width,
+                                C.cast(arr, C.POINTER(mra_rows_src)), len(srcs), ptr(plan), current_stream()), "mra_gather_rows")
+    return out
+
+
+def _plan_hip_reason(table: torch.Tensor, media: Sequence[torch.Tensor]) -> Optional[str]:
+    """None when ``mra_gather_rows`` applies, else why not."""
+    if not table.is_cuda or not all(x.is_cuda for x in media):
+        return "the table and the projections must be CUDA tensors"
+    if table.requires_grad and torch.is_grad_enabled():
+        return "the embedding table requires a gradient, which only the torch route computes"
+    if table.shape[1] % 8:
+        return f"width {table.shape[1]} is not a multiple of 8"
+    if table.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        return f"unsupported table dtype {table.dtype}"
+    for x in media:
+        if x.dtype != torch.float32 and x.dtype != table.dtype:
+            return f"a {x.dtype} projection into a {table.dtype} table (f32, or the table's own dtype)"
+    per = 4 if table.dtype == torch.float32 else 8
+    if table.stride(1) != 1 or table.stride(0) % per or table.stride(0) < table.shape[1] or table.data_ptr() % 16:
+        return "the table is not laid out as the entry reads it (unit column stride, 16-byte aligned rows), and no copy of it is made"
+    return None
+
+
+class _AssemblePlan(torch.autograd.Function):
+    """ONE node: the forward is one gather over (table, projections...), the backward one gather per projection that needs a gradient
+    (``mra_gather_rows`` with d_embeds as the source and the inverse plan), or ``index_select`` / ``index_copy_`` on the torch route."""
+
+    @staticmethod
+    def forward(ctx, dev, mods, use_hip, table, *media):
+        flat = [x.reshape(-1, x.shape[-1]) for x in media]
+        if use_hip:
+            flat = [x if x.stride(1) == 1 and x.stride(0) % (4 if x.dtype == torch.float32 else 8) == 0 and x.data_ptr() % 16 == 0 else x.contiguous()
+                    for x in flat]
+            out = gather_rows([table] + flat, dev["plan"], table.dtype)
+        else:
+            out = table.index_select(0, dev["tok"])
+            for m, x in zip(mods, flat):
+                out.index_copy_(0, dev["pos"][m], x.index_select(0, dev["row"][m]).to(table.dtype))
+        ctx.dev, ctx.mods, ctx.use_hip = dev, mods, use_hip
+        ctx.meta = (tuple(table.shape), table.dtype, [(tuple(x.shape), x.dtype) for x in media])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        dev, mods = ctx.dev, ctx.mods
+        tshape, tdtype, minfo = ctx.meta
+        g = g.reshape(-1, tshape[1])
+        grads: List[Optional[torch.Tensor]] = []
+        d_table = None
+        if ctx.needs_input_grad[3]:
+            d_table = torch.zeros(tshape, dtype=tdtype, device=g.device).index_add_(0, dev["tok"].index_select(0, dev["tok_pos"]),
+                                                                                     g.index_select(0, dev["tok_pos"]))
+        if ctx.use_hip and not (g.stride(1) == 1 and g.stride(0) % (4 if g.dtype == torch.float32 else 8) == 0 and g.data_ptr() % 16 == 0):
+            g = g.contiguous()
+        for k, (m, (shape, dtype)) in enumerate(zip(mods, minfo)):
+            if not ctx.needs_input_grad[4 + k]:
+                grads.append(None)
+            elif ctx.use_hip:
+                grads.append(gather_rows([g], dev["inv"][m], dtype).view(shape))
+            else:
+                d = torch.zeros(dev["inv"][m].shape[0], tshape[1], dtype=dtype, device=g.device)
+                d.index_copy_(0, dev["row"][m], g.index_select(0, dev["pos"][m]).to(dtype))
+                grads.append(d.view(shape))
+        return (None, None, None, d_table, *grads)
+
+
+def assemble_plan(plan: PromptPlan, table: torch.Tensor, media: Dict[str, torch.Tensor], hip: Optional[bool] = None):
+    """Execute a plan: ``(embeds [B, S, D] in the table's dtype, mask, targets)`` on the table's device (``targets`` is None for a
+    ``plan_generate`` plan).  ``table`` is the LM's embedding weight ``[V, D]``, ``media[m]`` the projection of modality ``m`` with
+    ``plan.rows[m]`` rows of D in any leading shape, fp32 or the table's dtype; the cast to the table's dtype happens inside the gather.
+    One autograd node; the gradient of a projection comes out in its own dtype.  ``hip=None`` takes ``mra_gather_rows`` when it applies
+    (CUDA, D % 8 == 0, a table that needs no gradient) and the torch route (``index_select`` / ``index_copy_``) otherwise; ``hip=True``
+    raises ``MraError`` naming the reason; ``hip=False`` is the torch route."""
+    B, S = plan.mask.shape
+    xs = []
+    for m in plan.modalities:
+        if m not in media:
+            raise MraError(f"assemble_plan: the plan uses modality {m!r}, which media does not hold")
+        x = media[m]
+        if x.shape[-1] != table.shape[1] or x.numel() != plan.rows[m] * table.shape[1]:
+            raise MraError(f"assemble_plan: {m} holds {tuple(x.shape)}, the plan expects {plan.rows[m]} rows of {table.shape[1]}")
+        xs.append(x)
+    plan.validate(int(table.shape[0]))
+    use = False
+    if hip is None or hip:
+        why = _plan_hip_reason(table, xs)
+        if why is not None and hip:
+            raise MraError(f"assemble_plan(hip=True): {why}")
+        use = why is None
+    dev = plan.on(table.device)
+    out = _AssemblePlan.apply(dev, tuple(plan.modalities), use, table, *xs)
+    return out.view(B, S, table.shape[1]), dev["mask"], dev["targets"]

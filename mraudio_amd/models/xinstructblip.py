@@ -151,7 +151,13 @@ def _timestamps(samples, bs: int, num: int) -> List[list]:
     return [t.tolist() if torch.is_tensor(t) else list(t) for t in ts]
 
 
-def _membership_targets(parse, windows: Sequence[str], stamps: Sequence[float], rows: torch.Tensor) -> torch.Tensor:
+def _is_grouped(samples) -> bool:
+    """One record per video with the LIST of its queries (``collate_grouped``), against one prompt string per sample."""
+    ti = samples.get("text_input")
+    return ti is not None and len(ti) > 0 and isinstance(ti[0], (list, tuple))
+
+
+def _membership_targets(parse,windows: Sequence[str], stamps: Sequence[float], rows: torch.Tensor) -> torch.Tensor:
     """Clip-membership targets, written into the zeroed ``rows`` [len(windows), len(stamps)] and returned: row ``p`` becomes 1 where a timestamp
     lies inside ANY of the windows that ``parse`` (``XInstructBLIP.parse_windows``) reads from ``windows[p]`` (union over windows, float
     seconds honoured)."""
@@ -219,6 +225,12 @@ class XInstructBLIP(nn.Module):
     # how the LM loss is computed (_lm_ce): "stock" = the LM's own forward with labels (lm_head over every position), "rows" = the LM's decoder,
     # then lm_head + cross-entropy on the labelled rows only as torch ops, "fused" = the same on the HIP entries (models/lm_head.py)
     lm_loss = "stock"
+    # how the prompt in front of the LM is put together: "cat" = PromptAssembler.assemble_* (torch.cat of its pieces), "plan" = a PromptPlan
+    # executed as one row gather (models/llm_prompt.py assemble_plan; mra_gather_rows).  Grouped batches always take the plan
+    prompt_assembly = "cat"
+    # the LM objective ("llm" / "both") on grouped batches (several queries per video: forward_multi's pass + the plan).  Off: such a batch
+    # is refused with MraError, as it always was
+    grouped_lm = False
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
@@ -228,11 +240,16 @@ class XInstructBLIP(nn.Module):
                  process_group=None, qformer_overrides: Optional[dict] = None, overlap_modalities: bool = True,
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
                  cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0,
-                 video_processor=None, lm_loss: str = "stock"):
+                 video_processor=None, lm_loss: str = "stock", prompt_assembly: str = "cat",
+                 grouped_lm: bool = False):
         super().__init__()
         if lm_loss not in ("stock", "rows", "fused"):
             raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
         self.lm_loss = lm_loss
+        if prompt_assembly not in ("cat", "plan"):
+            raise ValueError(f"prompt_assembly must be 'cat' or 'plan', got {prompt_assembly!r}")
+        self.prompt_assembly = prompt_assembly
+        self.grouped_lm = bool(grouped_lm)
         self.model_path, self.audio_path = model_path, audio_path
         self.modalities = list(modalities) if modalities is not None else ["audio", "video"]  # reference :71
         self.max_txt_len = 128           # reference :75
@@ -786,6 +803,23 @@ class XInstructBLIP(nn.Module):
             qf.forward_fused(ids_one, att_one, enc_one, want_query=True)
         return mode == "op" or (mode == "auto" and qf.cross_precision_report()["resolved"] == "op")
 
+    def _multi_forward(self, qf: QFormer, m: str, ids_n: torch.Tensor, att: torch.Tensor, enc: torch.Tensor, P: int, num: int,
+                       want_cls: bool = True):
+        """The inference forward of ``P`` prompt slots per item: ``(z [items * P, 32, H], cls [items * P, H] or None)`` in (item, slot)
+        row order.  ``forward_multi`` over one shared K/V cache; where split precision is in force one ordinary forward per slot."""
+        if self._multi_op_chain(qf, ids_n[0:num * P:P], att[0:num * P:P], enc[:num]):
+            res = qf.forward_multi(ids_n, att, enc, P, want_query=True, want_cls=want_cls)
+            return res["query"], res.get("cls")
+        if not getattr(self, "_multi_split_warned", False):
+            logging.warning("encode_fuse_multi: split precision is in force for %s -- one ordinary forward per prompt slot, "
+                            "no shared K/V cache", m)
+            self._multi_split_warned = True
+        items = int(enc.shape[0])
+        per = [qf.forward_fused(ids_n[p::P], att[p::P], enc, want_query=True, want_cls=want_cls) for p in range(P)]
+        z = torch.stack([r["query"] for r in per], dim=1).reshape(items * P, self.num_query_token, -1)
+        cls = torch.stack([r["cls"] for r in per], dim=1).reshape(items * P, -1) if want_cls else None
+        return z, cls
+
     @torch.no_grad()
     def encode_fuse_multi(self, samples, queries: Sequence[Sequence[str]]) -> Dict[str, object]:
         """``encode_fuse`` for several queries per video: ``queries[b]`` is the list of prompts of video ``b`` (ragged counts are
@@ -840,17 +874,7 @@ class XInstructBLIP(nn.Module):
                 qf: QFormer = getattr(self, f"{m}_Qformer")
                 with lane(m) as hand:
                     enc = qf.modality_ln(embeds[m].to(self._device))
-                    if self._multi_op_chain(qf, ids_n[0:num * P:P], att[0:num * P:P], enc[:num]):
-                        res = qf.forward_multi(ids_n, att, enc, P, want_query=True, want_cls=True)
-                        z, cls = res["query"], res["cls"]
-                    else:
-                        if not getattr(self, "_multi_split_warned", False):
-                            logging.warning("encode_fuse_multi: split precision is in force for %s -- one ordinary forward per prompt slot, "
-                                            "no shared K/V cache", m)
-                            self._multi_split_warned = True
-                        per = [qf.forward_fused(ids_n[p::P], att[p::P], enc, want_query=True, want_cls=True) for p in range(P)]
-                        z = torch.stack([r["query"] for r in per], dim=1).reshape(bs * num * P, self.num_query_token, -1)
-                        cls = torch.stack([r["cls"] for r in per], dim=1).reshape(bs * num * P, -1)
+                    z, cls = self._multi_forward(qf, m, ids_n, att, enc, P, num)
                     _, lg = scorer.cosine_scores(z, cls, want_sim=False)
                     # (b, t, p) -> (b, p, t): the scorer's heads then see bs * P "videos" of num positions
                     logit[m] = lg.index_select(0, bpt_index(bs, num, P).to(lg.device))
@@ -972,23 +996,74 @@ class XInstructBLIP(nn.Module):
             raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
         with torch.no_grad():
             out = self.encode_fuse(samples, want_llm=True)
+        if self.prompt_assembly == "plan":      # the gather reads the fp32 projections themselves and casts them
+            return out["inputs_llm"], out["atts_llm"]
         dt = self.llm_model.get_input_embeddings().weight.dtype
         return {m: v.to(dt) for m, v in out["inputs_llm"].items()}, out["atts_llm"]
+
+    def _plan_assemble(self, samples, media: Dict[str, torch.Tensor], generate: bool = False, first_rows=None):
+        """The plan route: ``(embeds, mask, targets)`` of ``samples`` (one prompt per sequence) over the projections ``media[m]``, whose
+        row ``first_rows[seq, pos] + q`` is query ``q`` of sequence ``seq`` at position ``pos`` (default: the ordinary ``[B, T * 32, D]``
+        layout).  ``media`` stays in its own dtype: the cast to the LM's dtype happens inside the gather."""
+        from .llm_prompt import assemble_plan
+
+        asm, Q = self.prompt_assembler, self.num_query_token
+        mods = [m for m in asm.modalities if m in media]
+        rows = {m: media[m].numel() // media[m].shape[-1] for m in mods}
+        num = None if first_rows is not None else rows[mods[0]] // (Q * len(samples["text_input"]))
+        build = asm.plan_generate if generate else asm.plan_forward
+        plan = build(samples, first_rows, Q, num=int(first_rows.shape[1]) if first_rows is not None else num, rows=rows, modalities=mods)
+        out = assemble_plan(plan, self.llm_model.get_input_embeddings().weight, {m: media[m] for m in mods})
+        return (*out, plan)
 
     @torch.no_grad()
     def generate_llm(self, samples, max_new_tokens: int = 64) -> List[str]:
         """Reference ``generate`` end to end (``:221-397``): hot path -> prompt assembly -> ``llm_model.generate``."""
         inputs_llm, atts_llm = self._llm_inputs(samples)
-        embeds, mask = self.prompt_assembler.assemble_generate(samples, inputs_llm, atts_llm)
+        if self.prompt_assembly == "plan":
+            embeds, mask, _, _ = self._plan_assemble(samples, inputs_llm, generate=True)
+        else:
+            embeds, mask = self.prompt_assembler.assemble_generate(samples, inputs_llm, atts_llm)
+        return self._llm_decode(embeds, mask, max_new_tokens)
+
+    def _llm_decode(self, embeds, mask, max_new_tokens: int) -> List[str]:
         outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens)
         outputs[outputs == 0] = 2                                      # :392
         return [o.strip() for o in self.llm_tokenizer.batch_decode(outputs, skip_special_tokens=True)]
+
+    @torch.no_grad()
+    def generate_multi_llm(self, samples, queries: Optional[Sequence[Sequence[str]]] = None, max_new_tokens: int = 64) -> List[List[str]]:
+        """``generate_llm`` for several queries per video: per video one decoded string per query.  The frozen route of the grouped pass
+        (``forward_multi`` per modality over one K/V projection per video, calls of at most ``max_queries_per_call`` prompt slots), the
+        projections in ``(video, position, prompt)`` row order as they come, ``plan_generate`` and ``llm_model.generate`` on one LM batch
+        per call holding its real ``(video, query)`` sequences."""
+        if self.prompt_assembler is None:
+            raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
+        queries = [list(q) for q in (queries if queries is not None else samples["text_input"])]
+        if not queries or any(len(q) == 0 for q in queries):
+            raise MraError("generate_multi_llm: every video needs at least one query")
+        texts: List[List[str]] = [[] for _ in queries]
+        for call in self._multi_calls(samples, queries, train=False, want_cls=False):
+            flat, first = self._multi_flatten(samples, queries, None, call)
+            media = {m: getattr(self, f"{m}_Qformer").llm_proj(z) for m, (z, _) in call["out"].items()}
+            embeds, mask, _, _ = self._plan_assemble(flat, media, generate=True, first_rows=first)
+            for (k, _), txt in zip(call["pairs"], self._llm_decode(embeds, mask, max_new_tokens)):
+                texts[call["vids"][k]].append(txt)
+        return texts
 
     def _check_lm_training(self) -> None:
         if self.prompt_assembler is None:
             raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
         if not getattr(self, "train_qformers", False):
             raise MraError("the LM objective trains the Q-Formers: call enable_qformer_training() first")
+
+    def _check_grouped_lm(self) -> None:
+        """The LM objective on a grouped batch is opt-in like every other switch here: with the default a grouped batch under an LM
+        objective is refused exactly as before."""
+        if not getattr(self, "grouped_lm", False):
+            raise MraError(f"objective {self.objective!r} on a grouped batch: the multi-query LM pass is off -- switch it on with "
+                           "XInstructBLIP(grouped_lm=True) / model.grouped_lm = True (Trainer does, for group_by_video with an LM objective), "
+                           "or train grouped batches with objective 'score'")
 
     def forward_llm(self, samples, train: Optional[bool] = None):
         """Reference ``forward`` end to end (``:399-606``): the LM's cross-entropy on the answer tokens.  ``train=False``: the
@@ -1006,15 +1081,22 @@ class XInstructBLIP(nn.Module):
         LoRA on and the Q-Formers frozen, ``train=False`` is the training route (the reference's regime)."""
         if train is None:
             train = self.objective != "score" and getattr(self, "train_qformers", False)
+        if _is_grouped(samples):           # one record per video with the lists of its queries: forward_multi's pass, the LM term alone
+            if train:
+                self._check_lm_training()
+            elif self.prompt_assembler is None:
+                raise MraError("no LLM attached: call attach_llm(llm_model, llm_tokenizer) first")
+            self._check_grouped_lm()
+            return {"loss": self._multi_losses(samples, None, None, want_score=False, want_llm=True, train=bool(train))["lm"]}
         if train:
             self._check_lm_training()
-            ti = samples.get("text_input")
-            if ti is not None and len(ti) > 0 and isinstance(ti[0], (list, tuple)):
-                raise MraError("the LM objective has no multi-query form: one text_input string per sample")
             _, inputs_llm, _, _ = self._train_pass(samples, want_score=False, want_llm=True)
             return {"loss": self._lm_loss(samples, inputs_llm)}
         inputs_llm, atts_llm = self._llm_inputs(samples)
-        embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, inputs_llm, atts_llm)
+        if getattr(self, "prompt_assembly", "cat") == "plan":
+            embeds, mask, targets, _ = self._plan_assemble(samples, inputs_llm)
+        else:
+            embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, inputs_llm, atts_llm)
         self._lora_unscale()
         loss = self._lm_ce(embeds, mask, targets)
         return {"loss": self._lora_loss(loss) if self.lora else loss}
@@ -1099,18 +1181,27 @@ class XInstructBLIP(nn.Module):
             if self.objective not in ("llm", "both"):
                 raise MraError(f"objective must be 'score', 'llm' or 'both', got {self.objective!r}")
             if grouped:
-                raise MraError(f"objective {self.objective!r} has no multi-query form: train grouped batches with objective 'score'")
+                self._check_grouped_lm()
             frozen = self.lora and not getattr(self, "train_qformers", False)     # the reference's regime: only the adapters train
             if self.objective == "llm":
                 return self.forward_llm(samples, train=not frozen)
+            if grouped:    # forward_multi's BCE and the LM term over ONE Q-Former forward (and backward) per modality and call
+                if not frozen:
+                    self._check_lm_training()
+                out = self._multi_losses(samples, None, None, want_score=True, want_llm=True, train=not frozen)
+                bce, lm = out["score"], out["lm"]
+                return {"loss": bce + self.lm_weight * lm, "loss_score": bce.detach(), "loss_lm": lm.detach()}
             if frozen:
                 with torch.no_grad():
                     out = self.encode_fuse(samples, want_llm=True)
                     bce = nn.functional.binary_cross_entropy_with_logits(out["fused"].view(out["bs"], out["num"]) * 20.0,
                                                                          self._targets(samples, out["bs"], out["num"]))
-                dt = self.llm_model.get_input_embeddings().weight.dtype
-                embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in out["inputs_llm"].items()},
-                                                                               out["atts_llm"])
+                if getattr(self, "prompt_assembly", "cat") == "plan":
+                    embeds, mask, targets, _ = self._plan_assemble(samples, out["inputs_llm"])
+                else:
+                    dt = self.llm_model.get_input_embeddings().weight.dtype
+                    embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in out["inputs_llm"].items()},
+                                                                                   out["atts_llm"])
                 self._lora_unscale()
                 lm = self._lora_loss(self._lm_ce(embeds, mask, targets))
                 return {"loss": bce + self.lm_weight * lm, "loss_score": bce.detach(), "loss_lm": lm.detach()}
@@ -1167,10 +1258,14 @@ class XInstructBLIP(nn.Module):
 
     def _lm_loss(self, samples, inputs_llm):
         """The attached LM's cross-entropy on the answer tokens over differentiable ``inputs_llm`` (``PromptAssembler.assemble_forward`` is
-        plain ``torch.cat``).  The value is the loss itself; only its gradient carries ``loss_scale`` into the LM."""
-        dt = self.llm_model.get_input_embeddings().weight.dtype
-        atts = {m: torch.ones(v.shape[0], v.shape[1], dtype=torch.long, device=self._device) for m, v in inputs_llm.items()}
-        embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in inputs_llm.items()}, atts)
+        plain ``torch.cat``; ``prompt_assembly = "plan"`` is one gather node).  The value is the loss itself; only its gradient carries
+        ``loss_scale`` into the LM."""
+        if self.prompt_assembly == "plan":      # one gather node: no .to(dt) copies, the gradient comes back fp32 in one launch per modality
+            embeds, mask, targets, _ = self._plan_assemble(samples, inputs_llm)
+        else:
+            dt = self.llm_model.get_input_embeddings().weight.dtype
+            atts = {m: torch.ones(v.shape[0], v.shape[1], dtype=torch.long, device=self._device) for m, v in inputs_llm.items()}
+            embeds, mask, targets = self.prompt_assembler.assemble_forward(samples, {m: v.to(dt) for m, v in inputs_llm.items()}, atts)
         self._lora_unscale()
         loss = self._lm_ce(embeds, mask, targets)
         return _ScaleGrad.apply(loss, float(self.loss_scale)) if self.loss_scale != 1.0 else loss
@@ -1198,7 +1293,9 @@ class XInstructBLIP(nn.Module):
         K/V weight gradient.  Ragged counts are padded by ``pad_queries``; padded slots carry no loss and no gradient.  Videos
         with more than ``max_queries_per_call`` queries run as consecutive calls of at most that many, each call's loss weighted by
         its share of the triples.  Prompts are always aligned to their own video (no ``compat_repeat`` on this path).  Without
-        ``enable_qformer_training()`` the loss is the forward-only value from ``encode_fuse_multi``."""
+        ``enable_qformer_training()`` the loss is the forward-only value from ``encode_fuse_multi``.  The pass itself is ``_multi_calls``,
+        which the LM objective on grouped batches (``forward`` / ``forward_llm`` with ``objective`` "llm" / "both") and
+        ``generate_multi_llm`` share."""
         queries = [list(q) for q in (queries if queries is not None else samples["text_input"])]
         if targets is None:
             targets = samples.get("text_output") or [["[[-1, -1]]"] * len(q) for q in queries]
@@ -1214,9 +1311,20 @@ class XInstructBLIP(nn.Module):
             tg = self._multi_targets(samples, targets, out["num"])
             total = sum(bce(f.float() * 20.0, t, reduction="sum") for f, t in zip(out["fused"], tg))
             return {"loss": total / float(sum(counts) * out["num"])}
+        out = self._multi_losses(samples, queries, targets, want_score=True, want_llm=False, train=True)
+        return {"loss": out["score"] if out["score"] is not None else torch.tensor(0.0)}
+
+    def _multi_calls(self, samples, queries: Sequence[Sequence[str]], train: bool, want_cls: bool):
+        """The pass ``forward_multi``, the grouped LM objective and ``generate_multi_llm`` share, as a generator of calls.  Encoders and the
+        modality LayerNorm once per video, then per call of at most ``max_queries_per_call`` prompt slots one Q-Former forward per modality:
+        ``forward_multi_train`` when ``train`` (connected to autograd), else the inference ``forward_multi`` under ``no_grad`` (with its
+        one-forward-per-slot fallback under split precision).  Yields ``vids`` (the videos that still have queries), ``cnt`` (their real
+        counts in this call), ``lo``, ``P``, ``num``, ``pairs`` (the real ``(k, p)`` = (video slot, prompt slot) in order) and ``out[m] =
+        (z, cls)`` in chain-row order ``(k * T + t) * P + p``.  Prompts are aligned to their own video."""
         step = int(self.max_queries_per_call)
         if step < 1:
             raise MraError("max_queries_per_call must be >= 1")
+        counts = [len(q) for q in queries]
         self._sync()
         encs: Dict[str, torch.Tensor] = {}
         bs = num = None
@@ -1226,12 +1334,9 @@ class XInstructBLIP(nn.Module):
                     raw, idx, bs, num = self._encode(samples, m)
                 encs[m] = self._train_norm(m, raw, idx, bs * num)
         if bs is None:
-            return {"loss": torch.tensor(0.0)}
+            return
         if bs != len(queries):
             raise MraError(f"forward_multi: {len(queries)} query lists for {bs} videos")
-        tg = self._multi_targets(samples, targets, num)
-        triples = float(sum(counts) * num)
-        loss = None
         for lo in range(0, max(counts), step):
             vids = [b for b, c in enumerate(counts) if c > lo]            # the videos that still have queries in this round
             padded, cnt = pad_queries([queries[b][lo: lo + step] for b in vids])
@@ -1240,21 +1345,90 @@ class XInstructBLIP(nn.Module):
             # chain row (b * T + t) * P + p carries prompt p of video b
             ids_n, att = _prompt_rows(ids, tmask, self.num_query_token, num, P)
             sel = None if nb == bs else torch.as_tensor(vids, device=self._device)
-            per_mod = []
+            out = {}
             for m, enc in encs.items():
                 if sel is not None:
                     enc = enc.view(bs, num, *enc.shape[1:]).index_select(0, sel).reshape(nb * num, *enc.shape[1:])
-                z, cls = getattr(self, f"{m}_Qformer").forward_multi_train(ids_n, att, enc, P)
-                per_mod.append(_train_logit(z, cls))
-            fused = _weighted_fuse(per_mod, self.fuse_weights).view(nb, num, P).permute(0, 2, 1)      # (b, t, p) -> [nb, P, T]
-            target = torch.zeros(nb, P, num, dtype=torch.float32, device=self._device)
-            real = torch.zeros(nb, P, 1, dtype=torch.float32, device=self._device)                  # 0 on padded slots: no loss, no gradient
-            for k, b in enumerate(vids):
-                target[k, :cnt[k]] = tg[b][lo: lo + cnt[k]]
-                real[k, :cnt[k]] = 1.0
-            part = (bce(fused * 20.0, target, reduction="none") * real).sum() / triples
-            loss = part if loss is None else loss + part
-        return {"loss": loss}
+                qf: QFormer = getattr(self, f"{m}_Qformer")
+                if train:
+                    out[m] = qf.forward_multi_train(ids_n, att, enc, P, want_cls)
+                else:
+                    with torch.no_grad():
+                        out[m] = self._multi_forward(qf, m, ids_n, att, enc, P, num, want_cls)
+            yield {"vids": vids, "cnt": cnt, "lo": lo, "P": P, "num": num, "bs": bs, "out": out,
+                   "pairs": [(k, p) for k in range(nb) for p in range(cnt[k])]}
+
+    def _multi_flatten(self, samples, queries, targets, call):
+        """One LM sequence per real ``(video, query)`` pair of a call: the flattened ``samples`` of ``PromptAssembler.plan_*`` and the table
+        ``first [n_seq, T]`` of each sequence's first projection row per position in the call's ``(k, t, p)`` row order."""
+        vids, lo, P, num, pairs = call["vids"], call["lo"], call["P"], call["num"], call["pairs"]
+        ts = _timestamps(samples, call["bs"], num)
+        flat = {"text_input": [queries[vids[k]][lo + p] for k, p in pairs], "timestamps": [ts[vids[k]] for k, _ in pairs],
+                "duration": [samples["duration"][vids[k]] for k, _ in pairs]}
+        if targets is not None:
+            flat["text_output"] = [targets[vids[k]][lo + p] for k, p in pairs]
+        kp = torch.tensor(pairs, dtype=torch.long)
+        first = ((kp[:, 0, None] * num + torch.arange(num)[None, :]) * P + kp[:, 1, None]) * self.num_query_token
+        return flat, first
+
+    def _multi_losses(self, samples, queries, targets, want_score: bool, want_llm: bool, train: bool):
+        """The loss terms of a grouped batch over ``_multi_calls``: ``score`` = ``forward_multi``'s BCE, ``lm`` = the attached LM's
+        cross-entropy over all labelled answer tokens of all real ``(video, query)`` pairs -- per call one LM batch over the projections in
+        ``(k, t, p)`` row order as they come (``llm_proj_train`` / ``llm_proj``, then the prompt plan), the calls combined with weights equal
+        to their shares of the labelled tokens after the causal shift.  Both terms hang off ONE Q-Former forward per modality and call, so
+        its backward runs once.  ``train`` False: the Q-Former side runs without grad (the frozen LoRA regime)."""
+        queries = [list(q) for q in (queries if queries is not None else samples["text_input"])]
+        if targets is None:
+            targets = samples.get("text_output") or [["[[-1, -1]]"] * len(q) for q in queries]
+        targets = [list(t) for t in targets]
+        if not queries or any(len(q) == 0 for q in queries):
+            raise MraError("forward_multi: every video needs at least one query")
+        if len(targets) != len(queries) or any(len(t) != len(q) for t, q in zip(targets, queries)):
+            raise MraError("forward_multi: targets must hold one text_output per query")
+        counts = [len(q) for q in queries]
+        bce = nn.functional.binary_cross_entropy_with_logits
+        tg = score = None
+        lm_parts = []
+        for call in self._multi_calls(samples, queries, train, want_cls=want_score):
+            vids, cnt, lo, P, num = call["vids"], call["cnt"], call["lo"], call["P"], call["num"]
+            nb = len(vids)
+            if want_score:
+                if tg is None:
+                    tg = self._multi_targets(samples, targets, num)
+                    triples = float(sum(counts) * num)
+                per_mod = [_train_logit(z, cls) for z, cls in call["out"].values()]
+                fused = _weighted_fuse(per_mod, self.fuse_weights).view(nb, num, P).permute(0, 2, 1)      # (b, t, p) -> [nb, P, T]
+                target = torch.zeros(nb, P, num, dtype=torch.float32, device=self._device)
+                real = torch.zeros(nb, P, 1, dtype=torch.float32, device=self._device)                  # 0 on padded slots: no loss, no gradient
+                for k, b in enumerate(vids):
+                    target[k, :cnt[k]] = tg[b][lo: lo + cnt[k]]
+                    real[k, :cnt[k]] = 1.0
+                part = (bce(fused * 20.0, target, reduction="none") * real).sum() / triples
+                score = part if score is None else score + part
+            if want_llm:
+                media = {}
+                for m, (z, _) in call["out"].items():
+                    qf, proj = getattr(self, f"{m}_Qformer"), getattr(self, f"{m}_llm_proj")
+                    media[m] = qf.llm_proj_train(z, proj.weight, proj.bias, grad_scale=self.loss_scale) if train else qf.llm_proj(z)
+                flat, first = self._multi_flatten(samples, queries, targets, call)
+                embeds, mask, labels, plan = self._plan_assemble(flat, media, first_rows=first)
+                probe = getattr(self, "_lm_probe", None)
+                if probe is not None:          # tests look at what goes into the LM
+                    probe({"call": call, "flat": flat, "media": media, "embeds": embeds, "mask": mask, "targets": labels})
+                self._lora_unscale()
+                loss = self._lm_ce(embeds, mask, labels)
+                if train:
+                    loss = _ScaleGrad.apply(loss, float(self.loss_scale)) if self.loss_scale != 1.0 else loss
+                elif self.lora:
+                    loss = self._lora_loss(loss)
+                lm_parts.append((loss, int((plan.targets[:, 1:] != -100).sum())))
+        lm = None
+        if lm_parts:
+            total = float(sum(n for _, n in lm_parts))
+            for loss, n in lm_parts:
+                part = loss if len(lm_parts) == 1 else loss * (n / total)
+                lm = part if lm is None else lm + part
+        return {"score": score, "lm": lm}
 
     def flat_optimizer_params(self) -> List[nn.Parameter]:
         """Parameters for an optimizer after ``enable_qformer_training()``: one flat parameter per Q-Former (bert.* and

@@ -37,6 +37,10 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
   * ``args.lm_loss`` ("stock" | "rows" | "fused", ``finetune --lm-loss``; needs an LM objective unless "stock"): how the LM loss is computed
     (``XInstructBLIP._lm_ce``).  "stock" is the LM's own forward with labels; "rows" and "fused" run the LM's decoder and then the head and
     the cross-entropy on the labelled rows only, as torch ops or on the HIP entries ``mra_lm_head_ce_*`` (``models/lm_head.py``).
+  * ``args.prompt_assembly`` ("cat" | "plan", ``finetune --prompt-assembly``; needs an LM objective unless "cat"): how the prompt in front
+    of the LM is put together -- ``torch.cat`` of its pieces, or a ``PromptPlan`` executed as one row gather (``models/llm_prompt.py``,
+    ``mra_gather_rows``).  ``group_by_video`` with an LM objective sets ``model.grouped_lm`` and always takes the plan: per call one LM batch over the real
+    ``(video, query)`` pairs, whose projections come from ONE ``forward_multi_train`` per modality.
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -123,6 +127,13 @@ class Trainer:
             if self.objective == "score":
                 raise ValueError("lm_loss changes how the LM loss is computed: it needs objective 'llm' or 'both'")
             model.lm_loss = lm_loss
+        prompt_assembly = getattr(args, "prompt_assembly", None) or "cat"
+        if prompt_assembly not in ("cat", "plan"):
+            raise ValueError(f"prompt_assembly must be 'cat' or 'plan', got {prompt_assembly!r}")
+        if prompt_assembly != "cat":
+            if self.objective == "score":
+                raise ValueError("prompt_assembly changes how the LM's prompt is put together: it needs objective 'llm' or 'both'")
+            model.prompt_assembly = prompt_assembly
         self.lora = bool(getattr(args, "lora", False))
         if self.lora:
             if self.objective == "score":
@@ -181,6 +192,8 @@ class Trainer:
             train_collate = collate_grouped
             if hasattr(model, "max_queries_per_call"):
                 model.max_queries_per_call = self.max_queries_per_call
+            if self.objective != "score":
+                model.grouped_lm = True         # the LM term over forward_multi's pass and the prompt plan (off by default on the model)
         bs, nw = getattr(args, "batch_size", 1), getattr(args, "num_workers", 0)
         self.train_sampler = DistributedSampler(train_dataset, shuffle=True, num_replicas=self.world_size, rank=self.rank)
         val_sampler = DistributedSampler(val_dataset, shuffle=False, num_replicas=self.world_size, rank=self.rank)
