@@ -261,7 +261,12 @@ int mra_qformer_cross_precision_report(mra_qformer* h, int32_t* resolved, int32_
  *                 rows); 2: the row factors of the split softmax computed inside the P . enc launch from the scores launch's tile
  *                 statistics (no fold_rowfactor launch).  All bit-identical to mask 0, which issues the launches as before.  Default 1: the
  *                 only bit that measured a gain in the step.  Bit 4 measured no difference and bit 2 measured a loss (+0.30 ms per
- *                 step: the P . enc launch grows by more than the launch it absorbs); both stay as tested opt-ins. */
+ *                 step: the P . enc launch grows by more than the launch it absorbs); both stay as tested opt-ins.
+ *   "self_fuse"   1: the Q|K|V projection and the masked self-attention core of every layer run as ONE launch (mra_debug_qkv_attention): Q, K
+ *                 and V pass through LDS, the QKV array is neither written nor read.  Taken by single-lane forwards (mra_qformer_forward,
+ *                 _forward_multi) with 32 + L <= 64 rows per item, 64-wide heads and a QKV GEMM on its ring tile ("chain_ring" bit 0, at
+ *                 least 1024 rows in all): there it is bit-identical to the two launches.  The pair forward, longer prompts, smaller
+ *                 forwards, forwards that return the full sequence (out_full) and the training forward keep the two launches.  0: the two launches everywhere.  Default 1: -0.08 to -0.11 ms per headline step, -0.16 ms at the reference item shape. */
 int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value);
 /* Derives what the folded path needs from the loaded weights (W_k of every cross layer regrouped per head) on
  * `stream`, if a load made it stale.  mra_qformer_forward does this itself; a caller that runs SEVERAL forwards of one
@@ -799,6 +804,21 @@ int mra_debug_fold_query(const void* x, const int64_t* x_view, size_t x_bytes, c
                          const void* w_k, size_t w_k_bytes, void* q_prime, size_t q_prime_bytes, int32_t rows, int32_t H, int32_t E, int32_t Q,
                          int32_t heads, int32_t dtype, void* stream);
 int64_t mra_debug_fold_query_launches(void);
+/* mra_debug_qkv_attention: steps 1 + 2 of a layer in ONE launch (mra_qformer_set_option "self_fuse"), hidden H = heads * 64:
+ *   rows [items][S][H], wqkv [3 H][H], bqkv [3 H] fp32 or NULL, mask [items][S] int64 or NULL (as mra_debug_self_attention), ctx [items][S][H].
+ * ctx is what mra_debug_gemm on a ring tile followed by mra_debug_self_attention gives, bit for bit.  S > 64 is outside the launch's plan:
+ * MRA_EINVAL, like every null or misaligned (16 bytes) buffer, before any launch; zero items is a no-op.
+ * mra_debug_qkv_attention_launches: such launches since the library was loaded (the forward's included).  mra_debug_attention_launches:
+ * launches of the one-wave-per-unit attention core, masked != 0 the masked form (the self-attention of a layer), 0 the unmasked one.
+ * mra_debug_self_fuse_plan: 1 when a forward of `lanes` lanes (2 = the pair forward) of `items` items with S rows each, `hidden` and `heads`
+ * takes the fused launch under the values `option` of "self_fuse" and `chain_ring` of "chain_ring", 0 when it keeps the two launches;
+ * want_full != 0: the forward returns the full sequence (out_full), which keeps them too (no GPU needed). */
+int mra_debug_qkv_attention(const void* rows, const void* wqkv, const float* bqkv, const int64_t* mask, int32_t dtype, int32_t items, int32_t S,
+                            int32_t heads, void* ctx, void* stream);
+int64_t mra_debug_qkv_attention_launches(void);
+int64_t mra_debug_attention_launches(int32_t masked);
+int32_t mra_debug_self_fuse_plan(int32_t option, int32_t chain_ring, int32_t lanes, int32_t items, int32_t S, int32_t hidden, int32_t heads,
+                                 int32_t dtype, int32_t want_full);
 /* launches of the row-factor kernel (mra_debug_fold_rowfactor and the forwards' step 6c, plain and probe) since the library was loaded */
 int64_t mra_debug_fold_rowfactor_launches(void);
 int mra_debug_fold_rowfactor(const float* stat_m, const float* stat_l, float* factors, int32_t rows, int32_t R, int32_t ntiles, void* P, int64_t ld_p,

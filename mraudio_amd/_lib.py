@@ -214,6 +214,11 @@ PROTOTYPES = {
     "mra_debug_fold_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mra_debug_fold_query_launches": (C.c_int64, []),
+    "mra_debug_qkv_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p]),
+    "mra_debug_qkv_attention_launches": (C.c_int64, []),
+    "mra_debug_attention_launches": (C.c_int64, [C.c_int32]),
+    "mra_debug_self_fuse_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mra_debug_fold_rowfactor_launches": (C.c_int64, []),
     "mra_debug_fold_rowfactor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p]),

@@ -21,6 +21,9 @@
 // attn_combine_kernel) so that 384 (item, head) units still fill 256 CUs.
 // Several prompts per clip (AttnArgs::kv_share > 1): attn_kernel takes the K/V of item n / kv_share; attn_shared_kernel below is the
 // core built for that case, one workgroup-shared K/V ring under the query blocks of 4 prompts.
+#include <atomic>
+#include <type_traits>
+
 #include "kernels.h"
 #include "mra_common.h"
 
@@ -42,6 +45,97 @@ constexpr int SH_STAGES = 3;
 constexpr int SH_STAGE_B = SH_TPS * 2 * TILE_B;        // [tile][K tile | V tile]
 constexpr int SH_PARK_B = (32 * OPAD + 64) * 4;        // one wave's O scratch + m + l
 constexpr int SH_LDS = SH_STAGES * SH_STAGE_B > 4 * SH_PARK_B ? SH_STAGES * SH_STAGE_B : 4 * SH_PARK_B;
+
+// One KV tile of 32 tokens under one wave's 32 queries: S^T = K Q^T, the online softmax in log2 units, O^T += V^T P^T.  kb: the K tile in
+// LDS (128-byte rows, chunks XOR (tok >> 1) & 7), vtile: the LDS address of the V tile (chunks XOR ((tok >> 1) & 1) << 2), koff / vlane: the
+// fragment read offsets of attn_kernel, qf: the Q fragments, wm: the additive mask of the tile's 32 tokens in log2 units (MASKED; -inf past
+// kv_len).  Shared by attn_kernel and qkv_attn_kernel: the same instructions on the same operands, so the same bits.
+template <typename T, bool MASKED>
+__device__ __forceinline__ void attn_tile_step(const char* kb, unsigned vtile, const int (&koff)[4], const unsigned (&vlane)[2],
+                                               const typename Vec8<T>::type (&qf)[4], const float* wm, int tok0, int kv_len, float sl2, int h4,
+                                               float& m_run, float& l_run, f32x16 (&ot)[2]) {
+  // S^T = K * Q^T
+  f32x16 st;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) st[i] = 0.f;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) st = mfma32<T>(lds_read8<T>(kb + koff[s]), qf[s], st);
+
+  // scores in log2 units, tail / padding mask
+  float mx = -INFINITY;
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    f32x4 madd;
+    if (MASKED) {
+      madd = *reinterpret_cast<const f32x4*>(wm + 8 * g4 + h4);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 4 * g4 + e;
+      float y = st[i] * sl2;
+      if (MASKED) {
+        y += madd[e];
+      } else {
+        if (tok0 + 8 * g4 + h4 + e >= kv_len) y = -INFINITY;
+      }
+      st[i] = y;
+      mx = fmaxf(mx, y);
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  const float m_new = fmaxf(m_run, mx);
+  const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+  m_run = m_new;
+  float psum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float p = __builtin_amdgcn_exp2f(st[i] - m_new);
+    st[i] = p;
+    psum += p;
+  }
+  l_run = l_run * alpha + psum;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { ot[0][i] *= alpha; ot[1][i] *= alpha; }
+
+  // P^T fragments (B operand): k-step s uses accumulator registers 8 s .. 8 s + 7
+  typename Vec8<T>::type pf[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pf[s][j] = from_f32<T>(st[8 * s + j]);
+
+  // O^T += V^T * P^T.  The transposed reads go through inline asm: as compiler-visible LDS
+  // loads hipcc orders them behind every pending LDS-DMA (s_waitcnt vmcnt(0)), which would
+  // drain the prefetch of the next tile.  Loads and their wait sit in one statement.
+  {
+    const unsigned vaddr0 = vtile + vlane[0];
+    const unsigned vaddr1 = vtile + vlane[1];
+    i16x4 r00, r01, r02, r03, r10, r11, r12, r13;
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %8\n\t"
+        "ds_read_b64_tr_b16 %1, %8 offset:1024\n\t"
+        "ds_read_b64_tr_b16 %2, %8 offset:2048\n\t"
+        "ds_read_b64_tr_b16 %3, %8 offset:3072\n\t"
+        "ds_read_b64_tr_b16 %4, %9\n\t"
+        "ds_read_b64_tr_b16 %5, %9 offset:1024\n\t"
+        "ds_read_b64_tr_b16 %6, %9 offset:2048\n\t"
+        "ds_read_b64_tr_b16 %7, %9 offset:3072\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(r00), "=&v"(r01), "=&v"(r02), "=&v"(r03), "=&v"(r10), "=&v"(r11), "=&v"(r12), "=&v"(r13)
+        : "v"(vaddr0), "v"(vaddr1)
+        : "memory");
+    auto cat = [](i16x4 lo, i16x4 hi) {
+      i16x8 v8;
+      v8[0] = lo[0]; v8[1] = lo[1]; v8[2] = lo[2]; v8[3] = lo[3];
+      v8[4] = hi[0]; v8[5] = hi[1]; v8[6] = hi[2]; v8[7] = hi[3];
+      return __builtin_bit_cast(typename Vec8<T>::type, v8);
+    };
+    ot[0] = mfma32<T>(cat(r00, r01), pf[0], ot[0]);
+    ot[0] = mfma32<T>(cat(r02, r03), pf[1], ot[0]);
+    ot[1] = mfma32<T>(cat(r10, r11), pf[0], ot[1]);
+    ot[1] = mfma32<T>(cat(r12, r13), pf[1], ot[1]);
+  }
+}
 
 template <typename T, bool MASKED, int SPLITW>
 __global__ void __launch_bounds__(256) attn_kernel(const AttnArgs a) {
@@ -164,90 +258,8 @@ __global__ void __launch_bounds__(256) attn_kernel(const AttnArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     const char* kb = wl + buf * 2 * TILE_B;
-    const char* vb = kb + TILE_B;
-
-    // S^T = K * Q^T
-    f32x16 st;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st[i] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) st = mfma32<T>(lds_read8<T>(kb + koff[s]), qf[s], st);
-
-    // scores in log2 units, tail / padding mask
-    const int tok0 = t * KVT;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      f32x4 madd;
-      if (MASKED) {
-        madd = *reinterpret_cast<const f32x4*>(wmask + tok0 + 8 * g4 + h4);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int i = 4 * g4 + e;
-        float y = st[i] * sl2;
-        if (MASKED) {
-          y += madd[e];
-        } else {
-          if (tok0 + 8 * g4 + h4 + e >= a.kv_len) y = -INFINITY;
-        }
-        st[i] = y;
-        mx = fmaxf(mx, y);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    float psum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float p = __builtin_amdgcn_exp2f(st[i] - m_new);
-      st[i] = p;
-      psum += p;
-    }
-    l_run = l_run * alpha + psum;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { ot[0][i] *= alpha; ot[1][i] *= alpha; }
-
-    // P^T fragments (B operand): k-step s uses accumulator registers 8 s .. 8 s + 7
-    typename Vec8<T>::type pf[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[s][j] = from_f32<T>(st[8 * s + j]);
-
-    // O^T += V^T * P^T.  The transposed reads go through inline asm: as compiler-visible LDS
-    // loads hipcc orders them behind every pending LDS-DMA (s_waitcnt vmcnt(0)), which would
-    // drain the prefetch of the next tile.  Loads and their wait sit in one statement.
-    {
-      const unsigned vaddr0 = wl_lds + buf * 2 * TILE_B + TILE_B + vlane[0];
-      const unsigned vaddr1 = wl_lds + buf * 2 * TILE_B + TILE_B + vlane[1];
-      i16x4 r00, r01, r02, r03, r10, r11, r12, r13;
-      asm volatile(
-          "ds_read_b64_tr_b16 %0, %8\n\t"
-          "ds_read_b64_tr_b16 %1, %8 offset:1024\n\t"
-          "ds_read_b64_tr_b16 %2, %8 offset:2048\n\t"
-          "ds_read_b64_tr_b16 %3, %8 offset:3072\n\t"
-          "ds_read_b64_tr_b16 %4, %9\n\t"
-          "ds_read_b64_tr_b16 %5, %9 offset:1024\n\t"
-          "ds_read_b64_tr_b16 %6, %9 offset:2048\n\t"
-          "ds_read_b64_tr_b16 %7, %9 offset:3072\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(r00), "=&v"(r01), "=&v"(r02), "=&v"(r03), "=&v"(r10), "=&v"(r11), "=&v"(r12), "=&v"(r13)
-          : "v"(vaddr0), "v"(vaddr1)
-          : "memory");
-      auto cat = [](i16x4 lo, i16x4 hi) {
-        i16x8 v8;
-        v8[0] = lo[0]; v8[1] = lo[1]; v8[2] = lo[2]; v8[3] = lo[3];
-        v8[4] = hi[0]; v8[5] = hi[1]; v8[6] = hi[2]; v8[7] = hi[3];
-        return __builtin_bit_cast(typename Vec8<T>::type, v8);
-      };
-      ot[0] = mfma32<T>(cat(r00, r01), pf[0], ot[0]);
-      ot[0] = mfma32<T>(cat(r02, r03), pf[1], ot[0]);
-      ot[1] = mfma32<T>(cat(r10, r11), pf[0], ot[1]);
-      ot[1] = mfma32<T>(cat(r12, r13), pf[1], ot[1]);
-    }
+    attn_tile_step<T, MASKED>(kb, wl_lds + buf * 2 * TILE_B + TILE_B, koff, vlane, qf, MASKED ? wmask + t * KVT : nullptr, t * KVT, a.kv_len, sl2, h4,
+                              m_run, l_run, ot);
     buf ^= 1;
   }
 
@@ -344,6 +356,8 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(const AttnArgs a) {
   *reinterpret_cast<typename Vec8<T>::type*>(op) = r;
 }
 
+std::atomic<long long>& attn_launch_counter(bool masked);
+
 template <typename T>
 int launch_t(const AttnArgs& a, hipStream_t stream) {
   const int qblocks = (a.q_rows + 31) >> 5;
@@ -372,8 +386,286 @@ int launch_t(const AttnArgs& a, hipStream_t stream) {
   if (shared && a.nsplit > 1) {
     hipLaunchKernelGGL(attn_combine_kernel<T>, dim3(nunits), dim3(256), 0, stream, a);
   }
-  return hipGetLastError() == hipSuccess ? 0 : -4;
+  if (hipGetLastError() != hipSuccess) return -4;
+  if (!shared) attn_launch_counter(masked).fetch_add(1, std::memory_order_relaxed);
+  return 0;
 }
+
+// =================================================================================================
+// Fused Q|K|V projection + masked self-attention: steps 1 + 2 of a layer in ONE launch (mra_qformer_set_option "self_fuse")
+// =================================================================================================
+// A workgroup owns one head of G = 2 consecutive items (S <= 64 tokens each): 8 waves, the whole 160 KB of LDS, one workgroup per CU.
+//   phase 1  [Q_h | K_h | V_h] of both items = X W^T for the head's 192 rows of wqkv (rows h * 64 .. + 63 of each of its three H-row
+//            blocks) x 128 activation rows (item slot g = rows 64 g .. 64 g + 63, tokens past S and the item past N clamped: computed,
+//            finite, never stored).  This is gemm_ring_kernel's loop on its 192 x 128 tile: 64-deep K tiles through a ring of 4 LDS
+//            slots staged 2 ahead by LDS-DMA behind a counted vmcnt (one tile, 5 x 1 KiB pieces per wave, stays in flight across the
+//            barrier), two groups of 4 waves on alternating K tiles -- one reads its tile's fragments while its SIMD partners multiply.
+//            An output element is therefore the ring kernel's: the 16 x 16 x 32 MFMA chain of the even K tiles + the chain of the odd
+//            ones + bias, rounded to the operand dtype -- the bits qkv16 holds after the chain's QKV launch on any ring tile.
+//   hand-over  the groups exchange halves of their partial sums through the dead ring (as the ring kernel's epilogue), finish their half
+//            and write it BEHIND the exchange area as the tiles the attention core reads: per item slot Q, K, V as [64 tokens][128 B],
+//            Q and K chunks XOR (tok >> 1) & 7 (ds_read_b128 fragments), V chunks XOR ((tok >> 1) & 1) << 2 (transposed reads).
+//   phase 2  waves 0 .. G * qblocks - 1 each own one (item slot, 32-query block): attn_kernel<T, true, 1>'s unit on attn_tile_step, the
+//            tiles read where phase 1 left them, the mask row and the O scratch in the wave's own 16 KB of the dead exchange area; no
+//            workgroup barrier after the hand-over.  ctx rows go where attn_kernel puts them, with its merge arithmetic (one partial).
+struct QkvAttnArgs {
+  const void* X;           // [N * S][H]
+  const void* W;           // wqkv [3 H][H]
+  const float* bias;       // [3 H] or nullptr
+  const long long* mask;   // [N][S] or nullptr (all ones)
+  void* O;                 // ctx [N * S][H]
+  int N, S, H, heads;
+  float scale;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(512) qkv_attn_kernel(const QkvAttnArgs a) {
+  constexpr int BK = 64, ROWB = BK * 2, G = 2;
+  constexpr int TN = 192, TM = 64 * G, WGN = 2, WGM = 2, STAGES = 4;
+  constexpr int NWC = WGN * WGM, NW = 2 * NWC;
+  constexpr int WTN = TN / WGN, WTM = TM / WGM, FN = WTN / 16, FM = WTM / 16;
+  constexpr int ROWS = TN + TM, NPIECE = ROWS / 8, PPW = NPIECE / NW;
+  constexpr int BUF = ROWS * ROWB;
+  constexpr int RED_BYTES = NWC * FN * FM * 1024;
+  constexpr int HEAD_B = 64 * ROWB, SLOT_B = 3 * HEAD_B;      // one of Q / K / V of an item slot; the slot's three
+  constexpr int PRIV_B = 16384, PRIV_MASK = 32 * OPAD * 4 + 256;   // phase 2, per wave: O scratch + m + l, then the mask row
+  static_assert(NPIECE == PPW * NW && (STAGES - 3) * PPW <= 63, "every wave stages PPW whole pieces per K tile; vmcnt holds 6 bits");
+  static_assert(RED_BYTES + G * SLOT_B <= STAGES * BUF && (FN * FM) % 2 == 0, "exchange area + Q/K/V tiles reuse the ring");
+  static_assert(4 * PRIV_B <= RED_BYTES && PRIV_MASK + 64 * 4 <= PRIV_B && WTM == 64, "phase 2 scratch lies in the exchange area");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using V8 = typename Vec8<T>::type;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int group = wave / NWC, gw = wave - group * NWC;
+  const int wn0 = (gw / WGM) * WTN;
+  const int wm0 = (gw % WGM) * WTM;
+  const int head = blockIdx.x % a.heads, item0 = (blockIdx.x / a.heads) * G;
+  const int S = a.S, H = a.H, N = a.N;
+  const int nk = H / BK;
+
+  // ---- phase 1 ----
+  // this wave's pieces of every K tile: p = wave + i * NW; piece p = LDS rows 8 p .. 8 p + 7 (rows [0, TN) weights, then activations)
+  const char* src[PPW];
+#pragma unroll
+  for (int i = 0; i < PPW; ++i) {
+    const int p = wave + i * NW;
+    const int row = p * 8 + (lane >> 3), c = (lane & 7) ^ ((row >> 1) & 7);
+    if (row < TN) {   // wave-uniform
+      const long long wr = (long long)(row >> 6) * H + head * 64 + (row & 63);
+      src[i] = (const char*)a.W + (wr * H + c * 8) * 2;
+    } else {
+      const int m = row - TN;
+      const int item = min(item0 + (m >> 6), N - 1), tok = min(m & 63, S - 1);
+      src[i] = (const char*)a.X + (((long long)item * S + tok) * H + c * 8) * 2;
+    }
+  }
+  auto stage = [&](int slot, int kt) {
+    char* base = smem + slot * BUF + wave * 1024;
+    const long long koff = (long long)kt * ROWB;
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) glds16(src[i] + koff, base + i * (NW * 1024));
+  };
+#pragma unroll
+  for (int t = 0; t < STAGES - 2; ++t)
+    if (t < nk) stage(t, t);
+  int foff[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const int r = lane & 15;
+    const int c = (4 * ks + (lane >> 4)) ^ ((r >> 1) & 7);
+    foff[ks] = r * ROWB + c * 16;
+  }
+  f32x4 acc[FN][FM];
+#pragma unroll
+  for (int i = 0; i < FN; ++i)
+#pragma unroll
+    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  {
+    V8 fa[2][FN], fb[2][FM];
+    int rslot = 0, fslot = STAGES - 2;   // slots of tile kt and of tile kt + STAGES - 2
+    // one interval of the ring kernel: the barrier that publishes tile kt, then this group's role (compile-time at each call site)
+    auto interval = [&](auto GRP, auto PAR, int kt) {
+      constexpr int g = decltype(GRP)::value, par = decltype(PAR)::value;
+      // tile kt must have landed; tile kt + 1 (issued in the interval since) may stay in flight
+      if (kt < nk) {
+        if (kt + STAGES - 3 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 3) * PPW) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if constexpr (par == g) {
+        if (kt < nk) {   // this group's turn: the fragments of tile kt into registers
+          const char* wb = smem + rslot * BUF + wn0 * ROWB;
+          const char* xb = smem + rslot * BUF + TN * ROWB + wm0 * ROWB;
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int i = 0; i < FN; ++i) fa[ks][i] = lds_read8<T>(wb + i * 16 * ROWB + foff[ks]);
+#pragma unroll
+            for (int j = 0; j < FM; ++j) fb[ks][j] = lds_read8<T>(xb + j * 16 * ROWB + foff[ks]);
+          }
+        }
+      } else {
+        if (kt >= 1) {   // the MFMAs of tile kt - 1 (read in the previous interval)
+          __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int i = 0; i < FN; ++i)
+#pragma unroll
+              for (int j = 0; j < FM; ++j) acc[i][j] = mfma16<T>(fa[ks][i], fb[ks][j], acc[i][j]);
+          __builtin_amdgcn_s_setprio(0);
+        }
+      }
+      if (kt + STAGES - 2 < nk) stage(fslot, kt + STAGES - 2);   // the slot's last readers passed this barrier
+      rslot = rslot + 1 == STAGES ? 0 : rslot + 1;
+      fslot = fslot + 1 == STAGES ? 0 : fslot + 1;
+    };
+    auto run = [&](auto GRP) {
+#pragma clang loop unroll(disable)
+      for (int kt = 0; kt <= nk; kt += 2) {
+        interval(GRP, std::integral_constant<int, 0>{}, kt);
+        if (kt + 1 <= nk) interval(GRP, std::integral_constant<int, 1>{}, kt + 1);
+      }
+    };
+    if (group == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
+  }
+
+  // ---- hand-over ----
+  f32x4 bvs[FN];
+  {
+    const int ln = (lane >> 4) * 4;
+#pragma unroll
+    for (int i = 0; i < FN; ++i) {
+      const int n = wn0 + i * 16 + ln;
+      bvs[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (a.bias) bvs[i] = *reinterpret_cast<const f32x4*>(a.bias + (long long)(n >> 6) * H + head * 64 + (n & 63));
+    }
+  }
+  __syncthreads();   // the ring is dead
+  char* const qkv = smem + RED_BYTES;   // [slot][Q | K | V][64 tokens][128 B]
+  {
+    constexpr int HALF = FN * FM / 2;
+    f32x4* out_red = reinterpret_cast<f32x4*>(smem) + ((size_t)(group * NWC + gw) * HALF) * 64 + lane;
+    const f32x4* in_red = reinterpret_cast<const f32x4*>(smem) + ((size_t)((group ^ 1) * NWC + gw) * HALF) * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+      for (int j = 0; j < FM; ++j)
+        if (((i * FM + j) & 1) != group) out_red[((i * FM + j) >> 1) * 64] = acc[i][j];
+    __syncthreads();
+    const int lm = lane & 15, ln = (lane >> 4) * 4;
+    char* const slot_base = qkv + (wm0 >> 6) * SLOT_B;
+#pragma unroll
+    for (int i = 0; i < FN; ++i) {
+      const int n = wn0 + i * 16 + ln, blk = n >> 6, d = n & 63;   // blk: 0 Q, 1 K, 2 V (uniform over the fragment)
+      const f32x4 bv = bvs[i];
+#pragma unroll
+      for (int j = 0; j < FM; ++j) {
+        if (((i * FM + j) & 1) != group) continue;
+        const f32x4 v = acc[i][j] + in_red[((i * FM + j) >> 1) * 64] + bv;
+        typename Vec4<T>::type o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(v[e]);
+        const int tok = j * 16 + lm;
+        const int swz = blk == 2 ? ((tok >> 1) & 1) << 2 : (tok >> 1) & 7;
+        *reinterpret_cast<typename Vec4<T>::type*>(slot_base + blk * HEAD_B + tok * ROWB + (((d >> 3) ^ swz) << 4) + (d & 4) * 2) = o;
+      }
+    }
+  }
+  __syncthreads();   // Q, K, V of both slots are complete; the exchange area is dead
+
+  // ---- phase 2 ----
+  const int qblocks = (S + 31) >> 5;   // = KV tiles
+  if (wave >= G * qblocks) return;     // (wave-uniform; no workgroup barrier from here on)
+  const int slot = wave / qblocks, qb = wave - slot * qblocks;
+  const int item = item0 + slot;
+  if (item >= N) return;               // ragged last group
+  const int q0 = qb * 32;
+  char* const priv = smem + wave * PRIV_B;
+  float* const wmask = reinterpret_cast<float*>(priv + PRIV_MASK);
+  {
+    float v = -INFINITY;
+    if (lane < S) {
+      const long long mv = a.mask ? a.mask[(long long)item * S + lane] : 1;
+      v = (1.0f - (float)mv) * (-10000.0f * LOG2E);
+    }
+    wmask[lane] = v;
+  }
+  const char* const qt = qkv + slot * SLOT_B;
+  int koff[4];
+  {
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) koff[s] = r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) << 4);
+  }
+  unsigned vlane[2];
+  {
+    const int g = lane >> 4, i = lane & 15, q4 = i >> 2, p = i & 3, h = lane >> 5;
+    const int row = 4 * h + q4;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int c = 4 * mt + 2 * (g & 1) + (p >> 1);
+      const int pc = c ^ (((q4 >> 1) & 1) << 2);
+      vlane[mt] = row * 128 + pc * 16 + (p & 1) * 8;
+    }
+  }
+  V8 qf[4];   // rows past S hold the projection of token S - 1: attn_kernel's clamped query rows
+#pragma unroll
+  for (int s = 0; s < 4; ++s) qf[s] = lds_read8<T>(qt + q0 * ROWB + koff[s]);
+  const unsigned v_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(qt + 2 * HEAD_B);
+  const float sl2 = a.scale * LOG2E;
+  float m_run = -1e30f, l_run = 0.f;
+  f32x16 ot[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { ot[0][i] = 0.f; ot[1][i] = 0.f; }
+  const int h4 = 4 * (lane >> 5);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's mask row has landed (its LDS operations run in order)
+  for (int t = 0; t < qblocks; ++t)
+    attn_tile_step<T, true>(qt + HEAD_B + t * TILE_B, v_lds + t * TILE_B, koff, vlane, qf, wmask + t * KVT, t * KVT, S, sl2, h4, m_run, l_run, ot);
+
+  // attn_kernel's merge of ONE partial, through the wave's own scratch
+  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  float* ow = reinterpret_cast<float*>(priv);
+  float* mw = ow + 32 * OPAD;
+  float* lw = mw + 32;
+  {
+    const int q = lane & 31;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        f32x4 v = {ot[mt][4 * g4], ot[mt][4 * g4 + 1], ot[mt][4 * g4 + 2], ot[mt][4 * g4 + 3]};
+        *reinterpret_cast<f32x4*>(ow + q * OPAD + 32 * mt + 8 * g4 + h4) = v;
+      }
+    if (lane < 32) { mw[q] = m_run; lw[q] = l_tot; }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  for (int idx = lane; idx < 256; idx += 64) {
+    const int q = idx >> 3, dc = idx & 7;
+    const float M = fmaxf(-1e30f, mw[q]);
+    const float wgt = __builtin_amdgcn_exp2f(mw[q] - M);
+    const float L = 0.f + wgt * lw[q];
+    const f32x4 x0 = *reinterpret_cast<const f32x4*>(ow + q * OPAD + 8 * dc);
+    const f32x4 x1 = *reinterpret_cast<const f32x4*>(ow + q * OPAD + 8 * dc + 4);
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = 0.f + wgt * x0[e]; o[4 + e] = 0.f + wgt * x1[e]; }
+    if (q0 + q >= S) continue;
+    const float inv = 1.0f / L;
+    V8 r;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r[e] = from_f32<T>(o[e] * inv);
+    T* op = (T*)a.O + ((long long)item * S + q0 + q) * H + head * 64 + 8 * dc;
+    *reinterpret_cast<V8*>(op) = r;
+  }
+}
+
+std::atomic<long long> g_qkv_attn_launches, g_attn_launches[2];
+std::atomic<long long>& attn_launch_counter(bool masked) { return g_attn_launches[masked ? 1 : 0]; }
 
 // Several prompts over one K/V stream.  Workgroup = (K/V item, head, group of 4 prompt slots, grid split); wave w owns the 32 queries of
 // slot 4 group + w exactly as a wave of attn_kernel<T, false, 1> owns its unit (Q fragments in registers, own online softmax, no cross-wave
@@ -653,6 +945,28 @@ int launch_attention(const AttnArgs& args, int op_dtype, hipStream_t stream) {
   if (a.items % a.kv_share) return -1;
   return op_dtype == OP_F16 ? launch_t<f16>(a, stream) : launch_t<bf16>(a, stream);
 }
+
+bool qkv_attn_supported(int S, int H, int heads) { return S >= 1 && S <= 64 && heads >= 1 && H == heads * 64; }
+
+int launch_qkv_attention(const void* X, const void* wqkv, const float* bqkv, const long long* mask, void* ctx, int N, int S, int H, int heads,
+                         int op_dtype, hipStream_t stream) {
+  if (N <= 0) return 0;
+  if (!X || !wqkv || !ctx || !qkv_attn_supported(S, H, heads) || (op_dtype != OP_F16 && op_dtype != OP_BF16)) return -1;
+  const long long groups = ((long long)N + 1) / 2;
+  if (groups * heads > 0x7fffffffLL) return -1;
+  const QkvAttnArgs a{X, wqkv, bqkv, mask, ctx, N, S, H, heads, 0.125f};
+  constexpr size_t lds = 4 * (192 + 128) * 128;   // the ring: 4 slots of one 64-deep K tile of 192 weight + 128 activation rows, 160 KB
+  const void* fn = op_dtype == OP_F16 ? (const void*)qkv_attn_kernel<f16> : (const void*)qkv_attn_kernel<bf16>;
+  if (!ensure_lds(fn, lds)) return -3;
+  const dim3 grid((unsigned)(groups * heads));
+  if (op_dtype == OP_F16) hipLaunchKernelGGL(qkv_attn_kernel<f16>, grid, dim3(512), lds, stream, a);
+  else hipLaunchKernelGGL(qkv_attn_kernel<bf16>, grid, dim3(512), lds, stream, a);
+  if (hipGetLastError() != hipSuccess) return -4;
+  g_qkv_attn_launches.fetch_add(1, std::memory_order_relaxed);
+  return 0;
+}
+long long qkv_attn_launch_count() { return g_qkv_attn_launches.load(std::memory_order_relaxed); }
+long long attn_launch_count(int masked) { return g_attn_launches[masked ? 1 : 0].load(std::memory_order_relaxed); }
 
 int attn_shared_pick_split(int kv_items, int kv_share, int heads, int kv_len) {
   const int units = kv_items * heads * ((kv_share + 3) / 4);

@@ -427,6 +427,15 @@ int launch_attention(const AttnArgs& a, int op_dtype, hipStream_t stream);
 // (merged by the same combine kernel).
 int attn_shared_pick_split(int kv_items, int kv_share, int heads, int kv_len);
 int launch_attention_shared(const AttnArgs& a, int op_dtype, hipStream_t stream);
+// Steps 1 + 2 of a layer in one launch (attention.hip: qkv_attn_kernel; mra_qformer_set_option "self_fuse"): the fused Q|K|V projection of the
+// rows X [N * S][H] by wqkv [3H][H] (+ bqkv) and the masked self-attention core over them, one workgroup per (two consecutive items, head); Q, K
+// and V pass through LDS and never reach HBM.  ctx [N * S][H] gets what launch_gemm on a ring tile + launch_attention give, bit for bit.
+// S in 1 .. 64, H = heads * 64; -1 for any other shape (qkv_attn_supported).
+bool qkv_attn_supported(int S, int H, int heads);
+int launch_qkv_attention(const void* X, const void* wqkv, const float* bqkv, const long long* mask, void* ctx, int N, int S, int H, int heads,
+                         int op_dtype, hipStream_t stream);
+long long qkv_attn_launch_count();        // launches since the library was loaded (read-only diagnostics, as gemm_launch_count)
+long long attn_launch_count(int masked);  // launch_attention launches of the one-wave-per-unit core: masked (self-attention) / not
 
 // ---- normalisation / embeddings / conversions -----------------------------------------------
 // y = LN(x) over H (multiple of 256, <= 1024) with gain/bias; writes f32 and/or op-dtype copies.

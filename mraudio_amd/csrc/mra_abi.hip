@@ -676,6 +676,18 @@ int check_loaded(mra_qformer* h) {
   return miss > tolerated ? fail(MRA_ESTATE, std::string("parameters not loaded: ") + names) : MRA_OK;
 }
 
+// Steps 1 + 2 of every layer in one launch (launch_qkv_attention) instead of two: the option, a single lane, S <= 64 and 64-wide heads (H is
+// then a multiple of the 64-deep K step; the operand dtype of a handle is always f16 or bf16) -- and a forward whose QKV GEMM would run its
+// ring tile (chain_ring bit 0, >= 1024 rows, 3 H a multiple of 144).  The fused launch adds the ring kernel's two accumulator chains (even and
+// odd K tiles), the two-buffer tiles of smaller forwards ONE chain over K: with the last condition the option never changes a bit of any
+// forward, so the pair forward and the single-lane forwards stay equal at every size.  A forward that returns the full sequence (out_full: the
+// reference-style call, not the scoring path) keeps the launch sequence that "chain_ring" alone selects -- tests/test_gpu_parity.py counts its
+// QKV ring launches per mask.  Everything else keeps the two launches.
+bool self_fuse_plan(int option, int lanes, long long rows, int S, int hidden, int heads, int op, int chain_ring, bool want_full) {
+  return option == 1 && lanes == 1 && !want_full && (op == OP_F16 || op == OP_BF16) && qkv_attn_supported(S, hidden, heads) && (chain_ring & 1) && rows >= 1024 &&
+         (3 * hidden) % 144 == 0;
+}
+
 // The Q-Former forward of nl lanes (1: mra_qformer_forward, 2: mra_qformer_forward_pair) of N items with L text rows: embeddings, the
 // layers, the last layer's LayerNorms into the lanes' outputs.  A grouped launch holds the query problems of every lane, then their text
 // problems.  Split precision, out_full, query_embeds and the fused residual + LayerNorm (chain_ring bit 3) are single-lane only.
@@ -701,6 +713,7 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
   const size_t t_off32 = (size_t)Q * H;                     // element offset (f32)
 
   // residual projection + LayerNorm in ONE launch (chain_ring bit 3, on the 96 x 64 ring tile): its per-row-tile counters start at zero
+  const bool self_fuse = self_fuse_plan(h->self_fuse, nl, (long long)N * S, S, H, c.heads, op, h->chain_ring, lanes[0].out_full != nullptr);
   const bool ln_fuse = !pair && (h->chain_ring & 12) == 12 && H % 96 == 0 && H % 256 == 0 && H <= 1024;
   int rc;
   for (int l = 0; l < nl; ++l) {
@@ -746,27 +759,33 @@ int run_lanes(Lane* lanes, int nl, const int64_t* input_ids, const int64_t* atte
     // no row reaches lane_rows)
     const LayerW* Lw[2] = {&lanes[0].h->layers[i], &lanes[nl - 1].h->layers[i]};
     const bool last = i == c.layers - 1;
-    // 1. fused Q|K|V projection of all S rows
-    {
-      GemmProb p[2] = {};
-      for (int l = 0; l < nl; ++l) {
-        p[l].A = lanes[l].w.hA16; p[l].a = all_rows;
-        p[l].W = Lw[l]->wqkv; p[l].bias = Lw[l]->bqkv;
-        p[l].C = lanes[l].w.qkv16; p[l].c = plain(N * S, 3 * H);
-        p[l].M = N * S; p[l].N = 3 * H; p[l].K = H;
-        // The chain GEMMs at ~1-2 k rows are bound by the operand bytes each CU pulls through its load path (~33 B / clk from L2),
-        // not by tile count: 128 x 128 tiles (288 of them) move half the bytes per flop of the 1152 64 x 64 tiles the automatic
-        // choice makes (headline step 6.75 -> 6.67 ms, reference item shape 2.65 -> 2.55 ms together with the down-projection below)
-        p[l].tile_cfg = N * S >= 1024 ? GT_128 : GT_AUTO;
-        // ... and at ~2 k rows the ring kernel's 144 x 128 tile is exactly one workgroup per CU (2048 x 2304 = 16 x 16 tiles): 14.4 vs 17.6 us stand-alone
-        if ((lanes[l].h->chain_ring & 1) && N * S >= 1024 && (3 * H) % 144 == 0) p[l].tile_cfg = GT_RING_144x128;
+    if (self_fuse) {
+      // 1 + 2. Q|K|V projection and self-attention core in one launch: Q, K, V pass through LDS, qkv16 is neither written nor read
+      rc = launch_qkv_attention(w.hA16, Lw[0]->wqkv, Lw[0]->bqkv, mask, w.ctx16, N, S, H, c.heads, op, stream);
+      if (rc) return chk(rc, "qkv + self attention");
+    } else {
+      // 1. fused Q|K|V projection of all S rows
+      {
+        GemmProb p[2] = {};
+        for (int l = 0; l < nl; ++l) {
+          p[l].A = lanes[l].w.hA16; p[l].a = all_rows;
+          p[l].W = Lw[l]->wqkv; p[l].bias = Lw[l]->bqkv;
+          p[l].C = lanes[l].w.qkv16; p[l].c = plain(N * S, 3 * H);
+          p[l].M = N * S; p[l].N = 3 * H; p[l].K = H;
+          // The chain GEMMs at ~1-2 k rows are bound by the operand bytes each CU pulls through its load path (~33 B / clk from L2),
+          // not by tile count: 128 x 128 tiles (288 of them) move half the bytes per flop of the 1152 64 x 64 tiles the automatic
+          // choice makes (headline step 6.75 -> 6.67 ms, reference item shape 2.65 -> 2.55 ms together with the down-projection below)
+          p[l].tile_cfg = N * S >= 1024 ? GT_128 : GT_AUTO;
+          // ... and at ~2 k rows the ring kernel's 144 x 128 tile is exactly one workgroup per CU (2048 x 2304 = 16 x 16 tiles): 14.4 vs 17.6 us stand-alone
+          if ((lanes[l].h->chain_ring & 1) && N * S >= 1024 && (3 * H) % 144 == 0) p[l].tile_cfg = GT_RING_144x128;
+        }
+        rc = launch_gemm(p, nl, EPI_OP, op, stream);
+        if (rc) return chk(rc, "qkv gemm");
       }
-      rc = launch_gemm(p, nl, EPI_OP, op, stream);
-      if (rc) return chk(rc, "qkv gemm");
+      // 2. self-attention core of all nl N items
+      rc = launch_attention(self_attn_args(c, w.qkv16, w.ctx16, mask, nl * N, S), op, stream);
+      if (rc) return chk(rc, "self attention");
     }
-    // 2. self-attention core of all nl N items
-    rc = launch_attention(self_attn_args(c, w.qkv16, w.ctx16, mask, nl * N, S), op, stream);
-    if (rc) return chk(rc, "self attention");
     // 3. output projection + residual, 4. LayerNorm -> hB
     {
       GemmProb p[2] = {};
@@ -1381,6 +1400,11 @@ int mra_qformer_set_option(mra_qformer* h, const char* name, int32_t value) {
     if (value < 0 || (value & ~7))
       return fail(MRA_EINVAL, "cross_fuse is a mask of 1 (query projection and Q' in one launch), 2 (row factors inside the P.enc launch) and 4 (context GEMM on the 64 x 64 tile)");
     h->cross_fuse = value;
+    return MRA_OK;
+  }
+  if (key == "self_fuse") {
+    if (value < 0 || value > 1) return fail(MRA_EINVAL, "self_fuse is 0 (QKV GEMM, then the self-attention core) or 1 (both in one launch)");
+    h->self_fuse = value;
     return MRA_OK;
   }
   if (key == "multi_core") {
@@ -2227,5 +2251,29 @@ int mra_debug_fold_query(const void* x, const int64_t* x_view, size_t x_bytes, c
 
 int64_t mra_debug_fold_query_launches(void) { return fold_query_launch_count(); }
 int64_t mra_debug_fold_rowfactor_launches(void) { return fold_rowfactor_launch_count(); }
+
+// Steps 1 + 2 of a layer in ONE launch (attention.hip: qkv_attn_kernel; "self_fuse") on its own, through the launch function the forward calls;
+// hidden = heads * 64.  Shapes outside the plan (S > 64) are refused, nothing is launched.
+int mra_debug_qkv_attention(const void* rows, const void* wqkv, const float* bqkv, const int64_t* mask, int32_t dtype, int32_t items, int32_t S,
+                            int32_t heads, void* ctx, void* stream) {
+  int op;
+  if (items < 0 || S < 1 || heads < 1 || heads > 16) return fail(MRA_EINVAL, "sizes: items >= 0, S >= 1, heads in 1..16");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (!qkv_attn_supported(S, heads * 64, heads)) return fail(MRA_EINVAL, "the fused launch takes S <= 64 (longer prompts run the two launches)");
+  if (items == 0) return MRA_OK;
+  if (!rows || !wqkv || !ctx) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(rows, 16) || !dbg_aligned(wqkv, 16) || !dbg_aligned(ctx, 16) || !dbg_aligned(bqkv, 16))
+    return fail(MRA_EINVAL, "rows, wqkv, bqkv and ctx must be 16-byte aligned");
+  return chk(launch_qkv_attention(rows, wqkv, bqkv, (const long long*)mask, ctx, items, S, heads * 64, heads, op, as_stream(stream)), "qkv + self attention");
+}
+int64_t mra_debug_qkv_attention_launches(void) { return qkv_attn_launch_count(); }
+int64_t mra_debug_attention_launches(int32_t masked) { return attn_launch_count(masked); }
+// 1: a forward with `lanes` lanes of `items` items at S rows each takes the fused launch under the option values given; 0: it keeps the two launches
+int32_t mra_debug_self_fuse_plan(int32_t option, int32_t chain_ring, int32_t lanes, int32_t items, int32_t S, int32_t hidden, int32_t heads,
+                                 int32_t dtype, int32_t want_full) {
+  int op;
+  if (!dbg_op(dtype, &op) || items < 0 || S < 0) return 0;
+  return self_fuse_plan(option, lanes, (long long)items * S, S, hidden, heads, op, chain_ring, want_full != 0) ? 1 : 0;
+}
 
 }  // extern "C"

@@ -172,6 +172,10 @@ struct mra_qformer {
   // the P . enc launch from the scores launch's tile statistics (GemmProb::ps_stats: no fold_rowfactor launch, no factor array; bit-identical,
   // but that launch grows by 61 us to save 11: measured slower, opt-in only); 0 = the launches as they were
   int cross_fuse = 1;   // measured in the step, one process, masks in turn: 0 / 1 / 2 / 3 / 4 / 7 = 6.463 / 6.380 / 6.760 / 6.675 / 6.460 / 6.668 ms
+  // steps 1 + 2 of a layer (QKV projection, masked self-attention) in ONE launch (mra_qformer_set_option "self_fuse"; attention.hip:
+  // qkv_attn_kernel, bit-identical to the two launches, qkv16 neither written nor read): single-lane forwards with S <= 64, 64-wide heads and
+  // the QKV GEMM on its ring tile (>= 1024 rows); the pair forward, longer prompts, smaller forwards and the training forward keep the two launches
+  int self_fuse = 1;    // measured in the step, parent / this build alternating: 6.4095 -> 6.303 ms and, a second session, 6.520 -> 6.440 ms; reference item shape 2.616 -> 2.452 ms
   // mra_qformer_forward_multi: the cross core that lets several prompts read one K/V stream (mra_qformer_set_option "multi_core"):
   // 0 attn_kernel with AttnArgs::kv_share, 1 the shared-stream core (attn_shared_kernel).  The rule for the default: whichever the line of
   // tools/bench_multi_query.py shows faster at P >= 4 on both of its shapes.  Measured (profiles/multi_query_line.json, one session): 1 at
