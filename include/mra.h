@@ -362,6 +362,30 @@ int mra_lm_head_ce_forward(const void* h, int64_t ldh, int32_t R, int32_t K, con
 int mra_lm_head_ce_backward(const float* g, const void* W, int64_t ldw, int32_t V, int32_t K, int32_t dtype, const int32_t* labels, const float* lse,
                             void* workspace, size_t workspace_bytes, void* dh, int64_t lddh, int32_t R, void* stream);
 
+/* ---- LM decode: one-token attention over a K/V cache read in place ------------------------------------------------
+ * replaces: scaled_dot_product_attention with ONE query row per head inside the reference's self.llm_model.generate(inputs_embeds=...,
+ * attention_mask=...) (models/xinstructblip.py:383-391), and with a static cache the torch.cat of a growing one.  Stateless like mra_lora_* and
+ * mra_lm_head_ce_*: caller-owned buffers, a stream, no allocation, no synchronisation.  q, out [B][Hq][D], k, v [B][Hkv][S][D] in `dtype`
+ * (MRA_F16 / MRA_BF16) with ELEMENT strides (*_sb batch, *_sh head, *_ss key; D contiguous), so a static cache's [B][Hkv][Smax][D] buffer is
+ * read as it lies.  mask [B][S] bytes with batch stride mask_sb, nonzero = attend, NULL = every key.  With G = Hq / Hkv:
+ *   out[b,h] = softmax_s(scale * q[b,h] . k[b, h / G, s] over the attended s) v[b, h / G]      lse[b,h] = log sum_s exp(scale q.k)  (f32, nullable)
+ * Logits, softmax and the P V sum are fp32, P is never rounded to 16 bits, out is rounded once.  A row with no attended key gives out = +0 and
+ * lse = -inf.  A masked key is never read: masking is a select, whatever bits the slot holds.
+ * A workgroup owns (b, kv head, a chunk of 256 keys) for all G query heads and leaves fp32 partials (m, l, acc[D]) in the workspace; a second
+ * launch merges the chunks in ascending order, skipping a chunk without an attended key.  No atomics: two runs give the same bits.
+ * Accepted: D 64 or 128, G 1, 2, 4 or 8, S >= 1, B and Hkv at most 65535.  Checked before any launch (MRA_EINVAL, named in mra_last_error):
+ * negative B, unknown dtype, another D or G or Hq % Hkv != 0, S < 1, NULL q / k / v / out / workspace, one of them not 16-byte aligned, a
+ * stride that is not a multiple of 8 elements, k_ss or v_ss below D, lse not 4-byte aligned, a scale that is not finite, a short workspace.
+ * B == 0 launches nothing and returns MRA_OK whatever else is passed.
+ *
+ * Workspace bytes, with C = ceil(S / 256) chunks and up(x) = x rounded up to 256:   2 up(4 B Hq C) + up(4 B Hq C D)
+ * Host only; 0 (and a message) for B < 0, Hq < 1, S < 1 or another D. */
+size_t mra_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t S, int32_t D);
+int mra_decode_attention(const void* q, int64_t q_sb, int64_t q_sh, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v,
+                         int64_t v_sb, int64_t v_sh, int64_t v_ss, const uint8_t* mask, int64_t mask_sb, int32_t B, int32_t Hq, int32_t Hkv,
+                         int32_t S, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb, int64_t o_sh, float* lse, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- LM objective: prompt assembly as one row gather -------------------------------------------------------------
  * replaces: the torch.cat of cue, media, timestamp, duration and prompt pieces in front of the LM (models/xinstructblip.py:341-381, :541-595)
  * and, through the inverse plan, its backward.  Stateless like mra_lora_* and mra_lm_head_ce_*: caller-owned buffers, a stream, no allocation,

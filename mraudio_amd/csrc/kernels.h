@@ -264,6 +264,16 @@ int launch_lm_head_fwd(const void* H, long long ldh, int R, int K, const void* W
 // dh [R][K] (operand dtype, pitch lddh) = sum_v g_r exp(tmax - lse) P~ W - g_r W[y_r]; part f32 [lm_head_splits][R][K] is workspace.
 int launch_lm_head_bwd(const float* g, const void* W, long long ldw, int V, int K, const int* labels, const float* lse, const float* tmax,
                        const void* P, float* part, void* dh, long long lddh, int R, int op_dtype, hipStream_t stream);
+// One-token attention over a K/V cache read in place (decode_attn.hip): q, out [B][Hq][D], k, v [B][Hkv][S][D] in the operand dtype with element
+// strides (D contiguous, every stride a multiple of 8), mask [B][S] bytes (NULL: all attended), lse f32 [B][Hq] (may be NULL).  A workgroup owns
+// DECODE_CHUNK keys of one (b, kv head) for all Hq / Hkv query heads; pm, pl f32 [B][Hq][chunks] and pacc f32 [B][Hq][chunks][D] are workspace.
+// D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}; two launches, no atomics.
+constexpr int DECODE_CHUNK = 256;
+inline int decode_chunks(int S) { return (int)(((long long)S + DECODE_CHUNK - 1) / DECODE_CHUNK); }
+int launch_decode_attention(const void* q, long long q_sb, long long q_sh, const void* k, long long k_sb, long long k_sh, long long k_ss,
+                            const void* v, long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq,
+                            int Hkv, int S, int D, float scale, void* out, long long o_sb, long long o_sh, float* lse, float* pm, float* pl,
+                            float* pacc, int op_dtype, hipStream_t stream);
 // Row gather with a cast (prompt.hip): out [n_rows][width] (out_dtype 0 / 1 / 2 = f32 / f16 / bf16, pitch ldo) row i = source plan[i][0], row
 // plan[i][1]; source -1 -> +0, any other entry out of range -> NaN, nothing read.  The per-source arguments are host arrays of n_src <=
 // GATHER_MAX_SRC entries; plan int32 [n_rows][2] on the device.  width % 8 == 0, 16-byte aligned rows everywhere; a wave owns a row, no atomics.

@@ -1629,6 +1629,67 @@ int mra_lm_head_ce_backward(const float* g, const void* W, int64_t ldw, int32_t 
              "lm_head_ce_backward");
 }
 
+// ---- one-token attention of the LM's decode over a K/V cache read in place (decode_attn.hip) -----------------------------------------------
+// replaces: scaled_dot_product_attention with one query row per head inside self.llm_model.generate(...), models/xinstructblip.py:383-391.
+// Every check comes before a launch.
+namespace {
+
+// the workspace, in this order: chunk maxima, chunk sums [B][Hq][chunks] f32 | chunk accumulators [B][Hq][chunks][D] f32
+struct DecodeWs {
+  size_t stat, acc, total;
+};
+DecodeWs decode_ws(int32_t B, int32_t Hq, int32_t S, int32_t D) {
+  DecodeWs w{};
+  const size_t rows = (size_t)B * (size_t)Hq * (size_t)decode_chunks(S);
+  w.stat = up256(4 * rows);
+  w.acc = up256(4 * rows * (size_t)D);
+  w.total = 2 * w.stat + w.acc;
+  return w;
+}
+
+}  // namespace
+
+size_t mra_decode_attention_workspace_bytes(int32_t B, int32_t Hq, int32_t S, int32_t D) {
+  if (B < 0 || Hq < 1 || S < 1 || (D != 64 && D != 128)) {
+    fail(MRA_EINVAL, "decode_attention_workspace_bytes: B >= 0, Hq >= 1, S >= 1, D 64 or 128");
+    return 0;
+  }
+  return decode_ws(B, Hq, S, D).total;
+}
+
+int mra_decode_attention(const void* q, int64_t q_sb, int64_t q_sh, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v,
+                         int64_t v_sb, int64_t v_sh, int64_t v_ss, const uint8_t* mask, int64_t mask_sb, int32_t B, int32_t Hq, int32_t Hkv,
+                         int32_t S, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb, int64_t o_sh, float* lse, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  const std::string w("decode_attention");
+  if (B < 0) return fail(MRA_EINVAL, w + ": negative B");
+  if (B == 0) return MRA_OK;   // launches nothing, touches nothing
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": dtype must be MRA_F16 or MRA_BF16");
+  if (D != 64 && D != 128) return fail(MRA_EINVAL, w + ": D must be 64 or 128");
+  if (S < 1) return fail(MRA_EINVAL, w + ": S must be at least 1");
+  if (Hq < 1 || Hkv < 1 || Hq % Hkv) return fail(MRA_EINVAL, w + ": Hq must be a positive multiple of Hkv");
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return fail(MRA_EINVAL, w + ": Hq / Hkv must be 1, 2, 4 or 8");
+  if (B > 65535 || Hkv > 65535) return fail(MRA_EINVAL, w + ": B and Hkv must be at most 65535");
+  if (!q || !k || !v || !out || !workspace) return fail(MRA_EINVAL, w + ": null argument");
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(workspace))
+    return fail(MRA_EINVAL, w + ": q, k, v, out and the workspace must be 16-byte aligned");
+  if (q_sb % 8 || q_sh % 8 || k_sb % 8 || k_sh % 8 || k_ss % 8 || v_sb % 8 || v_sh % 8 || v_ss % 8 || o_sb % 8 || o_sh % 8)
+    return fail(MRA_EINVAL, w + ": the strides must be multiples of 8 elements (16 bytes)");
+  if (k_ss < D || v_ss < D) return fail(MRA_EINVAL, w + ": k_ss / v_ss < D");
+  if (lse && reinterpret_cast<uintptr_t>(lse) % 4) return fail(MRA_EINVAL, w + ": lse must be 4-byte aligned");
+  if (!std::isfinite(scale)) return fail(MRA_EINVAL, w + ": scale must be finite");
+  const DecodeWs ws = decode_ws(B, Hq, S, D);
+  if (workspace_bytes < ws.total) return fail(MRA_EINVAL, w + ": workspace too small (mra_decode_attention_workspace_bytes)");
+  char* base = static_cast<char*>(workspace);
+  float* pm = reinterpret_cast<float*>(base);
+  float* pl = reinterpret_cast<float*>(base + ws.stat);
+  float* pacc = reinterpret_cast<float*>(base + 2 * ws.stat);
+  return chk(launch_decode_attention(q, q_sb, q_sh, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, mask, mask_sb, B, Hq, Hkv, S, D, scale, out, o_sb,
+                                     o_sh, lse, pm, pl, pacc, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)),
+             "decode_attention");
+}
+
 // ---- prompt assembly: one row gather with a cast (prompt.hip) -----------------------------------------------------------------------------
 // replaces: the torch.cat in front of the LM, models/xinstructblip.py:341-381, :541-595.  Every check comes before a launch.
 int mra_gather_rows(void* out, int64_t ldo, int32_t out_dtype, int32_t n_rows, int32_t width, const mra_rows_src* srcs, int32_t n_src,

@@ -130,6 +130,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-queries-per-call", type=int, default=16, help="with --group-by-video: most queries of one video scored in one call")
     ap.add_argument("--llm-path", default=None, help="local directory of the causal LM (local_files_only, bf16): predictions then come from "
                                                      "generate_llm, the reference's decode")
+    ap.add_argument("--lm-decode", choices=("stock", "hip"), default="stock",
+                    help="with --llm-path: how the LM decodes: stock = llm_model.generate as it comes; hip = the same greedy decode over a static "
+                         "cache with the one-token attention on mra_decode_attention")
     ap.add_argument("--lora", action="store_true", help="with --llm-path: put LoRA adapters on the LM and load their weights (llm_model.* keys) from --checkpoint")
     ap.add_argument("--lora-r", type=int, default=8)
     ap.add_argument("--lora-alpha", type=float, default=8.0)
@@ -172,6 +175,7 @@ def main(argv=None) -> None:
                           **({} if llm is None else {"op_dtype": torch.bfloat16, "llm_hidden_size": llm.get_input_embeddings().weight.shape[1]}))
     if llm is not None:
         model.attach_llm(llm, tok)
+        model.lm_decode = args.lm_decode
         if args.lora:       # the adapters must exist before the file's llm_model.* keys can be routed into them
             model.enable_lora(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout)
             if args.checkpoint:

@@ -112,6 +112,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="how the prompt in front of the LM is put together: cat = torch.cat of its pieces; plan = a table of (source, row) "
                          "executed as one row gather forward and one per modality backward (mra_gather_rows); plan needs --objective llm or "
                          "both; --group-by-video with an LM objective always takes the plan")
+    ap.add_argument("--val-decode", choices=("score", "llm"), default="score",
+                    help="what validation scores: score = the scorer's span (as always); llm = the strings the attached LM decodes (generate_llm, "
+                         "the reference's own validation); llm needs --llm-path")
+    ap.add_argument("--lm-decode", choices=("stock", "hip"), default="stock",
+                    help="how the LM decodes: stock = llm_model.generate as it comes; hip = the same greedy decode over a static cache with the "
+                         "one-token attention on mra_decode_attention")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
                          "(mra_video_frames_forward) instead of as float32 pixels made on the host")
@@ -137,6 +143,8 @@ def main(argv=None):
         parser.error("--lm-loss rows / fused needs --objective llm or both")
     if args.prompt_assembly != "cat" and args.objective == "score":
         parser.error("--prompt-assembly plan needs --objective llm or both")
+    if args.val_decode == "llm" and not args.llm_path:
+        parser.error("--val-decode llm needs --llm-path DIR")
     logging.basicConfig(level=logging.INFO)
     return run_train(args)
 

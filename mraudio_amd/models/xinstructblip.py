@@ -231,6 +231,9 @@ class XInstructBLIP(nn.Module):
     # the LM objective ("llm" / "both") on grouped batches (several queries per video: forward_multi's pass + the plan).  Off: such a batch
     # is refused with MraError, as it always was
     grouped_lm = False
+    # how generate_llm / generate_multi_llm decode (_llm_decode): "stock" = llm_model.generate as it comes (a growing cache, SDPA), "hip" = the
+    # same greedy generate over a static cache with the one-token attention on mra_decode_attention (models/lm_decode.py)
+    lm_decode = "stock"
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
@@ -241,8 +244,11 @@ class XInstructBLIP(nn.Module):
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
                  cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0,
                  video_processor=None, lm_loss: str = "stock", prompt_assembly: str = "cat",
-                 grouped_lm: bool = False):
+                 grouped_lm: bool = False, lm_decode: str = "stock"):
         super().__init__()
+        if lm_decode not in ("stock", "hip"):
+            raise ValueError(f"lm_decode must be 'stock' or 'hip', got {lm_decode!r}")
+        self.lm_decode = lm_decode
         if lm_loss not in ("stock", "rows", "fused"):
             raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
         self.lm_loss = lm_loss
@@ -1027,7 +1033,19 @@ class XInstructBLIP(nn.Module):
         return self._llm_decode(embeds, mask, max_new_tokens)
 
     def _llm_decode(self, embeds, mask, max_new_tokens: int) -> List[str]:
-        outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens)
+        """``lm_decode = "stock"``: the reference's call.  ``"hip"``: the same greedy decode over a static cache (no ``torch.cat`` of the K/V per
+        token) with every one-token attention on ``mra_decode_attention`` (``models/lm_decode.py``); ``disable_compile`` because ``generate``
+        would otherwise compile the forward around the ctypes launches.  The LM is as it was after the call."""
+        if self.lm_decode == "stock":
+            outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens)
+        elif self.lm_decode == "hip":
+            from .lm_decode import hip_decode
+
+            with hip_decode(self.llm_model):
+                outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens,
+                                                  cache_implementation="static", disable_compile=True)
+        else:
+            raise MraError(f"lm_decode must be 'stock' or 'hip', got {self.lm_decode!r}")
         outputs[outputs == 0] = 2                                      # :392
         return [o.strip() for o in self.llm_tokenizer.batch_decode(outputs, skip_special_tokens=True)]
 

@@ -41,6 +41,11 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     of the LM is put together -- ``torch.cat`` of its pieces, or a ``PromptPlan`` executed as one row gather (``models/llm_prompt.py``,
     ``mra_gather_rows``).  ``group_by_video`` with an LM objective sets ``model.grouped_lm`` and always takes the plan: per call one LM batch over the real
     ``(video, query)`` pairs, whose projections come from ONE ``forward_multi_train`` per modality.
+  * ``args.val_decode`` ("score" | "llm", ``finetune --val-decode``; "llm" needs an attached LM, else ``MraError``): what ``eval_epoch`` scores.
+    "score" is the scorer's span; "llm" is the reference's own validation (``:157-165``): the strings ``generate_llm`` decodes (a validation
+    loader of grouped records: ``generate_multi_llm``, flattened in the loader's order) through the same ``post_process`` ->
+    ``moment_str_to_list`` -> ``eval_submission`` tail -- the validation under which frozen Q-Formers with LoRA adapters move the metric.
+    ``args.lm_decode`` ("stock" | "hip", ``finetune --lm-decode``): how that decode runs (``XInstructBLIP._llm_decode``, ``models/lm_decode.py``).
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -134,6 +139,19 @@ class Trainer:
             if self.objective == "score":
                 raise ValueError("prompt_assembly changes how the LM's prompt is put together: it needs objective 'llm' or 'both'")
             model.prompt_assembly = prompt_assembly
+        # val_decode "llm": validation decodes with the attached LM (generate_llm, the reference's own validation) instead of the scorer's span;
+        # lm_decode "hip": that decode over a static cache with the one-token attention on HIP (models/lm_decode.py)
+        self.val_decode = getattr(args, "val_decode", None) or "score"
+        if self.val_decode not in ("score", "llm"):
+            raise ValueError(f"val_decode must be 'score' or 'llm', got {self.val_decode!r}")
+        if self.val_decode == "llm" and getattr(model, "llm_model", None) is None:
+            from .._lib import MraError
+            raise MraError("val_decode 'llm' needs a model with an LM attached (attach_llm; finetune --llm-path)")
+        lm_decode = getattr(args, "lm_decode", None) or "stock"
+        if lm_decode not in ("stock", "hip"):
+            raise ValueError(f"lm_decode must be 'stock' or 'hip', got {lm_decode!r}")
+        if lm_decode != "stock":
+            model.lm_decode = lm_decode
         self.lora = bool(getattr(args, "lora", False))
         if self.lora:
             if self.objective == "score":
@@ -283,7 +301,17 @@ class Trainer:
         results = []
         for samples in self.val_dataloader:
             samples = prepare_sample(samples, self.device if self.device.type == "cuda" else None)
-            outputs = self.model.generate(samples)
+            grouped = self.val_decode == "llm" and bool(samples["text_input"]) and isinstance(samples["text_input"][0], (list, tuple))
+            if grouped:       # one record per video with the lists of its queries: flattened in the loader's order
+                per_video = self.model.generate_multi_llm(samples)
+                outputs = [txt for texts in per_video for txt in texts]
+                samples = {"qid": [x for v in samples["qid"] for x in v], "query": [x for v in samples["query"] for x in v],
+                           "vid": [vid for vid, v in zip(samples["vid"], samples["qid"]) for _ in v],
+                           "text_output": [x for v in samples["text_output"] for x in v]}
+            elif self.val_decode == "llm":
+                outputs = self.model.generate_llm(samples)
+            else:
+                outputs = self.model.generate(samples)
             if not results and self.rank == 0 and hasattr(self.model, "cross_precision_report") and not getattr(self, "_precision_logged", False):
                 from ..evaluate import format_cross_precision   # once, after the first validation batch
                 logging.info("cross-attention precision: %s", format_cross_precision(self.model.cross_precision_report()))
@@ -341,6 +369,6 @@ def default_args(**kw) -> SimpleNamespace:
     """The reference's ``finetune.py`` defaults (``:44-62``) as a namespace, for programmatic use."""
     base = dict(model="X-InstructBLIP", model_path=None, audio_encoder=None, video_folder=None, train_annotation_file=None,
                 val_annotation_file=None, output_dir="out", val_freq=1, save_freq=1, max_epoch=50, batch_size=1, num_workers=0,
-                dataset="Charades_STA", gpu=0)
+                dataset="Charades_STA", gpu=0, val_decode="score", lm_decode="stock")
     base.update(kw)
     return SimpleNamespace(**base)
