@@ -796,6 +796,14 @@ int mra_debug_attention_bwd(const void* q, const void* k, const void* v, const v
  *   qkv  [items][S][3 * heads * 64]  q | k | v rows as the QKV GEMM writes them; K and V are read in place
  *   mask [items][S] int64 (1 = attend; additive (1 - m) * -10000) or NULL = all ones (the unmasked kernels)
  *   ctx  [items][S][heads * 64]      lse [items][heads][S] fp32 log2-sum-exp2 of the scaled, masked scores, or NULL
+ * mra_debug_self_attention_bwd: the attention backward core (launch_attn_bwd) in the self-attention layout of mra_qformer_backward(_multi),
+ *   built by the training step's own argument builder for hidden = heads * 64: Q, K and V are read in place from the packed rows.
+ *   qkv, mask     as mra_debug_self_attention takes them (mask NULL = no mask term: all ones)
+ *   ctx, d_ctx    [items][S][heads * 64]  the forward's context rows and their upstream gradient, operand dtype
+ *   lse           [items][heads][S]       fp32, log2 units, mask included (what mra_debug_self_attention writes)
+ *   dqkv          [items][S][3 * heads * 64]  dq | dk | dv, the layout of qkv; every column of every row is written
+ *   MRA_EINVAL with a message, nothing written: a NULL pointer other than mask, items / S / heads < 1, a dtype that is not f16 / bf16, a
+ *   misaligned buffer, S > 448 (the fp32 dQ / lse / delta areas of ceil(S / 32) > 14 query blocks pass 160 KB of LDS).
  * mra_debug_ln_rows: launch_ln_rows4.  params: HOST array of 8 device pointers gain1, bias1, .. gain4, bias4 (sets 2 - 4 may be NULL pairs);
  *   rows >= lane_rows take sets (3, 4) for (1, 2); with a second set of the pair, rows with row % period >= split take it.  Either output
  *   may be NULL (not both).
@@ -809,6 +817,8 @@ int mra_debug_attention_bwd(const void* q, const void* k, const void* v, const v
  *   (rows = heads, C = enc_width); src_view, chunk and parts are read by kind 0 only. */
 int mra_debug_self_attention(const void* qkv, const int64_t* mask, int32_t dtype, int32_t items, int32_t S, int32_t heads, void* ctx, float* lse,
                              void* stream);
+int mra_debug_self_attention_bwd(const void* qkv, const int64_t* mask, const void* ctx, const void* d_ctx, const float* lse, int32_t dtype,
+                                 int32_t items, int32_t S, int32_t heads, void* dqkv, void* stream);
 int mra_debug_ln_rows(const float* x, const int64_t* x_view, int32_t rows, int32_t H, const float* const* params, int32_t lane_rows, int32_t period,
                       int32_t split, float eps, float* y32, const int64_t* y32_view, void* y16, const int64_t* y16_view, int32_t dtype, void* stream);
 int mra_debug_embed_ln(const int64_t* ids, int32_t items, int32_t L, int32_t Q, int32_t H, int32_t vocab, const float* query, int64_t query_item_stride,

@@ -1759,6 +1759,25 @@ int mra_debug_self_attention(const void* qkv, const int64_t* mask, int32_t dtype
   return chk(launch_attention(self_attn_args(c, qkv, ctx, (const long long*)mask, items, S, lse), op, as_stream(stream)), "self attention");
 }
 
+// The attention backward core in the self-attention layout of mra_qformer_backward(_multi): the step's own argument builder for hidden = heads * 64.
+int mra_debug_self_attention_bwd(const void* qkv, const int64_t* mask, const void* ctx, const void* d_ctx, const float* lse, int32_t dtype,
+                                 int32_t items, int32_t S, int32_t heads, void* dqkv, void* stream) {
+  int op;
+  if (items < 1 || S < 1 || heads < 1) return fail(MRA_EINVAL, "sizes: items / S / heads >= 1");
+  if (!dbg_op(dtype, &op)) return fail(MRA_EINVAL, "dtype must be f16 or bf16");
+  if (!qkv || !ctx || !d_ctx || !lse || !dqkv) return fail(MRA_EINVAL, "null argument");
+  if (!dbg_aligned(qkv, 16) || !dbg_aligned(ctx, 16) || !dbg_aligned(d_ctx, 16) || !dbg_aligned(dqkv, 16))
+    return fail(MRA_EINVAL, "qkv, ctx, d_ctx and dqkv must be 16-byte aligned");
+  if ((long long)items * heads > 0x7fffffffLL || (long long)heads * 192 > 0x7fffffffLL) return fail(MRA_EINVAL, "items * heads exceeds int32");
+  if (attn_bwd_max_share(S) < 1)
+    return fail(MRA_EINVAL, "S " + std::to_string(S) + " exceeds 448, what the backward core's LDS holds: ceil(S / 32) <= 14 query blocks");
+  mra_cfg c{};
+  c.hidden = heads * 64;
+  c.heads = heads;
+  const int rc = launch_attn_bwd(self_attn_bwd_args(c, qkv, ctx, d_ctx, (const long long*)mask, lse, items, S, dqkv), op, as_stream(stream));
+  return rc ? chk(rc, "self attention backward") : MRA_OK;
+}
+
 int mra_debug_ln_rows(const float* x, const int64_t* x_view, int32_t rows, int32_t H, const float* const* params, int32_t lane_rows, int32_t period,
                       int32_t split, float eps, float* y32, const int64_t* y32_view, void* y16, const int64_t* y16_view, int32_t dtype, void* stream) {
   int op;

@@ -246,6 +246,21 @@ inline AttnArgs self_attn_args(const mra_cfg& c, const void* qkv16, void* ctx16,
   a.items = items; a.heads = c.heads; a.q_rows = S; a.kv_len = S; a.scale = 0.125f; a.nsplit = 1; a.lse = lse;
   return a;
 }
+// its backward: Q, K, V in place in the same packed rows, dQ | dK | dV into rows of the same layout, the context and its gradient [items][S][H]
+inline AttnBwdArgs self_attn_bwd_args(const mra_cfg& c, const void* qkv16, const void* ctx16, const void* dctx16, const long long* mask,
+                                      const float* lse, int items, int S, void* dqkv16) {
+  const int H = c.hidden;
+  AttnBwdArgs g{};
+  g.Q = qkv16; g.K = (const char*)qkv16 + (size_t)H * 2; g.V = (const char*)qkv16 + (size_t)2 * H * 2; g.O = ctx16; g.dO = dctx16;
+  g.dQ = dqkv16; g.dK = (char*)dqkv16 + (size_t)H * 2; g.dV = (char*)dqkv16 + (size_t)2 * H * 2;
+  g.q_item_stride = g.k_item_stride = g.v_item_stride = g.dq_item_stride = g.dk_item_stride = g.dv_item_stride = (long long)S * 3 * H;
+  g.q_ld = g.k_ld = g.v_ld = g.dq_ld = g.dk_ld = g.dv_ld = 3 * H;
+  g.k_head_stride = g.v_head_stride = g.dk_head_stride = g.dv_head_stride = 64;
+  g.o_item_stride = (long long)S * H; g.o_ld = H;
+  g.mask = mask; g.mask_ld = S; g.lse = lse;
+  g.items = items; g.heads = c.heads; g.q_rows = S; g.kv_len = S; g.scale = 0.125f;
+  return g;
+}
 // cross-attention core of cross layer ci over the head-major K/V cache [ncross][k | v][items][heads][kv][64]: Q and the context [items][32][H]
 inline AttnArgs kv_cross_attn_args(const mra_cfg& c, const void* q16, const char* kv16, int ci, void* ctx16, int items, int kv, int nsplit,
                                    float* part, float* lse = nullptr) {

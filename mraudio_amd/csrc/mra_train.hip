@@ -517,18 +517,8 @@ int backward_body(mra_qformer* h, const int64_t* input_ids, const int64_t* atten
       if ((rc = launch_ln_bwd(a, H, op, stream))) return chk(rc, "attn ln bwd");
     }
     if ((rc = X.gemm(t.dpre16b, all_rows, W.woT, nullptr, t.dctx16, all_rows, nullptr, all_rows, N * S, H, H, EPI_OP))) return chk(rc, "d_ctx");
-    {
-      AttnBwdArgs g{};
-      g.Q = b.qkv16; g.K = b.qkv16 + (size_t)H * 2; g.V = b.qkv16 + (size_t)2 * H * 2; g.O = b.ctx16; g.dO = t.dctx16;
-      g.dQ = t.dqkv16; g.dK = t.dqkv16 + (size_t)H * 2; g.dV = t.dqkv16 + (size_t)2 * H * 2;
-      g.q_item_stride = g.k_item_stride = g.v_item_stride = g.dq_item_stride = g.dk_item_stride = g.dv_item_stride = (long long)S * 3 * H;
-      g.q_ld = g.k_ld = g.v_ld = g.dq_ld = g.dk_ld = g.dv_ld = 3 * H;
-      g.k_head_stride = g.v_head_stride = g.dk_head_stride = g.dv_head_stride = 64;
-      g.o_item_stride = SH; g.o_ld = H;
-      g.mask = (const long long*)attention_mask; g.mask_ld = S; g.lse = b.lse_s;
-      g.items = N; g.heads = c.heads; g.q_rows = S; g.kv_len = S; g.scale = 0.125f;
-      if ((rc = launch_attn_bwd(g, op, stream))) return chk(rc, "self attention bwd");
-    }
+    if ((rc = launch_attn_bwd(self_attn_bwd_args(c, b.qkv16, b.ctx16, t.dctx16, (const long long*)attention_mask, b.lse_s, N, S, t.dqkv16), op, stream)))
+      return chk(rc, "self attention bwd");
     fork();
     if ((rc = X.wgrad(t.dpre16b, all_rows, 64, b.ctx16, all_rows, N * S, H, H, G(p + "attention.output.dense.weight"), G(p + "attention.output.dense.bias"))))
       return chk(rc, "dWo");
