@@ -386,6 +386,132 @@ int mra_decode_attention(const void* q, int64_t q_sb, int64_t q_sh, const void* 
                          int32_t S, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb, int64_t o_sh, float* lse, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- LM decode: one whole token per call (weight-streaming layers, head, greedy bookkeeping) ------------------------
+ * replaces: one iteration of the reference's self.llm_model.generate(inputs_embeds=..., attention_mask=..., max_new_tokens=64)
+ * (models/xinstructblip.py:383-391, utils/trainer.py:157-165) behind the prefill: the forward of a Llama-shaped LM on one new token per
+ * sequence (RMSNorm, q / k / v / o / gate / up / down projections with their optional LoRA branch of models/model_utils.py:4-14, rotary, the
+ * cache update, SwiGLU, the residuals, the final norm and lm_head), the argmax and generate's eos / pad bookkeeping.  Stateless like mra_lora_*
+ * and mra_decode_attention: caller-owned buffers and workspace, a stream, no allocation, no synchronisation.  1 <= B <= 8 sequences.
+ *
+ * A linear is W [N][K] in `dtype` (MRA_F16 / MRA_BF16) read as stored with pitch ldw, never copied or transposed, plus an optional adapter:
+ * fp32 masters A [R][K] and Bw [N][R] (the layouts mra_lora_* take as MRA_LORA_RN / MRA_LORA_NR), R <= 16 (0: none), scale = alpha / R.
+ *   y[b][n] = sum_k x[b][k] W[n][k] + scale * sum_j u[b][j] Bw[n][j],   u[b][j] = sum_k A[j][k] x[b][k]      all fp32, j ascending
+ * x is the linear's own input: the normalised rows for q / k / v / gate / up, the attention output for o, the activation for down.  Eval mode:
+ * no dropout, nothing is hashed.  Roundings to `dtype`, one each: the residual stream h, q, k, v, the attention output, the SwiGLU activation.
+ * Everything inside a launch is fp32: RMSNorm xn = (x * rsqrt(mean(x^2) + eps)) * gain is kept as an fp32 copy and never rounded; the logits
+ * are fp32.  Rotary is transformers' Llama rotate-half: x cos + rotate_half(x) sin over the pairs (i, i + D/2), cos / sin fp32 rows
+ * [rope_rows][rope_ld] (D values each) indexed by position[b] + pos_offset; a position outside the table writes NaN and reads nothing.
+ * k and v of the token go to slot `slot` of the layer's cache [B][Hkv][Smax][D] (ELEMENT strides, as mra_decode_attention takes them), then
+ * mra_decode_attention's launch function runs over S = slot + 1 keys under mask [B][>= slot + 1] bytes (the caller has set byte `slot`).
+ * Argmax: the first maximum; a NaN counts as the maximum (as torch.argmax), the first NaN wins.  Bookkeeping (finished != NULL): a finished
+ * sequence emits pad; a sequence that emits one of the n_eos <= 8 eos ids becomes finished.  tokens_out [B], finished [B] are int32.
+ * tokens_in (int32 [B] on the device; NULL: h holds the rows already) selects the embedding rows that start the step; a token outside
+ * [0, V) gives a row of NaN.
+ *
+ * Launches of one call, all plain, in stream order (no atomics, no waits between workgroups; two runs give the same bits):
+ *   per token   1 embedding gather (tokens_in != NULL) + 1 final-norm prologue + 1 head + 1 argmax
+ *   per layer   8:  norm + u prologue | q / k / v + LoRA + rotary + cache write | attention chunks | attention merge | o + residual |
+ *                   norm + u prologue | gate / up + SwiGLU | down + residual;  + 1 for an adapter on o, + 1 for one on down (their u = A x)
+ * Refused before any launch (MRA_EINVAL, named in mra_last_error): struct_bytes != sizeof, B outside 1..8, hidden / intermediate not positive
+ * multiples of 8, D outside {64, 128}, Hq / Hkv outside {1, 2, 4, 8}, L < 1, V < 1, an unknown dtype, R outside 0..16, an N that is not the
+ * layer's, slot outside [0, Smax), a NULL or misaligned (16 bytes; int32 / fp32 vectors 4) buffer, a pitch or stride that is short or not a
+ * multiple of 8 elements, a short workspace, eps or attn_scale not finite, n_eos outside 0..8.
+ *
+ * Workspace bytes, up(x) = x rounded up to 256:  up(4 B hidden) + 3 up(64 B) + 2 up(2 B Hq D) + up(2 B intermediate)
+ *                                               + mra_decode_attention_workspace_bytes(B, Hq, Smax, D).   Host only; 0 (and a message) when refused. */
+typedef struct mra_lm_linear {
+  const void* W;   /* [N][K] dtype */
+  int64_t ldw;
+  const float* A;  /* [R][K] fp32, NULL when R == 0 */
+  const float* Bw; /* [N][R] fp32 */
+  int32_t N;
+  int32_t R;
+  float scale;
+  int32_t reserved;
+} mra_lm_linear;
+typedef struct mra_lm_layer {
+  const void* norm1; /* input_layernorm.weight [hidden] dtype */
+  const void* norm2; /* post_attention_layernorm.weight */
+  mra_lm_linear q, k, v, o, gate, up, down;
+  void* kcache; /* [B][Hkv][Smax][D] dtype, strides below */
+  void* vcache;
+} mra_lm_layer;
+typedef struct mra_lm_step_desc {
+  uint64_t struct_bytes;
+  int32_t B, hidden, intermediate, Hq, Hkv, D, L, V, dtype, Smax;
+  float eps, attn_scale;
+  const mra_lm_layer* layers; /* HOST array of L records */
+  const void* embed;          /* [V][hidden] dtype */
+  int64_t ld_embed;
+  const void* final_norm;
+  const void* head;           /* lm_head.weight [V][hidden] dtype */
+  int64_t ld_head;
+  int64_t k_sb, k_sh, k_ss, v_sb, v_sh, v_ss;
+  const uint8_t* mask;
+  int64_t mask_sb;
+  const int32_t* position;
+  int32_t pos_offset, slot;
+  const float* cos;
+  const float* sin;
+  int64_t rope_ld;
+  int32_t rope_rows, n_eos;
+  const int32_t* tokens_in;
+  void* h;                    /* [B][hidden] dtype, dense: the residual stream; holds the final hidden rows afterwards */
+  float* logits;              /* [B][ld_logits >= V] fp32 */
+  int64_t ld_logits;
+  int32_t* tokens_out;
+  int32_t* finished;          /* may be NULL */
+  int32_t pad;
+  int32_t eos[8];
+  int32_t reserved;
+  void* workspace;
+  uint64_t workspace_bytes;
+} mra_lm_step_desc;
+size_t mra_lm_step_workspace_bytes(int32_t B, int32_t hidden, int32_t intermediate, int32_t Hq, int32_t D, int32_t Smax);
+int mra_lm_step(const mra_lm_step_desc* desc, void* stream);
+
+/* mra_debug_lm_skinny: ONE launch of the step's skinny kernel in any of its forms (behind its prologue launch when norm_gain or an adapter is
+ * given), as mra_lm_step issues it.  epilogue 0 plain (out_f32 != 0: fp32 output) | 1 + residual | 2 SwiGLU (seg 0 gate, seg 1 up, out[0]) |
+ * 3 rotary + cache write (seg 0 / 1 / 2 = q / k / v with N = Hq D, Hkv D, Hkv D; q to out[0]).  nseg 1..3 segments share x [B][K] (pitch ldx).
+ * Every buffer comes with its byte size; checked on the host before the launch (MRA_EINVAL with a message): struct_bytes, the refusals of
+ * mra_lm_step that apply, every pointer NULL / misaligned, every pitch below its width or not a multiple of 8 elements (fp32: 4), every
+ * footprint ((rows - 1) pitch + width elements; a cache: through slot `slot` of the last head of the last row) beyond its byte size.
+ * workspace: up(4 B K) + 3 up(64 B) bytes. */
+typedef struct mra_lm_skinny_desc {
+  uint64_t struct_bytes;
+  int32_t B, K, dtype, epilogue, nseg, out_f32;
+  const void* x;
+  int64_t ldx;
+  uint64_t x_bytes;
+  const void* norm_gain; /* [K] dtype; NULL: no RMSNorm prologue */
+  float eps;
+  int32_t reserved;
+  mra_lm_linear seg[3];
+  uint64_t w_bytes[3];
+  void* out[3];
+  int64_t ldo[3];
+  uint64_t out_bytes[3];
+  const void* res;
+  int64_t ldres;
+  uint64_t res_bytes;
+  int32_t Hq, Hkv, D, slot, pos_offset, rope_rows;
+  const int32_t* position;
+  const float* cos;
+  const float* sin;
+  int64_t rope_ld;
+  uint64_t rope_bytes;
+  void* kcache;
+  void* vcache;
+  int64_t k_sb, k_sh, k_ss, v_sb, v_sh, v_ss;
+  uint64_t kcache_bytes, vcache_bytes;
+  void* workspace;
+  uint64_t workspace_bytes;
+} mra_lm_skinny_desc;
+int mra_debug_lm_skinny(const mra_lm_skinny_desc* desc, void* stream);
+/* mra_debug_lm_argmax: the step's argmax + bookkeeping launch alone.  logits fp32 [B][ld >= V]; eos HOST array of n_eos <= 8 ids. */
+int mra_debug_lm_argmax(const float* logits, int64_t ld, int32_t B, int32_t V, int32_t* tokens_out, int32_t* finished, int32_t pad,
+                        const int32_t* eos, int32_t n_eos, void* stream);
+
 /* ---- LM objective: prompt assembly as one row gather -------------------------------------------------------------
  * replaces: the torch.cat of cue, media, timestamp, duration and prompt pieces in front of the LM (models/xinstructblip.py:341-381, :541-595)
  * and, through the inverse plan, its backward.  Stateless like mra_lora_* and mra_lm_head_ce_*: caller-owned buffers, a stream, no allocation,

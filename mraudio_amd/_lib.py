@@ -76,6 +76,59 @@ class mra_gemm_desc(C.Structure):
     ]
 
 
+class mra_lm_linear(C.Structure):
+    """include/mra.h mra_lm_linear: W [N][K] (16-bit, pitch ldw) with an optional fp32 adapter A [R][K], Bw [N][R]."""
+    _fields_ = [("W", C.c_void_p), ("ldw", C.c_int64), ("A", C.c_void_p), ("Bw", C.c_void_p), ("N", C.c_int32), ("R", C.c_int32),
+                ("scale", C.c_float), ("reserved", C.c_int32)]
+
+
+class mra_lm_layer(C.Structure):
+    _fields_ = [("norm1", C.c_void_p), ("norm2", C.c_void_p), ("q", mra_lm_linear), ("k", mra_lm_linear), ("v", mra_lm_linear),
+                ("o", mra_lm_linear), ("gate", mra_lm_linear), ("up", mra_lm_linear), ("down", mra_lm_linear), ("kcache", C.c_void_p),
+                ("vcache", C.c_void_p)]
+
+
+class mra_lm_step_desc(C.Structure):
+    """include/mra.h mra_lm_step_desc.  ``struct_bytes`` must be ``ctypes.sizeof(mra_lm_step_desc)``."""
+    _fields_ = [
+        ("struct_bytes", C.c_uint64),
+        ("B", C.c_int32), ("hidden", C.c_int32), ("intermediate", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32), ("D", C.c_int32),
+        ("L", C.c_int32), ("V", C.c_int32), ("dtype", C.c_int32), ("Smax", C.c_int32),
+        ("eps", C.c_float), ("attn_scale", C.c_float),
+        ("layers", C.POINTER(mra_lm_layer)), ("embed", C.c_void_p), ("ld_embed", C.c_int64), ("final_norm", C.c_void_p),
+        ("head", C.c_void_p), ("ld_head", C.c_int64),
+        ("k_sb", C.c_int64), ("k_sh", C.c_int64), ("k_ss", C.c_int64), ("v_sb", C.c_int64), ("v_sh", C.c_int64), ("v_ss", C.c_int64),
+        ("mask", C.c_void_p), ("mask_sb", C.c_int64), ("position", C.c_void_p), ("pos_offset", C.c_int32), ("slot", C.c_int32),
+        ("cos", C.c_void_p), ("sin", C.c_void_p), ("rope_ld", C.c_int64), ("rope_rows", C.c_int32), ("n_eos", C.c_int32),
+        ("tokens_in", C.c_void_p), ("h", C.c_void_p), ("logits", C.c_void_p), ("ld_logits", C.c_int64), ("tokens_out", C.c_void_p),
+        ("finished", C.c_void_p), ("pad", C.c_int32), ("eos", C.c_int32 * 8), ("reserved", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64),
+    ]
+
+
+class mra_lm_skinny_desc(C.Structure):
+    """include/mra.h mra_lm_skinny_desc: one launch of the step's skinny kernel (mra_debug_lm_skinny), every buffer with its byte size."""
+    _fields_ = [
+        ("struct_bytes", C.c_uint64),
+        ("B", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32), ("epilogue", C.c_int32), ("nseg", C.c_int32), ("out_f32", C.c_int32),
+        ("x", C.c_void_p), ("ldx", C.c_int64), ("x_bytes", C.c_uint64),
+        ("norm_gain", C.c_void_p), ("eps", C.c_float), ("reserved", C.c_int32),
+        ("seg", mra_lm_linear * 3), ("w_bytes", C.c_uint64 * 3),
+        ("out", C.c_void_p * 3), ("ldo", C.c_int64 * 3), ("out_bytes", C.c_uint64 * 3),
+        ("res", C.c_void_p), ("ldres", C.c_int64), ("res_bytes", C.c_uint64),
+        ("Hq", C.c_int32), ("Hkv", C.c_int32), ("D", C.c_int32), ("slot", C.c_int32), ("pos_offset", C.c_int32), ("rope_rows", C.c_int32),
+        ("position", C.c_void_p), ("cos", C.c_void_p), ("sin", C.c_void_p), ("rope_ld", C.c_int64), ("rope_bytes", C.c_uint64),
+        ("kcache", C.c_void_p), ("vcache", C.c_void_p),
+        ("k_sb", C.c_int64), ("k_sh", C.c_int64), ("k_ss", C.c_int64), ("v_sb", C.c_int64), ("v_sh", C.c_int64), ("v_ss", C.c_int64),
+        ("kcache_bytes", C.c_uint64), ("vcache_bytes", C.c_uint64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64),
+    ]
+
+
+LM_EPI_PLAIN, LM_EPI_RES, LM_EPI_SWIGLU, LM_EPI_ROPE = 0, 1, 2, 3     # mra_lm_skinny_desc.epilogue (csrc/kernels.h LmEpi)
+LM_CB = 16                                                           # columns per workgroup of the skinny kernel (the rotary form: D)
+
+
 # name -> (restype, argtypes); must list every symbol include/mra.h declares (tests check this)
 PROTOTYPES = {
     "mra_cfg_default": (None, [C.POINTER(mra_cfg), C.c_int32]),
@@ -135,6 +188,11 @@ PROTOTYPES = {
     "mra_decode_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                        C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mra_lm_step_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mra_lm_step": (C.c_int, [C.POINTER(mra_lm_step_desc), C.c_void_p]),
+    "mra_debug_lm_skinny": (C.c_int, [C.POINTER(mra_lm_skinny_desc), C.c_void_p]),
+    "mra_debug_lm_argmax": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                      C.c_void_p]),
     "mra_gather_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(mra_rows_src), C.c_int32, C.c_void_p,
                                   C.c_void_p]),
     "mra_fuse_logits": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p,

@@ -274,6 +274,39 @@ int launch_decode_attention(const void* q, long long q_sb, long long q_sh, const
                             const void* v, long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq,
                             int Hkv, int S, int D, float scale, void* out, long long o_sb, long long o_sh, float* lse, float* pm, float* pl,
                             float* pacc, int op_dtype, hipStream_t stream);
+// The one-token step of the LM's decode (lm_step.hip): a skinny weight-streaming GEMM y [B][N] = x [B][K] W[N][K]^T for B <= LM_MAX_B rows
+// with its prologue launch (RMSNorm to an fp32 copy, u = A x of up to three adapters), the embedding gather and the argmax with generate's
+// greedy bookkeeping.  A workgroup owns LM_CB columns (rotary form: one head of D columns); W is read as stored and never copied.
+constexpr int LM_MAX_B = 8, LM_MAX_R = 16, LM_MAX_EOS = 8, LM_CB = 16, LM_MAX_CB = 128;
+enum LmEpi { LM_EPI_PLAIN = 0, LM_EPI_RES = 1, LM_EPI_SWIGLU = 2, LM_EPI_ROPE = 3 };
+struct LmSeg {
+  const void* W; long long ldw; int N;          // [N][K] operand dtype, pitch ldw
+  int R; const float* Bw; const float* u; float scale;   // adapter: Bw [N][R], u [B][R] fp32 (R == 0: none)
+  void* out; long long ldo;                     // [B][N]; SwiGLU writes segment 0's, the rotary form segment 0's (q) and the caches
+};
+struct LmSkinny {
+  int B, K, nseg, epi, x_f32, out_f32;          // x_f32: x is the fp32 copy lm_prep left; out_f32: plain output in fp32
+  const void* x; long long ldx;
+  LmSeg seg[3];                                 // plain / residual: independent outputs; SwiGLU: gate, up; rotary: q, k, v
+  const void* res; long long ldres;             // residual rows (may be the output)
+  int Hq, Hkv, D, slot, pos_offset, rope_rows;  // rotary form: position[b] + pos_offset indexes cos / sin fp32 [rope_rows][rope_ld]
+  const int* position; const float* cos; const float* sin; long long rope_ld;
+  void* kc; void* vc; long long k_sb, k_sh, k_ss, v_sb, v_sh, v_ss;   // caches [B][Hkv][Smax][D] with element strides; slot `slot` is written
+  int cb, nblk[3];                              // set by the launch function
+};
+struct LmPrep {
+  int B, K; const void* x; long long ldx;       // operand dtype rows
+  const void* gain; float eps; float* xn;       // gain (operand dtype) NULL: no norm, u is taken from x itself; xn fp32 [B][K] dense
+  const float* A[3]; int R[3]; float* u[3];     // A [R][K] fp32 -> u [B][R] fp32
+};
+struct LmGreedy {
+  int* tokens_out; int* finished;               // [B] int32 each; finished NULL: plain argmax
+  int pad, n_eos, eos[LM_MAX_EOS];
+};
+int launch_lm_embed(const int* tokens, const void* table, long long ld, int V, int B, int K, void* h, long long ldh, int op_dtype, hipStream_t stream);
+int launch_lm_prep(const LmPrep& p, int op_dtype, hipStream_t stream);
+int launch_lm_skinny(const LmSkinny& p, int op_dtype, hipStream_t stream);
+int launch_lm_argmax(const float* logits, long long ld, int B, int V, const LmGreedy& g, hipStream_t stream);
 // Row gather with a cast (prompt.hip): out [n_rows][width] (out_dtype 0 / 1 / 2 = f32 / f16 / bf16, pitch ldo) row i = source plan[i][0], row
 // plan[i][1]; source -1 -> +0, any other entry out of range -> NaN, nothing read.  The per-source arguments are host arrays of n_src <=
 // GATHER_MAX_SRC entries; plan int32 [n_rows][2] on the device.  width % 8 == 0, 16-byte aligned rows everywhere; a wave owns a row, no atomics.

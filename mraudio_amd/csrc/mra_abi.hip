@@ -1690,6 +1690,303 @@ int mra_decode_attention(const void* q, int64_t q_sb, int64_t q_sh, const void* 
              "decode_attention");
 }
 
+// ---- one whole token of the LM's decode (lm_step.hip) ---------------------------------------------------------------------------------------
+// replaces: one iteration of self.llm_model.generate(...) behind the prefill, models/xinstructblip.py:383-391.  Every check comes before a launch.
+namespace {
+
+struct LmStepWs {
+  size_t xn, u, q, act, attn, total;
+};
+LmStepWs lm_step_ws(int32_t B, int32_t hidden, int32_t inter, int32_t Hq, int32_t D, int32_t Smax) {
+  LmStepWs w{};
+  w.xn = up256(4 * (size_t)B * (size_t)hidden);
+  w.u = up256(4 * (size_t)B * LM_MAX_R);
+  w.q = up256(2 * (size_t)B * (size_t)Hq * (size_t)D);
+  w.act = up256(2 * (size_t)B * (size_t)inter);
+  w.attn = decode_ws(B, Hq, Smax, D).total;
+  w.total = w.xn + 3 * w.u + 2 * w.q + w.act + w.attn;
+  return w;
+}
+
+bool aligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
+
+// one linear of a step or of the debug entry: pointers, pitch, adapter
+int lm_linear_check(const std::string& w, const mra_lm_linear& l, int32_t N, int32_t K) {
+  if (!l.W) return fail(MRA_EINVAL, w + ": null W");
+  if (!aligned16(l.W)) return fail(MRA_EINVAL, w + ": W must be 16-byte aligned");
+  if (l.N != N || N < 1) return fail(MRA_EINVAL, w + ": N is not the layer's");
+  if (l.ldw < K || l.ldw % 8) return fail(MRA_EINVAL, w + ": ldw must be at least K and a multiple of 8 elements");
+  if (l.R < 0 || l.R > LM_MAX_R) return fail(MRA_EINVAL, w + ": R must be in 0..16");
+  if (l.R > 0) {
+    if (!l.A || !l.Bw) return fail(MRA_EINVAL, w + ": null adapter");
+    if (!aligned16(l.A) || !aligned4(l.Bw)) return fail(MRA_EINVAL, w + ": the adapters must be aligned (A 16 bytes, Bw 4)");
+    if (!std::isfinite(l.scale)) return fail(MRA_EINVAL, w + ": scale must be finite");
+  }
+  return MRA_OK;
+}
+
+LmSeg lm_seg(const mra_lm_linear& l, const float* u, void* out, long long ldo) {
+  LmSeg s{};
+  s.W = l.W; s.ldw = l.ldw; s.N = l.N; s.R = l.R; s.Bw = l.Bw; s.u = u; s.scale = l.scale; s.out = out; s.ldo = ldo;
+  return s;
+}
+
+int lm_dims_check(const std::string& w, int32_t B, int32_t dtype, int32_t Hq, int32_t Hkv, int32_t D) {
+  if (B < 1 || B > LM_MAX_B) return fail(MRA_EINVAL, w + ": B must be in 1..8");
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": dtype must be MRA_F16 or MRA_BF16");
+  if (D != 64 && D != 128) return fail(MRA_EINVAL, w + ": D must be 64 or 128");
+  if (Hq < 1 || Hkv < 1 || Hq % Hkv) return fail(MRA_EINVAL, w + ": Hq must be a positive multiple of Hkv");
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return fail(MRA_EINVAL, w + ": Hq / Hkv must be 1, 2, 4 or 8");
+  return MRA_OK;
+}
+
+}  // namespace
+
+size_t mra_lm_step_workspace_bytes(int32_t B, int32_t hidden, int32_t intermediate, int32_t Hq, int32_t D, int32_t Smax) {
+  if (B < 1 || B > LM_MAX_B || hidden < 8 || hidden % 8 || intermediate < 8 || intermediate % 8 || Hq < 1 || (D != 64 && D != 128) || Smax < 1) {
+    fail(MRA_EINVAL, "lm_step_workspace_bytes: B in 1..8, hidden and intermediate positive multiples of 8, Hq >= 1, D 64 or 128, Smax >= 1");
+    return 0;
+  }
+  return lm_step_ws(B, hidden, intermediate, Hq, D, Smax).total;
+}
+
+int mra_lm_step(const mra_lm_step_desc* d, void* stream) {
+  const std::string w("lm_step");
+  if (!d) return fail(MRA_EINVAL, w + ": null descriptor");
+  if (d->struct_bytes != sizeof(mra_lm_step_desc)) return fail(MRA_EINVAL, w + ": struct_bytes is not sizeof(mra_lm_step_desc)");
+  if (int rc = lm_dims_check(w, d->B, d->dtype, d->Hq, d->Hkv, d->D)) return rc;
+  const int B = d->B, H = d->hidden, I = d->intermediate, Hq = d->Hq, Hkv = d->Hkv, D = d->D;
+  if (H < 8 || H % 8 || I < 8 || I % 8) return fail(MRA_EINVAL, w + ": hidden and intermediate (K) must be positive multiples of 8");
+  if (d->L < 1 || d->V < 1) return fail(MRA_EINVAL, w + ": L and V must be at least 1");
+  if (!std::isfinite(d->eps) || !std::isfinite(d->attn_scale)) return fail(MRA_EINVAL, w + ": eps and attn_scale must be finite");
+  if (d->Smax < 1 || d->slot < 0 || d->slot >= d->Smax) return fail(MRA_EINVAL, w + ": slot must be in [0, Smax)");
+  if (d->n_eos < 0 || d->n_eos > LM_MAX_EOS) return fail(MRA_EINVAL, w + ": n_eos must be in 0..8");
+  if (!d->layers || !d->final_norm || !d->head || !d->mask || !d->position || !d->cos || !d->sin || !d->h || !d->logits || !d->tokens_out || !d->workspace)
+    return fail(MRA_EINVAL, w + ": null argument");
+  if (d->tokens_in && !d->embed) return fail(MRA_EINVAL, w + ": tokens_in without an embedding table");
+  if (!aligned16(d->final_norm) || !aligned16(d->head) || !aligned16(d->h) || !aligned16(d->workspace) || !aligned16(d->cos) || !aligned16(d->sin) ||
+      !aligned16(d->logits) || (d->embed && !aligned16(d->embed)))
+    return fail(MRA_EINVAL, w + ": embed, final_norm, head, h, logits, cos, sin and the workspace must be 16-byte aligned");
+  if (!aligned4(d->position) || !aligned4(d->tokens_in) || !aligned4(d->tokens_out) || !aligned4(d->finished))
+    return fail(MRA_EINVAL, w + ": position, tokens and finished must be 4-byte aligned");
+  if (d->ld_head < H || d->ld_head % 8 || (d->embed && (d->ld_embed < H || d->ld_embed % 8)))
+    return fail(MRA_EINVAL, w + ": ld_head / ld_embed must be at least hidden and multiples of 8 elements");
+  if (d->ld_logits < d->V) return fail(MRA_EINVAL, w + ": ld_logits < V");
+  if (d->rope_ld < D || d->rope_rows < 1) return fail(MRA_EINVAL, w + ": the rotary table needs rope_rows >= 1 rows of rope_ld >= D values");
+  if (d->k_sb % 8 || d->k_sh % 8 || d->k_ss % 8 || d->v_sb % 8 || d->v_sh % 8 || d->v_ss % 8)
+    return fail(MRA_EINVAL, w + ": the cache strides must be multiples of 8 elements (16 bytes)");
+  if (d->k_ss < D || d->v_ss < D) return fail(MRA_EINVAL, w + ": k_ss / v_ss < D");
+  if (d->mask_sb < (int64_t)d->slot + 1 && B > 1) return fail(MRA_EINVAL, w + ": mask_sb < slot + 1");
+  for (int l = 0; l < d->L; ++l) {
+    const mra_lm_layer& y = d->layers[l];
+    const std::string wl = w + ": layer " + std::to_string(l);
+    if (!y.norm1 || !y.norm2 || !y.kcache || !y.vcache) return fail(MRA_EINVAL, wl + ": null argument");
+    if (!aligned16(y.norm1) || !aligned16(y.norm2) || !aligned16(y.kcache) || !aligned16(y.vcache))
+      return fail(MRA_EINVAL, wl + ": the gains and the caches must be 16-byte aligned");
+    if (int rc = lm_linear_check(wl + " q", y.q, Hq * D, H)) return rc;
+    if (int rc = lm_linear_check(wl + " k", y.k, Hkv * D, H)) return rc;
+    if (int rc = lm_linear_check(wl + " v", y.v, Hkv * D, H)) return rc;
+    if (int rc = lm_linear_check(wl + " o", y.o, H, Hq * D)) return rc;
+    if (int rc = lm_linear_check(wl + " gate", y.gate, I, H)) return rc;
+    if (int rc = lm_linear_check(wl + " up", y.up, I, H)) return rc;
+    if (int rc = lm_linear_check(wl + " down", y.down, H, I)) return rc;
+  }
+  const LmStepWs ws = lm_step_ws(B, H, I, Hq, D, d->Smax);
+  if (d->workspace_bytes < ws.total) return fail(MRA_EINVAL, w + ": workspace too small (mra_lm_step_workspace_bytes)");
+
+  char* base = static_cast<char*>(d->workspace);
+  float* xn = reinterpret_cast<float*>(base);
+  float* u[3] = {reinterpret_cast<float*>(base + ws.xn), reinterpret_cast<float*>(base + ws.xn + ws.u), reinterpret_cast<float*>(base + ws.xn + 2 * ws.u)};
+  void* q = base + ws.xn + 3 * ws.u;
+  void* ao = base + ws.xn + 3 * ws.u + ws.q;
+  void* act = base + ws.xn + 3 * ws.u + 2 * ws.q;
+  char* aws = base + ws.xn + 3 * ws.u + 2 * ws.q + ws.act;
+  const DecodeWs dws = decode_ws(B, Hq, d->slot + 1, D);
+  float* pm = reinterpret_cast<float*>(aws);
+  float* pl = reinterpret_cast<float*>(aws + dws.stat);
+  float* pacc = reinterpret_cast<float*>(aws + 2 * dws.stat);
+  const int op = d->dtype == MRA_BF16 ? OP_BF16 : OP_F16;
+  hipStream_t st = as_stream(stream);
+
+  auto prep = [&](const void* x, int K, const void* gain, const mra_lm_linear* a0, const mra_lm_linear* a1, const mra_lm_linear* a2) {
+    LmPrep p{};
+    p.B = B; p.K = K; p.x = x; p.ldx = K; p.gain = gain; p.eps = d->eps; p.xn = xn;
+    const mra_lm_linear* as[3] = {a0, a1, a2};
+    for (int a = 0; a < 3; ++a) {
+      p.A[a] = as[a] ? as[a]->A : nullptr;
+      p.R[a] = as[a] ? as[a]->R : 0;
+      p.u[a] = u[a];
+    }
+    return launch_lm_prep(p, op, st);
+  };
+  auto skinny = [&](int epi, const void* x, int x_f32, int K) {
+    LmSkinny p{};
+    p.B = B; p.K = K; p.epi = epi; p.x = x; p.x_f32 = x_f32; p.ldx = K;
+    return p;
+  };
+#define MRA_LM_DO(call)                       \
+  if (int rc = (call)) return chk(rc, "lm_step")
+  if (d->tokens_in) MRA_LM_DO(launch_lm_embed(d->tokens_in, d->embed, d->ld_embed, d->V, B, H, d->h, H, op, st));
+  for (int l = 0; l < d->L; ++l) {
+    const mra_lm_layer& y = d->layers[l];
+    MRA_LM_DO(prep(d->h, H, y.norm1, &y.q, &y.k, &y.v));
+    {
+      LmSkinny p = skinny(LM_EPI_ROPE, xn, 1, H);
+      p.nseg = 3;
+      p.seg[0] = lm_seg(y.q, u[0], q, (long long)Hq * D);
+      p.seg[1] = lm_seg(y.k, u[1], nullptr, 0);
+      p.seg[2] = lm_seg(y.v, u[2], nullptr, 0);
+      p.Hq = Hq; p.Hkv = Hkv; p.D = D; p.slot = d->slot; p.pos_offset = d->pos_offset; p.rope_rows = d->rope_rows;
+      p.position = d->position; p.cos = d->cos; p.sin = d->sin; p.rope_ld = d->rope_ld;
+      p.kc = y.kcache; p.vc = y.vcache;
+      p.k_sb = d->k_sb; p.k_sh = d->k_sh; p.k_ss = d->k_ss; p.v_sb = d->v_sb; p.v_sh = d->v_sh; p.v_ss = d->v_ss;
+      MRA_LM_DO(launch_lm_skinny(p, op, st));
+    }
+    MRA_LM_DO(launch_decode_attention(q, (long long)Hq * D, D, y.kcache, d->k_sb, d->k_sh, d->k_ss, y.vcache, d->v_sb, d->v_sh, d->v_ss, d->mask,
+                                      d->mask_sb, B, Hq, Hkv, d->slot + 1, D, d->attn_scale, ao, (long long)Hq * D, D, nullptr, pm, pl, pacc, op, st));
+    if (y.o.R > 0) MRA_LM_DO(prep(ao, Hq * D, nullptr, &y.o, nullptr, nullptr));
+    {
+      LmSkinny p = skinny(LM_EPI_RES, ao, 0, Hq * D);
+      p.nseg = 1;
+      p.seg[0] = lm_seg(y.o, u[0], d->h, H);
+      p.res = d->h; p.ldres = H;
+      MRA_LM_DO(launch_lm_skinny(p, op, st));
+    }
+    MRA_LM_DO(prep(d->h, H, y.norm2, &y.gate, &y.up, nullptr));
+    {
+      LmSkinny p = skinny(LM_EPI_SWIGLU, xn, 1, H);
+      p.nseg = 2;
+      p.seg[0] = lm_seg(y.gate, u[0], act, I);
+      p.seg[1] = lm_seg(y.up, u[1], nullptr, 0);
+      MRA_LM_DO(launch_lm_skinny(p, op, st));
+    }
+    if (y.down.R > 0) MRA_LM_DO(prep(act, I, nullptr, &y.down, nullptr, nullptr));
+    {
+      LmSkinny p = skinny(LM_EPI_RES, act, 0, I);
+      p.nseg = 1;
+      p.seg[0] = lm_seg(y.down, u[0], d->h, H);
+      p.res = d->h; p.ldres = H;
+      MRA_LM_DO(launch_lm_skinny(p, op, st));
+    }
+  }
+  MRA_LM_DO(prep(d->h, H, d->final_norm, nullptr, nullptr, nullptr));
+  {
+    LmSkinny p = skinny(LM_EPI_PLAIN, xn, 1, H);
+    p.nseg = 1;
+    p.out_f32 = 1;
+    mra_lm_linear head{};
+    head.W = d->head; head.ldw = d->ld_head; head.N = d->V;
+    p.seg[0] = lm_seg(head, nullptr, d->logits, d->ld_logits);
+    MRA_LM_DO(launch_lm_skinny(p, op, st));
+  }
+  LmGreedy g{};
+  g.tokens_out = d->tokens_out; g.finished = d->finished; g.pad = d->pad; g.n_eos = d->n_eos;
+  for (int e = 0; e < d->n_eos; ++e) g.eos[e] = d->eos[e];
+  MRA_LM_DO(launch_lm_argmax(d->logits, d->ld_logits, B, d->V, g, st));
+#undef MRA_LM_DO
+  return MRA_OK;
+}
+
+int mra_debug_lm_skinny(const mra_lm_skinny_desc* d, void* stream) {
+  const std::string w("debug_lm_skinny");
+  if (!d) return fail(MRA_EINVAL, w + ": null descriptor");
+  if (d->struct_bytes != sizeof(mra_lm_skinny_desc)) return fail(MRA_EINVAL, w + ": struct_bytes is not sizeof(mra_lm_skinny_desc)");
+  const int epi = d->epilogue, B = d->B, K = d->K;
+  if (epi < LM_EPI_PLAIN || epi > LM_EPI_ROPE) return fail(MRA_EINVAL, w + ": epilogue must be 0 .. 3");
+  if (B < 1 || B > LM_MAX_B) return fail(MRA_EINVAL, w + ": B must be in 1..8");
+  if (d->dtype != MRA_F16 && d->dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": dtype must be MRA_F16 or MRA_BF16");
+  if (K < 8 || K % 8) return fail(MRA_EINVAL, w + ": K must be a positive multiple of 8");
+  if (d->nseg < 1 || d->nseg > 3) return fail(MRA_EINVAL, w + ": nseg must be in 1..3");
+  if (epi == LM_EPI_SWIGLU && (d->nseg != 2 || d->seg[0].N != d->seg[1].N)) return fail(MRA_EINVAL, w + ": SwiGLU takes two segments of one N");
+  if (epi == LM_EPI_ROPE) {
+    if (int rc = lm_dims_check(w, B, d->dtype, d->Hq, d->Hkv, d->D)) return rc;
+    if (d->nseg != 3 || d->seg[0].N != d->Hq * d->D || d->seg[1].N != d->Hkv * d->D || d->seg[2].N != d->Hkv * d->D)
+      return fail(MRA_EINVAL, w + ": the rotary form takes q, k, v with N = Hq D, Hkv D, Hkv D");
+  }
+  if (d->out_f32 && epi != LM_EPI_PLAIN) return fail(MRA_EINVAL, w + ": fp32 output belongs to the plain epilogue");
+  if (!d->x || !aligned16(d->x)) return fail(MRA_EINVAL, w + ": x must be non-null and 16-byte aligned");
+  if (d->ldx < K || d->ldx % 8) return fail(MRA_EINVAL, w + ": ldx must be at least K and a multiple of 8 elements");
+  if (d->x_bytes < 2 * ((uint64_t)(B - 1) * (uint64_t)d->ldx + (uint64_t)K)) return fail(MRA_EINVAL, w + ": x footprint beyond x_bytes");
+  if (d->norm_gain && !aligned16(d->norm_gain)) return fail(MRA_EINVAL, w + ": norm_gain must be 16-byte aligned");
+  if (!std::isfinite(d->eps)) return fail(MRA_EINVAL, w + ": eps must be finite");
+  bool need_prep = d->norm_gain != nullptr;
+  const size_t out_es = d->out_f32 ? 4 : 2;
+  for (int s = 0; s < d->nseg; ++s) {
+    const std::string wsn = w + ": segment " + std::to_string(s);
+    if (int rc = lm_linear_check(wsn, d->seg[s], d->seg[s].N, K)) return rc;
+    if (d->w_bytes[s] < 2 * ((uint64_t)(d->seg[s].N - 1) * (uint64_t)d->seg[s].ldw + (uint64_t)K)) return fail(MRA_EINVAL, wsn + ": W footprint beyond w_bytes");
+    need_prep = need_prep || d->seg[s].R > 0;
+    const bool has_out = epi == LM_EPI_PLAIN || epi == LM_EPI_RES || s == 0;
+    if (has_out) {
+      if (!d->out[s] || !aligned16(d->out[s])) return fail(MRA_EINVAL, wsn + ": out must be non-null and 16-byte aligned");
+      if (d->ldo[s] < d->seg[s].N || (!d->out_f32 && d->ldo[s] % 8)) return fail(MRA_EINVAL, wsn + ": ldo must be at least N and a multiple of 8 elements");
+      if (d->out_bytes[s] < out_es * ((uint64_t)(B - 1) * (uint64_t)d->ldo[s] + (uint64_t)d->seg[s].N)) return fail(MRA_EINVAL, wsn + ": out footprint beyond out_bytes");
+    }
+  }
+  if (epi == LM_EPI_RES) {
+    if (d->nseg != 1) return fail(MRA_EINVAL, w + ": the residual epilogue takes one segment");
+    if (!d->res || !aligned16(d->res)) return fail(MRA_EINVAL, w + ": res must be non-null and 16-byte aligned");
+    if (d->ldres < d->seg[0].N || d->ldres % 8) return fail(MRA_EINVAL, w + ": ldres must be at least N and a multiple of 8 elements");
+    if (d->res_bytes < 2 * ((uint64_t)(B - 1) * (uint64_t)d->ldres + (uint64_t)d->seg[0].N)) return fail(MRA_EINVAL, w + ": res footprint beyond res_bytes");
+  }
+  if (epi == LM_EPI_ROPE) {
+    if (!d->position || !d->cos || !d->sin || !d->kcache || !d->vcache) return fail(MRA_EINVAL, w + ": null rotary / cache argument");
+    if (!aligned4(d->position) || !aligned16(d->cos) || !aligned16(d->sin) || !aligned16(d->kcache) || !aligned16(d->vcache))
+      return fail(MRA_EINVAL, w + ": position (4), cos, sin and the caches (16) must be aligned");
+    if (d->rope_rows < 1 || d->rope_ld < d->D) return fail(MRA_EINVAL, w + ": the rotary table needs rope_rows >= 1 rows of rope_ld >= D values");
+    if (d->rope_bytes < 4 * ((uint64_t)(d->rope_rows - 1) * (uint64_t)d->rope_ld + (uint64_t)d->D)) return fail(MRA_EINVAL, w + ": rotary footprint beyond rope_bytes");
+    if (d->slot < 0) return fail(MRA_EINVAL, w + ": negative slot");
+    if (d->k_sb % 8 || d->k_sh % 8 || d->k_ss % 8 || d->v_sb % 8 || d->v_sh % 8 || d->v_ss % 8 || d->k_sb < 0 || d->k_sh < 0 || d->v_sb < 0 || d->v_sh < 0)
+      return fail(MRA_EINVAL, w + ": the cache strides must be non-negative multiples of 8 elements (16 bytes)");
+    if (d->k_ss < d->D || d->v_ss < d->D) return fail(MRA_EINVAL, w + ": k_ss / v_ss < D");
+    const uint64_t kf = (uint64_t)(B - 1) * d->k_sb + (uint64_t)(d->Hkv - 1) * d->k_sh + (uint64_t)d->slot * d->k_ss + d->D;
+    const uint64_t vf = (uint64_t)(B - 1) * d->v_sb + (uint64_t)(d->Hkv - 1) * d->v_sh + (uint64_t)d->slot * d->v_ss + d->D;
+    if (d->kcache_bytes < 2 * kf || d->vcache_bytes < 2 * vf) return fail(MRA_EINVAL, w + ": slot beyond the cache (footprint beyond kcache_bytes / vcache_bytes)");
+  }
+  const size_t xn_b = up256(4 * (size_t)B * (size_t)K), u_b = up256(4 * (size_t)B * LM_MAX_R);
+  if (need_prep) {
+    if (!d->workspace || !aligned16(d->workspace)) return fail(MRA_EINVAL, w + ": workspace must be non-null and 16-byte aligned");
+    if (d->workspace_bytes < xn_b + 3 * u_b) return fail(MRA_EINVAL, w + ": workspace too small");
+  }
+  char* base = static_cast<char*>(d->workspace);
+  float* xn = reinterpret_cast<float*>(base);
+  const int op = d->dtype == MRA_BF16 ? OP_BF16 : OP_F16;
+  LmSkinny p{};
+  p.B = B; p.K = K; p.nseg = d->nseg; p.epi = epi; p.out_f32 = d->out_f32;
+  p.x = d->norm_gain ? (const void*)xn : d->x;
+  p.x_f32 = d->norm_gain ? 1 : 0;
+  p.ldx = d->norm_gain ? K : d->ldx;
+  LmPrep pp{};
+  pp.B = B; pp.K = K; pp.x = d->x; pp.ldx = d->ldx; pp.gain = d->norm_gain; pp.eps = d->eps; pp.xn = xn;
+  for (int s = 0; s < d->nseg; ++s) {
+    float* u = need_prep ? reinterpret_cast<float*>(base + xn_b + s * u_b) : nullptr;
+    pp.A[s] = d->seg[s].A; pp.R[s] = d->seg[s].R; pp.u[s] = u;
+    p.seg[s] = lm_seg(d->seg[s], u, d->out[s], d->ldo[s]);
+  }
+  p.res = d->res; p.ldres = d->ldres;
+  p.Hq = d->Hq; p.Hkv = d->Hkv; p.D = d->D; p.slot = d->slot; p.pos_offset = d->pos_offset; p.rope_rows = d->rope_rows;
+  p.position = d->position; p.cos = d->cos; p.sin = d->sin; p.rope_ld = d->rope_ld;
+  p.kc = d->kcache; p.vc = d->vcache;
+  p.k_sb = d->k_sb; p.k_sh = d->k_sh; p.k_ss = d->k_ss; p.v_sb = d->v_sb; p.v_sh = d->v_sh; p.v_ss = d->v_ss;
+  if (need_prep)
+    if (int rc = launch_lm_prep(pp, op, as_stream(stream))) return chk(rc, "debug_lm_skinny (prologue)");
+  return chk(launch_lm_skinny(p, op, as_stream(stream)), "debug_lm_skinny");
+}
+
+int mra_debug_lm_argmax(const float* logits, int64_t ld, int32_t B, int32_t V, int32_t* tokens_out, int32_t* finished, int32_t pad,
+                        const int32_t* eos, int32_t n_eos, void* stream) {
+  const std::string w("debug_lm_argmax");
+  if (B < 1 || V < 1 || ld < V) return fail(MRA_EINVAL, w + ": B >= 1, V >= 1 and ld >= V expected");
+  if (n_eos < 0 || n_eos > LM_MAX_EOS || (n_eos > 0 && !eos)) return fail(MRA_EINVAL, w + ": n_eos must be in 0..8 (with a host array)");
+  if (!logits || !tokens_out) return fail(MRA_EINVAL, w + ": null argument");
+  if (!aligned4(logits) || !aligned4(tokens_out) || !aligned4(finished)) return fail(MRA_EINVAL, w + ": buffers must be 4-byte aligned");
+  LmGreedy g{};
+  g.tokens_out = tokens_out; g.finished = finished; g.pad = pad; g.n_eos = n_eos;
+  for (int e = 0; e < n_eos; ++e) g.eos[e] = eos[e];
+  return chk(launch_lm_argmax(logits, ld, B, V, g, as_stream(stream)), "debug_lm_argmax");
+}
+
 // ---- prompt assembly: one row gather with a cast (prompt.hip) -----------------------------------------------------------------------------
 // replaces: the torch.cat in front of the LM, models/xinstructblip.py:341-381, :541-595.  Every check comes before a launch.
 int mra_gather_rows(void* out, int64_t ldo, int32_t out_dtype, int32_t n_rows, int32_t width, const mra_rows_src* srcs, int32_t n_src,

@@ -7,6 +7,7 @@ namespace mra {
 
 typedef _Float16 f16;
 typedef __bf16 bf16;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));

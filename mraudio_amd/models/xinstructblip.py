@@ -232,7 +232,8 @@ class XInstructBLIP(nn.Module):
     # is refused with MraError, as it always was
     grouped_lm = False
     # how generate_llm / generate_multi_llm decode (_llm_decode): "stock" = llm_model.generate as it comes (a growing cache, SDPA), "hip" = the
-    # same greedy generate over a static cache with the one-token attention on mra_decode_attention (models/lm_decode.py)
+    # same greedy generate over a static cache with the one-token attention on mra_decode_attention (models/lm_decode.py), "hip_step" = the
+    # prefill through the LM's own forward, then one mra_lm_step per token (models/lm_step.py)
     lm_decode = "stock"
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
@@ -246,8 +247,8 @@ class XInstructBLIP(nn.Module):
                  video_processor=None, lm_loss: str = "stock", prompt_assembly: str = "cat",
                  grouped_lm: bool = False, lm_decode: str = "stock"):
         super().__init__()
-        if lm_decode not in ("stock", "hip"):
-            raise ValueError(f"lm_decode must be 'stock' or 'hip', got {lm_decode!r}")
+        if lm_decode not in ("stock", "hip", "hip_step"):
+            raise ValueError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
         self.lm_decode = lm_decode
         if lm_loss not in ("stock", "rows", "fused"):
             raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
@@ -1035,7 +1036,9 @@ class XInstructBLIP(nn.Module):
     def _llm_decode(self, embeds, mask, max_new_tokens: int) -> List[str]:
         """``lm_decode = "stock"``: the reference's call.  ``"hip"``: the same greedy decode over a static cache (no ``torch.cat`` of the K/V per
         token) with every one-token attention on ``mra_decode_attention`` (``models/lm_decode.py``); ``disable_compile`` because ``generate``
-        would otherwise compile the forward around the ctypes launches.  The LM is as it was after the call."""
+        would otherwise compile the forward around the ctypes launches.  ``"hip_step"``: the prefill through the LM's own forward, then one
+        ``mra_lm_step`` per token (``models/lm_step.py``: weight-streaming layers, head and greedy bookkeeping on HIP).  The LM is as it was
+        after the call."""
         if self.lm_decode == "stock":
             outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens)
         elif self.lm_decode == "hip":
@@ -1044,8 +1047,15 @@ class XInstructBLIP(nn.Module):
             with hip_decode(self.llm_model):
                 outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens,
                                                   cache_implementation="static", disable_compile=True)
+        elif self.lm_decode == "hip_step":
+            from .lm_step import HipLmDecoder
+
+            dec = getattr(self, "_lm_stepper", None)
+            if dec is None or dec.llm is not self.llm_model:
+                dec = self._lm_stepper = HipLmDecoder(self.llm_model)
+            outputs = dec.generate(embeds, mask, max_new_tokens)
         else:
-            raise MraError(f"lm_decode must be 'stock' or 'hip', got {self.lm_decode!r}")
+            raise MraError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {self.lm_decode!r}")
         outputs[outputs == 0] = 2                                      # :392
         return [o.strip() for o in self.llm_tokenizer.batch_decode(outputs, skip_special_tokens=True)]
 

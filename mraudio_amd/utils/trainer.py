@@ -45,7 +45,7 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     "score" is the scorer's span; "llm" is the reference's own validation (``:157-165``): the strings ``generate_llm`` decodes (a validation
     loader of grouped records: ``generate_multi_llm``, flattened in the loader's order) through the same ``post_process`` ->
     ``moment_str_to_list`` -> ``eval_submission`` tail -- the validation under which frozen Q-Formers with LoRA adapters move the metric.
-    ``args.lm_decode`` ("stock" | "hip", ``finetune --lm-decode``): how that decode runs (``XInstructBLIP._llm_decode``, ``models/lm_decode.py``).
+    ``args.lm_decode`` ("stock" | "hip" | "hip_step", ``finetune --lm-decode``): how that decode runs (``XInstructBLIP._llm_decode``, ``models/lm_decode.py``).
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -140,7 +140,8 @@ class Trainer:
                 raise ValueError("prompt_assembly changes how the LM's prompt is put together: it needs objective 'llm' or 'both'")
             model.prompt_assembly = prompt_assembly
         # val_decode "llm": validation decodes with the attached LM (generate_llm, the reference's own validation) instead of the scorer's span;
-        # lm_decode "hip": that decode over a static cache with the one-token attention on HIP (models/lm_decode.py)
+        # lm_decode "hip": that decode over a static cache with the one-token attention on HIP (models/lm_decode.py);
+        # "hip_step": one mra_lm_step per token behind the LM's own prefill (models/lm_step.py)
         self.val_decode = getattr(args, "val_decode", None) or "score"
         if self.val_decode not in ("score", "llm"):
             raise ValueError(f"val_decode must be 'score' or 'llm', got {self.val_decode!r}")
@@ -148,8 +149,8 @@ class Trainer:
             from .._lib import MraError
             raise MraError("val_decode 'llm' needs a model with an LM attached (attach_llm; finetune --llm-path)")
         lm_decode = getattr(args, "lm_decode", None) or "stock"
-        if lm_decode not in ("stock", "hip"):
-            raise ValueError(f"lm_decode must be 'stock' or 'hip', got {lm_decode!r}")
+        if lm_decode not in ("stock", "hip", "hip_step"):
+            raise ValueError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
         if lm_decode != "stock":
             model.lm_decode = lm_decode
         self.lora = bool(getattr(args, "lora", False))

@@ -5,8 +5,12 @@
                shape), S in {1900, 5400} (the prefix the prompt assembler builds at T = 20 / T = 60).  ms per call and TB/s on the
                algorithmic bytes 2 * B * Hkv * S * D * 2 (K and V read once).
   (b) generate 64 greedy tokens of a 4-layer Llama (hidden 1024, 8 heads of 128: the model of tools/bench_lora.py) behind a prefix of 1900
-               embedded positions, B = 2, on three routes: stock (``generate`` as it comes: a growing cache, SDPA), static (stock attention
-               over a static cache, ``disable_compile``) and hip (``hip_decode``: the static cache with the one-token attention on HIP).
+               embedded positions, B = 2, on four routes: stock (``generate`` as it comes: a growing cache, SDPA), static (stock attention
+               over a static cache, ``disable_compile``), hip (``hip_decode``: the static cache with the one-token attention on HIP) and
+               hip_step (``HipLmDecoder``: the LM's own prefill, then one ``mra_lm_step`` per token).
+  (c) layer    ms per token of ``mra_lm_step`` alone on ONE 7B-shaped layer with random weights (hidden 4096, intermediate 11008, 32 heads of
+               128, a 64-token vocabulary so that the head does not count, 21 cached keys: slot 20) at B = 1, 2 and 8, beside the same seven products as
+               ``F.linear`` calls; bytes streamed = the seven weight matrices once, TB/s and the fraction of 8 TB/s on them.
 
 ms = median of ``--reps`` repetitions between device events, the routes alternating inside each repetition, one process; (a) times
 ``--inner`` back-to-back calls per repetition.  One JSON line on stdout, also written to ``--out`` (profiles/lm_decode_line.json is such a line).
@@ -26,6 +30,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mraudio_amd.models.lm_decode import decode_attention, hip_decode  # noqa: E402
+from mraudio_amd.models.lm_step import HipLmDecoder, rope_table, step_workspace_bytes  # noqa: E402
 
 
 def _time(fn, inner: int) -> float:
@@ -92,12 +97,62 @@ def bench_generate(dev, reps: int, warmup: int, prefix: int, new_tokens: int) ->
         with hip_decode(llm):
             tokens["hip"] = llm.generate(cache_implementation="static", disable_compile=True, **kw)
 
+    dec = HipLmDecoder(llm)
+
+    def hip_step():
+        tokens["hip_step"] = dec.generate(embeds, mask, new_tokens, ignore_eos=True)
+
     with torch.no_grad():
-        out = _alternate({"stock": stock, "static": static, "hip": hip}, reps, warmup, 1)
+        out = _alternate({"stock": stock, "static": static, "hip": hip, "hip_step": hip_step}, reps, warmup, 1)
     n = tokens["stock"].numel()
     return {"layers": 4, "hidden": 1024, "heads": 8, "head_dim": 128, "B": B, "prefix": prefix, "new_tokens": new_tokens, "routes": out,
-            "tokens_equal_to_stock": {k: f"{int((tokens[k] == tokens['stock']).sum())}/{n}" for k in ("static", "hip")},
-            "ratio_hip_over_stock": round(out["hip"]["ms"] / out["stock"]["ms"], 3), "ratio_hip_over_static": round(out["hip"]["ms"] / out["static"]["ms"], 3)}
+            "tokens_equal_to_stock": {k: f"{int((tokens[k] == tokens['stock']).sum())}/{n}" for k in ("static", "hip", "hip_step")},
+            "ratio_hip_over_stock": round(out["hip"]["ms"] / out["stock"]["ms"], 3), "ratio_hip_over_static": round(out["hip"]["ms"] / out["static"]["ms"], 3),
+            "ratio_hip_step_over_stock": round(out["hip_step"]["ms"] / out["stock"]["ms"], 3)}
+
+
+def bench_layer(dev, reps: int, warmup: int, inner: int) -> dict:
+    import ctypes as C
+
+    import transformers as tf
+
+    from mraudio_amd._lib import check, current_stream, lib
+
+    torch.manual_seed(0)
+    H, I, heads, D, V, Smax, slot = 4096, 11008, 32, 128, 64, 64, 20
+    cfg = tf.LlamaConfig(vocab_size=V, hidden_size=H, intermediate_size=I, num_hidden_layers=1, num_attention_heads=heads,
+                         num_key_value_heads=heads, max_position_embeddings=4096, pad_token_id=0, bos_token_id=1, eos_token_id=2)
+    llm = tf.LlamaForCausalLM(cfg).to(dev).to(torch.bfloat16).eval().requires_grad_(False)
+    layer = llm.model.layers[0]
+    Ws = [layer.self_attn.q_proj.weight, layer.self_attn.k_proj.weight, layer.self_attn.v_proj.weight, layer.self_attn.o_proj.weight,
+          layer.mlp.gate_proj.weight, layer.mlp.up_proj.weight, layer.mlp.down_proj.weight]
+    nbytes = sum(w.numel() * 2 for w in Ws)
+    dec = HipLmDecoder(llm)
+    rows = []
+    for B in (1, 2, 8):
+        cache = (torch.randn(1, 2, B, heads, Smax, D, device=dev) * 0.1).to(torch.bfloat16)
+        mask8 = torch.ones(B, Smax, dtype=torch.uint8, device=dev)
+        position = torch.full((B,), slot, dtype=torch.int32, device=dev)
+        rope = rope_table(llm, Smax + 1, dev)
+        h = torch.empty(B, H, dtype=torch.bfloat16, device=dev)
+        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+        ws = torch.empty(step_workspace_bytes(B, H, I, heads, D, Smax), dtype=torch.uint8, device=dev)
+        tin = torch.arange(B, dtype=torch.int32, device=dev)
+        tout = torch.empty(B, dtype=torch.int32, device=dev)
+        d = dec.descriptor(B, cache, mask8, position, rope, h, logits, None, ws, 0, [])
+        d.slot, d.pos_offset, d.tokens_in, d.tokens_out = slot, 0, tin.data_ptr(), tout.data_ptr()
+        step, stream = lib().mra_lm_step, current_stream()
+        x, act = torch.randn(B, H, device=dev).to(torch.bfloat16), torch.randn(B, I, device=dev).to(torch.bfloat16)
+        lin = torch.nn.functional.linear
+        routes = {"mra_lm_step": lambda: check(step(C.byref(d), stream), "mra_lm_step"),
+                  "f_linear_x7": lambda: [lin(x, w) for w in Ws[:6]] + [lin(act, Ws[6])]}
+        out = _alternate(routes, reps, warmup, inner)
+        for r in out.values():
+            r["tb_per_s"] = round(nbytes / (r["ms"] * 1e-3) / 1e12, 3)
+            r["fraction_of_8_tb_per_s"] = round(nbytes / (r["ms"] * 1e-3) / 8e12, 3)
+        rows.append({"B": B, "routes": out, "ratio_step_over_f_linear": round(out["mra_lm_step"]["ms"] / out["f_linear_x7"]["ms"], 3)})
+    return {"hidden": H, "intermediate": I, "heads": heads, "head_dim": D, "weight_bytes": nbytes, "cached_keys": slot + 1,
+            "launches_per_step": 8 * cfg.num_hidden_layers + 4, "rows": rows}
 
 
 def main(argv=None) -> None:
@@ -115,9 +170,11 @@ def main(argv=None) -> None:
     dev = torch.device("cuda:0")
     line = {"metric": "lm_decode", "dtype": "bf16", "reps": args.reps, "warmup": args.warmup, "inner": args.inner,
             "note": "ms = median of reps between device events, routes alternating inside each repetition; kernel: per call over `inner` "
-                    "back-to-back calls, B = 2, Hq = Hkv = 32, D = 128, TB/s on 2 * B * Hkv * S * D * 2 bytes; generate: per call of 64 greedy tokens",
+                    "back-to-back calls, B = 2, Hq = Hkv = 32, D = 128, TB/s on 2 * B * Hkv * S * D * 2 bytes; generate: per call of 64 greedy tokens; "
+                    "every section is measured anew by every run of this tool: a line holds one session; layer: per mra_lm_step call (one 7B-shaped layer + a 64-token head) over `inner` back-to-back calls, TB/s on the seven weight matrices",
             "kernel": [bench_kernel(dev, S, args.reps, args.warmup, args.inner) for S in args.seqs],
-            "generate": bench_generate(dev, args.reps, 1, args.prefix, args.new_tokens)}
+            "generate": bench_generate(dev, args.reps, 1, args.prefix, args.new_tokens),
+            "layer": bench_layer(dev, args.reps, args.warmup, args.inner)}
     text = json.dumps(line)
     print(text)
     if args.out:
