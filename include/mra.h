@@ -386,6 +386,33 @@ int mra_decode_attention(const void* q, int64_t q_sb, int64_t q_sh, const void* 
                          int32_t S, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb, int64_t o_sh, float* lse, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- LM prefill: causal grouped-query attention under a key byte mask -----------------------------------------------
+ * replaces: scaled_dot_product_attention under the explicit [Sq][Skv] mask in the prefill inside the reference's
+ * self.llm_model.generate(inputs_embeds=..., attention_mask=...) (models/xinstructblip.py:388-391): the first forward over the whole prefix
+ * (media rows, timestamps and prompt, left-padded, with padding inside).  Stateless like mra_decode_attention: caller-owned buffers, a stream,
+ * no allocation, no synchronisation, no workspace.  q [B][Hq][Sq][D], k, v [B][Hkv][Skv][D] in `dtype` (MRA_F16 / MRA_BF16) with ELEMENT
+ * strides (*_sb batch, *_sh head, *_ss position; D contiguous), so a transposed view of q and a static cache's [B][Hkv][Smax][D] buffer are
+ * read as they lie.  mask [B][Skv] bytes with batch stride mask_sb, nonzero = attend, NULL = every key; there is no [Sq][Skv] tensor.  Query
+ * row i sits at key slot q_offset + i.  out [B][Sq][Hq][D] with element strides o_sb (batch), o_ss (position), o_sh (head); lse f32
+ * [B][Hq][Sq] contiguous, natural log, nullable.  With G = Hq / Hkv, for query (b, h, i):
+ *   attended = {s : s <= q_offset + i, s < Skv, mask[b][s] != 0}
+ *   out = softmax_s(scale * q[b,h,i] . k[b, h / G, s] over the attended s) v[b, h / G]        lse = log sum_s exp(scale q.k)
+ * Logits, softmax statistics and the P V sum are fp32 (v_mfma_f32_32x32x16 for both products); P is rounded once to `dtype` for the second
+ * product; out is rounded once.  A row with no attended key gives out = +0 and lse = -inf.  Masking is a select on both sides: whatever bits
+ * sit in a masked slot, above the diagonal or behind the written part of a static cache reach nothing.
+ * A workgroup owns 256 query rows of one (b, query head) and walks tiles of 32 keys, staged once into LDS for its 4 waves, up to the diagonal
+ * of its last row; a tile whose mask bytes are all zero is skipped without touching the running maximum or sum; the latest query blocks are
+ * launched first.  One launch, no atomics: two runs give the same bits.
+ * Accepted: D 64 or 128, G 1, 2, 4 or 8, Sq >= 1, Skv >= 1, 0 <= q_offset, q_offset + Sq <= Skv <= 2^30, B and Hkv at most 65535,
+ * Sq at most 65535 * 256.  Checked before the launch (MRA_EINVAL, named in mra_last_error, nothing written): negative B, unknown dtype,
+ * another D or G or Hq % Hkv != 0, Sq or Skv < 1, a negative q_offset or q_offset + Sq > Skv, NULL q / k / v / out, one of them not 16-byte
+ * aligned, a stride that is not a multiple of 8 elements, q_ss / k_ss / v_ss / o_ss / o_sh below D, lse not 4-byte aligned, a scale that
+ * is not finite.  B == 0 launches nothing and returns MRA_OK whatever else is passed. */
+int mra_prefill_attention(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
+                          const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss, const uint8_t* mask, int64_t mask_sb, int32_t B, int32_t Hq,
+                          int32_t Hkv, int32_t Sq, int32_t Skv, int32_t q_offset, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb,
+                          int64_t o_ss, int64_t o_sh, float* lse, void* stream);
+
 /* ---- LM decode: one whole token per call (weight-streaming layers, head, greedy bookkeeping) ------------------------
  * replaces: one iteration of the reference's self.llm_model.generate(inputs_embeds=..., attention_mask=..., max_new_tokens=64)
  * (models/xinstructblip.py:383-391, utils/trainer.py:157-165) behind the prefill: the forward of a Llama-shaped LM on one new token per

@@ -274,6 +274,23 @@ int launch_decode_attention(const void* q, long long q_sb, long long q_sh, const
                             const void* v, long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq,
                             int Hkv, int S, int D, float scale, void* out, long long o_sb, long long o_sh, float* lse, float* pm, float* pl,
                             float* pacc, int op_dtype, hipStream_t stream);
+// Causal grouped-query attention of the LM's prefill (prefill_attn.hip): q [B][Hq][Sq][D], k, v [B][Hkv][Skv][D] in the operand dtype with
+// element strides (D contiguous, every stride a multiple of 8), mask [B][Skv] bytes (NULL: all attended), query row i at key slot q_offset + i,
+// out [B][Sq][Hq][D] with element strides, lse f32 [B][Hq][Sq] (may be NULL).  A workgroup owns PREFILL_QB query rows of one (b, query head)
+// and walks the key tiles of PREFILL_KT keys up to its diagonal.  D in {64, 128}; one launch, no workspace, no atomics.
+constexpr int PREFILL_QB = 256, PREFILL_KT = 32, PREFILL_MAX_SKV = 1 << 30;
+inline int prefill_qblocks(int Sq) { return (int)(((long long)Sq + PREFILL_QB - 1) / PREFILL_QB); }
+struct PrefillArgs {
+  const void* q; long long q_sb, q_sh, q_ss;
+  const void* k; long long k_sb, k_sh, k_ss;
+  const void* v; long long v_sb, v_sh, v_ss;
+  const unsigned char* mask; long long mask_sb;
+  int B, Hq, G, Sq, Skv, q_offset;              // G = Hq / Hkv
+  float scale;
+  void* out; long long o_sb, o_ss, o_sh;
+  float* lse;
+};
+int launch_prefill_attention(const PrefillArgs& a, int D, int op_dtype, hipStream_t stream);
 // The one-token step of the LM's decode (lm_step.hip): a skinny weight-streaming GEMM y [B][N] = x [B][K] W[N][K]^T for B <= LM_MAX_B rows
 // with its prologue launch (RMSNorm to an fp32 copy, u = A x of up to three adapters), the embedding gather and the argmax with generate's
 // greedy bookkeeping.  A workgroup owns LM_CB columns (rotary form: one head of D columns); W is read as stored and never copied.

@@ -1690,6 +1690,44 @@ int mra_decode_attention(const void* q, int64_t q_sb, int64_t q_sh, const void* 
              "decode_attention");
 }
 
+// ---- causal grouped-query attention of the LM's prefill (prefill_attn.hip) ----------------------------------------------------------------
+// replaces: scaled_dot_product_attention under the [Sq][Skv] mask in the prefill inside self.llm_model.generate(...),
+// models/xinstructblip.py:388-391.  Every check comes before the launch.
+int mra_prefill_attention(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
+                          const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss, const uint8_t* mask, int64_t mask_sb, int32_t B, int32_t Hq,
+                          int32_t Hkv, int32_t Sq, int32_t Skv, int32_t q_offset, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb,
+                          int64_t o_ss, int64_t o_sh, float* lse, void* stream) {
+  const std::string w("prefill_attention");
+  if (B < 0) return fail(MRA_EINVAL, w + ": negative B");
+  if (B == 0) return MRA_OK;   // launches nothing, touches nothing
+  if (dtype != MRA_F16 && dtype != MRA_BF16) return fail(MRA_EINVAL, w + ": dtype must be MRA_F16 or MRA_BF16");
+  if (D != 64 && D != 128) return fail(MRA_EINVAL, w + ": D must be 64 or 128");
+  if (Sq < 1 || Skv < 1) return fail(MRA_EINVAL, w + ": Sq and Skv must be at least 1");
+  if (q_offset < 0 || (int64_t)q_offset + Sq > Skv) return fail(MRA_EINVAL, w + ": 0 <= q_offset and q_offset + Sq <= Skv expected");
+  if (Hq < 1 || Hkv < 1 || Hq % Hkv) return fail(MRA_EINVAL, w + ": Hq must be a positive multiple of Hkv");
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return fail(MRA_EINVAL, w + ": Hq / Hkv must be 1, 2, 4 or 8");
+  if (B > 65535 || Hkv > 65535) return fail(MRA_EINVAL, w + ": B and Hkv must be at most 65535");
+  if (Skv > PREFILL_MAX_SKV || prefill_qblocks(Sq) > 65535) return fail(MRA_EINVAL, w + ": Skv must be at most 2^30 and Sq at most 65535 query blocks");
+  if (!q || !k || !v || !out) return fail(MRA_EINVAL, w + ": null argument");
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) return fail(MRA_EINVAL, w + ": q, k, v and out must be 16-byte aligned");
+  if (q_sb % 8 || q_sh % 8 || q_ss % 8 || k_sb % 8 || k_sh % 8 || k_ss % 8 || v_sb % 8 || v_sh % 8 || v_ss % 8 || o_sb % 8 || o_ss % 8 || o_sh % 8)
+    return fail(MRA_EINVAL, w + ": the strides must be multiples of 8 elements (16 bytes)");
+  if (q_ss < D || k_ss < D || v_ss < D || o_ss < D || o_sh < D) return fail(MRA_EINVAL, w + ": a position stride (or out's head stride) below D");
+  if (lse && reinterpret_cast<uintptr_t>(lse) % 4) return fail(MRA_EINVAL, w + ": lse must be 4-byte aligned");
+  if (!std::isfinite(scale)) return fail(MRA_EINVAL, w + ": scale must be finite");
+  PrefillArgs a{};
+  a.q = q; a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss;
+  a.k = k; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
+  a.v = v; a.v_sb = v_sb; a.v_sh = v_sh; a.v_ss = v_ss;
+  a.mask = mask; a.mask_sb = mask_sb;
+  a.B = B; a.Hq = Hq; a.G = G; a.Sq = Sq; a.Skv = Skv; a.q_offset = q_offset;
+  a.scale = scale;
+  a.out = out; a.o_sb = o_sb; a.o_ss = o_ss; a.o_sh = o_sh;
+  a.lse = lse;
+  return chk(launch_prefill_attention(a, D, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)), "prefill_attention");
+}
+
 // ---- one whole token of the LM's decode (lm_step.hip) ---------------------------------------------------------------------------------------
 // replaces: one iteration of self.llm_model.generate(...) behind the prefill, models/xinstructblip.py:383-391.  Every check comes before a launch.
 namespace {

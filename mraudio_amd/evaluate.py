@@ -136,6 +136,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lm-step", action="store_true",
                     help="with --llm-path: decode as finetune's --lm-decode hip_step does: the LM's own prefill, then one mra_lm_step per token "
                          "(not together with --lm-decode hip)")
+    ap.add_argument("--lm-prefill", choices=("stock", "hip"), default="stock",
+                    help="with --llm-path and --lm-decode hip or --lm-step: the prefill's attention on mra_prefill_attention under the key mask alone")
     ap.add_argument("--lora", action="store_true", help="with --llm-path: put LoRA adapters on the LM and load their weights (llm_model.* keys) from --checkpoint")
     ap.add_argument("--lora-r", type=int, default=8)
     ap.add_argument("--lora-alpha", type=float, default=8.0)
@@ -156,6 +158,8 @@ def main(argv=None) -> None:
     args = parser.parse_args(argv)
     if args.lm_step and args.lm_decode != "stock":
         parser.error("--lm-step and --lm-decode hip name two different decodes: give one of them")
+    if args.lm_prefill == "hip" and not (args.llm_path and (args.lm_step or args.lm_decode == "hip")):
+        parser.error("--lm-prefill hip needs --llm-path DIR and a HIP decode (--lm-decode hip or --lm-step)")
     if args.lora and not args.llm_path:
         parser.error("--lora needs --llm-path DIR")
     if args.llm_path and (args.group_by_video or args.top_k > 1):
@@ -181,6 +185,7 @@ def main(argv=None) -> None:
     if llm is not None:
         model.attach_llm(llm, tok)
         model.lm_decode = "hip_step" if args.lm_step else args.lm_decode
+        model.lm_prefill = args.lm_prefill
         if args.lora:       # the adapters must exist before the file's llm_model.* keys can be routed into them
             model.enable_lora(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout)
             if args.checkpoint:

@@ -118,6 +118,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lm-decode", choices=("stock", "hip", "hip_step"), default="stock",
                     help="how the LM decodes: stock = llm_model.generate as it comes; hip = the same greedy decode over a static cache with the "
                          "one-token attention on mra_decode_attention; hip_step = the LM's own prefill, then one mra_lm_step per token")
+    ap.add_argument("--lm-prefill", choices=("stock", "hip"), default="stock",
+                    help="the prefill in front of that decode: stock = the LM's forward as it is configured; hip = its attention on "
+                         "mra_prefill_attention under the key mask alone (needs --lm-decode hip or hip_step)")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
                          "(mra_video_frames_forward) instead of as float32 pixels made on the host")

@@ -13,8 +13,22 @@ whole K/V of every layer; the stock route (a ``DynamicCache`` whose ``update`` i
                                                all) to transformers' own ``sdpa_attention_forward`` with the arguments untouched
     hip_decode(llm)                            context manager: the LM runs with that implementation inside the block and is as it was after it
 
-A row with no attended key gives +0 where SDPA gives NaN; ``generate`` never produces one.  Out of scope: paged or quantised K/V, beam search
-and sampling, a prefill kernel, sliding windows and soft caps (such calls go to SDPA)."""
+The prefill in front of it (the reference's same ``generate`` call, ``models/xinstructblip.py:388-391``) is opt-in:
+
+    prefill_attention(q, k, v, key_mask, scale, q_offset=0)
+                                               out[b,i,h] = softmax over {s <= q_offset + i, key_mask[b,s]} of scale q[b,h,i] . k[b, h / G, s],
+                                               times v: causality and the key mask are applied inside, the HIP route has no [Sq, Skv] tensor;
+                                               ``mra_prefill_attention`` on the GPU, the same definition as torch ops elsewhere
+    register(prefill=True), hip_decode(llm, prefill=True)
+                                               a second name, "mra_prefill": its mask builder hands the FIRST prefill (q_offset 0, more than
+                                               one query, the plain causal mask function) the key mask alone, bool [B, 1, 1, kv_length]; its
+                                               attention function sends such calls to ``prefill_attention``, one-token calls to
+                                               ``decode_attention`` and everything else to SDPA (under the full causal mask, rebuilt if the
+                                               call carried the key mask alone)
+
+A row with no attended key gives +0 where SDPA gives NaN; ``generate`` never produces one behind a decode, and the left-pad query rows of a
+prefill, which are exactly that case, are attended by nothing downstream.  Out of scope: paged or quantised K/V, beam search and sampling,
+chunked prefill, a backward of the prefill attention, sliding windows and soft caps (such calls go to SDPA)."""
 from __future__ import annotations
 
 import contextlib
@@ -25,6 +39,7 @@ import torch
 from .._lib import MraError, check, current_stream, lib, mra_dtype, ptr
 
 NAME = "mra_decode"
+PREFILL_NAME = "mra_prefill"
 HEAD_DIMS, GROUPS = (64, 128), (1, 2, 4, 8)
 
 
@@ -108,6 +123,144 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Op
     return _torch_ops(q, k, v, mask, scale)
 
 
+def _prefill_shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], q_offset: int) -> Optional[str]:
+    """None when the tensors are a causal attention call, else what is wrong."""
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[3] != q.shape[3] or q.shape[2] < 1 or k.shape[2] < 1 \
+            or k.shape[1] < 1 or q.shape[1] % k.shape[1]:
+        return f"q [B, Hq, Sq, D], k / v [B, Hkv, Skv, D] with Hq a multiple of Hkv expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}"
+    if q_offset < 0 or q_offset + q.shape[2] > k.shape[2]:
+        return f"0 <= q_offset and q_offset + Sq <= Skv expected, got q_offset {q_offset}, Sq {q.shape[2]}, Skv {k.shape[2]}"
+    if key_mask is not None and (key_mask.dtype != torch.bool or key_mask.dim() != 4 or tuple(key_mask.shape[1:]) != (1, 1, k.shape[2])
+                                 or key_mask.shape[0] not in (1, q.shape[0])):
+        return f"key_mask must be bool [B, 1, 1, Skv] (True = attend) or None, got {key_mask.dtype} {tuple(key_mask.shape)}"
+    return None
+
+
+def _prefill_hip_reason(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor]) -> Optional[str]:
+    """None when ``mra_prefill_attention`` applies, else why not."""
+    if not (q.is_cuda and k.is_cuda and v.is_cuda and (key_mask is None or key_mask.is_cuda)):
+        return "q, k, v and the key mask must be CUDA tensors"
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in (torch.float16, torch.bfloat16):
+        return f"q, k and v must share a 16-bit dtype, got {q.dtype}, {k.dtype}, {v.dtype}"
+    if not accepted(q, k):
+        return f"D = {q.shape[3]} with Hq / Hkv = {q.shape[1] // k.shape[1]} is outside D in {HEAD_DIMS}, Hq / Hkv in {GROUPS}"
+    if k.shape[2] > 1 << 30 or q.shape[2] > 65535 * 256:
+        return f"Sq = {q.shape[2]}, Skv = {k.shape[2]} is outside the entry's grid"
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.stride(3) != 1 or any(s % 8 for s in t.stride()[:3]) or t.data_ptr() % 16 or t.stride(2) < t.shape[3]:
+            return f"{name} is not laid out as the entry reads it (unit stride along D, 16-byte aligned rows), and no copy of it is made"
+    return None
+
+
+def _prefill_entry(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], scale: float, q_offset: int, want_lse: bool):
+    B, Hq, Sq, D = q.shape
+    Hkv, Skv = k.shape[1], k.shape[2]
+    out = torch.empty(B, Sq, Hq, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, Hq, Sq, dtype=torch.float32, device=q.device) if want_lse else None
+    m8, m_sb = None, 0
+    if key_mask is not None:
+        m8 = (key_mask if key_mask.stride(3) == 1 or Skv == 1 else key_mask.contiguous()).view(torch.uint8)   # [B or 1, 1, 1, Skv] bytes
+        m_sb = m8.stride(0) if key_mask.shape[0] == B and B > 1 else 0
+    check(lib().mra_prefill_attention(ptr(q), q.stride(0), q.stride(1), q.stride(2), ptr(k), k.stride(0), k.stride(1), k.stride(2), ptr(v), v.stride(0),
+                                      v.stride(1), v.stride(2), None if m8 is None else ptr(m8), m_sb, B, Hq, Hkv, Sq, Skv, q_offset, D, mra_dtype(q.dtype),
+                                      float(scale), ptr(out), out.stride(0), out.stride(1), out.stride(2), None if lse is None else ptr(lse),
+                                      current_stream()), "mra_prefill_attention")
+    return out, lse
+
+
+def _prefill_torch_ops(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], scale: float, q_offset: int):
+    """The definition in fp32 (wider inputs keep their type): (out [B, Sq, Hq, D] in q's dtype, lse [B, Hq, Sq]).  Masking is a select on both
+    sides: the bits of a key that no row attends reach nothing."""
+    B, Hq, Sq, D = q.shape
+    Skv = k.shape[2]
+    G = Hq // k.shape[1]
+    ct = torch.float32 if q.dtype in (torch.float16, torch.bfloat16) else q.dtype
+    dev = q.device
+    on = torch.arange(Skv, device=dev)[None, :] <= (torch.arange(Sq, device=dev) + q_offset)[:, None]     # [Sq, Skv]: a few MB at the tests' sizes
+    on = on[None, None] if key_mask is None else on[None, None] & key_mask.to(dev)                           # [B or 1, 1, Sq, Skv]
+    some = on.any(dim=2)[..., None]                                                                     # [B or 1, 1, Skv, 1]: attended by a row
+    zero = torch.zeros((), dtype=ct, device=dev)
+    kf = torch.where(some, k.to(ct), zero).repeat_interleave(G, dim=1)                                        # [B, Hq, Skv, D]
+    vf = torch.where(some, v.to(ct), zero).repeat_interleave(G, dim=1)
+    z = torch.where(on, scale * (q.to(ct) @ kf.transpose(2, 3)), torch.full((), float("-inf"), dtype=ct, device=dev))   # [B, Hq, Sq, Skv]
+    m = z.max(dim=3, keepdim=True).values
+    live = m > float("-inf")
+    m = torch.where(live, m, torch.zeros_like(m))                                                             # a row with no attended key: every p is 0
+    p = torch.exp(z - m)
+    l = p.sum(dim=3, keepdim=True)
+    l1 = torch.where(live, l, torch.ones_like(l))
+    out = (p @ vf) / l1
+    lse = torch.where(live, m + torch.log(l1), torch.full((), float("-inf"), dtype=ct, device=dev))[..., 0]
+    return out.transpose(1, 2).contiguous().to(q.dtype), lse
+
+
+def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], scale: float, q_offset: int = 0,
+                      hip: Optional[bool] = None, want_lse: bool = False):
+    """``q`` [B, Hq, Sq, D], ``k`` / ``v`` [B, Hkv, Skv, D] (views with any batch / head / position strides), ``key_mask`` bool [B, 1, 1, Skv]
+    with True = attend, or None; query row i sits at key slot ``q_offset + i`` and attends the keys s <= q_offset + i that the mask lets
+    through: ``[B, Sq, Hq, D]`` in q's dtype (the layout transformers wants back), with ``want_lse`` the pair (out, lse fp32 [B, Hq, Sq]).
+    ``hip=None`` takes ``mra_prefill_attention`` where it accepts the call (CUDA, one 16-bit dtype, D 64 or 128, Hq / Hkv 1, 2, 4 or 8,
+    16-byte aligned rows) and the torch ops otherwise; ``hip=True`` raises ``MraError`` naming the reason; ``hip=False`` is the torch ops."""
+    q_offset = int(q_offset)
+    bad = _prefill_shapes(q, k, v, key_mask, q_offset)
+    if bad is not None:
+        raise ValueError(f"prefill_attention: {bad}")
+    res = None
+    if hip is None or hip:
+        why = _prefill_hip_reason(q, k, v, key_mask)
+        if why is None:
+            res = _prefill_entry(q, k, v, key_mask, scale, q_offset, want_lse)
+        elif hip:
+            raise MraError(f"prefill_attention(hip=True): {why}")
+    if res is None:
+        res = _prefill_torch_ops(q, k, v, key_mask, scale, q_offset)
+    return (res[0], res[1]) if want_lse else res[0]
+
+
+def _is_key_mask(query: torch.Tensor, key: torch.Tensor, attention_mask) -> bool:
+    """The mask ``prefill_mask`` hands a first prefill: bool [B, 1, 1, Skv] under more than one query row."""
+    return (isinstance(attention_mask, torch.Tensor) and attention_mask.dtype == torch.bool and query.dim() == 4 and query.shape[2] > 1
+            and attention_mask.dim() == 4 and tuple(attention_mask.shape[1:]) == (1, 1, key.shape[2]) and attention_mask.shape[0] in (1, query.shape[0]))
+
+
+def prefill_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kw):
+    """What ``register(prefill=True)`` registers.  More than one query row under the key mask of ``prefill_mask`` (q_offset 0), an evaluating
+    module, no dropout, no sliding window or soft cap and accepted shapes: ``prefill_attention``.  Such a call that is not accepted goes to
+    SDPA under the full causal mask, built here from the key mask.  Everything else is ``attention_forward``."""
+    if not _is_key_mask(query, key, attention_mask):
+        return attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kw)
+    Sq, Skv = query.shape[2], key.shape[2]
+    if (not module.training and not dropout and kw.get("sliding_window") is None and kw.get("softcap") is None and Sq <= Skv
+            and _prefill_shapes(query, key, value, attention_mask, 0) is None and accepted(query, key)):
+        scale = float(scaling) if scaling is not None else query.shape[3] ** -0.5
+        return prefill_attention(query, key, value, attention_mask, scale, q_offset=0), None       # [B, Sq, Hq, D] as it is wanted back
+    from transformers.integrations.sdpa_attention import sdpa_attention_forward
+
+    dev = query.device
+    causal = torch.arange(Skv, device=dev)[None, :] <= torch.arange(Sq, device=dev)[:, None]
+    full = (attention_mask & causal[None, None]).expand(query.shape[0], 1, Sq, Skv)                 # never silently non-causal
+    return sdpa_attention_forward(module, query, key, value, full, dropout=dropout, scaling=scaling, **kw)
+
+
+def prefill_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_function=None, attention_mask=None, **kw):
+    """The mask builder under ``"mra_prefill"``.  A first prefill (q_offset 0, kv_offset 0, more than one query row, the plain causal mask
+    function, a 2-D padding mask or none): the key mask alone, bool [B, 1, 1, kv_length] (ones without a padding mask; False behind the
+    padding mask's end, which is the unwritten tail of a static cache).  Everything else: ``sdpa_mask`` with the arguments as they came."""
+    from transformers.masking_utils import causal_mask_function, prepare_padding_mask, sdpa_mask
+
+    if mask_function is None:
+        mask_function = causal_mask_function
+    first = (mask_function is causal_mask_function and int(q_length) > 1 and int(kv_offset) == 0 and int(q_offset) == 0 and int(kv_length) >= int(q_length)
+             and kw.get("local_size") is None and (attention_mask is None or attention_mask.dim() == 2))
+    if not first:
+        return sdpa_mask(batch_size=batch_size, q_length=q_length, kv_length=kv_length, q_offset=q_offset, kv_offset=kv_offset,
+                         mask_function=mask_function, attention_mask=attention_mask, **kw)
+    pad = prepare_padding_mask(attention_mask, kv_length, kv_offset)
+    if pad is None:
+        return torch.ones(batch_size, 1, 1, kv_length, dtype=torch.bool, device=kw.get("device", "cpu"))
+    return pad[:, :kv_length].to(torch.bool)[:, None, None, :]
+
+
 def attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kw):
     """What ``register`` registers.  One query position, an evaluating module, no dropout, a bool mask (or none) over the keys and accepted
     shapes: ``decode_attention``; anything else: transformers' SDPA function with the arguments as they came."""
@@ -121,24 +274,26 @@ def attention_forward(module, query, key, value, attention_mask, dropout=0.0, sc
     return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kw)
 
 
-def register() -> str:
-    """Put ``attention_forward`` and SDPA's mask builder under ``"mra_decode"`` in transformers' registries.  Idempotent; returns the name."""
+def register(prefill: bool = False) -> str:
+    """Put ``attention_forward`` and SDPA's mask builder under ``"mra_decode"`` in transformers' registries; with ``prefill``,
+    ``prefill_attention_forward`` and ``prefill_mask`` under ``"mra_prefill"`` instead.  Idempotent; returns the name."""
     from transformers import AttentionInterface
     from transformers.masking_utils import AttentionMaskInterface, sdpa_mask
 
-    if AttentionInterface._global_mapping.get(NAME) is not attention_forward:
-        AttentionInterface.register(NAME, attention_forward)
-    if AttentionMaskInterface._global_mapping.get(NAME) is not sdpa_mask:
-        AttentionMaskInterface.register(NAME, sdpa_mask)
-    return NAME
+    name, fn, mask = (PREFILL_NAME, prefill_attention_forward, prefill_mask) if prefill else (NAME, attention_forward, sdpa_mask)
+    if AttentionInterface._global_mapping.get(name) is not fn:
+        AttentionInterface.register(name, fn)
+    if AttentionMaskInterface._global_mapping.get(name) is not mask:
+        AttentionMaskInterface.register(name, mask)
+    return name
 
 
 @contextlib.contextmanager
-def hip_decode(llm):
-    """Run ``llm`` with the registered attention inside the block; its ``config._attn_implementation`` is put back on the way out, also after
-    an exception.  Nothing else of the LM is touched."""
+def hip_decode(llm, prefill: bool = False):
+    """Run ``llm`` with the registered attention inside the block (``prefill``: the one that also takes the first prefill); its
+    ``config._attn_implementation`` is put back on the way out, also after an exception.  Nothing else of the LM is touched."""
     prev = llm.config._attn_implementation
-    llm.set_attn_implementation(register())
+    llm.set_attn_implementation(register(prefill))
     try:
         yield llm
     finally:

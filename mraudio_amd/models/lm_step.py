@@ -10,16 +10,19 @@ pure weight streaming, issued by ``generate`` as a few dozen small launches per 
                                                                   parameters as they lie (no weight is copied: tied embeddings work)
     HipLmDecoder.generate(inputs_embeds, attention_mask, n)       prefill through the LM's own forward, its K/V copied once into a static
                                                                   buffer, then one ``mra_lm_step`` per token with no torch op in between
+    HipLmDecoder(llm, prefill="hip")                              that forward runs inside ``hip_decode(llm, prefill=True)``: its attention is
+                                                                  ``mra_prefill_attention`` under the key mask, with no [S, S] mask tensor
 
 Where the kernels round (``dtype``), one rounding each: the residual stream, q / k / v, the attention output, the SwiGLU activation.  Everything
 inside a launch is fp32: the RMSNorm rows ``(x * rsqrt(mean(x^2) + eps)) * gain`` are an fp32 copy, the LoRA term ``scale * (x A^T) B^T`` is added
 to the fp32 product BEFORE the rotation, the logits are fp32.  (transformers rounds the normalised rows to the LM's dtype twice; this route does
 not, which is the finer of the two.)
 
-Out of scope: graph capture, a persistent whole-layer kernel, a prefill kernel, sampling and beam search, logits processors, paged or quantised
+Out of scope: graph capture, a persistent whole-layer kernel, the prefill's linears, norms and rotary, sampling and beam search, logits processors, paged or quantised
 K/V, 8-bit base weights, merged adapters, architectures that are not Llama-shaped, more than 8 sequences inside one launch."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
@@ -28,10 +31,12 @@ from torch import nn
 
 from .. import _lib
 from .._lib import MraError, check, current_stream, lib, mra_dtype
+from .lm_decode import hip_decode
 from .lora import ADAPTER, LoraLinear
 
 MAX_B, MAX_R, MAX_EOS = 8, 16, 8
 HEAD_DIMS, GROUPS = (64, 128), (1, 2, 4, 8)
+PREFILLS = ("stock", "hip")
 LINEARS = ("q", "k", "v", "o", "gate", "up", "down")
 # the named wrong versions of the step the tests must tell from the right one (tests/lm_step_cases.py)
 MUTANTS = ("rotate_half_sign", "position_from_slot", "slot_from_position", "lora_scale_dropped", "lora_after_rotation", "residual_dropped",
@@ -267,11 +272,16 @@ class HipLmDecoder:
 
     check_every = 8                 # steps between two looks of the host at ``finished`` (each look is a synchronisation)
 
-    def __init__(self, llm, ref: bool = False):
+    def __init__(self, llm, ref: bool = False, prefill: str = "stock"):
         """``ref``: every step runs ``lm_step_ref`` + ``argmax_ref`` + ``greedy_ref`` instead of ``mra_lm_step`` (any device and dtype): the
-        same loop around the definition, which is how the tests hold the loop against ``generate`` without a GPU."""
+        same loop around the definition, which is how the tests hold the loop against ``generate`` without a GPU.  ``prefill``: "stock" (the
+        LM's forward as it is configured) or "hip" (the same forward inside ``lm_decode.hip_decode(llm, prefill=True)``; the LM's attention
+        implementation is put back afterwards, also after an exception)."""
+        if prefill not in PREFILLS:
+            raise ValueError(f"prefill must be one of {PREFILLS}, got {prefill!r}")
         self.llm = llm
         self.ref = ref
+        self.prefill = prefill
         self._sig = None
         self._walk = None
         self._layers = None
@@ -410,7 +420,8 @@ class HipLmDecoder:
         was = llm.training
         llm.eval()
         try:
-            out = llm(inputs_embeds=embeds, attention_mask=mask, position_ids=pos, use_cache=True, return_dict=True, logits_to_keep=1)
+            with (hip_decode(llm, prefill=True) if self.prefill == "hip" else contextlib.nullcontext()):
+                out = llm(inputs_embeds=embeds, attention_mask=mask, position_ids=pos, use_cache=True, return_dict=True, logits_to_keep=1)
         finally:
             llm.train(was)
         Smax = S0 + n_new

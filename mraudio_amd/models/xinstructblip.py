@@ -216,6 +216,14 @@ def _window_texts(win: torch.Tensor, sc: torch.Tensor, cnt: torch.Tensor, ts: Se
     return scorer.windows_to_text(win, cnt, ts), scorer.windows_to_records(win, sc, cnt, ts)
 
 
+def check_lm_prefill(lm_prefill: str, lm_decode: str) -> None:
+    """``lm_prefill`` is "stock" or "hip", and "hip" needs ``lm_decode`` "hip" or "hip_step" (ValueError otherwise)."""
+    if lm_prefill not in ("stock", "hip"):
+        raise ValueError(f"lm_prefill must be 'stock' or 'hip', got {lm_prefill!r}")
+    if lm_prefill == "hip" and lm_decode not in ("hip", "hip_step"):
+        raise ValueError(f"lm_prefill='hip' needs lm_decode 'hip' or 'hip_step' (the stock decode is the reference's call, untouched), got lm_decode={lm_decode!r}")
+
+
 class XInstructBLIP(nn.Module):
     # what forward() trains on: "score" (the build-defined scorer loss), "llm" (the attached LM's cross-entropy on the answer tokens,
     # reference :399-606) or "both" (bce + lm_weight * lm over ONE Q-Former forward per modality).  loss_scale: the LM term's
@@ -235,6 +243,10 @@ class XInstructBLIP(nn.Module):
     # same greedy generate over a static cache with the one-token attention on mra_decode_attention (models/lm_decode.py), "hip_step" = the
     # prefill through the LM's own forward, then one mra_lm_step per token (models/lm_step.py)
     lm_decode = "stock"
+    # the prefill in front of that decode: "stock" = the LM's forward as it is configured (SDPA under the [S, S] bool mask), "hip" = the same
+    # forward with its attention on mra_prefill_attention under the key mask alone (models/lm_decode.py).  "hip" needs lm_decode "hip" or
+    # "hip_step": the stock decode is the reference's call and stays untouched
+    lm_prefill = "stock"
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
@@ -245,11 +257,13 @@ class XInstructBLIP(nn.Module):
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
                  cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0,
                  video_processor=None, lm_loss: str = "stock", prompt_assembly: str = "cat",
-                 grouped_lm: bool = False, lm_decode: str = "stock"):
+                 grouped_lm: bool = False, lm_decode: str = "stock", lm_prefill: str = "stock"):
         super().__init__()
         if lm_decode not in ("stock", "hip", "hip_step"):
             raise ValueError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
         self.lm_decode = lm_decode
+        check_lm_prefill(lm_prefill, lm_decode)
+        self.lm_prefill = lm_prefill
         if lm_loss not in ("stock", "rows", "fused"):
             raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
         self.lm_loss = lm_loss
@@ -1037,22 +1051,25 @@ class XInstructBLIP(nn.Module):
         """``lm_decode = "stock"``: the reference's call.  ``"hip"``: the same greedy decode over a static cache (no ``torch.cat`` of the K/V per
         token) with every one-token attention on ``mra_decode_attention`` (``models/lm_decode.py``); ``disable_compile`` because ``generate``
         would otherwise compile the forward around the ctypes launches.  ``"hip_step"``: the prefill through the LM's own forward, then one
-        ``mra_lm_step`` per token (``models/lm_step.py``: weight-streaming layers, head and greedy bookkeeping on HIP).  The LM is as it was
-        after the call."""
+        ``mra_lm_step`` per token (``models/lm_step.py``: weight-streaming layers, head and greedy bookkeeping on HIP).  ``lm_prefill = "hip"``
+        (with either HIP decode): the prefill's attention on ``mra_prefill_attention``.  The LM is as it was after the call."""
+        lm_prefill = getattr(self, "lm_prefill", "stock")
+        if lm_prefill != "stock":
+            check_lm_prefill(lm_prefill, self.lm_decode)
         if self.lm_decode == "stock":
             outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens)
         elif self.lm_decode == "hip":
             from .lm_decode import hip_decode
 
-            with hip_decode(self.llm_model):
+            with hip_decode(self.llm_model, prefill=lm_prefill == "hip"):
                 outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens,
                                                   cache_implementation="static", disable_compile=True)
         elif self.lm_decode == "hip_step":
             from .lm_step import HipLmDecoder
 
             dec = getattr(self, "_lm_stepper", None)
-            if dec is None or dec.llm is not self.llm_model:
-                dec = self._lm_stepper = HipLmDecoder(self.llm_model)
+            if dec is None or dec.llm is not self.llm_model or dec.prefill != lm_prefill:
+                dec = self._lm_stepper = HipLmDecoder(self.llm_model, prefill=lm_prefill)
             outputs = dec.generate(embeds, mask, max_new_tokens)
         else:
             raise MraError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {self.lm_decode!r}")

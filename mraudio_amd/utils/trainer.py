@@ -46,6 +46,7 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     loader of grouped records: ``generate_multi_llm``, flattened in the loader's order) through the same ``post_process`` ->
     ``moment_str_to_list`` -> ``eval_submission`` tail -- the validation under which frozen Q-Formers with LoRA adapters move the metric.
     ``args.lm_decode`` ("stock" | "hip" | "hip_step", ``finetune --lm-decode``): how that decode runs (``XInstructBLIP._llm_decode``, ``models/lm_decode.py``).
+    ``args.lm_prefill`` ("stock" | "hip", ``finetune --lm-prefill``; "hip" needs ``lm_decode`` "hip" or "hip_step"): the prefill's attention on ``mra_prefill_attention``.
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -153,6 +154,11 @@ class Trainer:
             raise ValueError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
         if lm_decode != "stock":
             model.lm_decode = lm_decode
+        lm_prefill = getattr(args, "lm_prefill", None) or "stock"
+        if lm_prefill != "stock":                        # "hip" needs a HIP decode: the rule is XInstructBLIP's (check_lm_prefill)
+            from ..models.xinstructblip import check_lm_prefill
+            check_lm_prefill(lm_prefill, lm_decode)
+            model.lm_prefill = lm_prefill
         self.lora = bool(getattr(args, "lora", False))
         if self.lora:
             if self.objective == "score":
@@ -370,6 +376,6 @@ def default_args(**kw) -> SimpleNamespace:
     """The reference's ``finetune.py`` defaults (``:44-62``) as a namespace, for programmatic use."""
     base = dict(model="X-InstructBLIP", model_path=None, audio_encoder=None, video_folder=None, train_annotation_file=None,
                 val_annotation_file=None, output_dir="out", val_freq=1, save_freq=1, max_epoch=50, batch_size=1, num_workers=0,
-                dataset="Charades_STA", gpu=0, val_decode="score", lm_decode="stock")
+                dataset="Charades_STA", gpu=0, val_decode="score", lm_decode="stock", lm_prefill="stock")
     base.update(kw)
     return SimpleNamespace(**base)
