@@ -165,46 +165,33 @@ __global__ __launch_bounds__(64) void decode_attn_merge_kernel(const float* __re
 }
 
 template <typename T, int D, int G>
-void launch_chunks(const void* q, long long q_sb, long long q_sh, const void* k, long long k_sb, long long k_sh, long long k_ss, const void* v,
-                   long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq, int Hkv, int S,
-                   float scale, int nc, float* pm, float* pl, float* pacc, hipStream_t stream) {
-  hipLaunchKernelGGL((decode_attn_chunk_kernel<T, D, G>), dim3(nc, Hkv, B), dim3(256), 0, stream, (const T*)q, q_sb, q_sh, (const T*)k, k_sb, k_sh,
-                     k_ss, (const T*)v, v_sb, v_sh, v_ss, mask, mask_sb, Hq, S, scale, nc, pm, pl, pacc);
+void launch_chunks(const DecodeArgs& a, int nc, hipStream_t stream) {
+  hipLaunchKernelGGL((decode_attn_chunk_kernel<T, D, G>), dim3(nc, a.Hkv, a.B), dim3(256), 0, stream, (const T*)a.q, a.q_sb, a.q_sh, (const T*)a.k,
+                     a.k_sb, a.k_sh, a.k_ss, (const T*)a.v, a.v_sb, a.v_sh, a.v_ss, a.mask, a.mask_sb, a.Hq, a.S, a.scale, nc, a.pm, a.pl, a.pacc);
 }
 
 template <typename T, int D>
-int launch_typed(const void* q, long long q_sb, long long q_sh, const void* k, long long k_sb, long long k_sh, long long k_ss, const void* v,
-                 long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq, int Hkv, int S,
-                 float scale, void* out, long long o_sb, long long o_sh, float* lse, float* pm, float* pl, float* pacc, hipStream_t stream) {
-  const int nc = decode_chunks(S), G = Hq / Hkv;
-#define MRA_DA_CASE(g)                                                                                                                         \
-  case g:                                                                                                                                      \
-    launch_chunks<T, D, g>(q, q_sb, q_sh, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, mask, mask_sb, B, Hq, Hkv, S, scale, nc, pm, pl, pacc, stream); \
-    break;
-  switch (G) {
-    MRA_DA_CASE(1)
-    MRA_DA_CASE(2)
-    MRA_DA_CASE(4)
-    MRA_DA_CASE(8)
+int launch_typed(const DecodeArgs& a, hipStream_t stream) {
+  const int nc = decode_chunks(a.S);
+  switch (a.Hq / a.Hkv) {
+    case 1: launch_chunks<T, D, 1>(a, nc, stream); break;
+    case 2: launch_chunks<T, D, 2>(a, nc, stream); break;
+    case 4: launch_chunks<T, D, 4>(a, nc, stream); break;
+    case 8: launch_chunks<T, D, 8>(a, nc, stream); break;
     default: return -1;
   }
-#undef MRA_DA_CASE
-  hipLaunchKernelGGL((decode_attn_merge_kernel<T, D>), dim3(Hq, B), dim3(64), 0, stream, pm, pl, pacc, Hq, nc, (T*)out, o_sb, o_sh, lse);
+  hipLaunchKernelGGL((decode_attn_merge_kernel<T, D>), dim3(a.Hq, a.B), dim3(64), 0, stream, a.pm, a.pl, a.pacc, a.Hq, nc, (T*)a.out, a.o_sb, a.o_sh,
+                     a.lse);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 }  // namespace
 
-int launch_decode_attention(const void* q, long long q_sb, long long q_sh, const void* k, long long k_sb, long long k_sh, long long k_ss,
-                            const void* v, long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq,
-                            int Hkv, int S, int D, float scale, void* out, long long o_sb, long long o_sh, float* lse, float* pm, float* pl,
-                            float* pacc, int op_dtype, hipStream_t stream) {
-  if (B <= 0) return 0;
-  if (S < 1 || Hkv < 1 || Hq % Hkv || (D != 64 && D != 128) || B > 65535 || Hkv > 65535) return -1;
-#define MRA_DA_ARGS q, q_sb, q_sh, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, mask, mask_sb, B, Hq, Hkv, S, scale, out, o_sb, o_sh, lse, pm, pl, pacc, stream
-  if (op_dtype == OP_BF16) return D == 64 ? launch_typed<bf16, 64>(MRA_DA_ARGS) : launch_typed<bf16, 128>(MRA_DA_ARGS);
-  return D == 64 ? launch_typed<f16, 64>(MRA_DA_ARGS) : launch_typed<f16, 128>(MRA_DA_ARGS);
-#undef MRA_DA_ARGS
+int launch_decode_attention(const DecodeArgs& a, int D, int op_dtype, hipStream_t stream) {
+  if (a.B <= 0) return 0;
+  if (a.S < 1 || a.Hkv < 1 || a.Hq % a.Hkv || (D != 64 && D != 128) || a.B > 65535 || a.Hkv > 65535) return -1;
+  if (op_dtype == OP_BF16) return D == 64 ? launch_typed<bf16, 64>(a, stream) : launch_typed<bf16, 128>(a, stream);
+  return D == 64 ? launch_typed<f16, 64>(a, stream) : launch_typed<f16, 128>(a, stream);
 }
 
 }  // namespace mra

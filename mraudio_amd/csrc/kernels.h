@@ -270,10 +270,18 @@ int launch_lm_head_bwd(const float* g, const void* W, long long ldw, int V, int 
 // D in {64, 128}, Hq / Hkv in {1, 2, 4, 8}; two launches, no atomics.
 constexpr int DECODE_CHUNK = 256;
 inline int decode_chunks(int S) { return (int)(((long long)S + DECODE_CHUNK - 1) / DECODE_CHUNK); }
-int launch_decode_attention(const void* q, long long q_sb, long long q_sh, const void* k, long long k_sb, long long k_sh, long long k_ss,
-                            const void* v, long long v_sb, long long v_sh, long long v_ss, const unsigned char* mask, long long mask_sb, int B, int Hq,
-                            int Hkv, int S, int D, float scale, void* out, long long o_sb, long long o_sh, float* lse, float* pm, float* pl,
-                            float* pacc, int op_dtype, hipStream_t stream);
+struct DecodeArgs {
+  const void* q; long long q_sb, q_sh;
+  const void* k; long long k_sb, k_sh, k_ss;
+  const void* v; long long v_sb, v_sh, v_ss;
+  const unsigned char* mask; long long mask_sb;
+  int B, Hq, Hkv, S;
+  float scale;
+  void* out; long long o_sb, o_sh;
+  float* lse;
+  float *pm, *pl, *pacc;                        // workspace
+};
+int launch_decode_attention(const DecodeArgs& a, int D, int op_dtype, hipStream_t stream);
 // Causal grouped-query attention of the LM's prefill (prefill_attn.hip): q [B][Hq][Sq][D], k, v [B][Hkv][Skv][D] in the operand dtype with
 // element strides (D contiguous, every stride a multiple of 8), mask [B][Skv] bytes (NULL: all attended), query row i at key slot q_offset + i,
 // out [B][Sq][Hq][D] with element strides, lse f32 [B][Hq][Sq] (may be NULL).  A workgroup owns PREFILL_QB query rows of one (b, query head)

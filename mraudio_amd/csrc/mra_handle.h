@@ -1,5 +1,5 @@
 // Private to the library: the handle behind include/mra.h, its parameter registry and small host helpers
-// shared by the inference path (mra_abi.hip) and the training path (mra_train.hip).
+// shared by the inference path (mra_abi.hip), the training path (mra_train.hip) and the attached LM's entries (mra_lm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +32,9 @@ inline int fail(int code, const std::string& msg) {
   } while (0)
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+inline bool aligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
 
 struct Param {
   void* ptr = nullptr;   // destination inside the arena

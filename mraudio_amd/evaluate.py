@@ -103,6 +103,8 @@ def format_cross_precision(report: dict) -> str:
 
 
 def build_parser() -> argparse.ArgumentParser:
+    from .models.xinstructblip import LM_DECODES, LM_PREFILLS
+
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="X-InstructBLIP")
     ap.add_argument("--model-path", default=None)
@@ -130,13 +132,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-queries-per-call", type=int, default=16, help="with --group-by-video: most queries of one video scored in one call")
     ap.add_argument("--llm-path", default=None, help="local directory of the causal LM (local_files_only, bf16): predictions then come from "
                                                      "generate_llm, the reference's decode")
-    ap.add_argument("--lm-decode", choices=("stock", "hip"), default="stock",
+    ap.add_argument("--lm-decode", choices=LM_DECODES[:2], default="stock",       # "hip_step" is --lm-step here
                     help="with --llm-path: how the LM decodes: stock = llm_model.generate as it comes; hip = the same greedy decode over a static "
                          "cache with the one-token attention on mra_decode_attention")
     ap.add_argument("--lm-step", action="store_true",
                     help="with --llm-path: decode as finetune's --lm-decode hip_step does: the LM's own prefill, then one mra_lm_step per token "
                          "(not together with --lm-decode hip)")
-    ap.add_argument("--lm-prefill", choices=("stock", "hip"), default="stock",
+    ap.add_argument("--lm-prefill", choices=LM_PREFILLS, default="stock",
                     help="with --llm-path and --lm-decode hip or --lm-step: the prefill's attention on mra_prefill_attention under the key mask alone")
     ap.add_argument("--lora", action="store_true", help="with --llm-path: put LoRA adapters on the LM and load their weights (llm_model.* keys) from --checkpoint")
     ap.add_argument("--lora-r", type=int, default=8)
@@ -151,7 +153,7 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> None:
     from torch.utils.data import DataLoader
 
-    from .models.xinstructblip import XInstructBLIP
+    from .models.xinstructblip import XInstructBLIP, check_lm_options
     from .utils.mr_dataset import MRDataset, SyntheticMRDataset, VideoGroupedDataset, collate_fn, collate_grouped
 
     parser = build_parser()
@@ -184,8 +186,9 @@ def main(argv=None) -> None:
                           **({} if llm is None else {"op_dtype": torch.bfloat16, "llm_hidden_size": llm.get_input_embeddings().weight.shape[1]}))
     if llm is not None:
         model.attach_llm(llm, tok)
-        model.lm_decode = "hip_step" if args.lm_step else args.lm_decode
-        model.lm_prefill = args.lm_prefill
+        lm_decode = "hip_step" if args.lm_step else args.lm_decode
+        check_lm_options(lm_decode, args.lm_prefill)
+        model.lm_decode, model.lm_prefill = lm_decode, args.lm_prefill
         if args.lora:       # the adapters must exist before the file's llm_model.* keys can be routed into them
             model.enable_lora(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout)
             if args.checkpoint:

@@ -61,6 +61,8 @@ def build_llm_model(args):
 
 
 def build_parser() -> argparse.ArgumentParser:
+    from .models.xinstructblip import LM_DECODES, LM_PREFILLS
+
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="X-InstructBLIP")
     ap.add_argument("--model-path", default=None)
@@ -115,10 +117,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--val-decode", choices=("score", "llm"), default="score",
                     help="what validation scores: score = the scorer's span (as always); llm = the strings the attached LM decodes (generate_llm, "
                          "the reference's own validation); llm needs --llm-path")
-    ap.add_argument("--lm-decode", choices=("stock", "hip", "hip_step"), default="stock",
+    ap.add_argument("--lm-decode", choices=LM_DECODES, default="stock",
                     help="how the LM decodes: stock = llm_model.generate as it comes; hip = the same greedy decode over a static cache with the "
                          "one-token attention on mra_decode_attention; hip_step = the LM's own prefill, then one mra_lm_step per token")
-    ap.add_argument("--lm-prefill", choices=("stock", "hip"), default="stock",
+    ap.add_argument("--lm-prefill", choices=LM_PREFILLS, default="stock",
                     help="the prefill in front of that decode: stock = the LM's forward as it is configured; hip = its attention on "
                          "mra_prefill_attention under the key mask alone (needs --lm-decode hip or hip_step)")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",

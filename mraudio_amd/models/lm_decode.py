@@ -43,13 +43,18 @@ PREFILL_NAME = "mra_prefill"
 HEAD_DIMS, GROUPS = (64, 128), (1, 2, 4, 8)
 
 
-def _shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor]) -> Optional[str]:
-    """None when the tensors are a one-token attention call, else what is wrong."""
-    if q.dim() != 4 or k.dim() != 4 or q.shape[2] != 1 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[3] != q.shape[3] or k.shape[2] < 1 \
-            or k.shape[1] < 1 or q.shape[1] % k.shape[1]:
-        return f"q [B, Hq, 1, D], k / v [B, Hkv, S, D] with Hq a multiple of Hkv expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}"
+def _shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], q_offset: Optional[int] = None) -> Optional[str]:
+    """None when the tensors are an attention call, else what is wrong.  ``q_offset`` None: the one-token call (one query row, which sits
+    at the last key slot); an int: the causal call of Sq rows, row i at key slot ``q_offset + i``."""
+    one = q_offset is None
+    sq, skv, mname = ("1", "S", "mask") if one else ("Sq", "Skv", "key_mask")
+    if q.dim() != 4 or k.dim() != 4 or (q.shape[2] != 1 if one else q.shape[2] < 1) or k.shape != v.shape or k.shape[0] != q.shape[0] \
+            or k.shape[3] != q.shape[3] or k.shape[2] < 1 or k.shape[1] < 1 or q.shape[1] % k.shape[1]:
+        return f"q [B, Hq, {sq}, D], k / v [B, Hkv, {skv}, D] with Hq a multiple of Hkv expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}"
+    if not one and (q_offset < 0 or q_offset + q.shape[2] > k.shape[2]):
+        return f"0 <= q_offset and q_offset + Sq <= Skv expected, got q_offset {q_offset}, Sq {q.shape[2]}, Skv {k.shape[2]}"
     if mask is not None and (mask.dtype != torch.bool or mask.dim() != 4 or tuple(mask.shape[1:]) != (1, 1, k.shape[2]) or mask.shape[0] not in (1, q.shape[0])):
-        return f"mask must be bool [B, 1, 1, S] (True = attend) or None, got {mask.dtype} {tuple(mask.shape)}"
+        return f"{mname} must be bool [B, 1, 1, {skv}] (True = attend) or None, got {mask.dtype} {tuple(mask.shape)}"
     return None
 
 
@@ -58,126 +63,65 @@ def accepted(q: torch.Tensor, k: torch.Tensor) -> bool:
     return q.shape[3] in HEAD_DIMS and q.shape[1] // k.shape[1] in GROUPS and q.shape[0] <= 65535 and k.shape[1] <= 65535
 
 
-def _hip_reason(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor]) -> Optional[str]:
-    """None when the HIP entry applies, else why not."""
+def _hip_reason(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], one: bool) -> Optional[str]:
+    """None when the HIP entry applies (``one``: ``mra_decode_attention``, else ``mra_prefill_attention``), else why not."""
     if not (q.is_cuda and k.is_cuda and v.is_cuda and (mask is None or mask.is_cuda)):
-        return "q, k, v and the mask must be CUDA tensors"
+        return f"q, k, v and the {'mask' if one else 'key mask'} must be CUDA tensors"
     if not (q.dtype == k.dtype == v.dtype) or q.dtype not in (torch.float16, torch.bfloat16):
         return f"q, k and v must share a 16-bit dtype, got {q.dtype}, {k.dtype}, {v.dtype}"
     if not accepted(q, k):
         return f"D = {q.shape[3]} with Hq / Hkv = {q.shape[1] // k.shape[1]} is outside D in {HEAD_DIMS}, Hq / Hkv in {GROUPS}"
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.stride(3) != 1 or any(s % 8 for s in t.stride()[:3]) or t.data_ptr() % 16 or (name != "q" and t.stride(2) < t.shape[3]):
-            return f"{name} is not laid out as the entry reads it (unit stride along D, 16-byte aligned rows), and no copy of it is made"
-    return None
-
-
-def _entry(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], scale: float) -> torch.Tensor:
-    B, Hq, _, D = q.shape
-    Hkv, S = k.shape[1], k.shape[2]
-    out = torch.empty(B, Hq, 1, D, dtype=q.dtype, device=q.device)
-    m8, m_sb = None, 0
-    if mask is not None:
-        m8 = (mask if mask.stride(3) == 1 or S == 1 else mask.contiguous()).view(torch.uint8)      # [B or 1, 1, 1, S] bytes: a few KB at most
-        m_sb = m8.stride(0) if mask.shape[0] == B and B > 1 else 0
-    nbytes = int(lib().mra_decode_attention_workspace_bytes(B, Hq, S, D))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-    check(lib().mra_decode_attention(ptr(q), q.stride(0), q.stride(1), ptr(k), k.stride(0), k.stride(1), k.stride(2), ptr(v), v.stride(0), v.stride(1),
-                                     v.stride(2), None if m8 is None else ptr(m8), m_sb, B, Hq, Hkv, S, D, mra_dtype(q.dtype), float(scale), ptr(out),
-                                     Hq * D, D, None, ptr(ws), nbytes, current_stream()), "mra_decode_attention")
-    return out
-
-
-def _torch_ops(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], scale: float) -> torch.Tensor:
-    """The definition in fp32 (wider inputs keep their type).  Masking is a select on both sides: a masked slot's bits reach nothing."""
-    G = q.shape[1] // k.shape[1]
-    ct = torch.float32 if q.dtype in (torch.float16, torch.bfloat16) else q.dtype
-    kf, vf = k.to(ct).repeat_interleave(G, dim=1), v.to(ct).repeat_interleave(G, dim=1)       # [B, Hq, S, D]
-    z = scale * (q.to(ct) @ kf.transpose(2, 3))                                               # [B, Hq, 1, S]
-    if mask is not None:
-        z = torch.where(mask, z, torch.full((), float("-inf"), dtype=ct, device=z.device))
-        vf = torch.where(mask.transpose(2, 3), vf, torch.zeros((), dtype=ct, device=z.device))
-    m = z.max(dim=3, keepdim=True).values
-    m = torch.where(m > float("-inf"), m, torch.zeros_like(m))                                # a row with no attended key: every p is 0
-    p = torch.exp(z - m)
-    l = p.sum(dim=3, keepdim=True)
-    out = (p @ vf) / torch.where(l > 0, l, torch.ones_like(l))
-    return out.to(q.dtype)
-
-
-def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], scale: float,
-                     hip: Optional[bool] = None) -> torch.Tensor:
-    """``q`` [B, Hq, 1, D], ``k`` / ``v`` [B, Hkv, S, D] (views with any batch / head / key strides), ``mask`` bool [B, 1, 1, S] with True =
-    attend, or None: ``[B, Hq, 1, D]`` in q's dtype.  ``hip=None`` takes ``mra_decode_attention`` where it accepts the call (CUDA, one 16-bit
-    dtype, D 64 or 128, Hq / Hkv 1, 2, 4 or 8, 16-byte aligned rows) and the torch ops otherwise; ``hip=True`` raises ``MraError`` naming the
-    reason; ``hip=False`` is the torch ops."""
-    bad = _shapes(q, k, v, mask)
-    if bad is not None:
-        raise ValueError(f"decode_attention: {bad}")
-    if hip is None or hip:
-        why = _hip_reason(q, k, v, mask)
-        if why is None:
-            return _entry(q, k, v, mask, scale)
-        if hip:
-            raise MraError(f"decode_attention(hip=True): {why}")
-    return _torch_ops(q, k, v, mask, scale)
-
-
-def _prefill_shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], q_offset: int) -> Optional[str]:
-    """None when the tensors are a causal attention call, else what is wrong."""
-    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[3] != q.shape[3] or q.shape[2] < 1 or k.shape[2] < 1 \
-            or k.shape[1] < 1 or q.shape[1] % k.shape[1]:
-        return f"q [B, Hq, Sq, D], k / v [B, Hkv, Skv, D] with Hq a multiple of Hkv expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}"
-    if q_offset < 0 or q_offset + q.shape[2] > k.shape[2]:
-        return f"0 <= q_offset and q_offset + Sq <= Skv expected, got q_offset {q_offset}, Sq {q.shape[2]}, Skv {k.shape[2]}"
-    if key_mask is not None and (key_mask.dtype != torch.bool or key_mask.dim() != 4 or tuple(key_mask.shape[1:]) != (1, 1, k.shape[2])
-                                 or key_mask.shape[0] not in (1, q.shape[0])):
-        return f"key_mask must be bool [B, 1, 1, Skv] (True = attend) or None, got {key_mask.dtype} {tuple(key_mask.shape)}"
-    return None
-
-
-def _prefill_hip_reason(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor]) -> Optional[str]:
-    """None when ``mra_prefill_attention`` applies, else why not."""
-    if not (q.is_cuda and k.is_cuda and v.is_cuda and (key_mask is None or key_mask.is_cuda)):
-        return "q, k, v and the key mask must be CUDA tensors"
-    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in (torch.float16, torch.bfloat16):
-        return f"q, k and v must share a 16-bit dtype, got {q.dtype}, {k.dtype}, {v.dtype}"
-    if not accepted(q, k):
-        return f"D = {q.shape[3]} with Hq / Hkv = {q.shape[1] // k.shape[1]} is outside D in {HEAD_DIMS}, Hq / Hkv in {GROUPS}"
-    if k.shape[2] > 1 << 30 or q.shape[2] > 65535 * 256:
+    if not one and (k.shape[2] > 1 << 30 or q.shape[2] > 65535 * 256):
         return f"Sq = {q.shape[2]}, Skv = {k.shape[2]} is outside the entry's grid"
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.stride(3) != 1 or any(s % 8 for s in t.stride()[:3]) or t.data_ptr() % 16 or t.stride(2) < t.shape[3]:
+    for name, t in (("q", q), ("k", k), ("v", v)):                   # the one query row of a decode has no position stride to speak of
+        if t.stride(3) != 1 or any(s % 8 for s in t.stride()[:3]) or t.data_ptr() % 16 or (not (one and name == "q") and t.stride(2) < t.shape[3]):
             return f"{name} is not laid out as the entry reads it (unit stride along D, 16-byte aligned rows), and no copy of it is made"
     return None
 
 
-def _prefill_entry(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], scale: float, q_offset: int, want_lse: bool):
+def _mask_bytes(mask: Optional[torch.Tensor], B: int):
+    """``(bytes, batch stride)`` of the mask as the entries read it, uint8 [B or 1, 1, 1, S] (a copy of a few KB at most, which the caller
+    keeps until its launch is enqueued); (None, 0) without one."""
+    if mask is None:
+        return None, 0
+    m8 = (mask if mask.stride(3) == 1 or mask.shape[3] == 1 else mask.contiguous()).view(torch.uint8)
+    return m8, m8.stride(0) if mask.shape[0] == B and B > 1 else 0
+
+
+def _entry(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], scale: float, q_offset: Optional[int], want_lse: bool):
+    """The HIP entries: ``(out, lse)`` with out [B, Hq, 1, D] and no lse for the one-token call, out [B, Sq, Hq, D] for the causal one."""
     B, Hq, Sq, D = q.shape
-    Hkv, Skv = k.shape[1], k.shape[2]
+    Hkv, S = k.shape[1], k.shape[2]
+    m8, m_sb = _mask_bytes(mask, B)
+    mp = None if m8 is None else ptr(m8)
+    if q_offset is None:
+        out = torch.empty(B, Hq, 1, D, dtype=q.dtype, device=q.device)
+        nbytes = int(lib().mra_decode_attention_workspace_bytes(B, Hq, S, D))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+        check(lib().mra_decode_attention(ptr(q), q.stride(0), q.stride(1), ptr(k), k.stride(0), k.stride(1), k.stride(2), ptr(v), v.stride(0), v.stride(1),
+                                         v.stride(2), mp, m_sb, B, Hq, Hkv, S, D, mra_dtype(q.dtype), float(scale), ptr(out), Hq * D, D, None, ptr(ws),
+                                         nbytes, current_stream()), "mra_decode_attention")
+        return out, None
     out = torch.empty(B, Sq, Hq, D, dtype=q.dtype, device=q.device)
     lse = torch.empty(B, Hq, Sq, dtype=torch.float32, device=q.device) if want_lse else None
-    m8, m_sb = None, 0
-    if key_mask is not None:
-        m8 = (key_mask if key_mask.stride(3) == 1 or Skv == 1 else key_mask.contiguous()).view(torch.uint8)   # [B or 1, 1, 1, Skv] bytes
-        m_sb = m8.stride(0) if key_mask.shape[0] == B and B > 1 else 0
     check(lib().mra_prefill_attention(ptr(q), q.stride(0), q.stride(1), q.stride(2), ptr(k), k.stride(0), k.stride(1), k.stride(2), ptr(v), v.stride(0),
-                                      v.stride(1), v.stride(2), None if m8 is None else ptr(m8), m_sb, B, Hq, Hkv, Sq, Skv, q_offset, D, mra_dtype(q.dtype),
-                                      float(scale), ptr(out), out.stride(0), out.stride(1), out.stride(2), None if lse is None else ptr(lse),
-                                      current_stream()), "mra_prefill_attention")
+                                      v.stride(1), v.stride(2), mp, m_sb, B, Hq, Hkv, Sq, S, q_offset, D, mra_dtype(q.dtype), float(scale), ptr(out),
+                                      out.stride(0), out.stride(1), out.stride(2), None if lse is None else ptr(lse), current_stream()),
+          "mra_prefill_attention")
     return out, lse
 
 
-def _prefill_torch_ops(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], scale: float, q_offset: int):
-    """The definition in fp32 (wider inputs keep their type): (out [B, Sq, Hq, D] in q's dtype, lse [B, Hq, Sq]).  Masking is a select on both
-    sides: the bits of a key that no row attends reach nothing."""
-    B, Hq, Sq, D = q.shape
+def _torch_ops(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], scale: float, q_offset: int):
+    """THE definition, in fp32 (wider inputs keep their type): ``(out [B, Hq, Sq, D] in q's dtype, lse [B, Hq, Sq])`` of query rows i at key
+    slots ``q_offset + i`` over the keys s <= q_offset + i that the mask lets through.  The one-token call is Sq = 1, q_offset = S - 1.
+    Masking is a select on both sides: the bits of a key that no row attends reach nothing."""
+    Hq, Sq = q.shape[1], q.shape[2]
     Skv = k.shape[2]
     G = Hq // k.shape[1]
     ct = torch.float32 if q.dtype in (torch.float16, torch.bfloat16) else q.dtype
     dev = q.device
     on = torch.arange(Skv, device=dev)[None, :] <= (torch.arange(Sq, device=dev) + q_offset)[:, None]     # [Sq, Skv]: a few MB at the tests' sizes
-    on = on[None, None] if key_mask is None else on[None, None] & key_mask.to(dev)                           # [B or 1, 1, Sq, Skv]
+    on = on[None, None] if mask is None else on[None, None] & mask.to(dev)                              # [B or 1, 1, Sq, Skv]
     some = on.any(dim=2)[..., None]                                                                     # [B or 1, 1, Skv, 1]: attended by a row
     zero = torch.zeros((), dtype=ct, device=dev)
     kf = torch.where(some, k.to(ct), zero).repeat_interleave(G, dim=1)                                        # [B, Hq, Skv, D]
@@ -189,9 +133,35 @@ def _prefill_torch_ops(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_ma
     p = torch.exp(z - m)
     l = p.sum(dim=3, keepdim=True)
     l1 = torch.where(live, l, torch.ones_like(l))
-    out = (p @ vf) / l1
     lse = torch.where(live, m + torch.log(l1), torch.full((), float("-inf"), dtype=ct, device=dev))[..., 0]
-    return out.transpose(1, 2).contiguous().to(q.dtype), lse
+    return ((p @ vf) / l1).to(q.dtype), lse
+
+
+def _attention(name: str, q, k, v, mask, scale: float, q_offset: Optional[int], hip: Optional[bool], want_lse: bool = False):
+    """``(out, lse)`` of ``decode_attention`` (``q_offset`` None) / ``prefill_attention``, each in its own output layout: the HIP entry where
+    ``hip`` allows it and it applies, ``MraError`` naming the reason under ``hip=True``, the torch ops otherwise."""
+    bad = _shapes(q, k, v, mask, q_offset)
+    if bad is not None:
+        raise ValueError(f"{name}: {bad}")
+    if hip is None or hip:
+        why = _hip_reason(q, k, v, mask, q_offset is None)
+        if why is None:
+            return _entry(q, k, v, mask, scale, q_offset, want_lse)
+        if hip:
+            raise MraError(f"{name}(hip=True): {why}")
+    if q_offset is None:
+        return _torch_ops(q, k, v, mask, scale, k.shape[2] - 1)
+    out, lse = _torch_ops(q, k, v, mask, scale, q_offset)
+    return out.transpose(1, 2).contiguous(), lse
+
+
+def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], scale: float,
+                     hip: Optional[bool] = None) -> torch.Tensor:
+    """``q`` [B, Hq, 1, D], ``k`` / ``v`` [B, Hkv, S, D] (views with any batch / head / key strides), ``mask`` bool [B, 1, 1, S] with True =
+    attend, or None: ``[B, Hq, 1, D]`` in q's dtype.  ``hip=None`` takes ``mra_decode_attention`` where it accepts the call (CUDA, one 16-bit
+    dtype, D 64 or 128, Hq / Hkv 1, 2, 4 or 8, 16-byte aligned rows) and the torch ops otherwise; ``hip=True`` raises ``MraError`` naming the
+    reason; ``hip=False`` is the torch ops."""
+    return _attention("decode_attention", q, k, v, mask, scale, None, hip)[0]
 
 
 def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], scale: float, q_offset: int = 0,
@@ -201,20 +171,17 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mas
     through: ``[B, Sq, Hq, D]`` in q's dtype (the layout transformers wants back), with ``want_lse`` the pair (out, lse fp32 [B, Hq, Sq]).
     ``hip=None`` takes ``mra_prefill_attention`` where it accepts the call (CUDA, one 16-bit dtype, D 64 or 128, Hq / Hkv 1, 2, 4 or 8,
     16-byte aligned rows) and the torch ops otherwise; ``hip=True`` raises ``MraError`` naming the reason; ``hip=False`` is the torch ops."""
-    q_offset = int(q_offset)
-    bad = _prefill_shapes(q, k, v, key_mask, q_offset)
-    if bad is not None:
-        raise ValueError(f"prefill_attention: {bad}")
-    res = None
-    if hip is None or hip:
-        why = _prefill_hip_reason(q, k, v, key_mask)
-        if why is None:
-            res = _prefill_entry(q, k, v, key_mask, scale, q_offset, want_lse)
-        elif hip:
-            raise MraError(f"prefill_attention(hip=True): {why}")
-    if res is None:
-        res = _prefill_torch_ops(q, k, v, key_mask, scale, q_offset)
-    return (res[0], res[1]) if want_lse else res[0]
+    out, lse = _attention("prefill_attention", q, k, v, key_mask, scale, int(q_offset), hip, want_lse)
+    return (out, lse) if want_lse else out
+
+
+def _plain_scale(module, query, key, value, mask, dropout, scaling, kw, q_offset: Optional[int]) -> Optional[float]:
+    """The scale of a call the two routes define -- an evaluating module, no dropout, no sliding window, no soft cap, a bool mask (or none)
+    over the keys and accepted shapes -- and None for every other call, which is SDPA's."""
+    if module.training or dropout or kw.get("sliding_window") is not None or kw.get("softcap") is not None \
+            or _shapes(query, key, value, mask, q_offset) is not None or not accepted(query, key):
+        return None
+    return float(scaling) if scaling is not None else query.shape[3] ** -0.5
 
 
 def _is_key_mask(query: torch.Tensor, key: torch.Tensor, attention_mask) -> bool:
@@ -229,14 +196,12 @@ def prefill_attention_forward(module, query, key, value, attention_mask, dropout
     SDPA under the full causal mask, built here from the key mask.  Everything else is ``attention_forward``."""
     if not _is_key_mask(query, key, attention_mask):
         return attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kw)
-    Sq, Skv = query.shape[2], key.shape[2]
-    if (not module.training and not dropout and kw.get("sliding_window") is None and kw.get("softcap") is None and Sq <= Skv
-            and _prefill_shapes(query, key, value, attention_mask, 0) is None and accepted(query, key)):
-        scale = float(scaling) if scaling is not None else query.shape[3] ** -0.5
+    scale = _plain_scale(module, query, key, value, attention_mask, dropout, scaling, kw, 0)
+    if scale is not None:
         return prefill_attention(query, key, value, attention_mask, scale, q_offset=0), None       # [B, Sq, Hq, D] as it is wanted back
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
-    dev = query.device
+    Sq, Skv, dev = query.shape[2], key.shape[2], query.device
     causal = torch.arange(Skv, device=dev)[None, :] <= torch.arange(Sq, device=dev)[:, None]
     full = (attention_mask & causal[None, None]).expand(query.shape[0], 1, Sq, Skv)                 # never silently non-causal
     return sdpa_attention_forward(module, query, key, value, full, dropout=dropout, scaling=scaling, **kw)
@@ -264,11 +229,9 @@ def prefill_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_
 def attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kw):
     """What ``register`` registers.  One query position, an evaluating module, no dropout, a bool mask (or none) over the keys and accepted
     shapes: ``decode_attention``; anything else: transformers' SDPA function with the arguments as they came."""
-    if (query.dim() == 4 and query.shape[2] == 1 and not module.training and not dropout and kw.get("sliding_window") is None
-            and kw.get("softcap") is None and _shapes(query, key, value, attention_mask) is None and accepted(query, key)):
-        scale = float(scaling) if scaling is not None else query.shape[3] ** -0.5
-        out = decode_attention(query, key, value, attention_mask, scale)                    # [B, Hq, 1, D]
-        return out.transpose(1, 2).contiguous(), None
+    scale = _plain_scale(module, query, key, value, attention_mask, dropout, scaling, kw, None)
+    if scale is not None:
+        return decode_attention(query, key, value, attention_mask, scale).transpose(1, 2).contiguous(), None      # [B, Hq, 1, D] -> [B, 1, Hq, D]
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kw)

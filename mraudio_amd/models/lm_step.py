@@ -31,11 +31,10 @@ from torch import nn
 
 from .. import _lib
 from .._lib import MraError, check, current_stream, lib, mra_dtype
-from .lm_decode import hip_decode
+from .lm_decode import GROUPS, HEAD_DIMS, _torch_ops, hip_decode
 from .lora import ADAPTER, LoraLinear
 
 MAX_B, MAX_R, MAX_EOS = 8, 16, 8
-HEAD_DIMS, GROUPS = (64, 128), (1, 2, 4, 8)
 PREFILLS = ("stock", "hip")
 LINEARS = ("q", "k", "v", "o", "gate", "up", "down")
 # the named wrong versions of the step the tests must tell from the right one (tests/lm_step_cases.py)
@@ -93,21 +92,12 @@ def swiglu_ref(g: torch.Tensor, u: torch.Tensor, mutant: Optional[str] = None) -
 
 
 def attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor, scale: float, mutant: Optional[str] = None) -> torch.Tensor:
-    """``q`` [B, Hq, D], ``k`` / ``v`` [B, Hkv, S, D], ``mask`` [B, S] (nonzero = attend): [B, Hq, D] in q's type; query head h reads kv head h / G."""
-    Hq, Hkv = q.shape[1], k.shape[1]
-    G = Hq // Hkv
-    idx = torch.arange(Hq, device=q.device) % Hkv if mutant == "head_modulo_groups" else torch.arange(Hq, device=q.device) // G
-    kf, vf = k.to(q.dtype)[:, idx], v.to(q.dtype)[:, idx]                                       # [B, Hq, S, D]
-    on = mask.to(torch.bool)[:, None, :]
-    z = scale * torch.einsum("bhd,bhsd->bhs", q, kf)
-    z = torch.where(on, z, torch.full((), float("-inf"), dtype=q.dtype, device=q.device))
-    vf = torch.where(on[..., None], vf, torch.zeros((), dtype=q.dtype, device=q.device))          # a masked slot's bits reach nothing
-    m = z.max(-1, keepdim=True).values
-    m = torch.where(m > float("-inf"), m, torch.zeros_like(m))
-    p = torch.exp(z - m)
-    p = torch.where(on, p, torch.zeros_like(p))
-    l = p.sum(-1, keepdim=True)
-    return torch.einsum("bhs,bhsd->bhd", p, vf) / torch.where(l > 0, l, torch.ones_like(l))
+    """``q`` [B, Hq, D], ``k`` / ``v`` [B, Hkv, S, D], ``mask`` [B, S] (nonzero = attend): [B, Hq, D] in q's type; query head h reads kv head h / G.
+    The one-token case of ``lm_decode``'s definition (the row sits at the last slot); a masked slot's bits reach nothing."""
+    if mutant == "head_modulo_groups":                     # the wrong kv head per query head, handed over as Hq kv heads of one query head each
+        idx = torch.arange(q.shape[1], device=q.device) % k.shape[1]
+        k, v = k[:, idx], v[:, idx]
+    return _torch_ops(q[:, :, None], k, v, mask.to(torch.bool)[:, None, None], scale, k.shape[2] - 1)[0][:, :, 0]
 
 
 def argmax_ref(logits: torch.Tensor, mutant: Optional[str] = None) -> torch.Tensor:

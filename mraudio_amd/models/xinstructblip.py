@@ -216,12 +216,23 @@ def _window_texts(win: torch.Tensor, sc: torch.Tensor, cnt: torch.Tensor, ts: Se
     return scorer.windows_to_text(win, cnt, ts), scorer.windows_to_records(win, sc, cnt, ts)
 
 
-def check_lm_prefill(lm_prefill: str, lm_decode: str) -> None:
-    """``lm_prefill`` is "stock" or "hip", and "hip" needs ``lm_decode`` "hip" or "hip_step" (ValueError otherwise)."""
-    if lm_prefill not in ("stock", "hip"):
+LM_DECODES, LM_PREFILLS = ("stock", "hip", "hip_step"), ("stock", "hip")       # XInstructBLIP.lm_decode / .lm_prefill; the CLIs' choices
+
+
+def check_lm_options(lm_decode: str, lm_prefill: str = "stock", unknown_decode=ValueError) -> None:
+    """The one rule for the pair: ``lm_decode`` in ``LM_DECODES`` (``unknown_decode`` otherwise), ``lm_prefill`` in ``LM_PREFILLS``, and
+    "hip" needs ``lm_decode`` "hip" or "hip_step" (ValueError otherwise)."""
+    if lm_decode not in LM_DECODES:
+        raise unknown_decode(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
+    if lm_prefill not in LM_PREFILLS:
         raise ValueError(f"lm_prefill must be 'stock' or 'hip', got {lm_prefill!r}")
-    if lm_prefill == "hip" and lm_decode not in ("hip", "hip_step"):
+    if lm_prefill == "hip" and lm_decode == "stock":
         raise ValueError(f"lm_prefill='hip' needs lm_decode 'hip' or 'hip_step' (the stock decode is the reference's call, untouched), got lm_decode={lm_decode!r}")
+
+
+def check_lm_prefill(lm_prefill: str, lm_decode: str) -> None:
+    """``check_lm_options`` under its earlier name and argument order."""
+    check_lm_options(lm_decode, lm_prefill)
 
 
 class XInstructBLIP(nn.Module):
@@ -259,11 +270,8 @@ class XInstructBLIP(nn.Module):
                  video_processor=None, lm_loss: str = "stock", prompt_assembly: str = "cat",
                  grouped_lm: bool = False, lm_decode: str = "stock", lm_prefill: str = "stock"):
         super().__init__()
-        if lm_decode not in ("stock", "hip", "hip_step"):
-            raise ValueError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
-        self.lm_decode = lm_decode
-        check_lm_prefill(lm_prefill, lm_decode)
-        self.lm_prefill = lm_prefill
+        check_lm_options(lm_decode, lm_prefill)
+        self.lm_decode, self.lm_prefill = lm_decode, lm_prefill
         if lm_loss not in ("stock", "rows", "fused"):
             raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
         self.lm_loss = lm_loss
@@ -1054,8 +1062,7 @@ class XInstructBLIP(nn.Module):
         ``mra_lm_step`` per token (``models/lm_step.py``: weight-streaming layers, head and greedy bookkeeping on HIP).  ``lm_prefill = "hip"``
         (with either HIP decode): the prefill's attention on ``mra_prefill_attention``.  The LM is as it was after the call."""
         lm_prefill = getattr(self, "lm_prefill", "stock")
-        if lm_prefill != "stock":
-            check_lm_prefill(lm_prefill, self.lm_decode)
+        check_lm_options(self.lm_decode, lm_prefill, unknown_decode=MraError)
         if self.lm_decode == "stock":
             outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens)
         elif self.lm_decode == "hip":
@@ -1064,15 +1071,13 @@ class XInstructBLIP(nn.Module):
             with hip_decode(self.llm_model, prefill=lm_prefill == "hip"):
                 outputs = self.llm_model.generate(inputs_embeds=embeds, attention_mask=mask, max_new_tokens=max_new_tokens,
                                                   cache_implementation="static", disable_compile=True)
-        elif self.lm_decode == "hip_step":
+        else:                                                          # "hip_step"
             from .lm_step import HipLmDecoder
 
             dec = getattr(self, "_lm_stepper", None)
             if dec is None or dec.llm is not self.llm_model or dec.prefill != lm_prefill:
                 dec = self._lm_stepper = HipLmDecoder(self.llm_model, prefill=lm_prefill)
             outputs = dec.generate(embeds, mask, max_new_tokens)
-        else:
-            raise MraError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {self.lm_decode!r}")
         outputs[outputs == 0] = 2                                      # :392
         return [o.strip() for o in self.llm_tokenizer.batch_decode(outputs, skip_special_tokens=True)]
 

@@ -149,15 +149,12 @@ class Trainer:
         if self.val_decode == "llm" and getattr(model, "llm_model", None) is None:
             from .._lib import MraError
             raise MraError("val_decode 'llm' needs a model with an LM attached (attach_llm; finetune --llm-path)")
-        lm_decode = getattr(args, "lm_decode", None) or "stock"
-        if lm_decode not in ("stock", "hip", "hip_step"):
-            raise ValueError(f"lm_decode must be 'stock', 'hip' or 'hip_step', got {lm_decode!r}")
+        from ..models.xinstructblip import check_lm_options
+        lm_decode, lm_prefill = getattr(args, "lm_decode", None) or "stock", getattr(args, "lm_prefill", None) or "stock"
+        check_lm_options(lm_decode, lm_prefill)           # "hip" prefill needs a HIP decode: the rule is XInstructBLIP's
         if lm_decode != "stock":
             model.lm_decode = lm_decode
-        lm_prefill = getattr(args, "lm_prefill", None) or "stock"
-        if lm_prefill != "stock":                        # "hip" needs a HIP decode: the rule is XInstructBLIP's (check_lm_prefill)
-            from ..models.xinstructblip import check_lm_prefill
-            check_lm_prefill(lm_prefill, lm_decode)
+        if lm_prefill != "stock":
             model.lm_prefill = lm_prefill
         self.lora = bool(getattr(args, "lora", False))
         if self.lora:
