@@ -413,6 +413,36 @@ int mra_prefill_attention(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_s
                           int32_t Hkv, int32_t Sq, int32_t Skv, int32_t q_offset, int32_t D, int32_t dtype, float scale, void* out, int64_t o_sb,
                           int64_t o_ss, int64_t o_sh, float* lse, void* stream);
 
+/* ---- LM training: backward of the causal grouped-query attention --------------------------------------------------
+ * replaces: the backward of scaled_dot_product_attention under the explicit [S][S] mask inside the reference's
+ * self.llm_model(inputs_embeds=..., labels=...) (models/xinstructblip.py:599-604), in every layer of the attached LM.  Stateless like
+ * mra_prefill_attention: caller-owned buffers and workspace, a stream, no allocation, no synchronisation, every view by ELEMENT strides (D
+ * contiguous).  q and dq are [B][Hq][Sq][D] views (the transposed view of a [B, Sq, Hq, D] tensor works for both), k, v, dk and dv
+ * [B][Hkv][Skv][D] views, out and dout [B][Sq][Hq][D] views, mask [B][Skv] bytes or NULL, lse f32 [B][Hq][Sq] as mra_prefill_attention
+ * writes it (mandatory).  With att(b, i) = {s : s <= q_offset + i, s < Skv, mask[b][s] != 0} and G = Hq / Hkv:
+ *     p_is = exp(scale q[b,h,i] . k[b,h/G,s] - lse_i) on att(b, i), 0 elsewhere and everywhere in a row with lse = -inf
+ *     delta_i = dO[b,i,h] . out[b,i,h]            ds_is = p_is (dO[b,i,h] . v[b,h/G,s] - delta_i)
+ *     dV[b,g,s] = sum_{h in g} sum_i p_is dO[b,i,h]     dQ[b,h,i] = scale sum_s ds_is k[b,h/G,s]     dK[b,g,s] = scale sum_{h in g} sum_i ds_is q[b,h,i]
+ * Logits, p, dp, delta and every sum in fp32 on the MFMAs' accumulators; p and ds are rounded once to `dtype` as MFMA operands, dQ / dK / dV
+ * once on the way out.  The sum over a group's query heads runs in registers in ascending head order.  Masking is a select: the bits of a
+ * K / V slot that no row attends, and of the dO / out rows of a query row with lse = -inf, reach nothing.  Every element of dq [.., Sq),
+ * dk and dv [.., Skv) is written: +0 for a key no row attends and for a row with no attended key.  No atomics: two runs give the same bits.
+ * The workspace holds delta, f32 [B][Hq][Sq]; mra_prefill_attention_backward_workspace_bytes gives its size (0 with a reason on bad arguments).
+ * Two launches on `stream`.
+ * MRA_EINVAL (reason in mra_last_error(), nothing written, before any launch): a negative B, another dtype, D or G, Hq % Hkv != 0, Sq or
+ * Skv < 1, a negative q_offset or q_offset + Sq > Skv, a NULL q / k / v / out / dout / lse / dq / dk / dv / workspace, one of the 16-bit
+ * buffers or the workspace not 16-byte aligned, lse not 4-byte aligned, a stride that is not a multiple of 8 elements, a position stride (or
+ * out's / dout's head stride) below D, a workspace shorter than the size function says, a scale that is not finite.  B == 0 launches nothing
+ * and returns MRA_OK whatever else is passed. */
+size_t mra_prefill_attention_backward_workspace_bytes(int32_t B, int32_t Hq, int32_t Sq);
+int mra_prefill_attention_backward(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
+                                   const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss, const uint8_t* mask, int64_t mask_sb, const void* out,
+                                   int64_t o_sb, int64_t o_ss, int64_t o_sh, const void* dout, int64_t do_sb, int64_t do_ss, int64_t do_sh,
+                                   const float* lse, int32_t B, int32_t Hq, int32_t Hkv, int32_t Sq, int32_t Skv, int32_t q_offset, int32_t D,
+                                   int32_t dtype, float scale, void* dq, int64_t dq_sb, int64_t dq_sh, int64_t dq_ss, void* dk, int64_t dk_sb,
+                                   int64_t dk_sh, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_sh, int64_t dv_ss, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* ---- LM decode: one whole token per call (weight-streaming layers, head, greedy bookkeeping) ------------------------
  * replaces: one iteration of the reference's self.llm_model.generate(inputs_embeds=..., attention_mask=..., max_new_tokens=64)
  * (models/xinstructblip.py:383-391, utils/trainer.py:157-165) behind the prefill: the forward of a Llama-shaped LM on one new token per

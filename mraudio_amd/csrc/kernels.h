@@ -299,6 +299,27 @@ struct PrefillArgs {
   float* lse;
 };
 int launch_prefill_attention(const PrefillArgs& a, int D, int op_dtype, hipStream_t stream);
+// Its backward (prefill_attn_bwd.hip): out, dout [B][Sq][Hq][D], lse f32 [B][Hq][Sq] of the forward, dq as q, dk / dv as k / v, all with
+// element strides; delta f32 [B][Hq][Sq] is the workspace.  Two launches: dQ (a workgroup owns PREFILL_BWD_QB query rows of one (b, query
+// head), walks the key tiles up to its diagonal and writes delta), then dK / dV (a workgroup owns PREFILL_BWD_KB keys of one (b, K/V head)
+// and walks the group's query heads in ascending order, each over the PREFILL_BWD_QT-row query tiles from its diagonal on).  No atomics.
+constexpr int PREFILL_BWD_QB = 128, PREFILL_BWD_KB = 128, PREFILL_BWD_QT = 32;
+struct PrefillBwdArgs {
+  const void* q; long long q_sb, q_sh, q_ss;
+  const void* k; long long k_sb, k_sh, k_ss;
+  const void* v; long long v_sb, v_sh, v_ss;
+  const unsigned char* mask; long long mask_sb;
+  const void* out; long long o_sb, o_ss, o_sh;
+  const void* dout; long long do_sb, do_ss, do_sh;
+  const float* lse;
+  int B, Hq, G, Sq, Skv, q_offset;              // G = Hq / Hkv
+  float scale;
+  void* dq; long long dq_sb, dq_sh, dq_ss;
+  void* dk; long long dk_sb, dk_sh, dk_ss;
+  void* dv; long long dv_sb, dv_sh, dv_ss;
+  float* delta;
+};
+int launch_prefill_attention_backward(const PrefillBwdArgs& a, int D, int op_dtype, hipStream_t stream);
 // The one-token step of the LM's decode (lm_step.hip): a skinny weight-streaming GEMM y [B][N] = x [B][K] W[N][K]^T for B <= LM_MAX_B rows
 // with its prologue launch (RMSNorm to an fp32 copy, u = A x of up to three adapters), the embedding gather and the argmax with generate's
 // greedy bookkeeping.  A workgroup owns LM_CB columns (rotary form: one head of D columns); W is read as stored and never copied.

@@ -3,12 +3,12 @@
 // The reference wraps a causal LM around the Q-Formers' projections: LoRA adapters in its linears (models/xinstructblip.py:163), the
 // cross-entropy of the answer tokens (:599-604), the prompt rows in front of it (:341-381, :541-595) and the greedy decode that picks
 // the best checkpoint (self.llm_model.generate, :383-391).  The kernels behind those are lora.hip, lm_head.hip, prompt.hip, decode_attn.hip,
-// prefill_attn.hip and lm_step.hip; this unit is the host code between the C entry and their launch functions (kernels.h).
+// prefill_attn.hip, prefill_attn_bwd.hip and lm_step.hip; this unit is the host code between the C entry and their launch functions (kernels.h).
 //
 // None of it has a handle: every entry takes device pointers, checks every argument before the first launch (a refused call writes nothing and
 // leaves its reason in mra_last_error()), allocates nothing and enqueues on `stream`.  What the entries ask alike is asked once: lm_heads_check
-// (operand type, head width, head grouping) by every attention-shaped entry, attn_call_check by mra_decode_attention and
-// mra_prefill_attention; DecodeWs is the one place the decode attention's workspace is laid out and carved, for the entry and for mra_lm_step.
+// (operand type, head width, head grouping) by every attention-shaped entry, attn_call_check by mra_decode_attention,
+// mra_prefill_attention and mra_prefill_attention_backward; DecodeWs is the one place the decode attention's workspace is laid out and carved, for the entry and for mra_lm_step.
 #include <cmath>
 #include <initializer_list>
 
@@ -265,6 +265,57 @@ int mra_prefill_attention(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_s
   a.out = out; a.o_sb = o_sb; a.o_ss = o_ss; a.o_sh = o_sh;
   a.lse = lse;
   return chk(launch_prefill_attention(a, D, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)), "prefill_attention");
+}
+
+// ---- its backward: dQ, dK, dV of the causal grouped-query attention in training (prefill_attn_bwd.hip) ------------------------------------
+// replaces: the backward of scaled_dot_product_attention under the [S][S] mask inside self.llm_model(inputs_embeds=..., labels=...),
+// models/xinstructblip.py:599-604.  Every check comes before a launch.  The workspace is delta, f32 [B][Hq][Sq].
+size_t mra_prefill_attention_backward_workspace_bytes(int32_t B, int32_t Hq, int32_t Sq) {
+  if (B < 0 || Hq < 1 || Sq < 1) {
+    fail(MRA_EINVAL, "prefill_attention_backward_workspace_bytes: B >= 0, Hq >= 1, Sq >= 1");
+    return 0;
+  }
+  return up256(4 * (size_t)B * (size_t)Hq * (size_t)Sq);
+}
+
+int mra_prefill_attention_backward(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
+                                   const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss, const uint8_t* mask, int64_t mask_sb, const void* out,
+                                   int64_t o_sb, int64_t o_ss, int64_t o_sh, const void* dout, int64_t do_sb, int64_t do_ss, int64_t do_sh,
+                                   const float* lse, int32_t B, int32_t Hq, int32_t Hkv, int32_t Sq, int32_t Skv, int32_t q_offset, int32_t D,
+                                   int32_t dtype, float scale, void* dq, int64_t dq_sb, int64_t dq_sh, int64_t dq_ss, void* dk, int64_t dk_sb,
+                                   int64_t dk_sh, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_sh, int64_t dv_ss, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  const std::string w("prefill_attention_backward");
+  if (B < 0) return fail(MRA_EINVAL, w + ": negative B");
+  if (B == 0) return MRA_OK;   // launches nothing, touches nothing
+  if (Sq < 1 || Skv < 1) return fail(MRA_EINVAL, w + ": Sq and Skv must be at least 1");
+  if (q_offset < 0 || (int64_t)q_offset + Sq > Skv) return fail(MRA_EINVAL, w + ": 0 <= q_offset and q_offset + Sq <= Skv expected");
+  if (Skv > 65535 * PREFILL_BWD_KB) return fail(MRA_EINVAL, w + ": Skv must be at most 65535 key blocks");
+  if (!lse) return fail(MRA_EINVAL, w + ": null argument (lse is mandatory)");
+  if (int rc = attn_call_check(w, B, dtype, Hq, Hkv, D, {q, k, v, out, dout, dq, dk, dv, workspace}, "q, k, v, out, dout, dq, dk, dv and the workspace",
+                               {q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_ss, o_sh, do_sb, do_ss, do_sh, dq_sb, dq_sh, dq_ss,
+                                dk_sb, dk_sh, dk_ss, dv_sb, dv_sh, dv_ss},
+                               lse, scale))
+    return rc;
+  if (q_ss < D || k_ss < D || v_ss < D || o_ss < D || o_sh < D || do_ss < D || do_sh < D || dq_ss < D || dk_ss < D || dv_ss < D)
+    return fail(MRA_EINVAL, w + ": a position stride (or out's / dout's head stride) below D");
+  if (workspace_bytes < up256(4 * (size_t)B * (size_t)Hq * (size_t)Sq))
+    return fail(MRA_EINVAL, w + ": workspace too small (mra_prefill_attention_backward_workspace_bytes)");
+  PrefillBwdArgs a{};
+  a.q = q; a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss;
+  a.k = k; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
+  a.v = v; a.v_sb = v_sb; a.v_sh = v_sh; a.v_ss = v_ss;
+  a.mask = mask; a.mask_sb = mask_sb;
+  a.out = out; a.o_sb = o_sb; a.o_ss = o_ss; a.o_sh = o_sh;
+  a.dout = dout; a.do_sb = do_sb; a.do_ss = do_ss; a.do_sh = do_sh;
+  a.lse = lse;
+  a.B = B; a.Hq = Hq; a.G = Hq / Hkv; a.Sq = Sq; a.Skv = Skv; a.q_offset = q_offset;
+  a.scale = scale;
+  a.dq = dq; a.dq_sb = dq_sb; a.dq_sh = dq_sh; a.dq_ss = dq_ss;
+  a.dk = dk; a.dk_sb = dk_sb; a.dk_sh = dk_sh; a.dk_ss = dk_ss;
+  a.dv = dv; a.dv_sb = dv_sb; a.dv_sh = dv_sh; a.dv_ss = dv_ss;
+  a.delta = static_cast<float*>(workspace);
+  return chk(launch_prefill_attention_backward(a, D, dtype == MRA_BF16 ? OP_BF16 : OP_F16, as_stream(stream)), "prefill_attention_backward");
 }
 
 // ---- one whole token of the LM's decode (lm_step.hip) ---------------------------------------------------------------------------------------

@@ -123,6 +123,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lm-prefill", choices=LM_PREFILLS, default="stock",
                     help="the prefill in front of that decode: stock = the LM's forward as it is configured; hip = its attention on "
                          "mra_prefill_attention under the key mask alone (needs --lm-decode hip or hip_step)")
+    ap.add_argument("--lm-attention", choices=("stock", "hip"), default="stock",
+                    help="the LM's attention in the training pass: stock = the LM's forward as it is configured (SDPA under the [S, S] mask); hip = "
+                         "one autograd node on mra_prefill_attention / mra_prefill_attention_backward under the key mask alone (needs "
+                         "--objective llm or both)")
     ap.add_argument("--video-on-device", dest="video_device", action="store_true",
                     help="decoded video goes to the GPU as uint8 frames and is cropped, resized, flipped and normalised there "
                          "(mra_video_frames_forward) instead of as float32 pixels made on the host")
@@ -146,6 +150,8 @@ def main(argv=None):
         parser.error("--lora needs --llm-path DIR and --objective llm or both")
     if args.lm_loss != "stock" and args.objective == "score":
         parser.error("--lm-loss rows / fused needs --objective llm or both")
+    if args.lm_attention != "stock" and args.objective == "score":
+        parser.error("--lm-attention hip needs --objective llm or both")
     if args.prompt_assembly != "cat" and args.objective == "score":
         parser.error("--prompt-assembly plan needs --objective llm or both")
     if args.val_decode == "llm" and not args.llm_path:

@@ -28,7 +28,7 @@ The prefill in front of it (the reference's same ``generate`` call, ``models/xin
 
 A row with no attended key gives +0 where SDPA gives NaN; ``generate`` never produces one behind a decode, and the left-pad query rows of a
 prefill, which are exactly that case, are attended by nothing downstream.  Out of scope: paged or quantised K/V, beam search and sampling,
-chunked prefill, a backward of the prefill attention, sliding windows and soft caps (such calls go to SDPA)."""
+chunked prefill, sliding windows and soft caps (such calls go to SDPA)."""
 from __future__ import annotations
 
 import contextlib

@@ -217,6 +217,7 @@ def _window_texts(win: torch.Tensor, sc: torch.Tensor, cnt: torch.Tensor, ts: Se
 
 
 LM_DECODES, LM_PREFILLS = ("stock", "hip", "hip_step"), ("stock", "hip")       # XInstructBLIP.lm_decode / .lm_prefill; the CLIs' choices
+LM_ATTENTIONS = ("stock", "hip")                                                # XInstructBLIP.lm_attention
 
 
 def check_lm_options(lm_decode: str, lm_prefill: str = "stock", unknown_decode=ValueError) -> None:
@@ -233,6 +234,28 @@ def check_lm_options(lm_decode: str, lm_prefill: str = "stock", unknown_decode=V
 def check_lm_prefill(lm_prefill: str, lm_decode: str) -> None:
     """``check_lm_options`` under its earlier name and argument order."""
     check_lm_options(lm_decode, lm_prefill)
+
+
+def _lm_ce_call(self, embeds, mask, targets):
+    """``XInstructBLIP._lm_ce`` under the attention implementation the LM has at this moment."""
+    if self.lm_loss == "stock":
+        return self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
+    if self.lm_loss not in ("rows", "fused"):
+        raise MraError(f"lm_loss must be 'stock', 'rows' or 'fused', got {self.lm_loss!r}")
+    from .lm_head import lm_head_ce
+
+    llm = self.llm_model
+    prefix = getattr(llm, "base_model_prefix", "")
+    dec = llm.get_decoder() if hasattr(llm, "get_decoder") else (getattr(llm, prefix, None) if prefix else None)
+    if dec is None or dec is llm:
+        raise MraError(f"lm_loss {self.lm_loss!r} needs an LM that exposes its decoder (get_decoder() or its base_model_prefix attribute)")
+    head = llm.get_output_embeddings() if hasattr(llm, "get_output_embeddings") else None
+    if head is None or getattr(head, "weight", None) is None:
+        raise MraError(f"lm_loss {self.lm_loss!r} needs an LM with an output embedding (get_output_embeddings())")
+    if getattr(head, "bias", None) is not None:
+        raise MraError(f"lm_loss {self.lm_loss!r}: the LM's output embedding has a bias, which the row-wise head does not take")
+    hidden = dec(inputs_embeds=embeds, attention_mask=mask, return_dict=True).last_hidden_state
+    return lm_head_ce(hidden, head.weight, targets, hip=False if self.lm_loss == "rows" else None)
 
 
 class XInstructBLIP(nn.Module):
@@ -258,6 +281,10 @@ class XInstructBLIP(nn.Module):
     # forward with its attention on mra_prefill_attention under the key mask alone (models/lm_decode.py).  "hip" needs lm_decode "hip" or
     # "hip_step": the stock decode is the reference's call and stays untouched
     lm_prefill = "stock"
+    # the LM's attention in the training pass (_lm_ce): "stock" = the LM's forward as it is configured (SDPA under the [S, S] bool mask, forward
+    # and backward), "hip" = the same forward inside lm_attention.hip_train: the causal attention as one autograd node on mra_prefill_attention
+    # and mra_prefill_attention_backward under the key mask alone (models/lm_attention.py).  Independent of lm_decode / lm_prefill
+    lm_attention = "stock"
 
     def __init__(self, model_path: Optional[str] = None, audio_path: Optional[str] = None, *,
                  modalities: Optional[Sequence[str]] = None, video_encoder: Optional[nn.Module] = None,
@@ -268,10 +295,13 @@ class XInstructBLIP(nn.Module):
                  llm_hidden_size: int = 4096, checkpoint: Optional[str] = None, checkpoint_strict: bool = True,
                  cross_precision: str = "op", audio_processor=None, top_k: int = 1, nms_thd: float = 0.25, max_window: int = 0,
                  video_processor=None, lm_loss: str = "stock", prompt_assembly: str = "cat",
-                 grouped_lm: bool = False, lm_decode: str = "stock", lm_prefill: str = "stock"):
+                 grouped_lm: bool = False, lm_decode: str = "stock", lm_prefill: str = "stock", lm_attention: str = "stock"):
         super().__init__()
         check_lm_options(lm_decode, lm_prefill)
         self.lm_decode, self.lm_prefill = lm_decode, lm_prefill
+        if lm_attention not in LM_ATTENTIONS:
+            raise ValueError(f"lm_attention must be 'stock' or 'hip', got {lm_attention!r}")
+        self.lm_attention = lm_attention
         if lm_loss not in ("stock", "rows", "fused"):
             raise ValueError(f"lm_loss must be 'stock', 'rows' or 'fused', got {lm_loss!r}")
         self.lm_loss = lm_loss
@@ -1000,25 +1030,18 @@ class XInstructBLIP(nn.Module):
         """The LM's cross-entropy on the answer tokens.  ``lm_loss = "stock"``: the LM's own forward with ``labels`` (the reference's call,
         ``:599-604``; ``lm_head`` runs over every position).  ``"rows"`` / ``"fused"``: the LM's decoder alone, then ``lm_head_ce`` on the
         final hidden states -- the head and the loss on the labelled rows only, as torch ops or on the HIP entries; ``lm_head`` itself is
-        never called, so its weight gets no gradient under ``"fused"`` (the reference never trains it)."""
-        if self.lm_loss == "stock":
-            return self.llm_model(inputs_embeds=embeds, attention_mask=mask, return_dict=True, labels=targets).loss
-        if self.lm_loss not in ("rows", "fused"):
-            raise MraError(f"lm_loss must be 'stock', 'rows' or 'fused', got {self.lm_loss!r}")
-        from .lm_head import lm_head_ce
+        never called, so its weight gets no gradient under ``"fused"`` (the reference never trains it).  ``lm_attention = "hip"``: the same
+        call, on any of the three routes, inside ``lm_attention.hip_train``."""
+        lm_attention = getattr(self, "lm_attention", "stock")
+        if lm_attention == "stock":
+            return _lm_ce_call(self, embeds, mask, targets)
+        if lm_attention not in LM_ATTENTIONS:
+            raise MraError(f"lm_attention must be 'stock' or 'hip', got {lm_attention!r}")
+        from .lm_attention import hip_train, hold_for_backward
 
-        llm = self.llm_model
-        prefix = getattr(llm, "base_model_prefix", "")
-        dec = llm.get_decoder() if hasattr(llm, "get_decoder") else (getattr(llm, prefix, None) if prefix else None)
-        if dec is None or dec is llm:
-            raise MraError(f"lm_loss {self.lm_loss!r} needs an LM that exposes its decoder (get_decoder() or its base_model_prefix attribute)")
-        head = llm.get_output_embeddings() if hasattr(llm, "get_output_embeddings") else None
-        if head is None or getattr(head, "weight", None) is None:
-            raise MraError(f"lm_loss {self.lm_loss!r} needs an LM with an output embedding (get_output_embeddings())")
-        if getattr(head, "bias", None) is not None:
-            raise MraError(f"lm_loss {self.lm_loss!r}: the LM's output embedding has a bias, which the row-wise head does not take")
-        hidden = dec(inputs_embeds=embeds, attention_mask=mask, return_dict=True).last_hidden_state
-        return lm_head_ce(hidden, head.weight, targets, hip=False if self.lm_loss == "rows" else None)
+        with hip_train(self.llm_model):
+            loss = _lm_ce_call(self, embeds, mask, targets)
+        return hold_for_backward(self.llm_model, loss)       # activation checkpointing: the recomputation runs the same attention
 
     def _llm_inputs(self, samples):
         if self.prompt_assembler is None:

@@ -47,6 +47,8 @@ What is different, because the data-parallel hot path here is the HIP Q-Former a
     ``moment_str_to_list`` -> ``eval_submission`` tail -- the validation under which frozen Q-Formers with LoRA adapters move the metric.
     ``args.lm_decode`` ("stock" | "hip" | "hip_step", ``finetune --lm-decode``): how that decode runs (``XInstructBLIP._llm_decode``, ``models/lm_decode.py``).
     ``args.lm_prefill`` ("stock" | "hip", ``finetune --lm-prefill``; "hip" needs ``lm_decode`` "hip" or "hip_step"): the prefill's attention on ``mra_prefill_attention``.
+  * ``args.lm_attention`` ("stock" | "hip", ``finetune --lm-attention``; "hip" needs an LM objective): the LM's attention of the training pass on
+    ``mra_prefill_attention`` / ``mra_prefill_attention_backward`` as one autograd node (``models/lm_attention.py``).
 
 ``LinearWarmupCosineLRScheduler`` restates the scheduler of the third-party ``salesforce-lavis`` package
 (``lavis/common/optims.py``; version unpinned by the reference, absent offline): linear warm-up over
@@ -156,6 +158,14 @@ class Trainer:
             model.lm_decode = lm_decode
         if lm_prefill != "stock":
             model.lm_prefill = lm_prefill
+        # lm_attention "hip": the LM's attention of the training pass as one autograd node on HIP (models/lm_attention.py)
+        lm_attention = getattr(args, "lm_attention", None) or "stock"
+        if lm_attention not in ("stock", "hip"):
+            raise ValueError(f"lm_attention must be 'stock' or 'hip', got {lm_attention!r}")
+        if lm_attention != "stock":
+            if self.objective == "score":
+                raise ValueError("lm_attention changes the LM's training pass: it needs objective 'llm' or 'both'")
+            model.lm_attention = lm_attention
         self.lora = bool(getattr(args, "lora", False))
         if self.lora:
             if self.objective == "score":
@@ -373,6 +383,6 @@ def default_args(**kw) -> SimpleNamespace:
     """The reference's ``finetune.py`` defaults (``:44-62``) as a namespace, for programmatic use."""
     base = dict(model="X-InstructBLIP", model_path=None, audio_encoder=None, video_folder=None, train_annotation_file=None,
                 val_annotation_file=None, output_dir="out", val_freq=1, save_freq=1, max_epoch=50, batch_size=1, num_workers=0,
-                dataset="Charades_STA", gpu=0, val_decode="score", lm_decode="stock", lm_prefill="stock")
+                dataset="Charades_STA", gpu=0, val_decode="score", lm_decode="stock", lm_prefill="stock", lm_attention="stock")
     base.update(kw)
     return SimpleNamespace(**base)
